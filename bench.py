@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric: restored images/sec, raindrop 64x64 patches, 100-step DDIM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of synthetic input on every rank: DWT of the
@@ -11,9 +11,17 @@ Workload at N=1 = BASELINE.json configs[1] (raindrop_wavelet 64x64, batch 64, 10
 N>1 shards independent images: every rank runs its own batch of 64 (weak scaling, configs[3]),
 weights are packed on rank 0 and broadcast over RCCL, outputs are all-gathered after the clock stops.
 
-Prints ONE JSON line on rank 0 (see README / the driver contract) including
-  roofline      live HIP-event timing of the dominant kernel (the fused 3x3 implicit-GEMM conv) inside this run
-  cpu_baseline  the CPU oracle timed on this box's host cores on a bounded sample (N=1 only)
+A plain run sets up, runs W warm-up steps and K timed steps, and prints ONE JSON line on rank 0 (see
+README / the driver contract); `ms_per_step` is the wall time of one timed step.
+  --dump-outputs DIR  after the timed steps, the arrays the last timed step returned go to DIR/<name>.npy (float32,
+                      64 MB at most: a fixed, seeded sample of rows when the outputs are larger).  Inputs and weights
+                      are seeded, so two builds run with the same arguments can be compared output for output.
+  --full              adds the legs that take runs of their own:
+    roofline      live HIP-event timing of the dominant kernel (the fused 3x3 implicit-GEMM conv) in one more pass,
+                  and the board's sustained MFMA rates (tools/abl_mfma_power)
+    cpu_baseline  the CPU oracle timed on this box's host cores on a bounded sample (N=1 only)
+    parity_mode   the fp32-tensor modes (f16, f32x3, exact f32) timed and checked against each other (N=1 only)
+    extras        configs[2] and configs[4] (N=1 only)
 """
 import argparse
 import json
@@ -75,6 +83,28 @@ def fail(msg, n_gpus, rank=0):
     sys.exit(2)
 
 
+DUMP_BUDGET = 64 * 1000 * 1000      # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor or None} -> path/<name>.npy in float32.  When the arrays hold more than DUMP_BUDGET bytes, every array keeps
+    the same fraction of its leading-dimension rows, picked by a fixed seed (the same rows from run to run) and kept in order."""
+    import numpy as np
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    total = sum(v.numel() * 4 for v in arrays.values())
+    frac = min(1.0, (DUMP_BUDGET - 4096 * len(arrays)) / total)          # (4 KB per file for the .npy header)
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        n = v.shape[0]
+        k = n if frac >= 1.0 else max(1, int(n * frac))
+        if k < n:
+            rows = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+            v = v[torch.from_numpy(rows).to(v.device)]
+            log(f"[bench] --dump-outputs: {name} sampled to rows {rows.tolist()} of {n}")
+        np.save(os.path.join(path, name + ".npy"), v.detach().float().cpu().numpy())
+        log(f"[bench] --dump-outputs: {os.path.join(path, name + '.npy')} {tuple(v.shape)} float32")
+
+
 def self_launch(n, backend):
     import socket
     import subprocess
@@ -107,10 +137,13 @@ def main():
                                                                  "split 6/6/6/6/6/5/5/5 over 8 ranks, one all-reduce(sum) of 2 x 3 x 120 x 180 floats per DDIM step")
     ap.add_argument("--full-length", action="store_true", help="c4 only: run the 4 steps restore() does not read (args.early_stop = False, the reference's step count)")
     ap.add_argument("--max-batch", type=int, default=0, help="UNet call batch cap (default max(batch, 64))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational legs of the default N=1 run (configs[2], configs[4]) AND the parity modes")
-    ap.add_argument("--parity-only", action="store_true", help="with --no-extras: keep the parity-mode leg (f16 / f32x3 / f32 timed and checked), skip configs[2] / configs[4]")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all: a fixed, seeded sample of rows beyond that)")
+    ap.add_argument("--full", action="store_true", help="also run the roofline leg, the CPU baseline, the parity modes and the extras (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the informational legs of the N=1 run (configs[2], configs[4]) AND the parity modes")
+    ap.add_argument("--parity-only", action="store_true", help="with --full --no-extras: keep the parity-mode leg (f16 / f32x3 / f32 timed and checked), skip configs[2] / configs[4]")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     args = ap.parse_args()
     # stdout carries the ONE JSON line and nothing else: whatever the libraries underneath print (the restore() front end mirrors the reference's
     # console messages) goes to stderr
@@ -133,6 +166,8 @@ def main():
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    if args.steps < 1 or args.warmup < 0:
+        fail(f"--steps {args.steps} --warmup {args.warmup}: a run needs at least one timed step and no negative warm-up", args.gpus, rank)
     if args.ddim_steps < 5:
         fail(f"--ddim-steps {args.ddim_steps}: the restored image is built from x0_preds[-5] (restoration.py:108), so a run needs at least 5 steps", args.gpus, rank)
     if world != args.gpus:
@@ -249,10 +284,14 @@ def main():
         gather_s, gather_bytes = time.perf_counter() - tg, gathered.numel() * gathered.element_size()
         assert gathered.shape[0] == B * world
     finite = bool(torch.isfinite(out).all())
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the restored images (all ranks' after the all-gather) and,
+        # from restore_batch(), the sampler's xs[-1] and x0_preds[-5] (rank 0's)
+        dump_outputs(args.dump_outputs, {"restored": gathered if world > 1 else out, "xs_last": xs_last, "x0_pred": x0})
 
-    # ---- roofline leg: one more pass of the SAME workload with HIP events around every conv launch
+    # ---- roofline leg (--full): one more pass of the SAME workload with HIP events around every conv launch
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         _lib.prof_enable(True)
         one_pass()
         torch.cuda.synchronize()
@@ -323,9 +362,9 @@ def main():
                                   "kernels": [{"kernel": e["kernel"], "launches": e["launches"], "avg_launch_us": round(e["ms"] / e["launches"] * 1e3, 2),
                                                "achieved": round(e["flops"] / e["ms"] / 1e9, 2), "frac": round(e["flops"] / e["ms"] / 1e9 / peak, 4)} for e in fam]}
 
-    # ---- CPU baseline leg: the oracle on this box's host cores, bounded sample (BASELINE configs[0])
+    # ---- CPU baseline leg (--full): the oracle on this box's host cores, bounded sample (BASELINE configs[0])
     cpu, cpu_sample = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "c1":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.workload == "c1":
         from oracle import wavedm_oracle as O
         nb, ns = 4, 10
         r4, xt4 = P.synthetic_batch(nb, patch_px=256, seed=61)
@@ -369,9 +408,9 @@ def main():
                              "sample": "1-step probe with every hardware thread (BASELINE.md §3 'all host cores'), scaled to the full length"}}
         cpu_sample = {"rainy": r4, "x_T": xt4, "xs_last": xs_cpu[-1], "x0_m5": x0_cpu[-5], "steps": ns}
 
-    # ---- informational legs of the default N = 1 run (driver-observed numbers instead of prose)
+    # ---- informational legs of the N = 1 run with --full (driver-observed numbers instead of prose)
     extras, parity_mode = None, None
-    if rank == 0 and world == 1 and args.workload == "c1" and (not args.no_extras or args.parity_only):
+    if rank == 0 and world == 1 and args.full and args.workload == "c1" and (not args.no_extras or args.parity_only):
         import contextlib, io
         extras = []
 

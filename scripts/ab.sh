@@ -1,10 +1,12 @@
 #!/bin/bash
-# A/B of environment-selected variants inside one gpurun call: scripts/ab.sh "VAR=a" "VAR=b" ...   (each runs bench.py briefly)
-# prints the JSON value and the per-shape lines of every variant into gpurun_out/ab_<i>.log
-mkdir -p gpurun_out
+# A/B of environment-selected variants on one box: scripts/ab.sh "VAR=a" "VAR=b" ...   (each runs bench.py --full briefly: its roofline leg prints the per-shape lines)
+# prints the JSON value of every variant; its JSON line and per-shape lines stay in $AB_OUT/ab_<i>.json / ab_<i>.log (default: a fresh temporary directory)
+OUT=${AB_OUT:-$(mktemp -d)}
+mkdir -p "$OUT"
+echo "logs in $OUT"
 i=0
 for v in "$@"; do
-  env $v python bench.py --steps 1 --warmup 1 --ddim-steps ${AB_DDIM:-20} --no-cpu-baseline ${AB_EXTRAS:---no-extras} > gpurun_out/ab_$i.json 2> gpurun_out/ab_$i.log
-  echo "== $v: $(python -c "import json,sys; d=json.loads(open('gpurun_out/ab_$i.json').read().strip().splitlines()[-1]); print(d['value'], d['unit'], d['roofline']['achieved'])")"
+  env $v python bench.py --full --steps 1 --warmup 1 --ddim-steps ${AB_DDIM:-20} --no-cpu-baseline ${AB_EXTRAS:---no-extras} > "$OUT/ab_$i.json" 2> "$OUT/ab_$i.log"
+  echo "== $v: $(python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(d['value'], d['unit'], d['roofline']['achieved'])" "$OUT/ab_$i.json")"
   i=$((i+1))
 done

@@ -100,8 +100,8 @@ def test_bench_parity_mode_is_the_fastest_conformant_mode():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--batch", "8", "--ddim-steps", "10", "--steps", "1", "--warmup", "1", "--no-extras",
-                        "--parity-only", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=repo)
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--batch", "8", "--ddim-steps", "10", "--steps", "1", "--warmup", "1", "--full",
+                        "--no-extras", "--parity-only", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     pm = line["parity_mode"]
@@ -120,3 +120,34 @@ def test_bench_parity_mode_is_the_fastest_conformant_mode():
     else:
         assert sus["peak"] == 1845.0 and line["roofline"]["frac"] < sus["frac"]
     assert line["roofline"]["traffic_source"] in ("quoted", None) and (line["roofline"]["traffic"] is None or "QUOTED" in line["roofline"]["traffic_unit"])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and runs none of the other legs; --dump-outputs writes what the last timed step
+    returned, bit for bit what restore_batch() gives on the same seeded crops and weights in this process."""
+    import json
+    import numpy as np
+    import wavedm_amd
+    from wavedm_amd import procedural as P
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--batch", "4", "--ddim-steps", "5", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["warmup"] == 0 and line["dtype"] == "bf16" and line["unit"] == "img/s" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(4 * 1e3 / line["ms_per_step"], rel=1e-2)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "parity_mode" not in line and "extras" not in line
+    assert sorted(os.listdir(out)) == ["restored.npy", "x0_pred.npy", "xs_last.npy"]
+    got = {n: np.load(out / f"{n}.npy") for n in ("restored", "xs_last", "x0_pred")}
+    assert got["restored"].shape == (4, 3, 256, 256) and got["xs_last"].shape == got["x0_pred"].shape == (4, 3, 64, 64)
+    assert all(v.dtype == np.float32 for v in got.values())
+    torch.set_grad_enabled(False)
+    cfg = P.raindrop_wavelet_config(image_size=64)
+    cfg.device = torch.device("cuda", 0)
+    args = SimpleNamespace(resume="", sampling_timesteps=5, local_rank=0, image_folder=str(tmp_path / "img"), test_set="raindrop", grid_r=16, max_batch=64)
+    d = wavedm_amd.DenoisingDiffusion_Wavelet(args, cfg, generator=lambda x: x, dtype="bf16")
+    d.model.load_state_dict(P.procedural_state_dict(cfg, seed=61), strict=True)
+    rainy, x_T = P.synthetic_batch(4, patch_px=256, seed=61)
+    want = d.restore_batch(rainy.cuda(), x_T.cuda())
+    for n, w in zip(("restored", "xs_last", "x0_pred"), want):
+        assert np.array_equal(got[n], w.float().cpu().numpy()), n

@@ -105,7 +105,7 @@ def test_bench_eight_rank_dress_rehearsal_configs3():
     train_weather_script.py:3: eight processes, one per GPU), rank 0 packs the weights, broadcast + adopt on the other seven, 64 crops per rank = BASELINE configs[3]'s
     global batch of 512, barriers and the max over ranks, the roofline leg on rank 0 while seven ranks wait, ragged-free all-gather after the clock.  gloo so that the
     eight ranks can share this box's GPU; the collectives' call sites are the ones RCCL will run."""
-    rec = _bench_ranks(8, ["--ddim-steps", "5"])            # (the shortest run that has an x0_preds[-5])
+    rec = _bench_ranks(8, ["--ddim-steps", "5", "--full"])  # (the shortest run that has an x0_preds[-5]; --full: the roofline leg)
     assert rec["n_gpus"] == 8 and rec["config"]["global_batch"] == 512 and rec["config"]["outputs_finite"] and rec["scaling"] == "weak"
     assert rec["rccl"]["rccl_ranks"] == 8 and rec["rccl"]["weight_broadcast_s"] is not None and rec["rccl"]["rank_elapsed_s_max"] >= rec["rccl"]["rank_elapsed_s_min"] > 0
     assert rec["value"] > 0 and rec["roofline"]["launches"] > 0 and rec["cpu_baseline"] is None

@@ -280,3 +280,26 @@ def test_f16_mode_layout_is_the_bf16_layout_plus_the_range_flag():
     assert HFRM(in_channel=3, dim=32, mid_blk_num=1, enc_blk_nums=[1], dec_blk_nums=[1], dtype="f16")._dtype_code == _lib.WDM_F32
     with pytest.raises(ValueError):
         wavedm_amd.DiffusionUNet(cfg, dtype="fp8")
+
+
+def test_bench_dump_outputs_keeps_the_same_rows_under_its_budget(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files; outputs over 64 MB keep a fixed, seeded sample of their rows -- the same rows in every array
+    and in every run, in order --, outputs under it are written whole."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(40, dtype=torch.float64).view(40, 1, 1, 1).expand(40, 3, 512, 512)       # 126 MB in float32, row k holds k
+    small = torch.arange(40 * 8, dtype=torch.float32).reshape(40, 8)
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), {"big": big, "small": small, "absent": None})
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "small.npy"]
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("big", "small")}
+    assert all(np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy")) for n in a)
+    assert a["big"].dtype == a["small"].dtype == np.float32
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in a) <= 64 * 1000 * 1000
+    rows = a["small"][:, 0] / 8
+    assert 0 < len(rows) < 40 and np.all(np.diff(rows) > 0) and np.array_equal(a["small"], small.numpy()[rows.astype(int)])
+    assert a["big"].shape == (len(rows), 3, 512, 512) and np.array_equal(a["big"], np.broadcast_to(rows.reshape(-1, 1, 1, 1), a["big"].shape))
+    bench.dump_outputs(str(tmp_path / "c"), {"small": small})
+    assert np.array_equal(np.load(tmp_path / "c" / "small.npy"), small.numpy())
