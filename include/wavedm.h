@@ -302,6 +302,29 @@ int wdm_trainer_adam_ema(wdm_trainer* t, int64_t step, float lr, float beta1, fl
 int wdm_trainer_set_grad_events(wdm_trainer* t, void* const* events, int n);
 int wdm_trainer_grad_buckets(const wdm_trainer* t, int64_t* bounds, int max_bounds, int* n_buckets);
 
+/* ---- HFRM training step -------------------------------------------------------------------------------
+ * Replaces the body of train_hfrm.py's loop (train_hfrm.py:240-268): HFRM forward, the back-propagated loss
+ * 2 * mean|255 out - 255 target| = 510 * mean|out - target| (the perceptual terms are commented out there) and its backward, and
+ * torch.optim.Adam with no EMA.  Exact fp32 only (cfg->dtype = WDM_F32), the reference's HFRM widths (dim 32, in_channel 3, <= 4 levels).
+ * Parameters, gradients and the Adam moments are four caller-allocated flat fp32 DEVICE buffers of wdm_hfrm_trainer_num_floats floats sharing one
+ * layout: wdm_hfrm_trainer_param_info gives name, shape and float offset of every state_dict entry, in the reference's registration order.
+ *   x (B, 3, H, W) NCHW f32, H and W multiples of 16; pass exactly one of target (B, 3, H, W) -- the reference loss, *loss (device float) is
+ *   written -- or dy (B, 3, H, W), an upstream gradient of the output (the loss is not computed, loss may be NULL).  The step writes every entry of
+ *   the gradient buffer (not accumulated); out (optional, B x 3 x H x W) receives the forward output.  Deterministic: no float atomics.
+ *   wdm_hfrm_trainer_workspace_bytes: the exact workspace of a step at (B, H, W) (a dry run of the step's allocations); 0 on a bad shape. */
+typedef struct wdm_hfrm_trainer wdm_hfrm_trainer;
+int wdm_hfrm_trainer_create(wdm_handle* h, const wdm_hfrm_config* cfg, wdm_hfrm_trainer** out);
+int wdm_hfrm_trainer_destroy(wdm_hfrm_trainer* t);
+int wdm_hfrm_trainer_num_params(const wdm_hfrm_trainer* t);
+int64_t wdm_hfrm_trainer_num_floats(const wdm_hfrm_trainer* t);
+int wdm_hfrm_trainer_param_info(const wdm_hfrm_trainer* t, int i, const char** name, int* ndim, int64_t shape[4], int64_t* offset);
+int wdm_hfrm_trainer_set_buffers(wdm_hfrm_trainer* t, float* params, float* grads, float* m, float* v);
+size_t wdm_hfrm_trainer_workspace_bytes(const wdm_hfrm_trainer* t, int B, int H, int W);
+int wdm_hfrm_trainer_step(wdm_hfrm_trainer* t, const float* x, const float* target, const float* dy, int B, int H, int W, float* loss, float* out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* the betas are doubles: torch forms 1 - beta and the bias corrections from the Python floats (an fp32 0.999 puts 1 - beta2 1.3e-5 off) */
+int wdm_hfrm_trainer_adam(wdm_hfrm_trainer* t, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay, void* stream);
+
 /* ---- live kernel timing (bench.py roofline leg) ----------------------------------------------
  * While enabled, every convolution launch is bracketed by two HIP events on its own stream and
  * tagged with its algorithmic flops (2*M*N*K) and bytes (input + weights + output once).

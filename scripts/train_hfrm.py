@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""Stage 1 of the reference's training recipe (train_hfrm.py): train the HFRM on the MI355X and write the checkpoint that stage 2
+(`wavedm_run.py train`) and `restore()` load.
+
+    python scripts/train_hfrm.py --data_dir <data> [--n_epochs 800 --batch_size 8 ...]
+
+Reads <data_dir>/<dataset_name>/train/{input,gt} (the reference's myImageFloder layout), trains from weights_init_normal (or, with
+--epoch N > 0, from <save_dir>/<dataset_name>/best.pth, weights only) with the reference's loss 2 * mean|255 out - 255 gt|, Adam
+(b1, b2) and lr = lr * 0.5 ** (step / 100000), and writes <save_dir>/<dataset_name>/lastest.pth every epoch and best.pth whenever the
+epoch PSNR beats the best so far.  Both hold the plain state_dict.  The forward, backward and Adam run on libwavedm_hip.so
+(wavedm_amd.HFRMTrainer); there is no torch autograd and no CPU path."""
+import argparse
+import datetime
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from wavedm_amd import datasets                                     # noqa: E402
+from wavedm_amd.hfrm_training import HFRM_DEFAULTS, HFRMTrainer     # noqa: E402
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--epoch", type=int, default=0, help="epoch to start training from (> 0: resume the weights of <save_dir>/<dataset_name>/best.pth)")
+    p.add_argument("--n_epochs", type=int, default=800, help="number of epochs of training")
+    p.add_argument("--dataset_name", type=str, default="raindrop", help="name of the dataset")
+    p.add_argument("--batch_size", type=int, default=8, help="size of the batches")
+    p.add_argument("--lr", type=float, default=0.0002,
+                   help="base of the learning-rate schedule lr * 0.5 ** (step / 100000) (the reference hard-codes 0.0002 there and ignores this flag)")
+    p.add_argument("--b1", type=float, default=0.5, help="adam: decay of first order momentum of gradient")
+    p.add_argument("--b2", type=float, default=0.999, help="adam: decay of second order momentum of gradient")
+    p.add_argument("--n_cpu", type=int, default=8, help="number of data loader workers")
+    p.add_argument("--data_dir", type=str, default=".", help="directory that holds <dataset_name>/train/{input,gt}")
+    p.add_argument("--save_dir", type=str, default="saved_models", help="checkpoints go to <save_dir>/<dataset_name>/{lastest,best}.pth")
+    p.add_argument("--max_steps", type=int, default=0, help="stop after this many optimizer steps (0: run all epochs)")
+    p.add_argument("--best_psnr", type=float, default=31.0, help="epoch PSNR best.pth has to beat first (the reference starts at 31)")
+    p.add_argument("--seed", type=int, default=0, help="seed of the conv biases' default init")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    opt = parse_args(argv)
+    print(opt)
+    out_dir = os.path.join(opt.save_dir, opt.dataset_name)
+    os.makedirs(out_dir, exist_ok=True)
+    trainer = HFRMTrainer(**HFRM_DEFAULTS, lr=opt.lr, betas=(opt.b1, opt.b2))
+    print("HFRM parameters:", sum(int(np.prod(s)) for _, s in trainer.layout.values()))
+    if opt.epoch != 0:
+        trainer.load_state_dict(torch.load(os.path.join(out_dir, "best.pth"), map_location="cpu"), strict=True)
+    else:
+        trainer.init_reference(opt.seed)
+    loader = datasets.hfrm_train_loader(os.path.join(opt.data_dir, opt.dataset_name, "train"), batch_size=opt.batch_size, num_workers=opt.n_cpu)
+    print("data loader finish!")
+    best_psnr = opt.best_psnr
+    prev_time = time.time()
+    done = False
+    for epoch in range(opt.epoch, opt.n_epochs):
+        epoch_psnr = []
+        for i, (real_A, real_B) in enumerate(loader):
+            real_A = real_A.to(trainer.device, non_blocking=True)
+            real_B = real_B.to(trainer.device, non_blocking=True)
+            loss, psnr = trainer.train_step(real_A, real_B)
+            epoch_psnr.append(psnr.mean().item())
+            print("PSNR this: %f", epoch_psnr[-1])
+            batches_done = epoch * len(loader) + i
+            batches_left = opt.n_epochs * len(loader) - batches_done
+            time_left = datetime.timedelta(seconds=batches_left * (time.time() - prev_time))
+            prev_time = time.time()
+            if i % 100 == 0:
+                lv = loss.item()
+                print("G loss: %f", lv)
+                sys.stdout.write("\r[Epoch %d/%d] [Batch %d/%d] [G loss: %f, pixel: %f] ETA: %s" %
+                                 (epoch, opt.n_epochs, i, len(loader), lv, lv / 510.0, time_left))
+            if opt.max_steps and trainer.step >= opt.max_steps:
+                done = True
+                break
+        print("epoch PSNR: %f, best psnr:%f" % (np.mean(epoch_psnr), best_psnr))
+        if np.mean(epoch_psnr) > best_psnr:
+            best_psnr = np.mean(epoch_psnr)
+            trainer.save(os.path.join(out_dir, "best.pth"))
+        trainer.save(os.path.join(out_dir, "lastest.pth"))
+        if done:
+            break
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -11,10 +11,11 @@ from .arch import HFRM
 from .ddm_wavelet import DenoisingDiffusion_Wavelet, data_transform, inverse_data_transform
 from .restoration import DiffusiveRestoration, torchPSNR
 from .sampling import get_beta_schedule, compute_alpha, overlapping_grid_indices, ddim_sample
-from .datasets import RainDrop, RainDropDataset
+from .datasets import RainDrop, RainDropDataset, HFRMImageFolder
 from .imageio import AsyncImageWriter
 from .training import Trainer
+from .hfrm_training import HFRMTrainer
 
 __all__ = ["WaveletTransform", "DiffusionUNet", "DiffusionUNet_Global", "DenoisingDiffusion_Wavelet", "DiffusiveRestoration",
            "data_transform", "inverse_data_transform", "torchPSNR", "get_beta_schedule", "compute_alpha",
-           "overlapping_grid_indices", "ddim_sample", "HFRM", "RainDrop", "RainDropDataset", "AsyncImageWriter", "Trainer"]
+           "overlapping_grid_indices", "ddim_sample", "HFRM", "RainDrop", "RainDropDataset", "HFRMImageFolder", "AsyncImageWriter", "Trainer", "HFRMTrainer"]

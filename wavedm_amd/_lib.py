@@ -112,6 +112,15 @@ def lib():
         "wdm_trainer_adam_ema": (i, [vp, i64, f, f, f, f, f, f, vp]),
         "wdm_trainer_set_grad_events": (i, [vp, C.POINTER(vp), i]),
         "wdm_trainer_grad_buckets": (i, [vp, C.POINTER(i64), i, C.POINTER(i)]),
+        "wdm_hfrm_trainer_create": (i, [vp, C.POINTER(HFRMConfig), C.POINTER(vp)]),
+        "wdm_hfrm_trainer_destroy": (i, [vp]),
+        "wdm_hfrm_trainer_num_params": (i, [vp]),
+        "wdm_hfrm_trainer_num_floats": (i64, [vp]),
+        "wdm_hfrm_trainer_param_info": (i, [vp, i, C.POINTER(C.c_char_p), C.POINTER(i), C.POINTER(i64 * 4), C.POINTER(i64)]),
+        "wdm_hfrm_trainer_set_buffers": (i, [vp, vp, vp, vp, vp]),
+        "wdm_hfrm_trainer_workspace_bytes": (sz, [vp, i, i, i]),
+        "wdm_hfrm_trainer_step": (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]),
+        "wdm_hfrm_trainer_adam": (i, [vp, i64, f, C.c_double, C.c_double, f, f, vp]),
         "wdm_dwt_fwd_affine": (i, [vp, vp, f, f, vp, i, i, i, vp]),
         "wdm_dwt_inv_compose": (i, [vp, vp, i, i, vp, vp, i, i, i, i, vp]),
         "wdm_conv2d_direct": (i, [vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, vp, vp]),
@@ -140,7 +149,8 @@ EXPORTED = ["wdm_abi_version", "wdm_last_error", "wdm_create", "wdm_destroy", "w
             "wdm_hfrm_create", "wdm_hfrm_destroy", "wdm_hfrm_num_params", "wdm_hfrm_param_info", "wdm_hfrm_packed_bytes",
             "wdm_hfrm_set_packed", "wdm_hfrm_load_param", "wdm_hfrm_finalize", "wdm_hfrm_workspace_bytes",
             "wdm_hfrm_forward", "wdm_image_sqdiff", "wdm_to_u8_hwc", "wdm_conv_backward", "wdm_gn_act_backward", "wdm_trainer_create", "wdm_trainer_destroy", "wdm_trainer_num_params",
-            "wdm_trainer_num_floats", "wdm_trainer_param_info", "wdm_trainer_set_buffers", "wdm_trainer_set_objective", "wdm_trainer_step", "wdm_trainer_adam_ema", "wdm_trainer_set_grad_events", "wdm_trainer_grad_buckets", "wdm_dwt_fwd_affine", "wdm_dwt_inv_compose", "wdm_conv2d_direct", "wdm_groupnorm", "wdm_cross_attention", "wdm_upsample_add",
+            "wdm_trainer_num_floats", "wdm_trainer_param_info", "wdm_trainer_set_buffers", "wdm_trainer_set_objective", "wdm_trainer_step", "wdm_trainer_adam_ema", "wdm_trainer_set_grad_events", "wdm_trainer_grad_buckets", "wdm_hfrm_trainer_create", "wdm_hfrm_trainer_destroy", "wdm_hfrm_trainer_num_params", "wdm_hfrm_trainer_num_floats",
+            "wdm_hfrm_trainer_param_info", "wdm_hfrm_trainer_set_buffers", "wdm_hfrm_trainer_workspace_bytes", "wdm_hfrm_trainer_step", "wdm_hfrm_trainer_adam", "wdm_dwt_fwd_affine", "wdm_dwt_inv_compose", "wdm_conv2d_direct", "wdm_groupnorm", "wdm_cross_attention", "wdm_upsample_add",
             "wdm_prof_enable", "wdm_prof_report", "wdm_env_refresh", "wdm_set_concurrent_streams"]
 
 

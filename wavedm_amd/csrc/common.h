@@ -286,6 +286,10 @@ int conv_wgrad(Ctx& c, int mode, const Tens& x0, const Tens* x1, const Tens& dy,
 int colsum(Ctx& c, const Tens& dy, float* out, bool per_image, bool accumulate, int out_ld = 0);
 int gn_act_backward(Ctx& c, const NormW& nw, const Tens& x0, const Tens* x1, const float* mean_rstd, const Tens& dy, int silu, void* dx0, bool acc0, void* dx1,
                     bool acc1, float* dgamma, float* dbeta, bool acc_param);
+// torch.optim.Adam (amsgrad = False) over n floats + EMAHelper.update when E != nullptr (train_unet.hip); step counts from 1.  The betas are
+// doubles: 1 - beta and the bias corrections are formed before rounding to fp32 (an fp32 0.999 leaves 1 - beta2 1.3e-5 off torch's value)
+int k_adam_ema(float* P, const float* G, float* M, float* V, float* E, long long n, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay,
+               float ema_mu, hipStream_t s);
 
 }  // namespace wdm
 

@@ -1,0 +1,1029 @@
+// HFRM training step (reference: train_hfrm.py:254-268 over models/arch.py:132-253): a training forward that keeps what the
+// backward needs, the backward of every layer, the reference's loss 2 * mean|255 out - 255 target| = 510 * mean|out - target|, and
+// Adam without EMA (train_unet.hip's update, k_adam_ema with no shadow) over one flat fp32 parameter / gradient / moment buffer set.  Exact fp32 only.
+//
+// Contractions reuse the existing primitives: every 1x1 conv (and the 2x2 stride-2 `downs`, after a space-to-depth gather) runs
+// forward AND dgrad on the MFMA conv kernel as a GEMM over the flattened pixels (MODE_P1, the path wdm_hfrm::gemm_rows drives: no
+// H / W constraint, the rows are a 16-wide grid with m_valid); dgrad reads the weights packed transposed ([K][cout]).  Weight
+// gradients are conv_wgrad (mode 3, train.hip: gather to channel-major + batched pixel-contraction GEMM + fixed-order reduction),
+// bias gradients colsum (train.hip).  conv_out's forward is run_conv (MODE_S1) as in the inference forward.  The rest -- LayerNorm2d,
+// depthwise 3x3 + gate, channel attention, beta / gamma, PixelShuffle, conv_in / conv_out's small-channel backward, the loss -- are the
+// kernels below.  Every reduction is two-stage in a fixed order: no float atomics, two identical steps give identical bits.
+//
+// Unlike the inference pack (hfrm.hip: finalize), beta / gamma are NOT folded into conv3 / conv5: d beta = sum dy * conv3(.) needs
+// the unscaled output, and beta = 0 at the reference's initialisation (models/model_dense.py:157-168).
+//
+// Saved per ResidualBlock (NHWC f32, M = B*H*W pixels, d channels): a1 = conv1 out (2d), a2 = depthwise out before the gate (2d),
+// c3 = conv3 out (d), y = x + beta*c3 (d), a4 = conv4 out (2d), c5 = conv5 out (d), the block output (d), pooled / channel scale
+// (B x d): 10 d floats per pixel.  Recomputed in the backward: both LayerNorm outputs and both gate outputs.
+#include <math.h>
+
+#include <algorithm>
+#include <map>
+#include <string>
+
+#include "common.h"
+
+namespace hft {
+using namespace wdm;
+
+static inline int gridn(long long n, int bs) { long long g = (n + bs - 1) / bs; return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g)); }
+static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+#define GS_LOOP(id, n) for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < (n); id += (long long)gridDim.x * blockDim.x)
+
+__device__ __forceinline__ float team_sum(float v) {      // sum over the 32 lanes of a half wave
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// ---- LayerNorm2d (arch.py:7-43), a team of 32 lanes per pixel, channel c = lane + 32 j --------------------------------
+constexpr int LN_TEAMS = 8;
+template <int NJ>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long long M, const float* __restrict__ w,
+                                                     const float* __restrict__ b) {
+    constexpr int C = 32 * NJ;
+    const int lane = threadIdx.x & 31;
+    for (long long p = (long long)blockIdx.x * LN_TEAMS + (threadIdx.x >> 5); p < M; p += (long long)gridDim.x * LN_TEAMS) {
+        float f[NJ], s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { f[j] = x[p * C + lane + 32 * j]; s += f[j]; }
+        const float mu = team_sum(s) / (float)C;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { const float dd = f[j] - mu; q += dd * dd; }
+        const float rstd = 1.0f / sqrtf(team_sum(q) / (float)C + 1e-6f);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { const int c = lane + 32 * j; y[p * C + c] = (f[j] - mu) * rstd * w[c] + b[c]; }
+    }
+}
+
+// LayerNormFunction.backward (arch.py:19-31): g = dn w, dx = rstd (g - xh mean(g xh) - mean(g)); dx = dres + that (dres may alias dx);
+// part[block][0][C] = sum dn xh, part[block][1][C] = sum dn over the block's pixels (teams joined in ascending order)
+template <int NJ>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dn, const float* __restrict__ w, const float* dres,
+                                                     float* dx, long long M, float* __restrict__ part) {
+    constexpr int C = 32 * NJ;
+    __shared__ float red[LN_TEAMS][2][C];
+    const int lane = threadIdx.x & 31, team = threadIdx.x >> 5;
+    float aw[NJ], ab[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { aw[j] = 0.f; ab[j] = 0.f; }
+    for (long long p = (long long)blockIdx.x * LN_TEAMS + team; p < M; p += (long long)gridDim.x * LN_TEAMS) {
+        float f[NJ], g[NJ], s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { f[j] = x[p * C + lane + 32 * j]; s += f[j]; }
+        const float mu = team_sum(s) / (float)C;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { const float dd = f[j] - mu; q += dd * dd; }
+        const float rstd = 1.0f / sqrtf(team_sum(q) / (float)C + 1e-6f);
+        float sg = 0.f, sgy = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = lane + 32 * j;
+            const float d = dn[p * C + c];
+            f[j] = (f[j] - mu) * rstd;                      // xh
+            g[j] = d * w[c];
+            sg += g[j]; sgy += g[j] * f[j];
+            aw[j] += d * f[j]; ab[j] += d;
+        }
+        const float mg = team_sum(sg) / (float)C, mgy = team_sum(sgy) / (float)C;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const long long i = p * C + lane + 32 * j;
+            dx[i] = dres[i] + rstd * (g[j] - f[j] * mgy - mg);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { red[team][0][lane + 32 * j] = aw[j]; red[team][1][lane + 32 * j] = ab[j]; }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * C; i += 256) {
+        const int k = i / C, c = i % C;
+        float s = 0.f;
+        for (int t = 0; t < LN_TEAMS; ++t) s += red[t][k][c];
+        part[(long long)blockIdx.x * 2 * C + i] = s;
+    }
+}
+
+// ---- per-channel sums: part[(b * nk + k) * C + c] = sum over chunk k of image b of a[p][c] (* m[p][c]) ---------------------------
+// grid (nk, B, ceil(C / 256)); 256 threads = (channels) x (pixel rows); rows joined in ascending order
+__global__ __launch_bounds__(256) void chan_part_kernel(const float* __restrict__ a, const float* __restrict__ m, int C, int HW, int chunk, int nk,
+                                                        float* __restrict__ part) {
+    __shared__ float red[256];
+    const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
+    const int cols = min(C - cb * 256, 256), rows = 256 / cols;
+    const int col = threadIdx.x % cols, r = threadIdx.x / cols, c = cb * 256 + col;
+    float s = 0.f;
+    if (r < rows) {
+        const int p1 = min((k + 1) * chunk, HW);
+        for (int p = k * chunk + r; p < p1; p += rows) {
+            const long long i = ((long long)b * HW + p) * C + c;
+            s += m ? a[i] * m[i] : a[i];
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (r == 0) {
+        for (int rr = 1; rr < rows; ++rr) s += red[rr * cols + col];
+        part[((long long)b * nk + k) * C + c] = s;
+    }
+}
+// out = scale * sum of the partial rows, images and chunks ascending.  per_image: one output row per image (o0[b][c]); else the
+// batch sum, channels [0, split) to o0 and [split, C) to o1 (the LayerNorm weight / bias pair)
+__global__ __launch_bounds__(256) void chan_final_kernel(const float* __restrict__ part, int B, int nk, int C, int per_image, float scale, float* __restrict__ o0,
+                                                         float* __restrict__ o1, int split) {
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    const int groups = per_image ? B : 1;
+    if (id >= groups * C) return;
+    const int g = id / C, c = id % C;
+    float s = 0.f;
+    for (int b = per_image ? g : 0; b < (per_image ? g + 1 : B); ++b)
+        for (int k = 0; k < nk; ++k) s += part[((long long)b * nk + k) * C + c];
+    s *= scale;
+    if (per_image) o0[(long long)g * C + c] = s;
+    else if (c < split) o0[c] = s;
+    else o1[c - split] = s;
+}
+
+// ---- elementwise ----------------------------------------------------------------------------------------------------------
+// SimpleGate (arch.py:132-141): g[p][c] = a[p][c] * a[p][d + c]  (* sc[b][c] when sc is given)
+__global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ a, float* __restrict__ g, long long n, int d, const float* __restrict__ sc, int HW) {
+    GS_LOOP(id, n) {
+        const long long p = id / d;
+        const int c = (int)(id % d);
+        float v = a[p * 2 * d + c] * a[p * 2 * d + d + c];
+        if (sc) v *= sc[(p / HW) * d + c];
+        g[id] = v;
+    }
+}
+__global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__ dg, const float* __restrict__ a, float* __restrict__ da, long long n, int d) {
+    GS_LOOP(id, n) {
+        const long long p = id / d;
+        const int c = (int)(id % d);
+        const float g = dg[id];
+        da[p * 2 * d + c] = g * a[p * 2 * d + d + c];
+        da[p * 2 * d + d + c] = g * a[p * 2 * d + c];
+    }
+}
+// out[p][c] = x[p][c] + s[c] * v[p][c]   (x == nullptr: s[c] * v[p][c])
+__global__ __launch_bounds__(256) void axpy_chan_kernel(const float* __restrict__ x, const float* __restrict__ s, const float* __restrict__ v, float* __restrict__ out,
+                                                        long long n, int C) {
+    GS_LOOP(id, n) {
+        const float t = s[id % C] * v[id];
+        out[id] = x ? x[id] + t : t;
+    }
+}
+// channel attention backward, pixel side: dg = dgs * sc[b][c] + dpool[b][c] / HW (in place)
+__global__ __launch_bounds__(256) void ca_dg_kernel(float* __restrict__ dg, const float* __restrict__ sc, const float* __restrict__ dpool, long long n, int d, int HW,
+                                                    float inv_hw) {
+    GS_LOOP(id, n) {
+        const int c = (int)(id % d);
+        const long long b = id / d / HW;
+        dg[id] = dg[id] * sc[b * d + c] + dpool[b * d + c] * inv_hw;
+    }
+}
+// channel attention backward, vector side (sc = W pooled + bias, B x d): dW[o][i] = sum_b dsc[b][o] pooled[b][i], db[o] = sum_b dsc[b][o],
+// dpool[b][i] = sum_o W[o][i] dsc[b][o]
+__global__ __launch_bounds__(256) void ca_bwd_kernel(const float* __restrict__ dsc, const float* __restrict__ pooled, const float* __restrict__ W, int B, int d,
+                                                     float* __restrict__ dW, float* __restrict__ db, float* __restrict__ dpool) {
+    const long long n0 = (long long)d * d, n1 = n0 + d, n2 = n1 + (long long)B * d;
+    GS_LOOP(id, n2) {
+        if (id < n0) {
+            const int o = (int)(id / d), i = (int)(id % d);
+            float s = 0.f;
+            for (int b = 0; b < B; ++b) s += dsc[b * d + o] * pooled[b * d + i];
+            dW[id] = s;
+        } else if (id < n1) {
+            const int o = (int)(id - n0);
+            float s = 0.f;
+            for (int b = 0; b < B; ++b) s += dsc[b * d + o];
+            db[o] = s;
+        } else {
+            const int b = (int)((id - n1) / d), i = (int)((id - n1) % d);
+            float s = 0.f;
+            for (int o = 0; o < d; ++o) s += W[o * d + i] * dsc[b * d + o];
+            dpool[b * d + i] = s;
+        }
+    }
+}
+
+// ---- depthwise 3x3, pad 1, on C channels (ResidualBlock.conv2, groups = 2d): forward, dgrad, wgrad ---------------------------
+__global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W, int C, long long n, const float* __restrict__ w,
+                                                     const float* __restrict__ bias) {
+    GS_LOOP(id, n) {
+        const int c = (int)(id % C);
+        const long long p = id / C;
+        const int px = (int)(p % W), py = (int)((p / W) % H);
+        const long long img = p - (long long)py * W - px;
+        float s = bias[c];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) s += x[(img + (long long)yy * W + xx) * C + c] * w[c * 9 + t];
+        }
+        y[id] = s;
+    }
+}
+// dx[q][c] = sum_t w[c][t] dy[q - (t / 3 - 1, t % 3 - 1)][c]
+__global__ __launch_bounds__(256) void dw_dgrad_kernel(const float* __restrict__ dy, float* __restrict__ dx, int H, int W, int C, long long n, const float* __restrict__ w) {
+    GS_LOOP(id, n) {
+        const int c = (int)(id % C);
+        const long long p = id / C;
+        const int px = (int)(p % W), py = (int)((p / W) % H);
+        const long long img = p - (long long)py * W - px;
+        float s = 0.f;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int yy = py - (t / 3 - 1), xx = px - (t % 3 - 1);
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) s += dy[(img + (long long)yy * W + xx) * C + c] * w[c * 9 + t];
+        }
+        dx[id] = s;
+    }
+}
+// part[(b * nk + k)][c][10]: sum over chunk k of image b of dy[p][c] x[p + tap][c] (taps 0..8) and of dy[p][c] (slot 9)
+__global__ __launch_bounds__(256) void dw_wgrad_part_kernel(const float* __restrict__ dy, const float* __restrict__ x, int H, int W, int C, int chunk, int nk,
+                                                            float* __restrict__ part) {
+    __shared__ float red[256 * 10];
+    const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
+    const int HW = H * W;
+    const int cols = min(C - cb * 256, 256), rows = 256 / cols;
+    const int col = threadIdx.x % cols, r = threadIdx.x / cols, c = cb * 256 + col;
+    float acc[10];
+#pragma unroll
+    for (int t = 0; t < 10; ++t) acc[t] = 0.f;
+    if (r < rows) {
+        const long long img = (long long)b * HW;
+        const int p1 = min((k + 1) * chunk, HW);
+        for (int p = k * chunk + r; p < p1; p += rows) {
+            const int py = p / W, px = p - py * W;
+            const float g = dy[(img + p) * C + c];
+            acc[9] += g;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) acc[t] += g * x[(img + (long long)yy * W + xx) * C + c];
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 10; ++t) red[threadIdx.x * 10 + t] = acc[t];
+    __syncthreads();
+    if (r == 0) {
+        for (int rr = 1; rr < rows; ++rr)
+#pragma unroll
+            for (int t = 0; t < 10; ++t) acc[t] += red[(rr * cols + col) * 10 + t];
+#pragma unroll
+        for (int t = 0; t < 10; ++t) part[(((long long)b * nk + k) * C + c) * 10 + t] = acc[t];
+    }
+}
+__global__ __launch_bounds__(256) void dw_wgrad_final_kernel(const float* __restrict__ part, int nparts, int C, float* __restrict__ dw, float* __restrict__ db) {
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= C * 10) return;
+    float s = 0.f;
+    for (int k = 0; k < nparts; ++k) s += part[(long long)k * C * 10 + id];
+    const int c = id / 10, t = id % 10;
+    if (t < 9) dw[c * 9 + t] = s;
+    else db[c] = s;
+}
+
+// ---- 2x2 stride-2 conv (downs) and PixelShuffle(2) (ups) --------------------------------------------------------------------
+// space-to-depth: u[b][y][x][(i*2+j)*d + c] = x[b][2y+i][2x+j][c]; add != 0: the adjoint, x[...] += u[...]
+__global__ __launch_bounds__(256) void unshuffle2_kernel(float* __restrict__ x, float* __restrict__ u, int B, int H, int W, int d, int add) {
+    const int h2 = H / 2, w2 = W / 2;
+    const long long n = (long long)B * h2 * w2 * 4 * d;
+    GS_LOOP(id, n) {
+        const int c = (int)(id % d);
+        const int ij = (int)((id / d) % 4);
+        const long long op = id / (4 * d);
+        const int ox = (int)(op % w2), oy = (int)((op / w2) % h2);
+        const long long b = op / ((long long)w2 * h2);
+        const long long xi = ((b * H + 2 * oy + (ij >> 1)) * W + 2 * ox + (ij & 1)) * d + c;
+        if (add) x[xi] += u[id];
+        else u[id] = x[xi];
+    }
+}
+// forward: out[b][2y+i][2x+j][c] = p[b][y][x][c*4 + i*2 + j] + skip[...];  adjoint: dp[b][y][x][c*4 + i*2 + j] = dout[b][2y+i][2x+j][c]
+__global__ __launch_bounds__(256) void pixel_shuffle_kernel(const float* __restrict__ p, const float* __restrict__ skip, float* __restrict__ out, int B, int h, int w,
+                                                            int dout) {
+    const long long n = (long long)B * 4 * h * w * dout;
+    GS_LOOP(id, n) {
+        const int c = (int)(id % dout);
+        const long long op = id / dout;
+        const int X = (int)(op % (2 * w)), Y = (int)((op / (2 * w)) % (2 * h));
+        const long long b = op / ((long long)4 * w * h);
+        out[id] = p[((b * h + (Y >> 1)) * w + (X >> 1)) * (4LL * dout) + c * 4 + (Y & 1) * 2 + (X & 1)] + skip[id];
+    }
+}
+__global__ __launch_bounds__(256) void pixel_unshuffle_kernel(const float* __restrict__ dout, float* __restrict__ dp, int B, int h, int w, int dch) {
+    const long long n = (long long)B * h * w * 4 * dch;
+    GS_LOOP(id, n) {
+        const int k = (int)(id % (4 * dch));
+        const long long q = id / (4 * dch);
+        const int x = (int)(q % w), y = (int)((q / w) % h);
+        const long long b = q / ((long long)w * h);
+        const int c = k >> 2, i = (k >> 1) & 1, j = k & 1;
+        dp[id] = dout[((b * 2 * h + 2 * y + i) * (2 * w) + 2 * x + j) * dch + c];
+    }
+}
+// GEMM-order weight gradient [cout][(i*2+j)*cin + c] -> OIHW [cout][cin][2][2]
+__global__ __launch_bounds__(256) void permute_down_grad_kernel(const float* __restrict__ g, float* __restrict__ dw, int cout, int cin, int kk) {
+    const long long n = (long long)cout * cin * kk;
+    GS_LOOP(id, n) {
+        const int ij = (int)(id % kk);
+        const int c = (int)((id / kk) % cin);
+        const long long o = id / ((long long)kk * cin);
+        dw[id] = g[o * cin * kk + (long long)ij * cin + c];
+    }
+}
+// OIHW [cout][cin][k][k] f32 -> GEMM matrix, K index kc = (i*k + j) * cin + c:  forward [rows][K] (rows >= cout zero) or transposed
+// [rows][cout] (row = kc, rows >= K zero): the dgrad GEMM's weights
+__global__ __launch_bounds__(256) void pack_gemm_kernel(const float* __restrict__ w, int cout, int cin, int kk, int transposed, float* __restrict__ dst, int rows) {
+    const int K = cin * kk;
+    const long long n = (long long)rows * (transposed ? cout : K);
+    GS_LOOP(id, n) {
+        int o, kc;
+        if (transposed) { kc = (int)(id / cout); o = (int)(id % cout); }
+        else { o = (int)(id / K); kc = (int)(id % K); }
+        float v = 0.f;
+        if (o < cout && kc < K) v = w[((long long)o * cin + kc % cin) * kk + kc / cin];
+        dst[id] = v;
+    }
+}
+
+// ---- conv_in (3 -> 32, 3x3) forward on the NCHW image, as in the inference forward (hfrm.hip) -----------------------------------
+template <int DIM>
+__global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int cin, const float* __restrict__ w,
+                                                      const float* __restrict__ bias) {
+    __shared__ float ws[16 * 9 * DIM + DIM];
+    for (int i = threadIdx.x; i < cin * 9 * DIM; i += 256) {
+        const int co = i % DIM, k = i / DIM;
+        ws[i] = w[(long long)co * cin * 9 + k];
+    }
+    for (int i = threadIdx.x; i < DIM; i += 256) ws[cin * 9 * DIM + i] = bias[i];
+    __syncthreads();
+    const long long M = (long long)B * H * W;
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= M) return;
+    const int px = (int)(pix % W), py = (int)((pix / W) % H);
+    const long long b = pix / ((long long)W * H);
+    float acc[DIM];
+#pragma unroll
+    for (int o = 0; o < DIM; ++o) acc[o] = ws[cin * 9 * DIM + o];
+    for (int ci = 0; ci < cin; ++ci) {
+        const float* xp = x + (b * cin + ci) * H * W;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+            const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
+            const float v = in ? xp[(long long)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)] : 0.f;
+            const float* wr = ws + (ci * 9 + t) * DIM;
+#pragma unroll
+            for (int o = 0; o < DIM; ++o) acc[o] += v * wr[o];
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < DIM; ++o) y[pix * DIM + o] = acc[o];
+}
+
+// conv_out (DIM -> NC, 3x3 pad 1) dgrad: dt[q][ci] = sum_{co, tap} w[co][ci][tap] dy[b][co][q - tap offset]  (dy NCHW, dt NHWC)
+template <int DIM, int NC>
+__global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dt, int B, int H, int W) {
+    __shared__ float ws[NC * DIM * 9];
+    for (int i = threadIdx.x; i < NC * DIM * 9; i += 256) ws[i] = w[i];
+    __syncthreads();
+    const long long M = (long long)B * H * W;
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= M) return;
+    const int px = (int)(pix % W), py = (int)((pix / W) % H);
+    const long long b = pix / ((long long)W * H);
+    float acc[DIM];
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) acc[i] = 0.f;
+    for (int co = 0; co < NC; ++co) {
+        const float* dp = dy + (b * NC + co) * H * W;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int yy = py - (t / 3 - 1), xx = px - (t % 3 - 1);
+            if ((unsigned)yy >= (unsigned)H || (unsigned)xx >= (unsigned)W) continue;
+            const float v = dp[(long long)yy * W + xx];
+#pragma unroll
+            for (int ci = 0; ci < DIM; ++ci) acc[ci] += v * ws[(co * DIM + ci) * 9 + t];
+        }
+    }
+#pragma unroll
+    for (int ci = 0; ci < DIM; ++ci) dt[pix * DIM + ci] = acc[ci];
+}
+
+// Weight gradient of a 3x3 pad-1 conv between a DIM-channel NHWC map A ("wide") and an NC-channel NCHW map N ("narrow"):
+//   S[c][n][tap] = sum_q A[q][c] N[n][q + sgn * tap offset]   (0 outside the map),  plus sum_q A[q][c] and sum_q N[n][q].
+//   conv_in:  A = dy (co), N = x (ci), sgn = +1  ->  dW[co][ci][tap], bias = sum A
+//   conv_out: A = t (ci),  N = dy (co), sgn = -1 ->  dW[co][ci][tap], bias = sum N
+// part[blk][DIM * NC * 9 + DIM + NC] over a chunk of pixels per workgroup; 256 threads = DIM channels x (256 / DIM) pixel rows
+template <int DIM, int NC>
+__global__ __launch_bounds__(256) void wgrad3_small_part_kernel(const float* __restrict__ A, const float* __restrict__ Nn, int B, int H, int W, int sgn, int chunk,
+                                                                float* __restrict__ part) {
+    constexpr int ROWS = 256 / DIM, NA = NC * 9 + 1 + NC, NOUT = DIM * NC * 9 + DIM + NC;
+    __shared__ float red[256 * NA];
+    const int c = threadIdx.x % DIM, r = threadIdx.x / DIM;
+    const long long HW = (long long)H * W, M = B * HW;
+    float acc[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) acc[i] = 0.f;
+    const long long p0 = (long long)blockIdx.x * chunk, p1 = p0 + chunk < M ? p0 + chunk : M;
+    for (long long p = p0 + r; p < p1; p += ROWS) {
+        const int px = (int)(p % W), py = (int)((p / W) % H);
+        const long long b = p / HW;
+        const float a = A[p * DIM + c];
+        acc[NC * 9] += a;
+#pragma unroll
+        for (int n = 0; n < NC; ++n) {
+            const float* np = Nn + (b * NC + n) * HW;
+            acc[NC * 9 + 1 + n] += np[(long long)py * W + px];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = py + sgn * (t / 3 - 1), xx = px + sgn * (t % 3 - 1);
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) acc[n * 9 + t] += a * np[(long long)yy * W + xx];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NA; ++i) red[threadIdx.x * NA + i] = acc[i];
+    __syncthreads();
+    for (int o = threadIdx.x; o < NOUT; o += 256) {
+        float s = 0.f;
+        if (o < DIM * NC * 9) {
+            const int cc = o / (NC * 9), k = o % (NC * 9);
+            for (int rr = 0; rr < ROWS; ++rr) s += red[(rr * DIM + cc) * NA + k];
+        } else if (o < DIM * NC * 9 + DIM) {
+            const int cc = o - DIM * NC * 9;
+            for (int rr = 0; rr < ROWS; ++rr) s += red[(rr * DIM + cc) * NA + NC * 9];
+        } else {
+            const int n = o - DIM * NC * 9 - DIM;
+            for (int rr = 0; rr < ROWS; ++rr) s += red[(rr * DIM) * NA + NC * 9 + 1 + n];      // every channel lane summed the same values: lane 0's
+        }
+        part[(long long)blockIdx.x * NOUT + o] = s;
+    }
+}
+template <int DIM, int NC>
+__global__ __launch_bounds__(256) void wgrad3_small_final_kernel(const float* __restrict__ part, int nblk, int wide_is_out, float* __restrict__ dw, float* __restrict__ db) {
+    constexpr int NOUT = DIM * NC * 9 + DIM + NC;
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= NOUT) return;
+    float s = 0.f;
+    for (int k = 0; k < nblk; ++k) s += part[(long long)k * NOUT + o];
+    if (o < DIM * NC * 9) {
+        const int c = o / (NC * 9), n = (o % (NC * 9)) / 9, t = o % 9;
+        if (wide_is_out) dw[(c * NC + n) * 9 + t] = s;          // conv_in: [co = c][ci = n]
+        else dw[(n * DIM + c) * 9 + t] = s;                     // conv_out: [co = n][ci = c]
+    } else if (o < DIM * NC * 9 + DIM) {
+        if (wide_is_out) db[o - DIM * NC * 9] = s;
+    } else if (!wide_is_out) {
+        db[o - DIM * NC * 9 - DIM] = s;
+    }
+}
+
+// ---- loss: 510 * mean|out - target| (train_hfrm.py:258, 2 * mean|255 out - 255 target|) and its gradient (torch's sign(0) = 0) ------
+constexpr int LOSS_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void l1_loss_kernel(const float* __restrict__ out, const float* __restrict__ tgt, float* __restrict__ dy, long long n, float scale,
+                                                      float* __restrict__ part) {
+    __shared__ float red[256];
+    float s = 0.f;
+    GS_LOOP(id, n) {
+        const float d = out[id] - tgt[id];
+        s += fabsf(d);
+        dy[id] = d > 0.f ? scale : (d < 0.f ? -scale : 0.f);
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+__global__ __launch_bounds__(256) void l1_loss_final_kernel(const float* __restrict__ part, int nparts, float scale, float* __restrict__ loss) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int k = threadIdx.x; k < nparts; k += 256) s += part[k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = red[0] * scale;
+}
+
+}  // namespace hft
+
+// =================================================================================================
+// the trainer object
+// =================================================================================================
+using namespace wdm;
+using namespace hft;
+
+namespace {
+struct TParam { std::string name; int ndim; int64_t shape[4]; int64_t off; int64_t numel; };
+// a layer that runs as a GEMM: forward matrix [rows_f][K] and transposed [rows_t][cout] in the step's pack region
+struct TGemm { int pw = -1, pb = -1; int cout = 0, cin = 0, kk = 1; size_t f_off = 0, t_off = 0;
+               int K() const { return cin * kk; } int rows_f() const { return conv_rows_pad(cout); } int rows_t() const { return conv_rows_pad(cin * kk); } };
+struct TBlock {
+    int d;
+    int beta, gamma, n1w, n1b, n2w, n2b, dww, dwb, caw, cab;
+    TGemm g1, g3, g4, g5;
+};
+struct BSave { float *a1, *a2, *c3, *y, *a4, *c5, *out, *pooled, *sc; };
+}  // namespace
+
+struct wdm_hfrm_trainer {
+    wdm_hfrm_config cfg;
+    std::vector<TParam> params;
+    int64_t nfloats = 0;
+    size_t pack_bytes = 0;
+    float *P = nullptr, *G = nullptr, *Mo = nullptr, *V = nullptr;
+    int p_cin_w, p_cin_b, p_cout_w, p_cout_b;
+    size_t cout_off = 0;
+    std::vector<std::vector<TBlock>> enc, dec;
+    std::vector<TBlock> mid;
+    std::vector<TGemm> downs, ups;
+    char* pk = nullptr;      // pack region of the current step
+
+    int add(const std::string& name, std::initializer_list<int64_t> shp) {
+        TParam p; p.name = name; p.ndim = (int)shp.size(); int i = 0; p.numel = 1;
+        for (auto v : shp) { p.shape[i++] = v; p.numel *= v; }
+        for (; i < 4; ++i) p.shape[i] = 0;
+        p.off = nfloats;
+        nfloats += (p.numel + 63) / 64 * 64;          // 256-byte aligned views
+        params.push_back(p);
+        return (int)params.size() - 1;
+    }
+    size_t take(size_t bytes) { size_t o = pack_bytes; pack_bytes = align_up(pack_bytes + bytes, 256); return o; }
+    TGemm gemm(int pw, int pb, int cout, int cin, int kk) {
+        TGemm g; g.pw = pw; g.pb = pb; g.cout = cout; g.cin = cin; g.kk = kk;
+        g.f_off = take((size_t)g.rows_f() * g.K() * 4); g.t_off = take((size_t)g.rows_t() * cout * 4);
+        return g;
+    }
+    TBlock block(const std::string& n, int d) {
+        TBlock b; b.d = d;
+        b.beta = add(n + ".beta", {1, d, 1, 1}); b.gamma = add(n + ".gamma", {1, d, 1, 1});
+        const int w1 = add(n + ".conv1.weight", {2 * d, d, 1, 1}), b1 = add(n + ".conv1.bias", {2 * d});
+        b.dww = add(n + ".conv2.weight", {2 * d, 1, 3, 3}); b.dwb = add(n + ".conv2.bias", {2 * d});
+        const int w3 = add(n + ".conv3.weight", {d, d, 1, 1}), b3 = add(n + ".conv3.bias", {d});
+        b.caw = add(n + ".channel_attn.chan_conv.weight", {d, d, 1, 1}); b.cab = add(n + ".channel_attn.chan_conv.bias", {d});
+        const int w4 = add(n + ".conv4.weight", {2 * d, d, 1, 1}), b4 = add(n + ".conv4.bias", {2 * d});
+        const int w5 = add(n + ".conv5.weight", {d, d, 1, 1}), b5 = add(n + ".conv5.bias", {d});
+        b.n1w = add(n + ".norm1.weight", {d}); b.n1b = add(n + ".norm1.bias", {d});
+        b.n2w = add(n + ".norm2.weight", {d}); b.n2b = add(n + ".norm2.bias", {d});
+        b.g1 = gemm(w1, b1, 2 * d, d, 1); b.g3 = gemm(w3, b3, d, d, 1); b.g4 = gemm(w4, b4, 2 * d, d, 1); b.g5 = gemm(w5, b5, d, d, 1);
+        return b;
+    }
+    // the reference's registration order (arch.py:206-233): conv_in, encoders, decoders, mid_blks, ups, downs, conv_out
+    void build() {
+        const int dim = cfg.dim;
+        p_cin_w = add("conv_in.weight", {dim, cfg.in_channel, 3, 3}); p_cin_b = add("conv_in.bias", {dim});
+        int d = dim;
+        enc.resize(cfg.n_enc); dec.resize(cfg.n_dec);
+        for (int i = 0; i < cfg.n_enc; ++i) {
+            for (int j = 0; j < cfg.enc_blk_nums[i]; ++j) enc[i].push_back(block("encoders." + std::to_string(i) + "." + std::to_string(j), d));
+            d *= 2;
+        }
+        const int dmid = d;
+        for (int i = 0; i < cfg.n_dec; ++i) {
+            d /= 2;
+            for (int j = 0; j < cfg.dec_blk_nums[i]; ++j) dec[i].push_back(block("decoders." + std::to_string(i) + "." + std::to_string(j), d));
+        }
+        for (int j = 0; j < cfg.mid_blk_num; ++j) mid.push_back(block("mid_blks." + std::to_string(j), dmid));
+        d = dmid;
+        for (int i = 0; i < cfg.n_dec; ++i) { const int pw = add("ups." + std::to_string(i) + ".0.weight", {2 * d, d, 1, 1}); ups.push_back(gemm(pw, -1, 2 * d, d, 1)); d /= 2; }
+        d = dim;
+        for (int i = 0; i < cfg.n_enc; ++i) {
+            const int pw = add("downs." + std::to_string(i) + ".weight", {2 * d, d, 2, 2}), pb = add("downs." + std::to_string(i) + ".bias", {2 * d});
+            downs.push_back(gemm(pw, pb, 2 * d, d, 4));
+            d *= 2;
+        }
+        p_cout_w = add("conv_out.weight", {cfg.in_channel, dim, 3, 3}); p_cout_b = add("conv_out.bias", {cfg.in_channel});
+        cout_off = take(conv_packed_bytes(dim, cfg.in_channel, 3, WDM_F32));
+    }
+    float* prm(int i) const { return P + params[i].off; }
+    float* grd(int i) const { return G + params[i].off; }
+    const float* wf(const TGemm& g) const { return (const float*)(pk + g.f_off); }
+    const float* wt(const TGemm& g) const { return (const float*)(pk + g.t_off); }
+
+    int gemm_run(Ctx& c, const float* w, int rows, int K, int N, const float* bias, const float* x, long long M, float* y);
+    int fwd_gemm(Ctx& c, const TGemm& g, const float* x, long long M, float* y) { return gemm_run(c, wf(g), g.rows_f(), g.K(), g.cout, g.pb >= 0 ? prm(g.pb) : nullptr, x, M, y); }
+    int dgrad_gemm(Ctx& c, const TGemm& g, const float* dy, long long M, float* dx) { return gemm_run(c, wt(g), g.rows_t(), g.cout, g.K(), nullptr, dy, M, dx); }
+    int wgrad(Ctx& c, const float* x, int cin, const float* dy, int cout, int H, int W, float* dw, float* db);
+    int chan_sums(Ctx& c, const float* a, const float* m, int C, int H, int W, bool per_image, float scale, float* o0, float* o1 = nullptr, int split = 1 << 30);
+    int ln_fwd(Ctx& c, const float* x, float* y, long long M, int d, const float* w, const float* b);
+    int ln_bwd(Ctx& c, const float* x, const float* dn, const float* w, float* dio, long long M, int d, float* dw, float* db);
+    int fwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, BSave& s);
+    int bwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, const BSave& s, float* dO);
+    int pack(hipStream_t s);
+    int step(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out);
+};
+
+int wdm_hfrm_trainer::gemm_run(Ctx& c, const float* w, int rows, int K, int N, const float* bias, const float* x, long long M, float* y) {
+    if (c.dry) return WDM_OK;
+    const int Hp = (int)align_up((size_t)((M + 15) / 16), 16);
+    ConvArgs a{};
+    a.x0 = x; a.C0 = K; a.xs0 = K; a.C1 = 0;
+    a.B = 1; a.Hin = a.Hout = Hp; a.Win = a.Wout = 16;
+    a.Cin = K; a.Cout = N;
+    a.w = w; a.w_tap_stride = 0; a.w_img_stride = 0; a.w_row_stride = K; a.w_rows = rows;
+    a.w_bytes = (unsigned)((size_t)rows * K * 4);
+    a.bias = bias; a.alpha = 1.f;
+    a.y = y; a.y_mode = Y_NHWC; a.y_s = N;
+    a.m_valid = M;
+    return launch_conv(a, MODE_P1, WDM_F32, c.s);
+}
+
+// dw [cout][cin] (the GEMM view of the layer) = sum over pixels dy[p][co] x[p][ci]  (conv_wgrad, mode 3); db = colsum(dy)
+int wdm_hfrm_trainer::wgrad(Ctx& c, const float* x, int cin, const float* dy, int cout, int H, int W, float* dw, float* db) {
+    Tens tx, tdy;
+    tx.p = const_cast<float*>(x); tx.C = cin; tx.H = H; tx.W = W; tx.xs = cin;
+    tdy.p = const_cast<float*>(dy); tdy.C = cout; tdy.H = H; tdy.W = W; tdy.xs = cout;
+    WDM_TRY(conv_wgrad(c, MODE_P1, tx, nullptr, tdy, cout, dw, false));
+    if (db) WDM_TRY(colsum(c, tdy, db, false, false));
+    return WDM_OK;
+}
+
+int wdm_hfrm_trainer::chan_sums(Ctx& c, const float* a, const float* m, int C, int H, int W, bool per_image, float scale, float* o0, float* o1, int split) {
+    const int HW = H * W;
+    const int nk = std::max(1, std::min(256, ceil_div(HW, 1024)));
+    const int chunk = ceil_div(HW, nk);
+    float* part = (float*)c.ar->alloc((size_t)c.B * nk * C * 4);
+    if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM channel sums)");
+    if (!c.dry) {
+        hipLaunchKernelGGL(chan_part_kernel, dim3(nk, c.B, ceil_div(C, 256)), dim3(256), 0, c.s, a, m, C, HW, chunk, nk, part);
+        hipLaunchKernelGGL(chan_final_kernel, dim3(ceil_div((long long)(per_image ? c.B : 1) * C, 256)), dim3(256), 0, c.s, part, c.B, nk, C, per_image ? 1 : 0, scale,
+                           o0, o1, split);
+        WDM_HIP(hipGetLastError());
+    }
+    c.ar->free(part);
+    return WDM_OK;
+}
+
+static int ln_grid(long long M) { return (int)std::min<long long>(1024, (M + LN_TEAMS * 4 - 1) / (LN_TEAMS * 4)); }
+
+#define LN_SWITCH(d, K, ...)                                                  \
+    switch (d) {                                                              \
+        case 32: { constexpr int K = 1; __VA_ARGS__; } break;                 \
+        case 64: { constexpr int K = 2; __VA_ARGS__; } break;                 \
+        case 128: { constexpr int K = 4; __VA_ARGS__; } break;                \
+        case 256: { constexpr int K = 8; __VA_ARGS__; } break;                \
+        case 512: { constexpr int K = 16; __VA_ARGS__; } break;               \
+        default: WDM_FAIL(WDM_EINVAL, "HFRM trainer: LayerNorm over %d channels unsupported", d); \
+    }
+
+int wdm_hfrm_trainer::ln_fwd(Ctx& c, const float* x, float* y, long long M, int d, const float* w, const float* b) {
+    if (c.dry) return WDM_OK;
+    LN_SWITCH(d, NJ, hipLaunchKernelGGL(ln_fwd_kernel<NJ>, dim3(ln_grid(M)), dim3(256), 0, c.s, x, y, M, w, b));
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+// dio (+)= LayerNorm backward of dn (dio holds the residual gradient on entry); dw / db = weight / bias gradients
+int wdm_hfrm_trainer::ln_bwd(Ctx& c, const float* x, const float* dn, const float* w, float* dio, long long M, int d, float* dw, float* db) {
+    const int g = ln_grid(M);
+    float* part = (float*)c.ar->alloc((size_t)g * 2 * d * 4);
+    if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM LayerNorm backward)");
+    if (!c.dry) {
+        LN_SWITCH(d, NJ, hipLaunchKernelGGL(ln_bwd_kernel<NJ>, dim3(g), dim3(256), 0, c.s, x, dn, w, dio, dio, M, part));
+        hipLaunchKernelGGL(chan_final_kernel, dim3(ceil_div(2 * d, 256)), dim3(256), 0, c.s, part, 1, g, 2 * d, 0, 1.0f, dw, db, d);
+        WDM_HIP(hipGetLastError());
+    }
+    c.ar->free(part);
+    return WDM_OK;
+}
+
+int wdm_hfrm_trainer::fwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, BSave& s) {
+    const int d = b.d, HW = H * W;
+    const long long M = (long long)B * HW, n1 = M * d;
+    auto A = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
+    s.a1 = A(2 * n1); s.a2 = A(2 * n1); s.c3 = A(n1); s.y = A(n1); s.a4 = A(2 * n1); s.c5 = A(n1); s.out = A(n1);
+    s.pooled = A((long long)B * d); s.sc = A((long long)B * d);
+    float* n = A(n1);
+    float* g = A(n1);
+    if (!s.a1 || !s.a2 || !s.c3 || !s.y || !s.a4 || !s.c5 || !s.out || !s.pooled || !s.sc || !n || !g) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block forward)");
+    const int ge = gridn(n1, 256);
+    WDM_TRY(ln_fwd(c, X, n, M, d, prm(b.n1w), prm(b.n1b)));
+    WDM_TRY(fwd_gemm(c, b.g1, n, M, s.a1));
+    if (!c.dry) {
+        hipLaunchKernelGGL(dw_fwd_kernel, dim3(gridn(2 * n1, 256)), dim3(256), 0, c.s, s.a1, s.a2, H, W, 2 * d, 2 * n1, prm(b.dww), prm(b.dwb));
+        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, g, n1, d, (const float*)nullptr, HW);
+    }
+    WDM_TRY(chan_sums(c, g, nullptr, d, H, W, true, 1.0f / (float)HW, s.pooled));
+    if (!c.dry) {
+        WDM_TRY(k_linear(s.pooled, B, d, prm(b.caw), prm(b.cab), d, s.sc, 0, c.s));
+        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, g, n1, d, (const float*)s.sc, HW);      // channel-scaled gate
+    }
+    WDM_TRY(fwd_gemm(c, b.g3, g, M, s.c3));
+    if (!c.dry) hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, X, prm(b.beta), s.c3, s.y, n1, d);      // y = x + beta * conv3
+    WDM_TRY(ln_fwd(c, s.y, n, M, d, prm(b.n2w), prm(b.n2b)));
+    WDM_TRY(fwd_gemm(c, b.g4, n, M, s.a4));
+    if (!c.dry) hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a4, g, n1, d, (const float*)nullptr, HW);
+    WDM_TRY(fwd_gemm(c, b.g5, g, M, s.c5));
+    if (!c.dry) {
+        hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, s.y, prm(b.gamma), s.c5, s.out, n1, d);  // out = y + gamma * conv5
+        WDM_HIP(hipGetLastError());
+    }
+    c.ar->free(g); c.ar->free(n);
+    return WDM_OK;
+}
+
+// dO: the gradient of the block output on entry, of its input X on return (in place)
+int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, const BSave& s, float* dO) {
+    const int d = b.d, HW = H * W;
+    const long long M = (long long)B * HW, n1 = M * d;
+    auto A = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
+    float* t1 = A(n1);          // dc5, dc3
+    float* t2 = A(n1);          // g2, n2, g, n1
+    float* t3 = A(2 * n1);      // da4, da2
+    float* t4 = A(n1);          // dg2, dn2, dgs / dg, dn1
+    float* t5 = A(n1);          // g * sc
+    float* t6 = A(2 * n1);      // da1
+    float* sm = A((long long)3 * B * d);      // dsc, dpool
+    if (!t1 || !t2 || !t3 || !t4 || !t5 || !t6 || !sm) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block backward)");
+    float* dsc = sm; float* dpool = sm + (size_t)B * d;
+    const int ge = gridn(n1, 256);
+    // out = y + gamma * c5
+    WDM_TRY(chan_sums(c, dO, s.c5, d, H, W, false, 1.0f, grd(b.gamma)));
+    if (!c.dry) {
+        hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, (const float*)nullptr, prm(b.gamma), dO, t1, n1, d);
+        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a4, t2, n1, d, (const float*)nullptr, HW);
+    }
+    // conv5
+    WDM_TRY(wgrad(c, t2, d, t1, d, H, W, grd(b.g5.pw), grd(b.g5.pb)));
+    WDM_TRY(dgrad_gemm(c, b.g5, t1, M, t4));
+    // gate, conv4, norm2
+    if (!c.dry) hipLaunchKernelGGL(gate_bwd_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.a4, t3, n1, d);
+    WDM_TRY(ln_fwd(c, s.y, t2, M, d, prm(b.n2w), prm(b.n2b)));
+    WDM_TRY(wgrad(c, t2, d, t3, 2 * d, H, W, grd(b.g4.pw), grd(b.g4.pb)));
+    WDM_TRY(dgrad_gemm(c, b.g4, t3, M, t4));
+    WDM_TRY(ln_bwd(c, s.y, t4, prm(b.n2w), dO, M, d, grd(b.n2w), grd(b.n2b)));      // dO is now d y
+    // y = x + beta * c3
+    WDM_TRY(chan_sums(c, dO, s.c3, d, H, W, false, 1.0f, grd(b.beta)));
+    if (!c.dry) {
+        hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, (const float*)nullptr, prm(b.beta), dO, t1, n1, d);
+        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, t2, n1, d, (const float*)nullptr, HW);       // g
+        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, t5, n1, d, (const float*)s.sc, HW);          // g * sc
+    }
+    // conv3
+    WDM_TRY(wgrad(c, t5, d, t1, d, H, W, grd(b.g3.pw), grd(b.g3.pb)));
+    WDM_TRY(dgrad_gemm(c, b.g3, t1, M, t4));
+    // channel attention: sc = W pooled + b, pooled = mean g
+    WDM_TRY(chan_sums(c, t4, t2, d, H, W, true, 1.0f, dsc));
+    if (!c.dry) {
+        const long long nca = (long long)d * d + d + (long long)B * d;
+        hipLaunchKernelGGL(ca_bwd_kernel, dim3(gridn(nca, 256)), dim3(256), 0, c.s, dsc, s.pooled, prm(b.caw), B, d, grd(b.caw), grd(b.cab), dpool);
+        hipLaunchKernelGGL(ca_dg_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.sc, dpool, n1, d, HW, 1.0f / (float)HW);
+        hipLaunchKernelGGL(gate_bwd_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.a2, t3, n1, d);                         // d a2
+    }
+    // depthwise conv2
+    {
+        const int C2 = 2 * d;
+        const int nk = std::max(1, std::min(256, ceil_div(HW, 1024)));
+        const int chunk = ceil_div(HW, nk);
+        float* part = A((long long)B * nk * C2 * 10);
+        if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM depthwise wgrad)");
+        if (!c.dry) {
+            hipLaunchKernelGGL(dw_wgrad_part_kernel, dim3(nk, B, ceil_div(C2, 256)), dim3(256), 0, c.s, t3, s.a1, H, W, C2, chunk, nk, part);
+            hipLaunchKernelGGL(dw_wgrad_final_kernel, dim3(ceil_div(C2 * 10, 256)), dim3(256), 0, c.s, part, B * nk, C2, grd(b.dww), grd(b.dwb));
+            hipLaunchKernelGGL(dw_dgrad_kernel, dim3(gridn(2 * n1, 256)), dim3(256), 0, c.s, t3, t6, H, W, C2, 2 * n1, prm(b.dww));
+            WDM_HIP(hipGetLastError());
+        }
+        c.ar->free(part);
+    }
+    // conv1, norm1
+    WDM_TRY(ln_fwd(c, X, t2, M, d, prm(b.n1w), prm(b.n1b)));
+    WDM_TRY(wgrad(c, t2, d, t6, 2 * d, H, W, grd(b.g1.pw), grd(b.g1.pb)));
+    WDM_TRY(dgrad_gemm(c, b.g1, t6, M, t4));
+    WDM_TRY(ln_bwd(c, X, t4, prm(b.n1w), dO, M, d, grd(b.n1w), grd(b.n1b)));        // dO is now d X
+    c.ar->free(sm); c.ar->free(t6); c.ar->free(t5); c.ar->free(t4); c.ar->free(t3); c.ar->free(t2); c.ar->free(t1);
+    return WDM_OK;
+}
+
+int wdm_hfrm_trainer::pack(hipStream_t s) {
+    auto pg = [&](const TGemm& g) {
+        const long long nf = (long long)g.rows_f() * g.K(), nt = (long long)g.rows_t() * g.cout;
+        hipLaunchKernelGGL(pack_gemm_kernel, dim3(gridn(nf, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 0, (float*)(pk + g.f_off), g.rows_f());
+        hipLaunchKernelGGL(pack_gemm_kernel, dim3(gridn(nt, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 1, (float*)(pk + g.t_off), g.rows_t());
+    };
+    auto pb = [&](const TBlock& b) { pg(b.g1); pg(b.g3); pg(b.g4); pg(b.g5); };
+    for (auto& lv : enc) for (auto& b : lv) pb(b);
+    for (auto& lv : dec) for (auto& b : lv) pb(b);
+    for (auto& b : mid) pb(b);
+    for (auto& g : ups) pg(g);
+    for (auto& g : downs) pg(g);
+    WDM_TRY(k_pack_conv(prm(p_cout_w), cfg.in_channel, cfg.dim, 3, pk + cout_off, conv_rows_pad(cfg.in_channel), 0, 1, WDM_F32, s));
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
+int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out) {
+    const int nlev = cfg.n_enc, dim = cfg.dim, nc = cfg.in_channel;
+    if (H % (1 << nlev) || W % (1 << nlev) || H % 16 || W % 16) WDM_FAIL(WDM_EINVAL, "HFRM trainer: H=%d W=%d must be multiples of 16 and of %d", H, W, 1 << nlev);
+    auto A = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
+    pk = (char*)c.ar->alloc(pack_bytes);
+    if (!pk) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer weights)");
+    if (!c.dry) WDM_TRY(pack(c.s));
+    const long long M0 = (long long)B * H * W;
+    // ---- forward, keeping what the backward reads
+    std::vector<const float*> ins;          // block inputs in execution order
+    std::vector<BSave> saves;
+    std::vector<float*> enc_out(nlev), up_in(cfg.n_dec);
+    float* cur = A(M0 * dim);
+    if (!cur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer)");
+    if (!c.dry) hipLaunchKernelGGL((conv_in_kernel<32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, cur, B, H, W, nc, prm(p_cin_w), prm(p_cin_b));
+    int d = dim, h = H, w = W;
+    auto run_blocks = [&](const std::vector<TBlock>& bl) -> int {
+        for (auto& b : bl) { BSave s; WDM_TRY(fwd_block(c, b, cur, B, h, w, s)); ins.push_back(cur); saves.push_back(s); cur = s.out; }
+        return WDM_OK;
+    };
+    for (int i = 0; i < nlev; ++i) {
+        WDM_TRY(run_blocks(enc[i]));
+        enc_out[i] = cur;
+        const long long Mn = (long long)B * (h / 2) * (w / 2);
+        float* u = A(Mn * 4 * d);
+        float* nt = A(Mn * 2 * d);
+        if (!u || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down)");
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(gridn(Mn * 4 * d, 256)), dim3(256), 0, c.s, cur, u, B, h, w, d, 0);
+        WDM_TRY(fwd_gemm(c, downs[i], u, Mn, nt));
+        c.ar->free(u);
+        cur = nt; d *= 2; h /= 2; w /= 2;
+    }
+    WDM_TRY(run_blocks(mid));
+    for (int i = 0; i < cfg.n_dec; ++i) {
+        const long long M = (long long)B * h * w;
+        float* p = A(M * 2 * d);
+        float* nt = A(M * 2 * d);           // (2h x 2w x d/2)
+        if (!p || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up)");
+        WDM_TRY(fwd_gemm(c, ups[i], cur, M, p));
+        if (!c.dry) hipLaunchKernelGGL(pixel_shuffle_kernel, dim3(gridn(M * 2 * d, 256)), dim3(256), 0, c.s, p, enc_out[nlev - 1 - i], nt, B, h, w, d / 2);
+        c.ar->free(p);
+        up_in[i] = cur;
+        cur = nt; d /= 2; h *= 2; w *= 2;
+        WDM_TRY(run_blocks(dec[i]));
+    }
+    // conv_out 3x3 + input (run_conv, as the inference forward), NCHW f32
+    float* xin = A(M0 * nc);
+    float* yo = out ? out : A(M0 * nc);
+    float* dY = A(M0 * nc);
+    float* lpart = A(LOSS_BLOCKS);
+    if (!xin || !yo || !dY || !lpart) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer output)");
+    {
+        if (!c.dry) WDM_TRY(k_nchw_to_nhwc(x, xin, B, nc, H, W, WDM_F32, c.s));
+        ConvW cwo; cwo.w = pk + cout_off; cwo.b = prm(p_cout_b); cwo.cin = dim; cwo.cout = nc; cwo.k = 3; cwo.rows_pad = conv_rows_pad(nc);
+        Tens t; t.p = cur; t.C = dim; t.H = H; t.W = W; t.xs = dim;
+        Tens xi; xi.p = xin; xi.C = nc; xi.H = H; xi.W = W; xi.xs = nc;
+        Tens dummy;
+        Ctx cc = c; cc.B = B;
+        WDM_TRY(run_conv(cc, cwo, MODE_S1, t, nullptr, nullptr, nullptr, nullptr, 0, 0, &xi, &dummy, Y_NCHW_F32, yo));
+    }
+    // ---- loss
+    const long long ny = M0 * nc;
+    if (!c.dry) {
+        if (target) {
+            const float sc = 510.0f / (float)ny;
+            hipLaunchKernelGGL(l1_loss_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, c.s, yo, target, dY, ny, sc, lpart);
+            if (loss) hipLaunchKernelGGL(l1_loss_final_kernel, dim3(1), dim3(256), 0, c.s, lpart, LOSS_BLOCKS, sc, loss);
+        } else {
+            WDM_HIP(hipMemcpyAsync(dY, dyext, (size_t)ny * 4, hipMemcpyDeviceToDevice, c.s));
+        }
+        WDM_HIP(hipGetLastError());
+    }
+    // ---- backward
+    float* dT = A(M0 * dim);
+    if (!dT) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer backward)");
+    {
+        const int chunk = 2048, nbk = ceil_div(M0, chunk);
+        constexpr int NOUT = 32 * 3 * 9 + 32 + 3;
+        float* part = A((long long)nbk * NOUT);
+        if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_out wgrad)");
+        if (nc != 3) WDM_FAIL(WDM_EINVAL, "HFRM trainer: in_channel must be 3");
+        if (!c.dry) {
+            hipLaunchKernelGGL((conv_out_dgrad_kernel<32, 3>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, dY, prm(p_cout_w), dT, B, H, W);
+            hipLaunchKernelGGL((wgrad3_small_part_kernel<32, 3>), dim3(nbk), dim3(256), 0, c.s, cur, dY, B, H, W, -1, chunk, part);
+            hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 0, grd(p_cout_w), grd(p_cout_b));
+            WDM_HIP(hipGetLastError());
+        }
+        c.ar->free(part);
+    }
+    int k = (int)saves.size();
+    auto back_blocks = [&](const std::vector<TBlock>& bl) -> int {
+        for (int j = (int)bl.size() - 1; j >= 0; --j) {
+            --k;
+            WDM_TRY(bwd_block(c, bl[j], ins[k], B, h, w, saves[k], dT));
+            const BSave& s = saves[k];
+            c.ar->free(s.sc); c.ar->free(s.pooled); c.ar->free(s.c5); c.ar->free(s.a4); c.ar->free(s.y); c.ar->free(s.c3); c.ar->free(s.a2); c.ar->free(s.a1);
+        }
+        return WDM_OK;
+    };
+    std::vector<float*> dskip(nlev);
+    for (int i = cfg.n_dec - 1; i >= 0; --i) {
+        WDM_TRY(back_blocks(dec[i]));
+        // ups[i]: nt = PixelShuffle(W up_in) + skip
+        const int dl = 2 * d;                                   // channels of up_in
+        const int hl = h / 2, wl = w / 2;
+        const long long M = (long long)B * hl * wl;
+        float* dp = A(M * 2 * dl);
+        float* dcur = A(M * dl);
+        if (!dp || !dcur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up backward)");
+        if (!c.dry) hipLaunchKernelGGL(pixel_unshuffle_kernel, dim3(gridn(M * 2 * dl, 256)), dim3(256), 0, c.s, dT, dp, B, hl, wl, d);
+        dskip[nlev - 1 - i] = dT;
+        WDM_TRY(wgrad(c, up_in[i], dl, dp, 2 * dl, hl, wl, grd(ups[i].pw), nullptr));
+        WDM_TRY(dgrad_gemm(c, ups[i], dp, M, dcur));
+        c.ar->free(dp);
+        dT = dcur; d = dl; h = hl; w = wl;
+    }
+    WDM_TRY(back_blocks(mid));
+    for (int i = nlev - 1; i >= 0; --i) {
+        // downs[i]: level i+1 input = W . unshuffle(enc_out[i]) + b
+        const int dl = d / 2, hl = 2 * h, wl = 2 * w;
+        const long long Mn = (long long)B * h * w;
+        float* u = A(Mn * 4 * dl);
+        float* gw = A((long long)2 * dl * 4 * dl);
+        if (!u || !gw) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down backward)");
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(gridn(Mn * 4 * dl, 256)), dim3(256), 0, c.s, enc_out[i], u, B, hl, wl, dl, 0);
+        WDM_TRY(wgrad(c, u, 4 * dl, dT, 2 * dl, h, w, gw, grd(downs[i].pb)));
+        if (!c.dry) hipLaunchKernelGGL(permute_down_grad_kernel, dim3(gridn((long long)2 * dl * 4 * dl, 256)), dim3(256), 0, c.s, gw, grd(downs[i].pw), 2 * dl, dl, 4);
+        WDM_TRY(dgrad_gemm(c, downs[i], dT, Mn, u));           // d u, over u
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(gridn(Mn * 4 * dl, 256)), dim3(256), 0, c.s, dskip[i], u, B, hl, wl, dl, 1);
+        c.ar->free(gw); c.ar->free(u); c.ar->free(dT);
+        dT = dskip[i]; d = dl; h = hl; w = wl;
+        WDM_TRY(back_blocks(enc[i]));
+    }
+    {   // conv_in: weight and bias only (the image needs no gradient)
+        const int chunk = 2048, nbk = ceil_div(M0, chunk);
+        constexpr int NOUT = 32 * 3 * 9 + 32 + 3;
+        float* part = A((long long)nbk * NOUT);
+        if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_in wgrad)");
+        if (!c.dry) {
+            hipLaunchKernelGGL((wgrad3_small_part_kernel<32, 3>), dim3(nbk), dim3(256), 0, c.s, dT, x, B, H, W, 1, chunk, part);
+            hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 1, grd(p_cin_w), grd(p_cin_b));
+            WDM_HIP(hipGetLastError());
+        }
+        c.ar->free(part);
+    }
+    return WDM_OK;
+}
+
+// =================================================================================================
+// C ABI
+// =================================================================================================
+extern "C" {
+
+int wdm_hfrm_trainer_create(wdm_handle* h, const wdm_hfrm_config* cfg, wdm_hfrm_trainer** out) {
+    (void)h;
+    if (!cfg || !out) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_create: null argument");
+    if (cfg->n_enc < 1 || cfg->n_enc > 8 || cfg->n_dec != cfg->n_enc) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_create: encoder/decoder level counts must match (1..8)");
+    if (cfg->dim != 32 || cfg->in_channel != 3) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_create: dim must be 32 and in_channel 3 (the reference's HFRM)");
+    if (cfg->n_enc > 4) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_create: at most 4 levels (LayerNorm widths up to 512)");
+    if (cfg->dtype != WDM_F32) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_create: training is exact fp32 only (WDM_F32)");
+    wdm_hfrm_trainer* t = new wdm_hfrm_trainer();
+    t->cfg = *cfg;
+    t->build();
+    *out = t;
+    return WDM_OK;
+}
+int wdm_hfrm_trainer_destroy(wdm_hfrm_trainer* t) { delete t; return WDM_OK; }
+int wdm_hfrm_trainer_num_params(const wdm_hfrm_trainer* t) { return t ? (int)t->params.size() : 0; }
+int64_t wdm_hfrm_trainer_num_floats(const wdm_hfrm_trainer* t) { return t ? t->nfloats : 0; }
+int wdm_hfrm_trainer_param_info(const wdm_hfrm_trainer* t, int i, const char** name, int* ndim, int64_t shape[4], int64_t* offset) {
+    if (!t || i < 0 || i >= (int)t->params.size()) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_param_info: index out of range");
+    const TParam& p = t->params[i];
+    if (name) *name = p.name.c_str();
+    if (ndim) *ndim = p.ndim;
+    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
+    if (offset) *offset = p.off;
+    return WDM_OK;
+}
+int wdm_hfrm_trainer_set_buffers(wdm_hfrm_trainer* t, float* params, float* grads, float* m, float* v) {
+    if (!t || !params || !grads) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_set_buffers: null argument");
+    t->P = params; t->G = grads; t->Mo = m; t->V = v;
+    return WDM_OK;
+}
+size_t wdm_hfrm_trainer_workspace_bytes(const wdm_hfrm_trainer* t, int B, int H, int W) {
+    if (!t || B <= 0) return 0;
+    Arena ar = Arena::dry();
+    Ctx c{nullptr, WDM_F32, B, &ar, true};
+    if (const_cast<wdm_hfrm_trainer*>(t)->step(c, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr) != WDM_OK) return 0;
+    return ar.peak() + 4096;
+}
+int wdm_hfrm_trainer_step(wdm_hfrm_trainer* t, const float* x, const float* target, const float* dy, int B, int H, int W, float* loss, float* out, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    if (!t || !x || !workspace || B <= 0) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_step: null argument");
+    if ((target == nullptr) == (dy == nullptr)) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_step: pass exactly one of target and dy");
+    if (!t->P || !t->G) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_trainer_step: call wdm_hfrm_trainer_set_buffers first");
+    if (((uintptr_t)workspace) & 255) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_step: workspace must be 256-byte aligned");
+    Arena ar(workspace, workspace_bytes);
+    Ctx c{(hipStream_t)stream, WDM_F32, B, &ar, false};
+    return t->step(c, x, target, dy, B, H, W, loss, out);
+}
+int wdm_hfrm_trainer_adam(wdm_hfrm_trainer* t, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay, void* stream) {
+    if (!t || !t->P || !t->G || !t->Mo || !t->V) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_trainer_adam: buffers not set");
+    if (step < 1) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_adam: step counts from 1");
+    return k_adam_ema(t->P, t->G, t->Mo, t->V, nullptr, (long long)t->nfloats, step, lr, beta1, beta2, eps, weight_decay, 0.f, (hipStream_t)stream);
+}
+
+}  // extern "C"

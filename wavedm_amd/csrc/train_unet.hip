@@ -146,15 +146,16 @@ __global__ void lin_bwd_x_final_kernel(const float* __restrict__ part, long long
     dx[id] = s;
 }
 // torch.optim.Adam (amsgrad = False) + EMAHelper.update, one pass over the flat buffers
+// (omb1 / omb2 = 1 - beta1 / 1 - beta2, rounded to fp32 once from the caller's values as torch does with its Python-float betas)
 __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M, float* __restrict__ V,
-                                                       float* __restrict__ E, long long n, float lr, float b1, float b2, float eps, float wd, float bc1,
-                                                       float bc2_sqrt, float mu) {
+                                                       float* __restrict__ E, long long n, float lr, float b1, float b2, float omb1, float omb2, float eps, float wd,
+                                                       float bc1, float bc2_sqrt, float mu) {
     for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (long long)gridDim.x * blockDim.x) {
         float g = G[id];
         const float p = P[id];
         if (wd != 0.f) g += wd * p;
-        const float m = b1 * M[id] + (1.f - b1) * g;
-        const float v = b2 * V[id] + (1.f - b2) * g * g;
+        const float m = b1 * M[id] + omb1 * g;
+        const float v = b2 * V[id] + omb2 * g * g;
         M[id] = m; V[id] = v;
         const float denom = sqrtf(v) / bc2_sqrt + eps;
         const float pn = p - (lr / bc1) * (m / denom);
@@ -189,6 +190,15 @@ int transpose_tokens(Ctx& c, const void* src, int N, int Cc, void* dst);
 void l_colsum_f32(hipStream_t s, const float* x, int C, int rows, float* out, float* scratch);
 
 #define BYT(DT, FN, ...) do { if ((DT) == WDM_BF16) FN<__bf16>(__VA_ARGS__); else FN<float>(__VA_ARGS__); } while (0)
+
+int k_adam_ema(float* P, const float* G, float* M, float* V, float* E, long long n, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay,
+               float ema_mu, hipStream_t s) {
+    const float bc1 = 1.0f - (float)std::pow(beta1, (double)step), bc2 = 1.0f - (float)std::pow(beta2, (double)step);
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(nb(n, 256)), dim3(256), 0, s, P, G, M, V, E, n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                       eps, weight_decay, bc1, std::sqrt(bc2), ema_mu);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
 
 }  // namespace wdm
 
@@ -709,12 +719,7 @@ int wdm_trainer_step(wdm_trainer* t, const float* x0, const float* tt, const flo
 int wdm_trainer_adam_ema(wdm_trainer* t, int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float ema_mu, void* stream) {
     if (!t || !t->P || !t->G || !t->M || !t->V) WDM_FAIL(WDM_ESTATE, "wdm_trainer_adam_ema: buffers not set");
     if (step < 1) WDM_FAIL(WDM_EINVAL, "wdm_trainer_adam_ema: step counts from 1");
-    const float bc1 = 1.0f - (float)std::pow((double)beta1, (double)step), bc2 = 1.0f - (float)std::pow((double)beta2, (double)step);
-    const long long n = (long long)t->nfloats;
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(nb(n, 256)), dim3(256), 0, (hipStream_t)stream, t->P, t->G, t->M, t->V, t->E, n, lr, beta1, beta2, eps, weight_decay, bc1,
-                       std::sqrt(bc2), ema_mu);
-    WDM_HIP(hipGetLastError());
-    return WDM_OK;
+    return k_adam_ema(t->P, t->G, t->M, t->V, t->E, (long long)t->nfloats, step, lr, beta1, beta2, eps, weight_decay, ema_mu, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -149,3 +149,41 @@ class RainDrop:
                                                  sampler=DistributedSampler(val_dataset, num_replicas=ws, rank=rank),
                                                  num_workers=cfg.data.num_workers, pin_memory=True, **wk)
         return train_loader, val_loader
+
+
+class HFRMImageFolder(torch.utils.data.Dataset):
+    """The HFRM training set: the reference's `myImageFloder` (datasets/dataset.py:77-132) as train_hfrm.py builds it (crop=False,
+    resize=False, ToTensor).  `<root>/input` and `<root>/gt` are listed and sorted by name separately and paired by position; under a
+    root whose path contains "raindrop", a pair whose input is not 720x480 is resized to 720x480 (PIL bilinear, both images).
+    Items: (input, gt), (3, H, W) float32 in [0, 1]."""
+
+    def __init__(self, root, transform=None):
+        super().__init__()
+        self.root = root
+        self.imgin_names = sorted(os.path.join(root, "input", f) for f in os.listdir(os.path.join(root, "input")) if f not in (".", ".."))
+        self.imgout_names = sorted(os.path.join(root, "gt", f) for f in os.listdir(os.path.join(root, "gt")) if f not in (".", ".."))
+        print(len(self.imgin_names), len(self.imgout_names))
+        assert len(self.imgin_names) == len(self.imgout_names)
+        self.transform = transform or to_tensor
+
+    def __getitem__(self, index):
+        from PIL import Image
+        img1 = Image.open(self.imgin_names[index]).convert("RGB")
+        img2 = Image.open(self.imgout_names[index]).convert("RGB")
+        if "raindrop" in self.root:
+            w, h = img1.size
+            if w != 720 or h != 480:
+                img1 = img1.resize((720, 480), Image.BILINEAR)
+                img2 = img2.resize((720, 480), Image.BILINEAR)
+        return self.transform(img1), self.transform(img2)
+
+    def __len__(self):
+        return len(self.imgin_names)
+
+
+def hfrm_train_loader(root, batch_size=8, num_workers=8, config=None):
+    """train_hfrm.py:189's DataLoader (shuffle=True, batch_size, n_cpu workers) with RainDrop's worker set-up (worker_kwargs: workers from a fork
+    server, pinned batches)."""
+    ds = HFRMImageFolder(root)
+    return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=True, num_workers=num_workers, pin_memory=True,
+                                       **worker_kwargs(config, num_workers))

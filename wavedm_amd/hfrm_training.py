@@ -1,0 +1,217 @@
+"""Training of the HFRM on the HIP library -- stage 1 of the reference's recipe (`train_hfrm.py`), whose `lastest.pth` stage 2 and
+`restore()` load (models/ddm_wavelet.py:142-147).
+
+`HFRMTrainer()` owns four flat fp32 device buffers -- parameters, gradients, Adam m / v -- in the layout the library reports
+(`wdm_hfrm_trainer_param_info`), and runs the body of the reference's loop (train_hfrm.py:240-268):
+
+    loss = trainer.loss_and_grads(inp, gt)      # HFRM forward, 2 * mean|255 out - 255 gt| and its backward (csrc/hfrm_train.hip)
+    trainer.optimizer_step()                    # torch.optim.Adam(betas=(0.5, 0.999)), lr = 2e-4 * 0.5 ** (step / 1e5), no EMA
+
+`state_dict()` uses the reference's keys, shapes and order; `save(path)` writes the plain state_dict that `wavedm_amd.HFRM` and the
+reference's `DenoisingDiffusion_Wavelet` load with strict=True.  Exact fp32 only."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from collections import OrderedDict
+
+import torch
+
+from . import _lib
+
+HFRM_DEFAULTS = dict(in_channel=3, dim=32, mid_blk_num=6, enc_blk_nums=(2, 2, 2, 4), dec_blk_nums=(2, 2, 2, 2))     # train_hfrm.py:88-95
+
+
+def hfrm_lr(step: int, base: float = 2e-4) -> float:
+    """The learning rate train_hfrm.py:244-246 sets before optimizer step `step` (counted from 1): base * 0.5 ** (step / 100000)."""
+    return base * 0.5 ** (step / 100000)
+
+
+def batch_psnr(target, pred):
+    """BatchPSNR (train_hfrm.py:27-31): per image, clamp both to [0, 1], RMSE over (C, H, W), 20 log10(1 / rmse)."""
+    d = pred.clamp(0, 1) - target.clamp(0, 1)
+    rmse = (d * d).mean(dim=(1, 2, 3)).sqrt()
+    return 20 * torch.log10(1 / rmse)
+
+
+def _resolve_train_dtype(dtype):
+    name = dtype or "f32"
+    if name not in _lib.DTYPES:
+        raise ValueError(f"unknown compute dtype {name!r} (use 'f32'; 'f32x3' and 'f16' train in exact fp32 as well)")
+    if _lib.DTYPES[name] == _lib.WDM_BF16:
+        raise NotImplementedError("HFRMTrainer: bf16 training is not built; the HFRM trains in exact fp32 (dtype='f32')")
+    return _lib.WDM_F32
+
+
+def reference_init_state_dict(shapes, seed: int = 0):
+    """The state the reference trains from (train_hfrm.py:111, `generator.apply(weights_init_normal)`, models/model_dense.py:157-168) for
+    an ordered {key: shape} table:
+      * every Conv weight zero, then `eye_` on its centre tap [:, :, k // 2, k // 2] -- for the depthwise conv2 that tap is a (2d, 1)
+        matrix, so only [0, 0] becomes 1;
+      * conv biases keep torch's default init, U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)), drawn here in table order from
+        torch.Generator().manual_seed(seed);
+      * LayerNorm2d weight / bias ones / zeros; beta / gamma zeros (arch.py:165-166).
+    At this point every ResidualBlock is the identity."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd = OrderedDict()
+    for key, shape in shapes.items():
+        shape = tuple(int(v) for v in shape)
+        leaf = key.rsplit(".", 1)[-1]
+        owner = key[: -len(leaf) - 1]
+        if leaf in ("beta", "gamma"):
+            t = torch.zeros(shape)
+        elif ".norm" in "." + owner.rsplit(".", 1)[-1] and len(shape) == 1:
+            t = torch.ones(shape) if leaf == "weight" else torch.zeros(shape)
+        elif len(shape) == 4:
+            t = torch.zeros(shape)
+            k = shape[2] // 2
+            n = min(shape[0], shape[1])
+            t[torch.arange(n), torch.arange(n), k, k] = 1.0
+        else:                                                   # a conv bias: the weight sits right before it in the table
+            wshape = shapes[owner + ".weight"]
+            fan_in = int(wshape[1]) * int(wshape[2]) * int(wshape[3])
+            bound = 1.0 / math.sqrt(fan_in)
+            t = torch.empty(shape).uniform_(-bound, bound, generator=g)
+        sd[key] = t
+    return sd
+
+
+class HFRMTrainer:
+    def __init__(self, in_channel=3, dim=32, mid_blk_num=6, enc_blk_nums=(2, 2, 2, 4), dec_blk_nums=(2, 2, 2, 2), device=None, dtype=None,
+                 lr=2e-4, betas=(0.5, 0.999), eps=1e-8):
+        self._dtype_code = _resolve_train_dtype(dtype)
+        if len(enc_blk_nums) != len(dec_blk_nums):
+            raise ValueError("HFRMTrainer: enc_blk_nums and dec_blk_nums must have the same length")
+        self.device = torch.device(device if device is not None else "cuda:0")
+        if self.device.type != "cuda":
+            raise RuntimeError("wavedm_amd.HFRMTrainer runs on MI355X only (no CPU path)")
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.hfrm_args = dict(in_channel=int(in_channel), dim=int(dim), mid_blk_num=int(mid_blk_num), enc_blk_nums=list(enc_blk_nums),
+                              dec_blk_nums=list(dec_blk_nums))
+        cfg = _lib.HFRMConfig()
+        cfg.in_channel, cfg.dim, cfg.mid_blk_num = int(in_channel), int(dim), int(mid_blk_num)
+        cfg.n_enc, cfg.n_dec = len(enc_blk_nums), len(dec_blk_nums)
+        for i, v in enumerate(enc_blk_nums):
+            cfg.enc_blk_nums[i] = int(v)
+        for i, v in enumerate(dec_blk_nums):
+            cfg.dec_blk_nums[i] = int(v)
+        cfg.dtype = self._dtype_code
+        self._cfg = cfg
+        L = _lib.lib()
+        t = C.c_void_p()
+        _lib.check(L.wdm_hfrm_trainer_create(None, C.byref(cfg), C.byref(t)))
+        self._t = t
+        self.layout = OrderedDict()                     # name -> (offset, shape)
+        name, ndim, shape, off = C.c_char_p(), C.c_int(), (C.c_int64 * 4)(), C.c_int64()
+        for i in range(L.wdm_hfrm_trainer_num_params(t)):
+            _lib.check(L.wdm_hfrm_trainer_param_info(t, i, C.byref(name), C.byref(ndim), C.byref(shape), C.byref(off)))
+            self.layout[name.value.decode()] = (int(off.value), tuple(int(shape[k]) for k in range(ndim.value)))
+        n = int(L.wdm_hfrm_trainer_num_floats(t))
+        with torch.cuda.device(self.device):
+            self.params = torch.zeros(n, device=self.device)
+            self.grads = torch.zeros(n, device=self.device)
+            self.exp_avg = torch.zeros(n, device=self.device)
+            self.exp_avg_sq = torch.zeros(n, device=self.device)
+            self._loss = torch.zeros(1, device=self.device)
+        _lib.check(L.wdm_hfrm_trainer_set_buffers(t, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq)))
+        self.step = 0
+        self._ws = None
+        self._ws_key = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_t", None):
+                _lib.lib().wdm_hfrm_trainer_destroy(self._t)
+                self._t = None
+        except Exception:
+            pass
+
+    # ---- parameters in the reference's naming ----------------------------------------------------------------------
+    def _view(self, flat, name):
+        off, shape = self.layout[name]
+        return flat[off:off + math.prod(shape)].view(shape)
+
+    def param_shapes(self):
+        return OrderedDict((k, v[1]) for k, v in self.layout.items())
+
+    def state_dict(self):
+        return OrderedDict((k, self._view(self.params, k).clone()) for k in self.layout)
+
+    def grad_dict(self):
+        return OrderedDict((k, self._view(self.grads, k).clone()) for k in self.layout)
+
+    def load_state_dict(self, sd, strict=True):
+        sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
+        missing = [k for k in self.layout if k not in sd]
+        extra = [k for k in sd if k not in self.layout]
+        if strict and (missing or extra):
+            raise RuntimeError(f"HFRMTrainer.load_state_dict: missing {missing[:4]}, unexpected {extra[:4]}")
+        for k in self.layout:
+            if k in sd:
+                v = torch.as_tensor(sd[k])
+                if tuple(v.shape) != self.layout[k][1]:
+                    raise RuntimeError(f"HFRMTrainer.load_state_dict: {k} has shape {tuple(v.shape)}, expected {self.layout[k][1]}")
+                self._view(self.params, k).copy_(v.to(self.device, torch.float32))
+
+    def init_reference(self, seed: int = 0):
+        """weights_init_normal (train_hfrm.py:111) with torch-default conv biases from a seeded generator: see reference_init_state_dict."""
+        self.load_state_dict(reference_init_state_dict(self.param_shapes(), seed), strict=True)
+
+    def save(self, path):
+        """The plain state_dict (train_hfrm.py:303-305 saves generator.module.state_dict(): no `module.` prefix, no optimizer state)."""
+        torch.save(OrderedDict((k, v.cpu()) for k, v in self.state_dict().items()), path)
+
+    # ---- one step ----------------------------------------------------------------------------------------------------
+    def _workspace(self, B, H, W):
+        key = (B, H, W)
+        if self._ws_key != key:
+            n = int(_lib.lib().wdm_hfrm_trainer_workspace_bytes(self._t, B, H, W))
+            if n == 0:
+                raise RuntimeError("wdm_hfrm_trainer_workspace_bytes failed: " + _lib.lib().wdm_last_error().decode(errors="replace"))
+            self._ws = None
+            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            self._ws_key = key
+        return self._ws
+
+    def _step(self, inp, gt, dy, out):
+        inp = _lib.require_cuda_f32(inp, "HFRM input")
+        B, Cc, H, W = inp.shape
+        if Cc != self.hfrm_args["in_channel"]:
+            raise ValueError(f"HFRMTrainer: {Cc} input channels, expected {self.hfrm_args['in_channel']}")
+        with torch.cuda.device(self.device):
+            ws = self._workspace(B, H, W)
+            _lib.check(_lib.lib().wdm_hfrm_trainer_step(self._t, _lib.ptr(inp), _lib.ptr(gt) if gt is not None else None, _lib.ptr(dy) if dy is not None else None,
+                                                        B, H, W, _lib.ptr(self._loss), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+
+    def loss_and_grads(self, inp, gt, return_output=False):
+        """inp, gt (B, 3, H, W) in [0, 1], H and W multiples of 16.  Fills self.grads with the gradient of 2 * mean|255 out - 255 gt|;
+        returns that loss as a 0-dim device tensor (and the network output when asked)."""
+        gt = _lib.require_cuda_f32(gt, "HFRM target")
+        out = torch.empty_like(gt)
+        if tuple(gt.shape) != tuple(inp.shape):
+            raise ValueError("HFRMTrainer: input and target shapes differ")
+        self._step(inp, gt, None, out)
+        return (self._loss[0], out) if return_output else self._loss[0]
+
+    def backward_from(self, inp, dy):
+        """Back-propagate an arbitrary upstream gradient dy (B, 3, H, W) of the output: fills self.grads, returns the output."""
+        dy = _lib.require_cuda_f32(dy, "dy")
+        if tuple(dy.shape) != tuple(inp.shape):
+            raise ValueError("HFRMTrainer: dy must have the input's shape")
+        out = torch.empty_like(dy)
+        self._step(inp, None, dy, out)
+        return out
+
+    def optimizer_step(self, lr=None):
+        """torch.optim.Adam step number self.step + 1 (no weight decay, no EMA); lr defaults to the reference's schedule on self.lr."""
+        self.step += 1
+        lr = hfrm_lr(self.step, self.lr) if lr is None else float(lr)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().wdm_hfrm_trainer_adam(self._t, self.step, lr, self.betas[0], self.betas[1], self.eps, 0.0, _lib.stream_ptr()))
+
+    def train_step(self, inp, gt):
+        """One iteration of train_hfrm.py's loop: loss, backward, Adam.  Returns (loss, per-image PSNR of this step's output), both on the device."""
+        loss, out = self.loss_and_grads(inp, gt, return_output=True)
+        loss, psnr = loss.clone(), batch_psnr(gt, out)
+        self.optimizer_step()
+        return loss, psnr
