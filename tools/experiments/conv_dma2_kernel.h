@@ -280,7 +280,6 @@ __global__ __launch_bounds__(256, 2) void conv_dma2_kernel(const ConvArgs a) {
     for (int p = 0; p < 2; ++p)
         conv_epilogue<T, 16, TW, 4, WN, WN, EpiNoHook, false, (PACKED ? 2 : 0)>(a, *(f32x4 (*)[4][WN])&acc[4 * p], smem, true, wave, lane, wave_m * 2 + p, wave_n, img0, oy0, ox0, n0, tile_in_img, 0,
                                                                                 EpiNoHook(), false);
-    gn_arrive<C::NTHREADS>(a, img0, 1, a.Hout * a.Wout, (int*)smem, tid);
 }
 
 }  // namespace wdm

@@ -17,7 +17,6 @@
 #pragma once
 #include "conv_kernel.h"
 #include "gn_inline.h"
-#include "gn_arrive.h"
 
 #ifndef WDM_DABL
 #define WDM_DABL 0
@@ -378,7 +377,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (half) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); }      // the first half's tile reads (same wave: the LDS runs them in order)
         conv_epilogue<T, 16, TW, 4, WN, 4, EpiNoHook, false, (PACKED ? 2 : 0)>(a, acc[half], smem, true, wave, lane, v_wave_m, wave_n, img0, vy, ox0, n0, v_tile, 0, EpiNoHook(), half == 0);
     }
-    gn_arrive<C::NTHREADS>(a, img0, 1, a.Hout * a.Wout, (int*)smem, (int)threadIdx.x);
 }
 
 }  // namespace wdm

@@ -55,7 +55,6 @@ static int launch_attn_fused_t(const AttnOperands& in, void* o, int B, int C, hi
     }
     ConvArgs pe{};
     if (proj) pe = *proj;
-    pe.fin_total = AttnFusedCfg::N / AttnFusedCfg::QB;          // gn_arrive.h: the image's query blocks
     if (qproj) { if constexpr (VTOK) hipLaunchKernelGGL((attn_fused_kernel<true, T, true, true>), dim3(((G + 7) / 8) * 32), dim3(Cf::NTHREADS), 160 * 1024, s, a, pe); }
     else if (proj) hipLaunchKernelGGL((attn_fused_kernel<true, T, VTOK>), dim3(((G + 7) / 8) * 32), dim3(Cf::NTHREADS), 160 * 1024, s, a, pe);
     else hipLaunchKernelGGL((attn_fused_kernel<false, T, VTOK>), dim3(((G + 7) / 8) * 32), dim3(Cf::NTHREADS), Cf::LDS_BYTES, s, a, pe);      // 8 images x 4 query blocks per group of 32

@@ -64,12 +64,9 @@ static int set_shortcut_extents(ConvArgs& a, double es, int kstep, const char* w
 }
 // GroupNorm-statistics slabs this tiling produces per image, the in-tile GroupNorm of the output (yn_ok: the kernel's tile holds whole images x whole groups),
 // and the two host-side queries.  *done: the call was a query, nothing to launch.
-// fin_total > 0: the kernel arrives (gn_arrive.h) and this many of its tiles complete an image
-static int check_stats(ConvArgs& a, int nslab, bool yn_ok, int fin_total, const char* who, bool* done) {
+static int check_stats(ConvArgs& a, int nslab, bool yn_ok, const char* who, bool* done) {
     *done = false;
-    if (a.query_nslab) { *a.query_nslab = nslab; if (a.query_yn) *a.query_yn = yn_ok ? 1 : 0; if (a.query_fin) *a.query_fin = fin_total > 0 ? 1 : 0; *done = true; return WDM_OK; }
-    if (a.fin_cnt && !(fin_total > 0 && a.stats && a.fin_scale && a.fin_shift && a.fin_gamma && a.fin_beta)) WDM_FAIL(WDM_EINVAL, "%s: producer-side GroupNorm finalize unsupported for this launch", who);
-    a.fin_total = fin_total;
+    if (a.query_nslab) { *a.query_nslab = nslab; if (a.query_yn) *a.query_yn = yn_ok ? 1 : 0; *done = true; return WDM_OK; }
     if (a.stats && (a.stats_nslab != nslab || a.Cout % 8 || (a.y_mode != Y_NHWC && a.y_mode != Y_NHWC_F32)))
         WDM_FAIL(WDM_EINVAL, "%s: inconsistent GroupNorm-statistics request (nslab %d vs %d)", who, a.stats_nslab, nslab);
     if (a.yn && !(yn_ok && a.stats && a.on_gamma && a.on_beta)) WDM_FAIL(WDM_EINVAL, "%s: in-tile GroupNorm of the output unsupported for this launch", who);
@@ -112,7 +109,7 @@ static int launch_cfg(const ConvArgs& a0, hipStream_t s) {
     WDM_TRY(set_extents(a, a.m_valid ? (double)a.m_valid : (double)a.B * a.Hin * a.Win, sizeof(WDM_T), "conv"));     // flattened GEMM rows: the real extent, not the padded grid
     constexpr int SPT = (TH * TW) / conv_stat_rows(TH, TW, 16 * WM);          // one statistics slab per wave tile in M
     bool done;
-    WDM_TRY(check_stats(a, (NI == 1 ? (a.Hout / TH) * (a.Wout / TW) : 1) * SPT, false, 0, "conv", &done));
+    WDM_TRY(check_stats(a, (NI == 1 ? (a.Hout / TH) * (a.Wout / TW) : 1) * SPT, false, "conv", &done));
     if (done) return WDM_OK;
     a.mtiles = (NI == 1) ? a.B * (a.Hout / TH) * (a.Wout / TW) : (a.B + NI - 1) / NI;
     a.ntiles = (a.Cout + C::BN - 1) / C::BN;
@@ -141,8 +138,7 @@ static int launch_dma(const ConvArgs& a0, hipStream_t s) {
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 2.0, "conv(dma)"));
     WDM_TRY(set_shortcut_extents(a, 2.0, 64, "conv(dma)"));
     bool done;      // 64-row statistics slabs; in-tile GroupNorm of the output on 16 x 16 maps: a workgroup holds one whole image x 128 columns
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, a.Hout == 16 && a.Wout == 16 && out_norm_shape_ok(a, C::BN), (a.Hout / 16) * (a.Wout / 16) * ((a.Cout + C::BN - 1) / C::BN),
-                        "conv(dma)", &done));
+    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, a.Hout == 16 && a.Wout == 16 && out_norm_shape_ok(a, C::BN), "conv(dma)", &done));
     if (done) return WDM_OK;
     use_slab_major(a);
     a.mtiles = a.B * (a.Hout / 16) * (a.Wout / 16);
@@ -166,7 +162,7 @@ static int launch_dma_big(const ConvArgs& a0, hipStream_t s) {
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 2.0, "conv(dma big)"));
     WDM_TRY(set_shortcut_extents(a, 2.0, 64, "conv(dma big)"));
     bool done;
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, (a.Hout / TH) * (a.Wout / 16) * (a.Cout / C::BN), "conv(dma big)", &done));          // the statistics slabs of the 16 x 16 / 128-column tiling
+    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, "conv(dma big)", &done));          // the statistics slabs of the 16 x 16 / 128-column tiling
     if (done) return WDM_OK;
     use_slab_major(a);
     a.mtiles = a.B * (a.Hout / TH) * (a.Wout / 16);
@@ -204,7 +200,7 @@ static int launch_dma8(const ConvArgs& a0, hipStream_t s) {
     WDM_TRY(set_extents(a, (double)a.B * 64, 2.0, "conv(dma8)"));
     WDM_TRY(set_shortcut_extents(a, 2.0, 64, "conv(dma8)"));
     bool done;      // in-tile GroupNorm of the output: a workgroup holds two whole images x BN columns
-    WDM_TRY(check_stats(a, 64 / conv_stat_rows(8, 8, 16 * C::WM), out_norm_shape_ok(a, C::BN), 0, "conv(dma8)", &done));
+    WDM_TRY(check_stats(a, 64 / conv_stat_rows(8, 8, 16 * C::WM), out_norm_shape_ok(a, C::BN), "conv(dma8)", &done));
     if (done) return WDM_OK;
     use_slab_major(a);
     a.mtiles = (a.B + C::NI - 1) / C::NI;
@@ -232,8 +228,7 @@ static int launch_up4(const ConvArgs& a0, hipStream_t s) {
     a.w_tap_stride = (long long)a.w_rows * 32; a.w_row_stride = 32; a.w_slab_stride = 16 * a.w_rows * 32;
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 2.0, "conv(up4)"));
     bool done;      // slabs of the (2H) x (2W) output: four phases
-    WDM_TRY(check_stats(a, 4 * (a.Hout / TILE) * (a.Wout / TILE) * ((TILE * TILE) / conv_stat_rows(TILE, TILE, 16 * C::WM)), false,
-                        (a.Hout / TILE) * (a.Wout / TILE) * 4 * ((a.Cout + C::BN - 1) / C::BN), "conv(up4)", &done));       // tiles x phases x N tiles per image
+    WDM_TRY(check_stats(a, 4 * (a.Hout / TILE) * (a.Wout / TILE) * ((TILE * TILE) / conv_stat_rows(TILE, TILE, 16 * C::WM)), false, "conv(up4)", &done));
     if (done) return WDM_OK;
     a.up4 = 1;
     a.up4_ntp = (a.Cout + C::BN - 1) / C::BN;
@@ -257,7 +252,7 @@ static int launch_s2(const ConvArgs& a0, hipStream_t s) {
     if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.sx0 || a.w_img_stride || a.m_valid || a.yn) WDM_FAIL(WDM_EINVAL, "conv(s2): unsupported operand combination (Cin=%d Cout=%d)", a.Cin, a.Cout);
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 2.0, "conv(s2)"));
     bool done;
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * (256 / conv_stat_rows(16, 16, 16 * C::WM)), false, 0, "conv(s2)", &done));
+    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * (256 / conv_stat_rows(16, 16, 16 * C::WM)), false, "conv(s2)", &done));
     if (done) return WDM_OK;
     use_slab_major(a);                               // (round 5: the Downsample convs carry the slab-major copy too: whole cache lines per DMA piece)
     a.mtiles = a.B * (a.Hout / 16) * (a.Wout / 16);
@@ -280,7 +275,7 @@ static int launch_gemm(const ConvArgs& a0, hipStream_t s) {
     if (a.Cin % C::BK || a.C0 % C::BK) WDM_FAIL(WDM_EINVAL, "conv(gemm): Cin=%d / C0=%d must be multiples of %d", a.Cin, a.C0, C::BK);
     WDM_TRY(set_extents(a, a.m_valid ? (double)a.m_valid : (double)(a.x_img_shared ? 1 : a.B) * a.Hin * a.Win, 2.0, "conv(gemm)"));
     bool done;
-    WDM_TRY(check_stats(a, (a.Hout * a.Wout) / 64, false, 0, "conv(gemm)", &done));
+    WDM_TRY(check_stats(a, (a.Hout * a.Wout) / 64, false, "conv(gemm)", &done));
     if (done) return WDM_OK;
     a.mtiles = a.B * (a.Hout / TH) * (a.Wout / 16);
     a.ntiles = (a.Cout + C::BN - 1) / C::BN;
@@ -315,7 +310,7 @@ static int launch_dmax3(const ConvArgs& a0, hipStream_t s) {
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 4.0, "conv(dmax3)"));
     WDM_TRY(set_shortcut_extents(a, 4.0, 32, "conv(dmax3)"));
     bool done;      // in-tile GroupNorm of the output: one whole image x 128 columns per tile
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, a.Hout == 16 && a.Wout == 16 && out_norm_shape_ok(a, C::BN), 0, "conv(dmax3)", &done));
+    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, a.Hout == 16 && a.Wout == 16 && out_norm_shape_ok(a, C::BN), "conv(dmax3)", &done));
     if (done) return WDM_OK;
     a.w_split = 0;
     if (a.w_sm) { a.w = a.w_sm; a.w_split = 1; }       // pre-split weights (same [tap][row][cin] strides)
@@ -348,7 +343,7 @@ static int launch_dmax3t(const ConvArgs& a0, hipStream_t s) {
         WDM_FAIL(WDM_EINVAL, "conv(dmax3t): unsupported operand combination (Cin=%d C0=%d)", a.Cin, a.C0);
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 4.0, "conv(dmax3t)"));
     bool done;
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, 0, "conv(dmax3t)", &done));      // the statistics slabs of the 16 x 16 tiling
+    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, "conv(dmax3t)", &done));      // the statistics slabs of the 16 x 16 tiling
     if (done) return WDM_OK;
     a.w = a.w_sm; a.w_split = 1;
     a.mtiles = a.B * (a.Hout / C::TH) * (a.Wout / 16);
@@ -368,7 +363,7 @@ static int launch_dma8x3(const ConvArgs& a0, hipStream_t s) {
     if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.w_img_stride || a.m_valid || a.sx0 || !a.w_sm) WDM_FAIL(WDM_EINVAL, "conv(dma8x3): unsupported operand combination");
     WDM_TRY(set_extents(a, (double)a.B * 64, 4.0, "conv(dma8x3)"));
     bool done;
-    WDM_TRY(check_stats(a, 64 / conv_stat_rows(8, 8, 16 * C::WM), out_norm_shape_ok(a, C::BN), 0, "conv(dma8x3)", &done));
+    WDM_TRY(check_stats(a, 64 / conv_stat_rows(8, 8, 16 * C::WM), out_norm_shape_ok(a, C::BN), "conv(dma8x3)", &done));
     if (done) return WDM_OK;
     a.w = a.w_sm; a.w_split = 1;
     a.mtiles = (a.B + C::NI - 1) / C::NI;
@@ -391,7 +386,7 @@ static int launch_up4x3(const ConvArgs& a0, hipStream_t s) {
     if (4.0 * a.w_tap_stride * 4.0 >= 4294901760.0) WDM_FAIL(WDM_EINVAL, "conv(up4x3): weights exceed the 4 GB buffer-offset range");
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 4.0, "conv(up4x3)"));
     bool done;
-    WDM_TRY(check_stats(a, 4 * (a.Hout / TILE) * (a.Wout / TILE) * ((TILE * TILE) / conv_stat_rows(TILE, TILE, 16 * C::WM)), false, 0, "conv(up4x3)", &done));
+    WDM_TRY(check_stats(a, 4 * (a.Hout / TILE) * (a.Wout / TILE) * ((TILE * TILE) / conv_stat_rows(TILE, TILE, 16 * C::WM)), false, "conv(up4x3)", &done));
     if (done) return WDM_OK;
     a.up4 = 1;
     a.up4_ntp = (a.Cout + C::BN - 1) / C::BN;
@@ -413,7 +408,7 @@ static int launch_gemmx3(const ConvArgs& a0, hipStream_t s) {
     if (a.Cin % C::BK || a.C0 % C::BK || a.pro || a.m_valid || a.img_mod || a.sx0 || a.yn) WDM_FAIL(WDM_EINVAL, "conv(gemmx3): unsupported operand combination (Cin=%d C0=%d)", a.Cin, a.C0);
     WDM_TRY(set_extents(a, (double)(a.x_img_shared ? 1 : a.B) * a.Hin * a.Win, 4.0, "conv(gemmx3)"));
     bool done;
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, 0, "conv(gemmx3)", &done));
+    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, "conv(gemmx3)", &done));
     if (done) return WDM_OK;
     a.mtiles = a.B * (a.Hout / 16) * (a.Wout / 16);
     a.ntiles = (a.Cout + C::BN - 1) / C::BN;
@@ -432,7 +427,7 @@ static int launch_s2x3(const ConvArgs& a0, hipStream_t s) {
     if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.sx0 || a.w_img_stride || a.m_valid || a.yn) WDM_FAIL(WDM_EINVAL, "conv(s2x3): unsupported operand combination (Cin=%d Cout=%d)", a.Cin, a.Cout);
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 4.0, "conv(s2x3)"));
     bool done;
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, 0, "conv(s2x3)", &done));
+    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, "conv(s2x3)", &done));
     if (done) return WDM_OK;
     a.mtiles = a.B * (a.Hout / 16) * (a.Wout / 16);
     a.ntiles = (a.Cout + C::BN - 1) / C::BN;
@@ -464,8 +459,7 @@ int WDM_LAUNCH_NAME(const ConvArgs& a, int mode, hipStream_t s) {
         if (yb >= 4026531840.0 || rb >= 4026531840.0)
             WDM_FAIL(WDM_EINVAL, "conv: output / residual tensor of %.0f bytes exceeds the 32-bit buffer-offset range", yb > rb ? yb : rb);
     }
-    if (a.query_yn) *a.query_yn = 0;                   // the launchers that can write yn / arrive say so (check_stats)
-    if (a.query_fin) *a.query_fin = 0;
+    if (a.query_yn) *a.query_yn = 0;                   // the launchers that can write yn say so (check_stats)
     if (a.yn && !a.query_nslab) {
         int ok = 0, ns = 0;
         ConvArgs q = a;
