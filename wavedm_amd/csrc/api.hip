@@ -184,7 +184,7 @@ int wdm_conv_forward(wdm_handle* h, const float* w, const float* b, int cin, int
     }
     Tens t0, out;
     WDM_TRY(to_nhwc(sc, c, x, cin, H, W, &t0));
-    WDM_TRY(run_conv(c, cw, mode, t0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &out, Y_NHWC, nullptr));
+    WDM_TRY(run_conv(c, cw, mode, {.x0 = &t0}, &out));
     return k_nhwc_to_nchw(out.p, y, B, cout, out.H, out.W, dtype, c.s);
 }
 

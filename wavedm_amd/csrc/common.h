@@ -230,15 +230,34 @@ void env_cfg_refresh();
 
 // ---- conv dispatch (conv_bf16.hip / conv_f32.hip) ---------------------------------------------
 int launch_conv(const ConvArgs& a, int mode, int dtype, hipStream_t s);
+// a plain GEMM on the MODE_P1 kernel: y[b][i][r] = alpha * sum_k x[b][i][k] * w[b][r][k] for the B x H x W rows i, k < K; x rows xs elements apart,
+// w rows ws apart, w_img elements between the images' weight matrices (0: shared); w has `rows` rows of which the first cout are outputs (y rows cout long)
+ConvArgs gemm_args(int B, int H, int W, const void* x, int xs, int K, const void* w, int ws, long long w_img, int rows, int cout, void* y, int y_mode, size_t es,
+                   float alpha = 1.f);
 
 // ---- blocks (blocks.hip) ----------------------------------------------------------------------
-// want_stats: also emit the GroupNorm partial statistics of the output (out->stats) from the conv epilogue
-// gn_inl: GroupNorm(+SiLU) of the single input x0 finalised in the conv's own prologue from x0.gst (gn_inline.h); scale / shift are then null
-int run_conv(Ctx& c, const ConvW& w, int mode, const Tens& x0, const Tens* x1, const float* scale, const float* shift,
-             const float* temb, int temb_ld, int temb_per_image, const Tens* res, Tens* out, int y_mode, void* y_ext,
-             bool want_stats = false, const ConvW* shortcut = nullptr, const Tens* sx0 = nullptr, const Tens* sx1 = nullptr, const NormW* gn_inl = nullptr,
-             ConvArgs* defer = nullptr,       // defer: fill *defer instead of launching (the caller hands it to another launcher: attn.hip)
-             const NormW* on = nullptr, int on_silu = 0);      // on: the consumer's norm -- out->nrm = act(GroupNorm(out)) from the conv itself where its kernel can
+// what run_conv computes beyond its weights and mode; call sites name only what they set (designated initializers, declaration order)
+struct ConvReq {
+    const Tens* x0 = nullptr;
+    const Tens* x1 = nullptr;          // channel concat [x0 | x1], or nullptr
+    const float* scale = nullptr;      // GroupNorm+SiLU prologue from a scale / shift table (run_gn), or nullptr
+    const float* shift = nullptr;
+    const NormW* gn_inl = nullptr;     // GroupNorm(+SiLU) of the single input x0 finalised in the conv's own prologue from x0.gst (gn_inline.h); scale / shift are then null
+    const float* temb = nullptr;
+    int temb_ld = 0;
+    int temb_per_image = 0;
+    const Tens* res = nullptr;
+    int y_mode = Y_NHWC;               // how y_ext is laid out
+    void* y_ext = nullptr;             // nullptr: out is allocated here (NHWC model dtype)
+    bool stats = false;                // also emit the GroupNorm partial statistics of the output (out->stats) from the conv epilogue
+    const ConvW* shortcut = nullptr;   // 1x1 conv over [sx0 | sx1] accumulated into the same tile
+    const Tens* sx0 = nullptr;
+    const Tens* sx1 = nullptr;
+    const NormW* on = nullptr;         // the consumer's norm -- out->nrm = act(GroupNorm(out)) from the conv itself where its kernel can
+    int on_silu = 0;
+};
+// defer: fill *defer instead of launching (the caller hands it to another launcher: attn.hip)
+int run_conv(Ctx& c, const ConvW& w, int mode, const ConvReq& r, Tens* out, ConvArgs* defer = nullptr);
 int run_gn(Ctx& c, const NormW& nw, const Tens& x0, const Tens* x1, int for_silu_conv, float** scale, float** shift);
 // next_n: the norm of the consumer of *out when that consumer normalises in a pass of its own (an AttnBlock, an 8 x 8 ResnetBlock): conv2 writes it (run_conv: on)
 int run_resblock(Ctx& c, const ResW& w, const Tens& x0, const Tens* x1, Tens* out, const NormW* next_n = nullptr, int next_silu = 0);

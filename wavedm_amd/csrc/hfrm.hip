@@ -437,20 +437,12 @@ int wdm_hfrm::finalize(hipStream_t s) {
 int wdm_hfrm::gemm_rows(Ctx& c, const GemmD& g, const void* x, long long M, const void* res, void* y) {
     if (c.dry) return WDM_OK;
     const int Hp = (int)align_up((size_t)((M + 15) / 16), 16);
-    ConvArgs a{};
-    a.x0 = x; a.C0 = g.cin; a.xs0 = g.cin; a.C1 = 0;
-    a.B = 1; a.Hin = a.Hout = Hp; a.Win = a.Wout = 16;
-    a.Cin = g.cin; a.Cout = g.cout;
     const ConvW w = cw(g);
-    a.w = w.w; a.w_tap_stride = 0; a.w_img_stride = 0; a.w_row_stride = g.cin; a.w_rows = g.rows_pad;
-    a.w_bytes = (unsigned)((size_t)g.rows_pad * g.cin * dsize(c.dtype));
-    a.bias = w.b; a.alpha = 1.f;
+    ConvArgs a = gemm_args(1, Hp, 16, x, g.cin, g.cin, w.w, g.cin, 0, g.rows_pad, g.cout, y, Y_NHWC, dsize(c.dtype));
+    a.bias = w.b;
     a.res = res; a.res_s = g.cout;
-    a.y = y; a.y_mode = Y_NHWC; a.y_s = g.cout;
-    a.m_valid = M;
-    // the descriptor extents must describe the real tensor (M rows), not the padded grid
-    int rc = launch_conv(a, MODE_P1, c.dtype, c.s);
-    return rc;
+    a.m_valid = M;      // the descriptor extents must describe the real tensor (M rows), not the padded grid
+    return launch_conv(a, MODE_P1, c.dtype, c.s);
 }
 
 int wdm_hfrm::run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W) {
@@ -561,7 +553,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         Tens xi; xi.p = xin; xi.C = cfg.in_channel; xi.H = h; xi.W = w; xi.xs = cfg.in_channel;
         Tens dummy;
         Ctx cc = c; cc.B = B;
-        WDM_TRY(run_conv(cc, cwo, MODE_S1, t, nullptr, nullptr, nullptr, nullptr, 0, 0, &xi, &dummy, Y_NCHW_F32, yout));
+        WDM_TRY(run_conv(cc, cwo, MODE_S1, {.x0 = &t, .res = &xi, .y_mode = Y_NCHW_F32, .y_ext = yout}, &dummy));
     }
     c.ar->free(t.p); c.ar->free(xin);
     return WDM_OK;

@@ -626,14 +626,8 @@ struct wdm_hfrm_trainer {
 int wdm_hfrm_trainer::gemm_run(Ctx& c, const float* w, int rows, int K, int N, const float* bias, const float* x, long long M, float* y) {
     if (c.dry) return WDM_OK;
     const int Hp = (int)align_up((size_t)((M + 15) / 16), 16);
-    ConvArgs a{};
-    a.x0 = x; a.C0 = K; a.xs0 = K; a.C1 = 0;
-    a.B = 1; a.Hin = a.Hout = Hp; a.Win = a.Wout = 16;
-    a.Cin = K; a.Cout = N;
-    a.w = w; a.w_tap_stride = 0; a.w_img_stride = 0; a.w_row_stride = K; a.w_rows = rows;
-    a.w_bytes = (unsigned)((size_t)rows * K * 4);
-    a.bias = bias; a.alpha = 1.f;
-    a.y = y; a.y_mode = Y_NHWC; a.y_s = N;
+    ConvArgs a = gemm_args(1, Hp, 16, x, K, K, w, K, 0, rows, N, y, Y_NHWC, 4);
+    a.bias = bias;
     a.m_valid = M;
     return launch_conv(a, MODE_P1, WDM_F32, c.s);
 }
@@ -878,7 +872,7 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
         Tens xi; xi.p = xin; xi.C = nc; xi.H = H; xi.W = W; xi.xs = nc;
         Tens dummy;
         Ctx cc = c; cc.B = B;
-        WDM_TRY(run_conv(cc, cwo, MODE_S1, t, nullptr, nullptr, nullptr, nullptr, 0, 0, &xi, &dummy, Y_NCHW_F32, yo));
+        WDM_TRY(run_conv(cc, cwo, MODE_S1, {.x0 = &t, .res = &xi, .y_mode = Y_NCHW_F32, .y_ext = yo}, &dummy));
     }
     // ---- loss
     const long long ny = M0 * nc;

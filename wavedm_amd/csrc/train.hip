@@ -807,16 +807,8 @@ int conv_wgrad(Ctx& c, int mode, const Tens& x0, const Tens* x1, const Tens& dy,
             {   // the nine taps as ONE batched GEMM: "image" i = tap * S + g reads dyT[g] and aT_{tap % 3}[g] shifted by (tap / 3 - 1) grid rows;
                 // a row is the concatenation of the group's Bg images (a shift that leaves an image's segment meets that image's zero border in dyT)
                 const int kg = Bg * kq;
-                ConvArgs a{};
-                a.x0 = dyT; a.C0 = kg; a.xs0 = kg; a.C1 = 0;
-                a.B = 9 * S; a.Hin = a.Hout = Hg; a.Win = a.Wout = Wg;
-                a.Cin = kg; a.Cout = cin;
-                a.w = aT3 + (size_t)Wq * es;
-                a.w_tap_stride = 0; a.w_img_stride = (long long)cin * kg; a.w_row_stride = kg; a.w_rows = cin;
+                ConvArgs a = gemm_args(9 * S, Hg, Wg, dyT, kg, kg, aT3 + (size_t)Wq * es, kg, (long long)cin * kg, cin, cin, part, Y_NHWC_F32, es);
                 a.img_mod = S; a.w_tx_stride = (long long)a_elems; a.w_ty_stride = Wq;
-                a.w_bytes = (unsigned)((size_t)cin * kg * es);
-                a.alpha = 1.f;
-                a.y = part; a.y_mode = Y_NHWC_F32; a.y_s = cin;
                 rc = launch_conv(a, MODE_P1, c.dtype, c.s);
             }
             if (rc == WDM_OK) {
@@ -846,15 +838,8 @@ int conv_wgrad(Ctx& c, int mode, const Tens& x0, const Tens* x1, const Tens& dy,
             const int oy = mode == MODE_P1 ? 0 : ty, ox = mode == MODE_P1 ? 0 : tx;      // Downsample: pad(0,1,0,1), stride 2
             BY_DTYPE(c.dtype, gather_t, c.s, s0->p, s0->xs, s0->C, s1 ? s1->p : nullptr, s1 ? s1->xs : 0, s1 ? s1->C : 0, c.B, H, W, Ho, Wo, stride, oy, ox, aT, cin, kp,
                      0, Bg, 1, 0);
-            ConvArgs a{};
-            a.x0 = dyT; a.C0 = kg; a.xs0 = kg; a.C1 = 0;
-            a.B = S; a.Hin = a.Hout = Hg; a.Win = a.Wout = Wg;
-            a.Cin = kg; a.Cout = cin;
-            a.w = aT; a.w_tap_stride = 0; a.w_img_stride = (long long)cin * kg; a.w_row_stride = kg; a.w_rows = cin;
-            a.w_bytes = (unsigned)((size_t)cin * kg * es);
-            a.alpha = 1.f;
-            a.y = part + (size_t)tap * S * rows_g * cin; a.y_mode = Y_NHWC_F32; a.y_s = cin;
-            rc = launch_conv(a, MODE_P1, c.dtype, c.s);
+            rc = launch_conv(gemm_args(S, Hg, Wg, dyT, kg, kg, aT, kg, (long long)cin * kg, cin, cin, part + (size_t)tap * S * rows_g * cin, Y_NHWC_F32, es), MODE_P1,
+                             c.dtype, c.s);
         }
         if (rc == WDM_OK) {
             const long long total = (long long)kk * cout * cin;

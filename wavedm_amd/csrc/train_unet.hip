@@ -337,9 +337,9 @@ int wdm_trainer::op_conv(const ConvP& p, int mode, TT* x0, TT* x1, int temb_row,
     void* wd = x0->needs_grad ? it->second.second : nullptr;
     w.w = pk;
     TT* o = new_act();
-    // want_stats: the conv's epilogue also leaves the GroupNorm partial statistics of its output (most conv outputs feed a GroupNorm)
-    WDM_TRY(run_conv(cx, w, mode, x0->t, x1 ? &x1->t : nullptr, nullptr, nullptr, temb_row >= 0 ? temb_all + temb_row : nullptr, temb_rows, 1, res ? &res->t : nullptr, &o->t,
-                     Y_NHWC, nullptr, true));
+    // stats: the conv's epilogue also leaves the GroupNorm partial statistics of its output (most conv outputs feed a GroupNorm)
+    WDM_TRY(run_conv(cx, w, mode, {.x0 = &x0->t, .x1 = x1 ? &x1->t : nullptr, .temb = temb_row >= 0 ? temb_all + temb_row : nullptr, .temb_ld = temb_rows, .temb_per_image = 1,
+                                   .res = res ? &res->t : nullptr, .stats = true}, &o->t));
     *out = o;
     const ConvP pp = p;
     tape_rng.push_back({(long long)std::min(pp.w, pp.b), (long long)std::max(pp.w + (size_t)pp.cout * pp.cin * pp.k * pp.k, pp.b + (size_t)pp.cout)});
@@ -420,6 +420,11 @@ int wdm_trainer::op_resblock(const ResP& r, TT* x0, TT* x1, TT** out) {
     return op_conv(r.c2, MODE_S1, a2, nullptr, -1, r.has_nin ? sc : x0, out);
 }
 
+// y[b][i][r] = alpha * sum_k xin[b][i][k] * w[b][r][k]   (i over the H x W tokens of each of the B images)
+static int bgemm(Ctx& cx, int B, const Tens& grid, const void* xin, int K, const void* w, int rows, long long w_img, void* y, int y_mode, float alpha) {
+    return launch_conv(gemm_args(B, grid.H, grid.W, xin, K, K, w, K, w_img, rows, rows, y, y_mode, dsize(cx.dtype), alpha), MODE_P1, cx.dtype, cx.s);
+}
+
 // AttnBlock (unet.py:141-193): out = x + proj(softmax(q k^T C^-1/2) v),  q,k,v = 1x1 convs of GroupNorm(x)
 int wdm_trainer::op_attn(const AttnP& a, TT* x, TT** out) {
     Ctx& cx = *c;
@@ -438,30 +443,15 @@ int wdm_trainer::op_attn(const AttnP& a, TT* x, TT** out) {
     TT* o = new_act();
     WDM_TRY(alloc_tens(cx, C, x->t.H, x->t.W, &o->t));
     if (!S || !Pm || !vT) WDM_FAIL(WDM_ENOMEM, "training workspace too small (attention)");
-    auto bgemm = [&](const void* xin, int K, const void* w, int rows, long long w_img, void* y, int y_mode, float alpha) -> int {
-        // y[b][i][r] = alpha * sum_k xin[b][i][k] * w[b][r][k]   (i over the N tokens)
-        ConvArgs g{};
-        g.x0 = xin; g.C0 = K; g.xs0 = K; g.B = B; g.Hin = g.Hout = x->t.H; g.Win = g.Wout = x->t.W; g.Cin = K; g.Cout = rows;
-        g.w = w; g.w_img_stride = w_img; g.w_row_stride = K; g.w_rows = rows; g.w_bytes = (unsigned)((size_t)rows * K * es);
-        g.alpha = alpha; g.y = y; g.y_mode = y_mode; g.y_s = rows;
-        return launch_conv(g, MODE_P1, cx.dtype, cx.s);
-    };
-    WDM_TRY(bgemm(q->t.p, C, k->t.p, N, (long long)N * C, S, Y_NHWC_F32, scale));
+    WDM_TRY(bgemm(cx, B, x->t, q->t.p, C, k->t.p, N, (long long)N * C, S, Y_NHWC_F32, scale));
     WDM_TRY(k_softmax_rows(S, Pm, (long long)B * N, N, cx.dtype, cx.s));
     WDM_TRY(transpose_tokens(cx, v->t.p, N, C, vT));
-    WDM_TRY(bgemm(Pm, N, vT, C, (long long)C * N, o->t.p, Y_NHWC, 1.f));
+    WDM_TRY(bgemm(cx, B, x->t, Pm, N, vT, C, (long long)C * N, o->t.p, Y_NHWC, 1.f));
     cx.ar->free(vT); cx.ar->free(S);
     tape_rng.push_back({-1, -1});
     tape.push_back([this, q, k, v, o, Pm, C, N, B, es, scale, x]() -> int {
         Ctx& cx = *c;
         if (!o->g) WDM_FAIL(WDM_ESTATE, "backward: attention output without gradient");
-        auto bgemm = [&](const void* xin, int K, const void* w, int rows, long long w_img, void* y, int y_mode, float alpha) -> int {
-            ConvArgs g{};
-            g.x0 = xin; g.C0 = K; g.xs0 = K; g.B = B; g.Hin = g.Hout = x->t.H; g.Win = g.Wout = x->t.W; g.Cin = K; g.Cout = rows;
-            g.w = w; g.w_img_stride = w_img; g.w_row_stride = K; g.w_rows = rows; g.w_bytes = (unsigned)((size_t)rows * K * es);
-            g.alpha = alpha; g.y = y; g.y_mode = y_mode; g.y_s = rows;
-            return launch_conv(g, MODE_P1, cx.dtype, cx.s);
-        };
         float* dP = (float*)cx.ar->alloc((size_t)B * N * N * 4);
         void* dS = cx.ar->alloc((size_t)B * N * N * es);
         void* t0 = cx.ar->alloc((size_t)B * N * std::max(N, C) * es);
@@ -469,22 +459,22 @@ int wdm_trainer::op_attn(const AttnP& a, TT* x, TT** out) {
         if (!dP || !dS || !t0 || !t1) WDM_FAIL(WDM_ENOMEM, "training workspace too small (attention backward)");
         bool f;
         // dP = dO v^T ;  dS = P * (dP - rowsum(dP P)) * scale
-        WDM_TRY(bgemm(o->g, C, v->t.p, N, (long long)N * C, dP, Y_NHWC_F32, 1.f));
+        WDM_TRY(bgemm(cx, B, x->t, o->g, C, v->t.p, N, (long long)N * C, dP, Y_NHWC_F32, 1.f));
         BYT(cx.dtype, l_softmax_bwd, cx.s, Pm, dP, dS, (long long)B * N, N, scale);
         // dV[j][c] = sum_i P[i][j] dO[i][c]
         WDM_TRY(transpose_tokens(cx, Pm, N, N, t0));                 // P^T [j][i]
         WDM_TRY(transpose_tokens(cx, o->g, N, C, t1));               // dO^T [c][i]
         WDM_TRY(grad_buf(v, &f));
-        WDM_TRY(bgemm(t0, N, t1, C, (long long)C * N, v->g, Y_NHWC, 1.f));
+        WDM_TRY(bgemm(cx, B, x->t, t0, N, t1, C, (long long)C * N, v->g, Y_NHWC, 1.f));
         // dQ[i][c] = sum_j dS[i][j] K[j][c]
         WDM_TRY(transpose_tokens(cx, k->t.p, N, C, t1));             // K^T [c][j]
         WDM_TRY(grad_buf(q, &f));
-        WDM_TRY(bgemm(dS, N, t1, C, (long long)C * N, q->g, Y_NHWC, 1.f));
+        WDM_TRY(bgemm(cx, B, x->t, dS, N, t1, C, (long long)C * N, q->g, Y_NHWC, 1.f));
         // dK[j][c] = sum_i dS[i][j] Q[i][c]
         WDM_TRY(transpose_tokens(cx, dS, N, N, t0));                 // dS^T [j][i]
         WDM_TRY(transpose_tokens(cx, q->t.p, N, C, t1));             // Q^T [c][i]
         WDM_TRY(grad_buf(k, &f));
-        WDM_TRY(bgemm(t0, N, t1, C, (long long)C * N, k->g, Y_NHWC, 1.f));
+        WDM_TRY(bgemm(cx, B, x->t, t0, N, t1, C, (long long)C * N, k->g, Y_NHWC, 1.f));
         cx.ar->free(t1); cx.ar->free(t0); cx.ar->free(dS); cx.ar->free(dP);
         WDM_HIP(hipGetLastError());
         return WDM_OK;
@@ -577,7 +567,7 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
         ConvW w; w.cin = conv_out.cin; w.cout = pc; w.k = 3; w.rows_pad = conv_rows_pad(pc); w.b = P + conv_out.b;
         w.w = packed.at(conv_out.w).first;
         Tens dummy;
-        WDM_TRY(run_conv(cc, w, MODE_S1, an->t, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &dummy, Y_NHWC_F32, outf));
+        WDM_TRY(run_conv(cc, w, MODE_S1, {.x0 = &an->t, .y_mode = Y_NHWC_F32, .y_ext = outf}, &dummy));
     }
     // ---- loss and its gradient
     void* dout = cc.ar->alloc((size_t)B * R * R * pc * es);

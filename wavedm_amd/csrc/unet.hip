@@ -330,7 +330,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
     }
     std::vector<Tens> hs;
     Tens h;
-    WDM_TRY(run_conv(c, cw(conv_in), MODE_S1, x, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &h, Y_NHWC, nullptr, true));
+    WDM_TRY(run_conv(c, cw(conv_in), MODE_S1, {.x0 = &x, .stats = true}, &h));
     if (xpad) c.ar->free(xpad);
     hs.push_back(h);
     for (int l = 0; l < nres; ++l) {
@@ -356,7 +356,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
         }
         if (l != nres - 1) {
             Tens o;
-            WDM_TRY(run_conv(c, cw(down_ds[l]), MODE_S2, hs.back(), nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &o, Y_NHWC, nullptr, true));
+            WDM_TRY(run_conv(c, cw(down_ds[l]), MODE_S2, {.x0 = &hs.back(), .stats = true}, &o));
             hs.push_back(o);
         }
     }
@@ -389,7 +389,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
         }
         if (l != 0) {
             Tens o;
-            WDM_TRY(run_conv(c, cw(up_us[l]), MODE_UPS, h, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &o, Y_NHWC, nullptr, true));
+            WDM_TRY(run_conv(c, cw(up_us[l]), MODE_UPS, {.x0 = &h, .stats = true}, &o));
             free_tens(c, h);
             h = o;
         }
@@ -399,7 +399,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
         float *sc, *sh;
         WDM_TRY(run_gn(c, nw(norm_out), h, nullptr, 1, &sc, &sh));
         Tens dummy;
-        WDM_TRY(run_conv(c, cw(conv_out), MODE_S1, h, nullptr, sc, sh, nullptr, 0, 0, nullptr, &dummy, Y_NCHW_F32, eps_out));
+        WDM_TRY(run_conv(c, cw(conv_out), MODE_S1, {.x0 = &h, .scale = sc, .shift = sh, .y_mode = Y_NCHW_F32, .y_ext = eps_out}, &dummy));
         c.ar->free(sc); c.ar->free(sh);
     }
     free_tens(c, h);
