@@ -104,3 +104,32 @@ def temb(t, ch, w0, b0, w1, b1):
                                   _lib.stream_ptr()))
     torch.cuda.synchronize()
     return out.cpu()
+
+
+def conv_backward(w, mode, x, dy, dtype, want_dx=True):
+    """wdm_conv_backward: (dx, dw, db) of conv mode 0..3 (see conv) on CPU tensors -> CPU tensors (dx None unless asked for)."""
+    L, h = _lib.lib(), _lib.handle(0)
+    wd, xd, dyd = w.to(dev()).contiguous(), x.to(dev()).contiguous(), dy.to(dev()).contiguous()
+    B, cin, H, W = xd.shape
+    cout = wd.shape[0]
+    dx = torch.empty_like(xd) if want_dx else None
+    dw = torch.empty_like(wd)
+    db = torch.empty(cout, device=dev())
+    sc = scratch(1 << 30)
+    _lib.check(L.wdm_conv_backward(h, _p(wd), cin, cout, mode, _p(xd), _p(dyd), B, H, W, _p(dx), _p(dw), _p(db), DT[dtype], _p(sc), sc.numel(),
+                                   _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    return (dx.cpu() if want_dx else None), dw.cpu(), db.cpu()
+
+
+def gn_act_backward(x, C0, gamma, beta, dy, silu, dtype):
+    """wdm_gn_act_backward: (dx, dgamma, dbeta) of GroupNorm (+ SiLU) over the concat x = [x[:, :C0] | x[:, C0:]] on CPU tensors -> CPU tensors."""
+    L, h = _lib.lib(), _lib.handle(0)
+    xd, dyd, gd, bd = x.to(dev()).contiguous(), dy.to(dev()).contiguous(), gamma.to(dev()).contiguous(), beta.to(dev()).contiguous()
+    B, Cc, H, W = xd.shape
+    dx, dg, db = torch.empty_like(xd), torch.empty(Cc, device=dev()), torch.empty(Cc, device=dev())
+    sc = scratch(1 << 28)
+    _lib.check(L.wdm_gn_act_backward(h, _p(xd), C0, Cc, _p(gd), _p(bd), _p(dyd), silu, B, H, W, _p(dx), _p(dg), _p(db), DT[dtype], _p(sc), sc.numel(),
+                                     _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    return dx.cpu(), dg.cpu(), db.cpu()
