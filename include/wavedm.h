@@ -256,6 +256,21 @@ int wdm_hfrm_forward(wdm_hfrm* m, const float* x, int B, int H, int W, float* y,
 int wdm_image_sqdiff(wdm_handle* h, const float* a, const float* b, int B, int H, int W, double* sums, void* stream);
 int wdm_to_u8_hwc(wdm_handle* h, const float* x, int B, int C, int H, int W, uint8_t* y, void* stream);
 
+/* wdm_image_ssim: a, b (B images each, layout by `kind`) on the device -> out[B] (device, fp64): SSIM of each pair as calculate_ssim defines it
+ * (utils/metrics.py:82-149; Y conversion :152-255) -- 11x11 Gaussian window (sigma 1.5) over the valid (H-10) x (W-10) region, C1 = (0.01*255)^2,
+ * C2 = (0.03*255)^2, moments and map in fp64, the map's mean.
+ *   kind WDM_IMG_F32_NCHW: (B,3,H,W) f32 in [0,1], taken as clamp(x*255, 0, 255) in f32 (models/restoration.py:144);
+ *        WDM_IMG_U8_HWC:   (B,H,W,3) u8;   WDM_IMG_F32_HWC: (B,H,W,3) f32 already on [0,255], taken as is.
+ *   y_only 1: to_y_channel's Y (float32 steps as the reference; weights [24.966, 128.553, 65.481] on the channels in storage order, as
+ *             wdm_image_sqdiff's Y) -> calculate_ssim(.., test_y_channel=True);  0: mean of the three per-channel SSIMs.
+ * H, W >= 11 (else WDM_EINVAL), 1 <= B <= 65535.  `scratch` holds per-tile partial sums: at least the byte count the size query returns for
+ * (B, H, W), else WDM_ENOMEM.  Fixed reduction order, no atomics: an image's value does not depend on the batch around it; identical inputs
+ * give exactly 1.0.  Queued on `stream`, no host synchronisation. */
+enum { WDM_IMG_F32_NCHW = 0, WDM_IMG_U8_HWC = 1, WDM_IMG_F32_HWC = 2 };
+size_t wdm_image_ssim_scratch_bytes(int B, int H, int W);
+int wdm_image_ssim(wdm_handle* h, const void* a, const void* b, int kind, int y_only, int B, int H, int W, double* out, void* scratch,
+                   size_t scratch_bytes, void* stream);
+
 /* ---- training step: backward primitives, test entry points --------------------------
  * wdm_conv_backward: autograd of one convolution of models/unet.py (mode as wdm_conv_forward: 0 conv3x3 s1 p1, 1 Downsample,
  * 2 Upsample, 3 conv1x1).  x (B,cin,H,W), dy (B,cout,Ho,Wo), w OIHW f32 -> dx (B,cin,H,W) (optional), dw OIHW f32, db (cout) (optional). */

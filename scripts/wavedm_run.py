@@ -8,7 +8,7 @@
 `eval` = eval_diffusion.py (DiffusiveRestoration.restore over the validation loader), `train` = train_diffusion.py (diffusion.train).
 --config is a file name under ./configs or a path.  Under torchrun every rank restores its share of the validation images (the
 loaders use a DistributedSampler) and rank 0 prints the PSNR over all of them; training all-reduces gradients over RCCL.
-Extras: --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --hfrm_ckpt PATH, --max_steps N (train)."""
+Extras: --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train)."""
 import argparse
 import os
 import random
@@ -41,6 +41,7 @@ def parse(argv=None):
     ap.add_argument("--hfrm_ckpt", default=None)
     ap.add_argument("--max_steps", type=int, default=None)
     ap.add_argument("--no_save", action="store_true", help="eval: metrics only, no PNGs")
+    ap.add_argument("--ssim", action="store_true", help="eval: also SSIM (Y channel) of every output against its gt, on the device; prints an `ssim all` line")
     a = ap.parse_args(argv)
     a.early_stop = not a.full_length
     a.images_per_call = a.images_per_call or None          # None: DiffusiveRestoration's automatic grouping
@@ -86,6 +87,11 @@ def main(argv=None):
         dist.all_reduce(mine)
         if args.rank == 0:
             print(f"psnr all ranks: {float(mine[0] / max(mine[1], 1.0)):.4f} over {int(mine[1])} images")
+        if args.ssim:
+            mine = torch.tensor([float(np.sum(restorer.last_ssims_y)), float(len(restorer.last_ssims_y))], dtype=torch.float64, device=config.device)
+            dist.all_reduce(mine)
+            if args.rank == 0:
+                print(f"ssim all ranks: {float(mine[0] / max(mine[1], 1.0)):.4f} over {int(mine[1])} images")
         dist.destroy_process_group()
     return 0
 

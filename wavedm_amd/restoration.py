@@ -7,6 +7,8 @@ numbers stays on the GPU:
 
 * metrics: one device reduction per image pair (imageio.sqdiff) gives the three PSNRs the reference prints
   (torchPSNR on a CPU copy, calculate_psnr_in_GPU, and the numpy calculate_psnr after two float D2H copies);
+  `args.ssim` (default off) adds SSIM(Y) of each output against its gt (metrics.ssim; utils/metrics.calculate_ssim(.., True)): one more device
+  reduction, read back in the same copy, kept in `last_ssims_y` and printed as one `ssim all` line after the PSNR lines;
 * PNGs: quantised on the device, copied on a side stream, encoded by a worker thread (imageio.AsyncImageWriter) --
   `save_images=False` switches them off.
 
@@ -32,7 +34,7 @@ import numpy as np
 import torch
 
 from .ddm_wavelet import data_transform, inverse_data_transform
-from . import _lib, imageio, sampling
+from . import _lib, imageio, metrics, sampling
 
 
 def torchPSNR(tar_img, prd_img):
@@ -226,6 +228,9 @@ class DiffusiveRestoration:
         # the three pairs the reference prints: output, "cond" (IDWT(DWT(x)) == x: the input), HFRM image (restoration.py:146 clamps x_output_wdnet first)
         self._mark("main: sampler queued")
         sums = torch.stack([imageio.sqdiff(gt, x_output), imageio.sqdiff(gt, inp), imageio.sqdiff(gt, hf.clamp(0.0, 1.0))])
+        if self._ssim:
+            # args.ssim: SSIM(Y) of the output against its gt (utils/metrics.py:110-149 on the [0,255] clamp of :144), behind the sums in the same copy
+            sums = torch.cat([sums.reshape(-1), metrics.ssim(gt, x_output, test_y_channel=True)])
         sums_host = _lib.pinned_dontfork(torch.empty(sums.shape, dtype=sums.dtype, pin_memory=True))
         sums_host.copy_(sums, non_blocking=True)
         done = torch.cuda.Event()
@@ -241,7 +246,11 @@ class DiffusiveRestoration:
         """Wait for a queued group's metric sums and print what the reference prints per image."""
         g["done"].synchronize()
         H, W = g["HW"]
-        m_out, m_cond, m_hf = (imageio.psnr_from_sums(g["sums"][j], H, W) for j in range(3))
+        n = len(g["names"])
+        sums = g["sums"][:3 * n * 2].view(3, n, 2) if self._ssim else g["sums"]
+        m_out, m_cond, m_hf = (imageio.psnr_from_sums(sums[j], H, W) for j in range(3))
+        if self._ssim:
+            acc["ssim"] += g["sums"][3 * n * 2:].tolist()
         for k, name in enumerate(g["names"]):
             acc["torch"].append(m_out[k][0]); acc["y"].append(m_out[k][1]); acc["wdnet"].append(m_hf[k][1])
             print("psnr this", m_out[k][0])
@@ -260,7 +269,8 @@ class DiffusiveRestoration:
             self.trace, self._t0 = [], time.perf_counter()
         if self.save_images and self.writer is None:
             self.writer = imageio.AsyncImageWriter()
-        acc = {"torch": [], "y": [], "wdnet": []}
+        self._ssim = bool(getattr(self.args, "ssim", False))
+        acc = {"torch": [], "y": [], "wdnet": [], "ssim": []}
         outputs, pending = [], None
         # groups staged ahead of the sampler: bounded by BYTES (args.prefetch_bytes, default 2 GB of device + pinned memory each), not by count -- a short
         # validation set is read to its end at once, which also lets a fork-based DataLoader's worker processes exit early (see _StageBudget)
@@ -305,7 +315,10 @@ class DiffusiveRestoration:
             print("psnr all np", float(np.mean(acc["y"])))
             print("psnr all GPU", float(np.mean(acc["y"])))       # deliberately the same accumulator: the reference's numpy and torch Y-PSNR agree
             print("psnr all wdnet", float(np.mean(acc["wdnet"])))
+            if self._ssim:
+                print("ssim all", float(np.mean(acc["ssim"])))
         self.last_outputs, self.last_psnrs, self.last_psnrs_y = outputs, acc["torch"], acc["y"]
+        self.last_ssims_y = acc["ssim"] if self._ssim else None
         return outputs, acc["torch"]
 
     def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None):
