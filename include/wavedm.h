@@ -117,6 +117,21 @@ int wdm_patch_accumulate(wdm_handle* h, const float* eps, const int32_t* patches
 int wdm_ddim_from_sums(wdm_handle* h, const float* acc_cnt, const float* x_t, int nimg, int H, int W, float sqrt_1m_at,
                        float sqrt_at, float sqrt_at_next, float c2, float* x0_out, float* x_next_out, void* stream);
 
+/* The four entry points above for ANY number of prediction channels (`channels` = model.pred_channels: 12 = the whole coarse level, 48 = every band
+ * diffused): eps (n, channels, p, p), x_t / x0_out / x_next_out / noise (NIMG, channels, H, W), acc_cnt 2 * NIMG*channels*H*W floats (sums | counts).
+ * A pixel's covering patches are searched within its image's span of the patch list only, once for up to four channels; each channel's sum still runs in
+ * patch-list order in fp32, so channels = 3 returns the bits of the entry points above.  patches == NULL is the element-wise identity form. */
+int wdm_ddim_update_c(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t,
+                      int nimg, int H, int W, float sqrt_1m_at, float sqrt_at, float sqrt_at_next, float c2,
+                      float* x0_out, float* x_next_out, void* stream);
+int wdm_ddim_update_eta_c(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t,
+                          int nimg, int H, int W, float sqrt_1m_at, float sqrt_at, float sqrt_at_next, float c1, float c2,
+                          const float* noise, float* x0_out, float* x_next_out, void* stream);
+int wdm_patch_accumulate_c(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, int nimg, int H, int W,
+                           float* acc_cnt, void* stream);
+int wdm_ddim_from_sums_c(wdm_handle* h, const float* acc_cnt, const float* x_t, int channels, int nimg, int H, int W, float sqrt_1m_at,
+                         float sqrt_at, float sqrt_at_next, float c2, float* x0_out, float* x_next_out, void* stream);
+
 /* NCHW f32 (B,C,H,W) -> NHWC dtype (B,H,W,C) and back (used by the drop-in model(x, t) call). */
 int wdm_nchw_to_nhwc(wdm_handle* h, const float* src, void* dst, int B, int C, int H, int W, int dtype,
                      void* stream);

@@ -133,7 +133,11 @@ int k_ddim_update(const float* eps, const int32_t* patches, int n, int p, const 
                   float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s, const float* noise = nullptr, float c1 = 0.f);
 int k_patch_accumulate(const float* eps, const int32_t* patches, int n, int p, int nimg, int H, int W, float* acc_cnt, hipStream_t s);
 int k_ddim_from_sums(const float* acc_cnt, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san, float c2, float* x0,
-                     float* xn, hipStream_t s);
+                     float* xn, hipStream_t s, int C = 3);
+// the same three for any number of prediction channels C (model.pred_channels)
+int k_ddim_update_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, int nimg, int H, int W,
+                    float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s, const float* noise = nullptr, float c1 = 0.f);
+int k_patch_accumulate_c(const float* eps, const int32_t* patches, int n, int p, int C, int nimg, int H, int W, float* acc_cnt, hipStream_t s);
 int k_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, int dtype, hipStream_t s);
 int k_nhwc_to_nchw(const void* src, float* dst, int B, int C, int H, int W, int dtype, hipStream_t s);
 // GroupNorm(32, eps): partial statistics float4[B][nslab][C] = (pivot, sum(x-K), sum((x-K)^2), n) and their finalisation

@@ -255,13 +255,125 @@ int k_patch_accumulate(const float* eps, const int32_t* patches, int n, int p, i
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }
-int k_ddim_from_sums(const float* acc_cnt, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s) {
-    const long long total = (long long)nimg * 3 * H * W;
+int k_ddim_from_sums(const float* acc_cnt, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s, int C) {
+    const long long total = (long long)nimg * C * H * W;
     if (total <= 0) WDM_FAIL(WDM_EINVAL, "ddim_from_sums: empty image");
     const int g = nblocks(total, 256) > 16384 ? 16384 : nblocks(total, 256);
     hipLaunchKernelGGL(ddim_from_sums_kernel, dim3(g), dim3(256), 0, s, acc_cnt, x_t, total, s1m, sa, san, c2, x0, xn);
     WDM_HIP(hipGetLastError());
     return WDM_OK;
+}
+
+// ---- any number of prediction channels (model.pred_channels: 3, 12, 48, ...).  Which patches cover a pixel does not depend on the channel, and a pixel is
+// covered only by patches of its own image.  Thread = (pixel, chunk of CH <= 4 channels), workgroup = 256 consecutive pixels of ONE image: the workgroup first finds
+// [k_lo, k_hi), the span of the patch list that holds its image's entries (a strided scan + min / max reduction; image-major lists -- what ddim_sample builds from
+// a corner list -- give exactly the image's slice, any other order a wider span that is still filtered by image below, so every list stays correct), then every
+// thread walks that span ONCE for its CH channels: one coverage test per (pixel, patch), CH accumulators in registers, each summed in patch-list order in fp32
+// exactly like ddim_update_kernel (at C = 3 the same bits).  Lanes are consecutive pixels: the eps reads of one (patch, channel) and all stores are coalesced.
+// ACCUM: the patch-sharded form, partial sums | partial counts instead of the update.  No atomics: a result element has one writer.
+template <int CH, bool ACCUM>
+__global__ __launch_bounds__(256) void scatter_update_c_kernel(const float* __restrict__ eps, const int32_t* __restrict__ patches, int n, int p, int C,
+                                                               const float* __restrict__ x_t, int H, int W, float s1m, float sa, float san, float c2,
+                                                               float* __restrict__ x0o, float* __restrict__ xno, const float* __restrict__ noise, float c1,
+                                                               float* __restrict__ acc_cnt, long long total) {
+    __shared__ int s_lo[4], s_hi[4];
+    const int img = blockIdx.y, c0 = blockIdx.z * CH;
+    const int HW = H * W;
+    int lo = n, hi = 0;
+    for (int k = threadIdx.x; k < n; k += 256)
+        if (patches[3 * k] == img) { lo = min(lo, k); hi = max(hi, k + 1); }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    lo = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
+    hi = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= HW) return;
+    const int yy = pix / W, xx = pix - yy * W;
+    float acc[CH], cnt = 0.f;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) acc[j] = 0.f;
+    const long long pp = (long long)p * p;
+    for (int k = lo; k < hi; ++k) {
+        const int pi = patches[3 * k], hi_ = patches[3 * k + 1], wi = patches[3 * k + 2];
+        if (pi == img && (unsigned)(yy - hi_) < (unsigned)p && (unsigned)(xx - wi) < (unsigned)p) {
+            const float* e = eps + ((long long)k * C + c0) * pp + (long long)(yy - hi_) * p + (xx - wi);
+#pragma unroll
+            for (int j = 0; j < CH; ++j)
+                if (c0 + j < C) acc[j] += e[j * pp];
+            cnt += 1.f;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        if (c0 + j >= C) continue;
+        const long long id = ((long long)img * C + c0 + j) * HW + pix;
+        if (ACCUM) {
+            acc_cnt[id] = acc[j];
+            acc_cnt[total + id] = cnt;
+        } else {
+            const float et = acc[j] / cnt;
+            const float xt = x_t[id];
+            const float x0 = (xt - et * s1m) / sa;
+            x0o[id] = x0;
+            xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;
+        }
+    }
+}
+// the identity patch list (every image is its own patch): the element-wise form, any channel count
+__global__ __launch_bounds__(256) void ddim_update_identity_kernel(const float* __restrict__ eps, const float* __restrict__ x_t, long long total, float s1m, float sa,
+                                                                   float san, float c2, float* __restrict__ x0o, float* __restrict__ xno,
+                                                                   const float* __restrict__ noise, float c1) {
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
+        const float et = eps[id] / 1.f;
+        const float xt = x_t[id];
+        const float x0 = (xt - et * s1m) / sa;
+        x0o[id] = x0;
+        xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;
+    }
+}
+template <bool ACCUM>
+static int launch_scatter_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san,
+                            float c2, float* x0, float* xn, const float* noise, float c1, float* acc_cnt, hipStream_t s) {
+    const long long total = (long long)nimg * C * H * W;
+    // channels per thread: 4, 2 or 1 -- the largest that still gives the chip 4 workgroups per CU.  Measured (scripts/update_kernel_ubench.py, EXPERIMENTS.md): with the search
+    // confined to the image's span, sharing it between channels buys little on short spans and too few workgroups cost a lot (12 channels of 7 x 120 x 180 in one
+    // 16-channel chunk, 595 workgroups: 161 us; in chunks of 4, 1785 workgroups: 63 us); on a long span (625 entries) one channel per thread loses again (262 vs 183 us)
+    const long long pixblocks = (long long)nblocks((long long)H * W, 256) * nimg;
+    int ch = 4;
+    while (ch > 1 && pixblocks * ((C + ch - 1) / ch) < 1024) ch >>= 1;
+    const dim3 grid(nblocks((long long)H * W, 256), nimg, (C + ch - 1) / ch);
+#define WDM_SCATTER_C(CH_) hipLaunchKernelGGL((scatter_update_c_kernel<CH_, ACCUM>), grid, dim3(256), 0, s, eps, patches, n, p, C, x_t, H, W, s1m, sa, san, c2, x0, xn, noise, c1, acc_cnt, total)
+    if (ch == 1) WDM_SCATTER_C(1);
+    else if (ch == 2) WDM_SCATTER_C(2);
+    else WDM_SCATTER_C(4);
+#undef WDM_SCATTER_C
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+static int check_scatter_c(const char* who, int n, int p, int C, int nimg, int H, int W) {
+    if (n <= 0 || nimg <= 0 || C <= 0 || p <= 0 || H <= 0 || W <= 0) WDM_FAIL(WDM_EINVAL, "%s: bad arguments", who);
+    if (nimg > 65535 || C > 65535 || (long long)H * W > 2147483647LL - 256) WDM_FAIL(WDM_EINVAL, "%s: %d images x %d channels x %dx%d exceeds the launch grid", who, nimg, C, H, W);
+    return WDM_OK;
+}
+int k_ddim_update_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san,
+                    float c2, float* x0, float* xn, hipStream_t s, const float* noise, float c1) {
+    if (int e = check_scatter_c("ddim_update_c", n, p, C, nimg, H, W)) return e;
+    if (patches == nullptr) {
+        if (p != H || p != W || n != nimg) WDM_FAIL(WDM_EINVAL, "ddim_update_c: identity patch list needs n == nimg, p == H == W");
+        const long long total = (long long)nimg * C * H * W;
+        const int g = nblocks(total, 256) > 16384 ? 16384 : nblocks(total, 256);
+        hipLaunchKernelGGL(ddim_update_identity_kernel, dim3(g), dim3(256), 0, s, eps, x_t, total, s1m, sa, san, c2, x0, xn, noise, c1);
+        WDM_HIP(hipGetLastError());
+        return WDM_OK;
+    }
+    return launch_scatter_c<false>(eps, patches, n, p, C, x_t, nimg, H, W, s1m, sa, san, c2, x0, xn, noise, c1, nullptr, s);
+}
+int k_patch_accumulate_c(const float* eps, const int32_t* patches, int n, int p, int C, int nimg, int H, int W, float* acc_cnt, hipStream_t s) {
+    if (!patches) WDM_FAIL(WDM_EINVAL, "patch_accumulate_c: bad arguments");
+    if (int e = check_scatter_c("patch_accumulate_c", n, p, C, nimg, H, W)) return e;
+    return launch_scatter_c<true>(eps, patches, n, p, C, nullptr, nimg, H, W, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, 0.f, acc_cnt, s);
 }
 
 // =================================================================================================

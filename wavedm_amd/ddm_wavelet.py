@@ -34,6 +34,10 @@ def inverse_data_transform(X):     # ddm_wavelet.py:31-32
     return torch.clamp((X + 1.0) / 2.0, 0.0, 1.0)
 
 
+def _identity_generator(x):        # the stand-in for a missing HFRM checkpoint (DenoisingDiffusion_Wavelet._make_generator)
+    return x
+
+
 class DenoisingDiffusion_Wavelet(object):
     def __init__(self, args, config, generator=None, dtype=None, verbose=False):
         super().__init__()
@@ -97,7 +101,7 @@ class DenoisingDiffusion_Wavelet(object):
             return g.to(self.device).eval().requires_grad_(False)
         import warnings
         warnings.warn(f"HFRM checkpoint {path!r} not found: using the identity stand-in for .generator", stacklevel=3)
-        return lambda x: x
+        return _identity_generator
 
     # ---- checkpoint (utils/logging.py:21-29 + ddm_wavelet.py:180-190) -------------------------
     def load_ddm_ckpt(self, load_path, ema=False):
@@ -151,15 +155,29 @@ class DenoisingDiffusion_Wavelet(object):
         return tr
 
     def assemble_training_sample(self, x):
-        """x (n, 6, H, W) in [0,1] = [degraded | ground truth] crops -> the 96-channel wavelet-domain sample of ddm_wavelet.py:218-243
-        (`use_other_channels` and `use_gt_in_train` as in raindrop_wavelet.yml): [DWT(input) 48 | DWT(gt) LL 3 | DWT(gt) bands 3..47]."""
+        """x (n, 6, H, W) in [0,1] = [degraded | ground truth] crops -> the wavelet-domain training sample of ddm_wavelet.py:218-246:
+        [DWT(input) 48 | DWT(gt)[:, :pred_channels] | other[:, other_channels_begin:]], where `other` is DWT(gt) with `model.use_gt_in_train` (raindrop_wavelet.yml)
+        and DWT(2 * HFRM(input) - 1) without it -- the bands the UNet will see at inference; the HFRM (`self.generator`) sees the [0,1] crop, without gradients."""
         m = self.config.model
-        if not (m.use_other_channels and getattr(m, "use_gt_in_train", True)):
-            raise NotImplementedError("only the use_other_channels / use_gt_in_train branch of raindrop_wavelet.yml is built")
-        x = data_transform(x.to(self.device).float())
-        cond = self.wavelet_dec(x[:, :3].contiguous())
-        gt = self.wavelet_dec(x[:, 3:].contiguous())
-        return torch.cat([cond, gt[:, :m.pred_channels], gt[:, m.other_channels_begin:]], dim=1).contiguous()
+        if not m.use_other_channels:
+            # the reference cannot train this setting either (noise_estimation_loss, ddm_wavelet.py:113-117: `x` is assigned only under use_other_channels), so no
+            # such checkpoint exists (DESIGN.md §7)
+            raise NotImplementedError("training with model.use_other_channels: False is not built (the reference's noise_estimation_loss fails on it too); to train the "
+                                      "model that diffuses every band, spell it use_other_channels: True with other_channels_begin == pred_channels == in_channels "
+                                      "(configs/raindrop_wavelet_pc48.yml): the same network, zero other channels")
+        x = x.to(self.device).float()
+        xt = data_transform(x)
+        cond = self.wavelet_dec(xt[:, :3].contiguous())
+        gt = self.wavelet_dec(xt[:, 3:].contiguous())
+        other = gt
+        if not getattr(m, "use_gt_in_train", True) and m.other_channels_begin < gt.shape[1]:
+            if self.generator is _identity_generator and not getattr(self, "_warned_identity_train", False):
+                import warnings
+                self._warned_identity_train = True
+                warnings.warn("model.use_gt_in_train: False with the identity stand-in for .generator: the UNet trains on the degraded image's own bands", stacklevel=2)
+            with torch.no_grad():
+                other = self.wavelet_dec.forward_affine(self.generator(x[:, :3].contiguous()).contiguous())      # :233-236
+        return torch.cat([cond, gt[:, :m.pred_channels], other[:, m.other_channels_begin:]], dim=1).contiguous()
 
     def train_step(self, x, group=None):
         """One iteration of the reference's loop body (:208-272) on a batch of crops x (n, 6, p, p): DWT, q-sample with antithetic
@@ -277,12 +295,10 @@ class DenoisingDiffusion_Wavelet(object):
         x_cond = _lib.require_cuda_f32(x_cond, "x_cond")
         total = _lib.require_cuda_f32(total, "total")
         nimg, pc, H, W = x.shape
-        if pc != 3:
-            raise NotImplementedError("the DDIM update kernels are built for 3 prediction channels")
         p = int(p_size)
         tri = [(im, int(hi), int(wi)) for im in range(nimg) for (hi, wi) in corners]
         patches = torch.tensor(tri, dtype=torch.int32).to(self.device)
-        L, h = _lib.lib(), _lib.handle(self.device.index or 0)
+        upd = sampling.scatter_update_fns(_lib.lib(), _lib.handle(self.device.index or 0), pc)
         abar = sampling.alpha_bar_table(b)
         seq_next = [-1] + seq[:-1]
         xs, x0_preds, xt = [x], [], x
@@ -299,13 +315,13 @@ class DenoisingDiffusion_Wavelet(object):
                 if eta != 0.:                                                       # ddm_wavelet.py:500-502
                     c1 = eta * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
                     noise = torch.randn_like(xt)
-                    _lib.check(L.wdm_ddim_update_eta(h, _lib.ptr(eps), _lib.ptr(patches), len(tri), p, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
-                                                     float(at.sqrt()), float(at_next.sqrt()), float(c1), float(((1 - at_next) - c1 ** 2).sqrt()),
-                                                     _lib.ptr(noise), _lib.ptr(x0), _lib.ptr(xn), _lib.stream_ptr()))
+                    upd.update_eta(_lib.ptr(eps), _lib.ptr(patches), len(tri), p, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
+                                   float(at.sqrt()), float(at_next.sqrt()), float(c1), float(((1 - at_next) - c1 ** 2).sqrt()),
+                                   _lib.ptr(noise), _lib.ptr(x0), _lib.ptr(xn), _lib.stream_ptr())
                 else:
-                    _lib.check(L.wdm_ddim_update(h, _lib.ptr(eps), _lib.ptr(patches), len(tri), p, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
-                                                 float(at.sqrt()), float(at_next.sqrt()), float((1 - at_next).sqrt()), _lib.ptr(x0), _lib.ptr(xn),
-                                                 _lib.stream_ptr()))
+                    upd.update(_lib.ptr(eps), _lib.ptr(patches), len(tri), p, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
+                               float(at.sqrt()), float(at_next.sqrt()), float((1 - at_next).sqrt()), _lib.ptr(x0), _lib.ptr(xn),
+                               _lib.stream_ptr())
                 x0_preds.append(x0)
                 xs.append(xn)
                 xt = xn
@@ -330,8 +346,8 @@ class DenoisingDiffusion_Wavelet(object):
         [input | x0_preds[-5] LL + ground-truth bands | output | ground truth] of each go into one 4-column PNG
         `<image_folder>/<dataset>/<validation>/<y>_output_epoch<epoch>.png`.  Returns that path."""
         cfg = self.config
-        if not (cfg.data.wavelet and not cfg.data.wavelet_in_unet and cfg.model.use_other_channels):
-            raise NotImplementedError("DenoisingDiffusion_Wavelet.restore: only the raindrop_wavelet.yml branch is accelerated")
+        if not (cfg.data.wavelet and not cfg.data.wavelet_in_unet):
+            raise NotImplementedError("DenoisingDiffusion_Wavelet.restore: only the data.wavelet / not data.wavelet_in_unet branch (raindrop_wavelet.yml) is accelerated")
         from . import imageio
         image_folder = os.path.join(self.args.image_folder, cfg.data.dataset, validation)
         pc, ob = cfg.model.pred_channels, cfg.model.other_channels_begin
@@ -345,13 +361,18 @@ class DenoisingDiffusion_Wavelet(object):
                 inp, gt = x[:, :3].contiguous(), x[:, 3:].contiguous()
                 x_cond = self.wavelet_dec(x_all[:, :3].contiguous())
                 x_gt = self.wavelet_dec(x_all[:, 3:].contiguous())
-                hf_wav = self.wavelet_dec(data_transform(self.generator(inp)).contiguous())
-                _, x0_preds = self.diffusive_restoration(x_cond, x_other=hf_wav[:, ob:].contiguous(), r=r, last=False,
-                                                         use_global=False, use_other=True,
+                # every band diffused (pred_channels == in_channels): no HFRM, no other channels (DiffusiveRestoration._launch_group has the rules)
+                split = pc < cfg.model.in_channels
+                use_other = bool(cfg.model.use_other_channels) and split
+                hf_wav = self.wavelet_dec(data_transform(self.generator(inp)).contiguous()) if split else None
+                _, x0_preds = self.diffusive_restoration(x_cond, x_other=hf_wav[:, ob:].contiguous() if use_other else None, r=r, last=False,
+                                                         use_global=False, use_other=use_other,
                                                          stop_at=-5 if getattr(self.args, "early_stop", True) else None)      # only x_output_list[1][-5] is read (ddm_wavelet.py:378)
                 pred = x0_preds[-5]
                 rec = lambda lo, hi: inverse_data_transform(self.wavelet_rec(torch.cat([lo[:, :pc], hi[:, pc:]], dim=1).contiguous()))
-                x_output, hrgt = rec(pred, hf_wav), rec(pred, x_gt)
+                # the second column splices the ground truth's remaining bands in; with none left it is the output itself (the reference reads an undefined
+                # x_output_hrgt_cat there, ddm_wavelet.py:379-389)
+                x_output, hrgt = rec(pred, hf_wav if split else pred), rec(pred, x_gt)
                 H, W = x_output.shape[-2:]
                 print("psnr", imageio.psnr_from_sums(imageio.sqdiff(gt, x_output), H, W)[0][0])
                 tiles += [inp, hrgt, x_output, gt]            # IDWT(DWT(x)) == x: the "cond" tile is the input
@@ -370,20 +391,24 @@ class DenoisingDiffusion_Wavelet(object):
     def restore_batch(self, rainy01, x_T, hfrm_out01=None, keep=-5, early_stop=False):
         """B independent patch_size x patch_size crops: DWT -> S-step DDIM -> IDWT, all on the GPU.
 
-        rainy01 (B,3,4R,4R) in [0,1]; x_T (B,3,R,R) start noise; returns the restored (B,3,4R,4R) in [0,1] built
+        rainy01 (B,3,4R,4R) in [0,1]; x_T (B,pred_channels,R,R) start noise; returns the restored (B,3,4R,4R) in [0,1] built
         from x0_preds[keep] like restoration.py:108-134, plus (xs[-1], x0_preds[keep])."""
         self._require_plain_unet("restore_batch")
         x_cond = self.wavelet_dec.forward_affine(rainy01)                        # DWT(2x - 1): data_transform folded into the kernel
-        hf = self.generator(rainy01) if hfrm_out01 is None else hfrm_out01
-        hf_wav = x_cond if hf is rainy01 else self.wavelet_dec.forward_affine(hf)   # identity stand-in: the same tensor, not a second pass
-        ob = self.config.model.other_channels_begin
-        x_other = hf_wav[:, ob:].contiguous()
+        m = self.config.model
+        pc, ob = m.pred_channels, m.other_channels_begin
+        split = pc < m.in_channels                                                # every band diffused: no HFRM, no other channels (DiffusiveRestoration._launch_group)
+        hf_wav = x_other = None
+        if split:
+            hf = self.generator(rainy01) if hfrm_out01 is None else hfrm_out01
+            hf_wav = x_cond if hf is rainy01 else self.wavelet_dec.forward_affine(hf)   # identity stand-in: the same tensor, not a second pass
+            if m.use_other_channels:
+                x_other = hf_wav[:, ob:].contiguous()
         skip = self.config.diffusion.num_diffusion_timesteps // self.args.sampling_timesteps
         seq = list(range(0, self.config.diffusion.num_diffusion_timesteps, skip))
         xs, x0_preds = sampling.ddim_sample(self.model, x_T, x_cond, x_other, seq, self.betas, corners=None,
                                             max_batch=getattr(self.args, "max_batch", 64), keep={keep, -1},     # x0_preds[keep], xs[-1] (xs[keep] after an early stop)
                                             stop_at=keep if early_stop else None)      # early_stop: skip the discarded tail
-        pc = self.config.model.pred_channels
         x0 = x0_preds[keep]
-        out = self.wavelet_rec.compose(x0, hf_wav, pc)                            # IDWT of [x0 low bands | HFRM bands], clamp((x + 1) / 2) on the way out
+        out = self.wavelet_rec.compose(x0, hf_wav if split else x0, pc)                            # IDWT of [x0 low bands | HFRM bands], clamp((x + 1) / 2) on the way out
         return out, (xs[-1] if xs[-1] is not None else xs[len(seq) + keep + 1]), x0

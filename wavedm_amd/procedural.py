@@ -83,6 +83,21 @@ def variant_config(kind):
 VARIANTS = ("no_other", "window", "wavelet_in_unet")
 
 
+# (pred_channels, use_other_channels, other_channels_begin): which wavelet bands the diffusion model predicts and which the HFRM supplies, beside the shipped (3, True, 3)
+PRED_CHANNEL_SETTINGS = ((48, False, 0), (48, True, 48), (12, True, 12), (12, False, 0))
+
+
+def pred_channels_config(pred_channels, use_other_channels=True, other_channels_begin=None, base=None, use_gt_in_train=True):
+    """`base` (default: reduced_config()) with the five keys that choose the predicted bands set together: out_ch follows pred_channels (the loss subtracts them)."""
+    c = reduced_config() if base is None else base
+    m = c.model
+    m.pred_channels = m.out_ch = int(pred_channels)
+    m.use_other_channels = bool(use_other_channels)
+    m.other_channels_begin = int(pred_channels if other_channels_begin is None else other_channels_begin)
+    m.use_gt_in_train = bool(use_gt_in_train)
+    return c
+
+
 def unet_in_channels(config) -> int:
     m = config.model
     if m.use_other_channels:

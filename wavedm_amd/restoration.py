@@ -2,7 +2,8 @@
 
 `restore(val_loader, validation, r)` consumes the loader contract `(x[B,6,H,W] in [0,1], img_id, total)`: DWT of the
 degraded image, HFRM -> DWT -> `x_other`, stitched DDIM sampling, `x0_preds[-5]` (restoration.py:108), concat with the
-HFRM high-frequency bands, IDWT, clamp, PSNR, PNG dumps.  Everything between the H2D copy of the batch and the PSNR
+HFRM high-frequency bands, IDWT, clamp, PSNR, PNG dumps -- for any `model.pred_channels`: with every band diffused (`pred_channels == in_channels`) there is no
+HFRM call, no `x_other` and no "wdnet" line, and only `_output` / `_cond` / `_gt` PNGs are written, as in the reference.  Everything between the H2D copy of the batch and the PSNR
 numbers stays on the GPU:
 
 * metrics: one device reduction per image pair (imageio.sqdiff) gives the three PSNRs the reference prints
@@ -200,10 +201,18 @@ class DiffusiveRestoration:
         x_cond = d.wavelet_dec.forward_affine(inp)                             # restoration.py:79, :88: DWT(2x - 1) in one kernel
         x_gt = d.wavelet_dec.forward_affine(gt)                                # :89
         self._mark("main: DWTs queued")
-        hf = d.generator(inp)                                                  # :94 (HFRM)
-        self._mark("main: HFRM queued")
-        hf_wav = d.wavelet_dec.forward_affine(hf.contiguous())                 # :95-96
-        x_other = hf_wav[:, ob:].contiguous()                                  # :102
+        # model.pred_channels == model.in_channels: every band is diffused -- no HFRM call, no HFRM DWT, no "wdnet" numbers (restoration.py:90-96, :111, :145).
+        # x_other exists only with use_other_channels (:98-104) AND at least one channel: `other_channels_begin == in_channels` means none, so the trainable
+        # spelling of the all-bands model (use_other_channels True, begin 48) restores like use_other_channels False
+        split = pc < cfg.model.in_channels
+        use_other = bool(cfg.model.use_other_channels) and split
+        hf = hf_wav = x_other = None
+        if split:
+            hf = d.generator(inp)                                              # :94 (HFRM)
+            self._mark("main: HFRM queued")
+            hf_wav = d.wavelet_dec.forward_affine(hf.contiguous())             # :95-96
+            if use_other:
+                x_other = hf_wav[:, ob:].contiguous()                          # :102
         early = bool(getattr(self.args, "early_stop", True))
         if int(self.diffusion.args.sampling_timesteps) < 5:
             raise IndexError("x0_preds[-5] needs at least 5 sampling steps (restoration.py:108)")
@@ -215,19 +224,23 @@ class DiffusiveRestoration:
             # they are encoded while it runs and only two per image are left for the end of the group (the order of the files on disk is nobody's contract)
             for k, name in enumerate(names):
                 sl = slice(k, k + 1)
-                w.save(rec(x_gt[sl], hf_wav[sl]), os.path.join(image_folder, f"{name}_lrgt_hrwdnet.png"))      # :118-120, :158
-                w.save(hf[sl], os.path.join(image_folder, f"{name}_all_wdnet.png"))
-                w.save(rec(x_gt[sl], x_cond[sl]), os.path.join(image_folder, f"{name}_lrgt_hrcond.png"))       # :121-123
+                if use_other:                                                  # :154-159: these four only with use_other_channels and pred_channels < in_channels
+                    w.save(rec(x_gt[sl], hf_wav[sl]), os.path.join(image_folder, f"{name}_lrgt_hrwdnet.png"))      # :118-120, :158
+                    w.save(hf[sl], os.path.join(image_folder, f"{name}_all_wdnet.png"))
+                    w.save(rec(x_gt[sl], x_cond[sl]), os.path.join(image_folder, f"{name}_lrgt_hrcond.png"))       # :121-123
                 w.save(inp[sl], os.path.join(image_folder, f"{name}_cond.png"))
                 w.save(gt[sl], os.path.join(image_folder, f"{name}_gt.png"))
         xs, x0_preds = self.diffusive_restoration(x_cond, x_other=x_other, r=r, last=False, total=None,
-                                                  use_global=False, use_other=True, stop_at=-5 if early else None)
+                                                  use_global=False, use_other=use_other, stop_at=-5 if early else None)
         pred = x0_preds[-5]                                                    # :108
-        x_output = rec(pred, hf_wav)                                           # :114-115, :124, :134
+        x_output = rec(pred, hf_wav if split else pred)                        # :114-115, :124, :134 (all bands diffused: the second source contributes nothing)
         H, W = x_output.shape[-2:]
         # the three pairs the reference prints: output, "cond" (IDWT(DWT(x)) == x: the input), HFRM image (restoration.py:146 clamps x_output_wdnet first)
         self._mark("main: sampler queued")
-        sums = torch.stack([imageio.sqdiff(gt, x_output), imageio.sqdiff(gt, inp), imageio.sqdiff(gt, hf.clamp(0.0, 1.0))])
+        pairs = [imageio.sqdiff(gt, x_output), imageio.sqdiff(gt, inp)]
+        if split:
+            pairs.append(imageio.sqdiff(gt, hf.clamp(0.0, 1.0)))
+        sums = torch.stack(pairs)
         if self._ssim:
             # args.ssim: SSIM(Y) of the output against its gt (utils/metrics.py:110-149 on the [0,255] clamp of :144), behind the sums in the same copy
             sums = torch.cat([sums.reshape(-1), metrics.ssim(gt, x_output, test_y_channel=True)])
@@ -239,7 +252,8 @@ class DiffusiveRestoration:
             for k, name in enumerate(names):
                 sl = slice(k, k + 1)
                 w.save(x_output[sl], os.path.join(image_folder, f"{name}_output.png"))
-                w.save(rec(pred[sl], x_gt[sl]), os.path.join(image_folder, f"{name}_lrdiff_hrgt.png"))         # :112-113
+                if use_other:
+                    w.save(rec(pred[sl], x_gt[sl]), os.path.join(image_folder, f"{name}_lrdiff_hrgt.png"))     # :112-113
         return dict(names=names, out=x_output, sums=sums_host, done=done, HW=(H, W), keep=(pinned, sums))
 
     def _finish_group(self, g, acc):
@@ -247,12 +261,16 @@ class DiffusiveRestoration:
         g["done"].synchronize()
         H, W = g["HW"]
         n = len(g["names"])
-        sums = g["sums"][:3 * n * 2].view(3, n, 2) if self._ssim else g["sums"]
-        m_out, m_cond, m_hf = (imageio.psnr_from_sums(sums[j], H, W) for j in range(3))
+        npair = 3 if self.config.model.pred_channels < self.config.model.in_channels else 2      # (no HFRM image when every band is diffused)
+        sums = g["sums"][:npair * n * 2].view(npair, n, 2) if self._ssim else g["sums"]
+        m = [imageio.psnr_from_sums(sums[j], H, W) for j in range(npair)]
+        m_out, m_cond, m_hf = m[0], m[1], (m[2] if npair == 3 else None)
         if self._ssim:
-            acc["ssim"] += g["sums"][3 * n * 2:].tolist()
+            acc["ssim"] += g["sums"][npair * n * 2:].tolist()
         for k, name in enumerate(g["names"]):
-            acc["torch"].append(m_out[k][0]); acc["y"].append(m_out[k][1]); acc["wdnet"].append(m_hf[k][1])
+            acc["torch"].append(m_out[k][0]); acc["y"].append(m_out[k][1])
+            if m_hf is not None:
+                acc["wdnet"].append(m_hf[k][1])
             print("psnr this", m_out[k][0])
             print("psnr cond", m_cond[k][0])
         return [g["out"][k:k + 1] for k in range(len(g["names"]))]
@@ -261,8 +279,10 @@ class DiffusiveRestoration:
         import queue
         import threading
         cfg, d = self.config, self.diffusion
-        if not (cfg.data.wavelet and not cfg.data.wavelet_in_unet and cfg.model.use_other_channels):
-            raise NotImplementedError("DiffusiveRestoration.restore: only the raindrop_wavelet.yml branch is accelerated")
+        if not (cfg.data.wavelet and not cfg.data.wavelet_in_unet):
+            raise NotImplementedError("DiffusiveRestoration.restore: only the data.wavelet / not data.wavelet_in_unet branch (raindrop_wavelet.yml) is accelerated")
+        if cfg.model.pred_channels > cfg.model.in_channels:
+            raise ValueError(f"model.pred_channels {cfg.model.pred_channels} exceeds the {cfg.model.in_channels} wavelet bands (model.in_channels)")
         image_folder = os.path.join(self.args.image_folder, cfg.data.dataset, validation)
         if os.environ.get("WAVEDM_RESTORE_TRACE", "0") == "1":
             import time
@@ -314,7 +334,8 @@ class DiffusiveRestoration:
             print("psnr all torch", float(np.mean(acc["torch"])))
             print("psnr all np", float(np.mean(acc["y"])))
             print("psnr all GPU", float(np.mean(acc["y"])))       # deliberately the same accumulator: the reference's numpy and torch Y-PSNR agree
-            print("psnr all wdnet", float(np.mean(acc["wdnet"])))
+            if acc["wdnet"]:                                      # restoration.py:167: only when an HFRM image exists (pred_channels < in_channels)
+                print("psnr all wdnet", float(np.mean(acc["wdnet"])))
             if self._ssim:
                 print("ssim all", float(np.mean(acc["ssim"])))
         self.last_outputs, self.last_psnrs, self.last_psnrs_y = outputs, acc["torch"], acc["y"]

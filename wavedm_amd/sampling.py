@@ -166,11 +166,46 @@ def graph_cache_clear():
     _GRAPHS = None
 
 
+class scatter_update_fns:
+    """The scatter-mean + DDIM update launches for `pc` prediction channels, with the argument lists of the 3-channel entry points.  pc == 3 (raindrop_wavelet.yml)
+    keeps the original kernels -- the shipped configuration runs what it always ran --, every other count goes to the channel-count entry points
+    (`wdm_ddim_update_c` ...: the coverage search confined to the image's span of the patch list and shared by up to four channels; the same bits at 3,
+    tests/test_gpu_pred_channels.py)."""
+
+    def __init__(self, L, h, pc):
+        self.L, self.h, self.pc = L, h, int(pc)
+
+    def update(self, eps, patches, n, p, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st):
+        if self.pc == 3:
+            _lib.check(self.L.wdm_ddim_update(self.h, eps, patches, n, p, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
+        else:
+            _lib.check(self.L.wdm_ddim_update_c(self.h, eps, patches, n, p, self.pc, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
+
+    def update_eta(self, eps, patches, n, p, xt, nimg, H, W, s1m, sa, san, c1, c2, noise, x0, xn, st):
+        if self.pc == 3:
+            _lib.check(self.L.wdm_ddim_update_eta(self.h, eps, patches, n, p, xt, nimg, H, W, s1m, sa, san, c1, c2, noise, x0, xn, st))
+        else:
+            _lib.check(self.L.wdm_ddim_update_eta_c(self.h, eps, patches, n, p, self.pc, xt, nimg, H, W, s1m, sa, san, c1, c2, noise, x0, xn, st))
+
+    def accumulate(self, eps, patches, n, p, nimg, H, W, acc_cnt, st):
+        if self.pc == 3:
+            _lib.check(self.L.wdm_patch_accumulate(self.h, eps, patches, n, p, nimg, H, W, acc_cnt, st))
+        else:
+            _lib.check(self.L.wdm_patch_accumulate_c(self.h, eps, patches, n, p, self.pc, nimg, H, W, acc_cnt, st))
+
+    def from_sums(self, acc_cnt, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st):
+        if self.pc == 3:
+            _lib.check(self.L.wdm_ddim_from_sums(self.h, acc_cnt, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
+        else:
+            _lib.check(self.L.wdm_ddim_from_sums_c(self.h, acc_cnt, xt, self.pc, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
+
+
 def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None, max_batch=64, keep="all", stop_at=None,
                 patch_group=None, streams=None, eta=0.0):
     """DDIM over `seq` (ascending list of timesteps) for NIMG images; eta = 0 (what every caller in the reference passes) is the deterministic sampler.
 
-    x (NIMG,3,H,W) start noise, x_cond (NIMG,48,H,W), x_other (NIMG,45,H,W): fp32 on the GPU.
+    x (NIMG,pc,H,W) start noise, x_cond (NIMG,48,H,W), x_other (NIMG,48 - other_channels_begin,H,W) or None: fp32 on the GPU.  pc = model.pred_channels is
+    read from x: 3 (raindrop_wavelet.yml), 12 (the whole coarse level), 48 (every band diffused, x_other None or empty) ... -- any count >= 1 the UNet was built for.
     corners: None -> every image is one p x p patch at (0,0) (p == H == W; the batched 64x64 case),
              or a list of (hi, wi) applied to EVERY image of the batch, like the reference's crops
              `x_cond[:, :, hi:hi+p, wi:wi+p]` (ddm_wavelet.py:467-478) -- image-major patch order, so each image's
@@ -207,8 +242,9 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
     ncond, nother = x_cond.shape[1], (x_other.shape[1] if x_other is not None else 0)      # x_other None: model.use_other_channels False
     cin = unet.in_channels
     assert ncond + pc + nother == cin, f"channel split {ncond}+{pc}+{nother} != UNet in_channels {cin}"
-    if pc != 3:        # wdm_ddim_update / wdm_patch_accumulate / wdm_ddim_from_sums scatter exactly 3 prediction channels per patch
-        raise NotImplementedError(f"ddim_sample: model.pred_channels = {pc}; the DDIM update kernels are built for 3 (raindrop_wavelet.yml)")
+    if pc < 1:
+        raise ValueError("ddim_sample: x has no prediction channels")
+    upd = scatter_update_fns(L, h, pc)
     with torch.cuda.device(dev):
         if corners is None:
             p = H
@@ -311,23 +347,22 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
                                 for i in range(lo, hi, max_batch):
                                     j = min(i + max_batch, hi)
                                     unet.forward_nhwc(x96[i:j], t_dev[k:k + 1], eps[i:j], temb_row=None if temb is None else temb[k], ws_slot=ci)
-                                _lib.check(L.wdm_ddim_update(h, _lib.ptr(eps[lo:hi]), None, hi - lo, p, _lib.ptr(xt[lo:hi]), hi - lo, H, W, s1m, sa, san, c2,
-                                                             _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc))
+                                upd.update(_lib.ptr(eps[lo:hi]), None, hi - lo, p, _lib.ptr(xt[lo:hi]), hi - lo, H, W, s1m, sa, san, c2,
+                                           _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc)
                     else:
                         if n:
                             _lib.check(L.wdm_pack_channels(h, _lib.ptr(xt), pc, H, W, pptr, n, p, _lib.ptr(x96), cin, ncond, unet._dtype_code, st))
                         for i in range(0, n, call_b):
                             unet.forward_nhwc(x96[i:i + call_b], t_dev[k:k + 1], eps[i:i + call_b], temb_row=None if temb is None else temb[k])
                         if sharded:
-                            _lib.check(L.wdm_patch_accumulate(h, _lib.ptr(eps), pptr, n, p, nimg, H, W, _lib.ptr(acc_cnt), st))
+                            upd.accumulate(_lib.ptr(eps), pptr, n, p, nimg, H, W, _lib.ptr(acc_cnt), st)      # sums | counts: 2 * NIMG * pc * H * W floats
                             dist.all_reduce(acc_cnt, op=dist.ReduceOp.SUM, group=grp)
-                            _lib.check(L.wdm_ddim_from_sums(h, _lib.ptr(acc_cnt), _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st))
+                            upd.from_sums(_lib.ptr(acc_cnt), _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st)
                         elif noise is not None:
-                            _lib.check(L.wdm_ddim_update_eta(h, _lib.ptr(eps), pptr, n, p, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c1, c2, _lib.ptr(noise),
-                                                             _lib.ptr(x0), _lib.ptr(xn), st))
+                            upd.update_eta(_lib.ptr(eps), pptr, n, p, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c1, c2, _lib.ptr(noise),
+                                           _lib.ptr(x0), _lib.ptr(xn), st)
                         else:
-                            _lib.check(L.wdm_ddim_update(h, _lib.ptr(eps), pptr, n, p, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2,
-                                                         _lib.ptr(x0), _lib.ptr(xn), st))
+                            upd.update(_lib.ptr(eps), pptr, n, p, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st)
                     # lists as the reference returns them; with `keep` given, what nobody asked for is dropped at once (inside a captured graph its memory is reused)
                     x0_preds.append(x0 if keep_set is None or (k - S) in keep_set else None)
                     xs.append(xn)

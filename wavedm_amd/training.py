@@ -110,7 +110,8 @@ class Trainer:
 
     # ---- one step ----------------------------------------------------------------------------------------------------
     def loss_and_grads(self, x0, t, e, return_output=False):
-        """x0 (B, 96, R, R) wavelet-domain [x_cond | x_tar | x_other]; t (B,) long; e (B, 3, R, R).  Fills self.grads; returns the
+        """x0 (B, Cin, R, R) wavelet-domain [x_cond | x_tar | x_other] (Cin = the UNet's input width, 96 for every other_channels_begin == pred_channels setting);
+        t (B,) long; e (B, pred_channels, R, R).  Fills self.grads; returns the
         loss as a 0-dim device tensor (and the network output when asked)."""
         x0 = _lib.require_cuda_f32(x0, "x0")
         e = _lib.require_cuda_f32(e, "e")
@@ -126,7 +127,7 @@ class Trainer:
             # ... plus the forward AND dgrad weight layouts of every conv, packed at the start of the step and kept for its whole length (train_unet.hip: pack_region):
             # about twice the parameter bytes in the model dtype -- without this term small batches took the double-and-retry path on every first step
             dsize = 2 if self._dtype_code == _lib.WDM_BF16 else 4
-            need = B * 96 * R * R * 4 * 160 + 2 * self._n_floats * dsize + (1 << 28)
+            need = B * Cc * R * R * 4 * 160 + 2 * self._n_floats * dsize + (1 << 28)
             if self._ws is None or self._ws.numel() < need:
                 self._ws = None
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -209,7 +210,7 @@ class Trainer:
                                                        _lib.stream_ptr()))
 
     def train_step(self, x0, group=None, generator=None):
-        """The body of the reference's loop for one batch of wavelet-domain samples x0 (B,96,R,R): noise, antithetic timesteps
+        """The body of the reference's loop for one batch of wavelet-domain samples x0 (B,Cin,R,R): noise (model.out_ch channels), antithetic timesteps
         (ddm_wavelet.py:249-256), loss, backward, all-reduce, Adam, EMA.  Returns the loss (device tensor)."""
         n = x0.shape[0]
         e = torch.randn((n, int(self.config.model.out_ch)) + tuple(x0.shape[2:]), device=self.device, generator=generator)
