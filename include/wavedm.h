@@ -299,6 +299,20 @@ int wdm_gn_act_backward(wdm_handle* h, const float* x, int C0, int C, const floa
                         int silu, int B, int H, int W, float* dx, float* dgamma, float* dbeta, int dtype, void* scratch,
                         size_t scratch_bytes, void* stream);
 
+/* Dropout of the training step (model.dropout; csrc/dropout.h).  No mask is stored: the kernels draw it from Philox4x32-10 with key = seed and
+ * counter = (e >> 3 low, e >> 3 high, layer, step) for the element index e = ((b H W) + pixel) C + c; element e takes 16-bit lane e & 7 of the call's
+ * 128 bits and is kept iff lane >= round(65536 p); kept elements are scaled by 65536 / (65536 - round(65536 p)).  layer = the ResnetBlock's position in
+ * wdm_trainer_param_info order (down, mid, up); step = the optimizer step being computed.
+ * wdm_dropout_mask: the factor (0 or the scale) of every element of a (B, C, H, W) tensor, fp32 NCHW (C a multiple of 8), from the device function the
+ * training kernels call.
+ * wdm_gn_act_dropout: y = factor * silu(GroupNorm(32, 1e-6)(x)) of one (B, C, H, W) tensor and its autograd, dy -> dx, dgamma, dbeta, on the kernels the
+ * training step launches for a ResnetBlock's norm2 (dtype: WDM_F32 or WDM_BF16).  p outside [0, 1) is WDM_EINVAL in all three. */
+int wdm_dropout_mask(wdm_handle* h, float p, int64_t seed, int64_t step, int layer, int B, int H, int W, int C, float* factor_nchw,
+                     void* stream);
+int wdm_gn_act_dropout(wdm_handle* h, const float* x, int C, const float* gamma, const float* beta, const float* dy, int B, int H, int W,
+                       float p, int64_t seed, int64_t step, int layer, float* y, float* dx, float* dgamma, float* dbeta, int dtype,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- training step object -----------------------------------------------------------
  * Replaces the body of DenoisingDiffusion_Wavelet.train's inner loop (models/ddm_wavelet.py:259-272) for the raindrop_wavelet.yml
  * branch: noise_estimation_loss (:108-124) forward + backward, torch.optim.Adam step (utils/optimize.py:5-8) and EMAHelper.update
@@ -318,6 +332,9 @@ int wdm_trainer_set_buffers(wdm_trainer* t, float* params, float* grads, float* 
 /* training.use_mse (ddm_wavelet.py:263-266): back-propagate mse_loss = mean_b sum (x_tar - x0_pred)^2 instead of the noise-space loss
  * (default 0).  *loss of wdm_trainer_step stays the noise-space value either way. */
 int wdm_trainer_set_objective(wdm_trainer* t, int use_mse);
+/* model.dropout: state of the handle, read by the next wdm_trainer_step calls.  step = the optimizer step those calls compute (the trainer's count + 1);
+ * p = 0 (the default) launches exactly the kernels of a model without dropout. */
+int wdm_trainer_set_dropout(wdm_trainer* t, float p, int64_t seed, int64_t step);
 int wdm_trainer_step(wdm_trainer* t, const float* x0, const float* tt, const float* sqrt_a, const float* sqrt_1ma, const float* e,
                      int B, int c_t0, float* loss, float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
 int wdm_trainer_adam_ema(wdm_trainer* t, int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay,

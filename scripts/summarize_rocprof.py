@@ -86,6 +86,9 @@ def _short(name: str) -> str:
     if m:
         a = [int(v) for v in re.findall(r"Li(\d+)E", m.group(2))]
         return f"convws_3x3s1_t{a[0]}x{a[1]}x{a[2]}_bn{16 * a[6] * a[4]}_{'bf16' if m.group(1) == 'DF16b' else 'f32'}"
+    m = re.match(r"_ZN3wdm\d+(gn_apply_kernel|gn_bwd_sums_kernel|gn_bwd_apply_kernel)I(?:DF16b|DF16_|f)Lb1E", name)
+    if m:                                            # training with model.dropout: the instantiations that draw the mask (csrc/dropout.h)
+        return m.group(1) + "<dropout>"
     m = re.match(r"_ZN3wdm\d+([A-Za-z0-9_]+?)(?:I|E)", name)
     if m:
         return m.group(1)

@@ -21,13 +21,14 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--cpu", action="store_true")
+    ap.add_argument("--dropout", type=float, default=0.0, help="model.dropout of the step (masks drawn in the GroupNorm kernels, csrc/dropout.h); 0: the plain step")
     ap.add_argument("--prof", action="store_true", help="one more step under the library's per-launch event profiler: per (kernel | shape) rows on stderr")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     cfg = P.raindrop_wavelet_config()
     cfg.device = dev
     sd = P.procedural_state_dict(cfg, seed=61)
-    tr = Trainer(cfg, dtype=a.dtype)
+    tr = Trainer(cfg, dtype=a.dtype, dropout=a.dropout, dropout_seed=3)
     tr.load_state_dict(sd)
     g = torch.Generator().manual_seed(1)
     x0 = torch.randn(a.batch, 96, 64, 64, generator=g).to(dev)
@@ -41,7 +42,7 @@ def main():
         loss = tr.train_step(x0, generator=gd)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.iters
-    out = {"what": "training step (loss + backward + Adam + EMA), raindrop_wavelet UNet 156.5 M params", "batch": a.batch, "dtype": a.dtype,
+    out = {"what": "training step (loss + backward + Adam + EMA), raindrop_wavelet UNet 156.5 M params", "batch": a.batch, "dtype": a.dtype, "dropout": a.dropout,
            "ms_per_step": dt * 1e3, "samples_per_s": a.batch / dt, "loss_first": losses[0], "loss_last": float(loss),
            # forward 80 GFLOP per sample, backward ~2x
            "approx_tflops": a.batch * 79.94e9 * 3 / dt / 1e12}

@@ -74,6 +74,8 @@ def main(argv=None):
         # parameters when it is built, as DistributedDataParallel does at construction, ddm_wavelet.py:168)
         reseed(args.seed + args.rank)
         diffusion.train(DATASET, max_steps=args.max_steps)
+        if args.rank == 0 and getattr(diffusion, "last_loss", None) is not None:
+            print(f"=> trained to step {diffusion.step}: last loss {float(diffusion.last_loss)}, every loss finite: {bool(diffusion.losses_finite)}")
         if args.world_size > 1:
             dist.destroy_process_group()
         return 0

@@ -8,6 +8,7 @@
 
 #include "../../include/wavedm.h"
 #include "conv_kernel.h"
+#include "dropout.h"
 
 namespace wdm {
 
@@ -153,8 +154,11 @@ bool gn_fused_pass_eligible(int C0, int C1, int dtype);
 int k_gn_finalize_apply(int B, const Tens& x0, const Tens* x1, const float* st0, int nslab0, const float* st1, int nslab1, const NormW& nw, float eps, int silu, void* y,
                         int dtype, hipStream_t s);
 // y[b][p][y_choff + c] = act(x*scale + shift); scale/shift rows are sc_ld long (channel concat: pass scale + C0), silu != 0 applies SiLU
+// drop (training, dense single-tensor output only: y_stride == x.C, y_choff == 0): the result is multiplied by the element's dropout factor (dropout.h)
+// before it is rounded; nullptr or a threshold of 0 launches the plain kernel
 int k_gn_apply(const Tens& x, int B, const float* scale, const float* shift, int sc_ld, void* y, int y_stride, int y_choff, int silu, int dtype,
-               hipStream_t s);
+               hipStream_t s, const Dropout* drop = nullptr);
+int k_dropout_mask(const Dropout& drop, int B, int H, int W, int C, float* factor_nchw, hipStream_t s);      // fp32 (B, C, H, W): 0 or the scale, every element
 int k_softmax_rows(const float* S, void* P, long long rows, int n, int dtype, hipStream_t s);
 int k_timestep_embedding(const float* t, int n_t, int dim, float* emb, hipStream_t s);
 // out[n][o] = post( W[o][:] . pre(in[n][:]) + b[o] );  act: 0 none, 1 SiLU on input, 2 SiLU on output
@@ -285,7 +289,7 @@ int conv_wgrad(Ctx& c, int mode, const Tens& x0, const Tens* x1, const Tens& dy,
                int dtemb_ld = 0);
 int colsum(Ctx& c, const Tens& dy, float* out, bool per_image, bool accumulate, int out_ld = 0);
 int gn_act_backward(Ctx& c, const NormW& nw, const Tens& x0, const Tens* x1, const float* mean_rstd, const Tens& dy, int silu, void* dx0, bool acc0, void* dx1,
-                    bool acc1, float* dgamma, float* dbeta, bool acc_param);
+                    bool acc1, float* dgamma, float* dbeta, bool acc_param, const Dropout* drop = nullptr);      // drop: y = factor * act(GroupNorm(x)) (dropout.h)
 // torch.optim.Adam (amsgrad = False) over n floats + EMAHelper.update when E != nullptr (train_unet.hip); step counts from 1.  The betas are
 // doubles: 1 - beta and the bias corrections are formed before rounding to fp32 (an fp32 0.999 leaves 1 - beta2 1.3e-5 off torch's value)
 int k_adam_ema(float* P, const float* G, float* M, float* V, float* E, long long n, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay,

@@ -616,9 +616,11 @@ int k_gn_finalize_apply(int B, const Tens& x0, const Tens* x1, const float* st0,
 // GroupNorm apply, optionally followed by SiLU: y = act(x*scale + shift).  Output pixel stride ys / channel offset via the y
 // pointer, scale/shift rows of length sc_ld: two calls materialise the channel concat of two tensors (AttnBlock.norm,
 // unet.py:169-170; the normalised+activated conv input of the 8x8 ResnetBlocks, unet.py:121-123 / 130-133).
-template <typename T>
+// DROP (training, ResnetBlock norm2: dense output, ys == C): the value is multiplied by its element's dropout factor (dropout.h) before it is rounded; the mask
+// is drawn here from the element index -- it is stored nowhere.  A template parameter: the plain instantiation is the code of the inference path.
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, int xs, int C, int HW, long long nvec, const float* __restrict__ scale,
-                                                       const float* __restrict__ shift, int sc_ld, T* __restrict__ y, int ys, int silu) {
+                                                       const float* __restrict__ shift, int sc_ld, T* __restrict__ y, int ys, int silu, DropArg<DROP> drop) {
     h16_mode_init<T>();
     constexpr int VEC = TI<T>::VEC;
     const int cols = C / VEC;
@@ -628,17 +630,65 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
         const long long b = bp / HW;
         const int c = col * VEC;
         const uint4 u = *(const uint4*)(x + bp * xs + c);
-        *(uint4*)(y + bp * ys + c) = gn_apply_vec<T>(u, scale + b * sc_ld + c, shift + b * sc_ld + c, silu);       // the arithmetic of the fused pass (gn_group.h)
+        if constexpr (DROP) {
+            float f[VEC], m[VEC];
+            TI<T>::unpack(u, f);
+            gn_act_f8<T>(f, scale + b * sc_ld + c, shift + b * sc_ld + c, silu);
+            dropout_factors<VEC>(drop.a, bp * ys + c, m);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) f[e] *= m[e];
+            *(uint4*)(y + bp * ys + c) = TI<T>::pack(f);
+        } else {
+            *(uint4*)(y + bp * ys + c) = gn_apply_vec<T>(u, scale + b * sc_ld + c, shift + b * sc_ld + c, silu);       // the arithmetic of the fused pass (gn_group.h)
+        }
     }
 }
 int k_gn_apply(const Tens& x, int B, const float* scale, const float* shift, int sc_ld, void* y, int y_stride, int y_choff, int silu, int dtype,
-               hipStream_t s) {
+               hipStream_t s, const Dropout* drop) {
     const int HW = x.H * x.W;
     const int vec = is_h16(dtype) ? 8 : 4;
     const long long nvec = (long long)B * HW * (x.C / vec);
     const int g = nblocks(nvec, 256) > 16384 ? 16384 : nblocks(nvec, 256);
-    if (is_h16(dtype)) WDM_H16_SWITCH(dtype, hipLaunchKernelGGL(gn_apply_kernel<H16>, dim3(g), dim3(256), 0, s, (const H16*)x.p, x.xs, x.C, HW, nvec, scale, shift, sc_ld, (H16*)y + y_choff, y_stride, silu));
-    else hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)x.p, x.xs, x.C, HW, nvec, scale, shift, sc_ld, (float*)y + y_choff, y_stride, silu);
+    if (drop && dropout_threshold(drop->p) > 0) {
+        // the element index e = (b HW + pixel) C + c is the index into the dense output
+        if (y_stride != x.C || y_choff != 0 || x.C % 32) WDM_FAIL(WDM_EINVAL, "groupnorm + dropout: the output must be the dense tensor of one %d-channel input", x.C);
+        const DropArg<true> da{dropout_args(*drop)};
+        const bool prof = prof_enabled();
+        if (prof) {
+            char name[64];
+            snprintf(name, sizeof(name), "gn_apply_kernel<dropout>|%dx%d C=%d", x.H, x.W, x.C);
+            prof_begin(s, name, 0.0, 2.0 * B * HW * x.C * (double)dsize(dtype));
+        }
+        if (is_h16(dtype)) WDM_H16_SWITCH(dtype, hipLaunchKernelGGL((gn_apply_kernel<H16, true>), dim3(g), dim3(256), 0, s, (const H16*)x.p, x.xs, x.C, HW, nvec, scale, shift, sc_ld, (H16*)y, y_stride, silu, da));
+        else hipLaunchKernelGGL((gn_apply_kernel<float, true>), dim3(g), dim3(256), 0, s, (const float*)x.p, x.xs, x.C, HW, nvec, scale, shift, sc_ld, (float*)y, y_stride, silu, da);
+        if (prof) prof_end(s);
+        WDM_HIP(hipGetLastError());
+        return WDM_OK;
+    }
+    if (is_h16(dtype)) WDM_H16_SWITCH(dtype, hipLaunchKernelGGL(gn_apply_kernel<H16>, dim3(g), dim3(256), 0, s, (const H16*)x.p, x.xs, x.C, HW, nvec, scale, shift, sc_ld, (H16*)y + y_choff, y_stride, silu, DropArg<false>{}));
+    else hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)x.p, x.xs, x.C, HW, nvec, scale, shift, sc_ld, (float*)y + y_choff, y_stride, silu, DropArg<false>{});
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
+// the factor (0 or the scale) of every element of a (B, C, H, W) tensor, written in NCHW fp32: the masks the three dropout kernels draw, for tests and for
+// Trainer.dropout_masks.  One thread per Philox call = eight consecutive NHWC elements (C % 8 == 0: one pixel).
+__global__ __launch_bounds__(256) void dropout_mask_kernel(DropoutArgs d, int C, int HW, long long ngroups, float* __restrict__ out) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ngroups) return;
+    const long long e0 = g * 8, bp = e0 / C;
+    const int c = (int)(e0 - bp * C);
+    const long long b = bp / HW;
+    const int p = (int)(bp - b * HW);
+    float m[8];
+    dropout_factors<8>(d, e0, m);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[(b * C + c + e) * HW + p] = m[e];
+}
+int k_dropout_mask(const Dropout& drop, int B, int H, int W, int C, float* factor_nchw, hipStream_t s) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) WDM_FAIL(WDM_EINVAL, "dropout mask: bad shape (%d, %d, %d, %d); C must be a multiple of 8", B, C, H, W);
+    const long long ngroups = (long long)B * H * W * C / 8;
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((ngroups + 255) / 256)), dim3(256), 0, s, dropout_args(drop), C, H * W, ngroups, factor_nchw);
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }

@@ -79,7 +79,7 @@ __device__ __forceinline__ void gn_scale_shift(float mean, float rstd, float gam
 }
 // act(x * scale + shift) of one 16-byte vector; sc / sh point at the vector's first channel (LDS or global)
 template <typename T>
-__device__ __forceinline__ uint4 gn_apply_f8(float* f, const float* sc, const float* sh, int silu) {
+__device__ __forceinline__ void gn_act_f8(float* f, const float* sc, const float* sh, int silu) {      // the values before they are packed
     constexpr int VEC = TI<T>::VEC;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) f[e] = __builtin_fmaf(f[e], sc[e], sh[e]);
@@ -89,6 +89,10 @@ __device__ __forceinline__ uint4 gn_apply_f8(float* f, const float* sc, const fl
 #pragma unroll
         for (int e = 0; e < VEC; ++e) f[e] = VEC == 8 ? f[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-f[e])) : f[e] / (1.0f + __expf(-f[e]));
     }
+}
+template <typename T>
+__device__ __forceinline__ uint4 gn_apply_f8(float* f, const float* sc, const float* sh, int silu) {
+    gn_act_f8<T>(f, sc, sh, silu);
     return TI<T>::pack(f);
 }
 template <typename T>

@@ -266,10 +266,12 @@ __global__ __launch_bounds__(256) void pad_channels_kernel(const T* __restrict__
 //   (3) apply:    dx = rstd (dv g - ma - xh mb)                                                    [gn_bwd_apply_kernel]
 // x = [x0 | x1] (channel concat), dy dense [B][HW][C]; dx0 / dx1 dense per source, optionally accumulated into.
 // grid (nslab, B, column blocks): 256 threads = (pixel rows) x (16-byte channel vectors); partial[b][slab][c] = {sum dv xh, sum dv}
-template <typename T>
+// DROP (y = factor * act(.), the ResnetBlocks' norm2 with model.dropout): dv = dy * factor(e) * silu'(pre) in (1) and (3), the factor drawn from the index
+// e = (b HW + p) C + c of dy's element (dropout.h) -- the mask of the forward pass, recomputed like silu'.  A template parameter: the plain instantiations are unchanged.
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(256) void gn_bwd_sums_kernel(const T* __restrict__ x0, int xs0, int C0, const T* __restrict__ x1, int xs1, int C, int HW, int nslab,
                                                           const T* __restrict__ dy, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          const float* __restrict__ mean_rstd, int silu, float2* __restrict__ partial) {
+                                                          const float* __restrict__ mean_rstd, int silu, float2* __restrict__ partial, DropArg<DROP> drop) {
     constexpr int VEC = TI<T>::VEC;
     __shared__ float red[256 * VEC * 2];
     const int cols = C / VEC;
@@ -305,6 +307,12 @@ __global__ __launch_bounds__(256) void gn_bwd_sums_kernel(const T* __restrict__ 
             const uint4 ud = *(const uint4*)(dy + bp * C + c);
             TI<T>::unpack(ux, xh);
             TI<T>::unpack(ud, dv);
+            if constexpr (DROP) {
+                float m[VEC];
+                dropout_factors<VEC>(drop.a, bp * C + c, m);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) dv[e] *= m[e];
+            }
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
                 xh[e] = (xh[e] - mean[e]) * rstd[e];
@@ -376,11 +384,11 @@ __global__ __launch_bounds__(256) void gn_bwd_param_kernel(const float* __restri
 // elementwise over (image, pixel, 16-byte channel vector).  grid (pixel chunks, B, column blocks): a thread keeps ONE channel vector -- its group statistics,
 // gamma and beta live in registers, and no index in the pixel loop divides by a run-time value (the first form did eleven such divisions per vector and ran
 // at a fifth of the memory rate).  Same arithmetic per element.
-template <typename T>
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__ x0, int xs0, int C0, const T* __restrict__ x1, int xs1, int C, int HW,
                                                            const T* __restrict__ dy, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const float* __restrict__ mean_rstd, const float* __restrict__ mab, int silu, T* __restrict__ dx0, int acc0,
-                                                           T* __restrict__ dx1, int acc1) {
+                                                           T* __restrict__ dx1, int acc1, DropArg<DROP> drop) {
     constexpr int VEC = TI<T>::VEC;
     const int cols = C / VEC, gw = C / 32, C1 = C - C0;
     const int cb = blockIdx.z;
@@ -412,6 +420,12 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
         float xh[VEC], dv[VEC], d[VEC];
         TI<T>::unpack(ux, xh);
         TI<T>::unpack(ud, dv);
+        if constexpr (DROP) {
+            float m[VEC];
+            dropout_factors<VEC>(drop.a, bp * C + c, m);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) dv[e] *= m[e];
+        }
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float h = (xh[e] - mean[e]) * rstd[e];
@@ -435,14 +449,19 @@ __global__ __launch_bounds__(256) void zero2_kernel(unsigned char* __restrict__ 
         if (i < n0) p0[i] = 0; else p1[i - n0] = 0;
     }
 }
-template <typename T>
+template <typename T, bool DROP = false>
 static void l_gn_act_bwd(hipStream_t s, int B, const void* x0, int xs0, int C0, const void* x1, int xs1, int C, int HW, const void* dy, const float* g, const float* bta,
                          const float* mr, int silu, void* dx0, int acc0, void* dx1, int acc1, float* dgp, float* dbp, float2* partial, int nslab, float* mab,
-                         float* dgamma, float* dbeta, int acc_param) {
+                         float* dgamma, float* dbeta, int acc_param, DropArg<DROP> drop = {}) {
     constexpr int VEC = TI<T>::VEC;
     const int cols = C / VEC;
-    hipLaunchKernelGGL(gn_bwd_sums_kernel<T>, dim3(nslab, B, (cols + 255) / 256), dim3(256), 0, s, (const T*)x0, xs0, C0, (const T*)x1, xs1, C, HW, nslab, (const T*)dy, g,
-                       bta, mr, silu, partial);
+    const bool prof = DROP && prof_enabled();      // (the plain form has never been timed per launch: its launches stay as they are)
+    char name[64];
+    const double tensor_bytes = (double)B * HW * C * sizeof(T);
+    if (prof) { snprintf(name, sizeof(name), "gn_bwd_sums_kernel<dropout>|%d px C=%d", HW, C); prof_begin(s, name, 0.0, 2.0 * tensor_bytes); }
+    hipLaunchKernelGGL((gn_bwd_sums_kernel<T, DROP>), dim3(nslab, B, (cols + 255) / 256), dim3(256), 0, s, (const T*)x0, xs0, C0, (const T*)x1, xs1, C, HW, nslab, (const T*)dy, g,
+                       bta, mr, silu, partial, drop);
+    if (prof) prof_end(s);
     hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(32, B), dim3(256), 0, s, partial, nslab, B, C, HW, g, dgp, dbp, mab);
     hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((2 * C * 8 + 255) / 256), dim3(256), 0, s, dgp, dbp, B, C, dgamma, dbeta, acc_param);
     {
@@ -450,9 +469,18 @@ static void l_gn_act_bwd(hipStream_t s, int B, const void* x0, int xs0, int C0, 
         const int rows = 256 / (cols < 256 ? cols : 256);
         int chunks = (HW + rows * 4 - 1) / (rows * 4);            // ~four vectors per thread
         if (chunks < 1) chunks = 1;
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3(chunks, B, cblocks), dim3(256), 0, s, (const T*)x0, xs0, C0, (const T*)x1, xs1, C, HW, (const T*)dy, g, bta, mr, mab,
-                           silu, (T*)dx0, acc0, (T*)dx1, acc1);
+        if (prof) { snprintf(name, sizeof(name), "gn_bwd_apply_kernel<dropout>|%d px C=%d", HW, C); prof_begin(s, name, 0.0, (acc0 ? 4.0 : 3.0) * tensor_bytes); }
+        hipLaunchKernelGGL((gn_bwd_apply_kernel<T, DROP>), dim3(chunks, B, cblocks), dim3(256), 0, s, (const T*)x0, xs0, C0, (const T*)x1, xs1, C, HW, (const T*)dy, g, bta, mr, mab,
+                           silu, (T*)dx0, acc0, (T*)dx1, acc1, drop);
+        if (prof) prof_end(s);
     }
+}
+// (an adapter: BY_DTYPE names a template of one argument)
+template <typename T>
+static void l_gn_act_bwd_drop(hipStream_t s, int B, const void* x0, int xs0, int C0, const void* x1, int xs1, int C, int HW, const void* dy, const float* g, const float* bta,
+                              const float* mr, int silu, void* dx0, int acc0, void* dx1, int acc1, float* dgp, float* dbp, float2* partial, int nslab, float* mab,
+                              float* dgamma, float* dbeta, int acc_param, DropoutArgs da) {
+    l_gn_act_bwd<T, true>(s, B, x0, xs0, C0, x1, xs1, C, HW, dy, g, bta, mr, silu, dx0, acc0, dx1, acc1, dgp, dbp, partial, nslab, mab, dgamma, dbeta, acc_param, DropArg<true>{da});
 }
 
 static int kalign(int dtype) { return dtype == WDM_BF16 ? 32 : 16; }
@@ -875,8 +903,9 @@ int colsum(Ctx& c, const Tens& dy, float* out, bool per_image, bool accumulate, 
 
 // GroupNorm (+SiLU) backward over [x0 | x1]; mean_rstd from the forward's finalize.  dgamma / dbeta (+)= batch sums.
 int gn_act_backward(Ctx& c, const NormW& nw, const Tens& x0, const Tens* x1, const float* mean_rstd, const Tens& dy, int silu, void* dx0, bool acc0, void* dx1,
-                    bool acc1, float* dgamma, float* dbeta, bool acc_param) {
+                    bool acc1, float* dgamma, float* dbeta, bool acc_param, const Dropout* drop) {
     const int C = x0.C + (x1 ? x1->C : 0), HW = x0.H * x0.W;
+    const bool dropping = drop && dropout_threshold(drop->p) > 0;
     const int vec = c.dtype == WDM_BF16 ? 8 : 4;
     if (C % 32 || x0.C % vec || C % vec) WDM_FAIL(WDM_EINVAL, "GroupNorm backward: %d (+%d) channels unsupported", x0.C, C - x0.C);
     // slabs: at most ~4 pixel iterations per thread (8 x 8 maps with hundreds of channels would otherwise run B long-latency workgroups)
@@ -891,8 +920,12 @@ int gn_act_backward(Ctx& c, const NormW& nw, const Tens& x0, const Tens* x1, con
     if (!c.dry) {
         float* slabs = part + (size_t)2 * c.B * C;
         float* mab = slabs + (size_t)2 * c.B * nslab * C;
-        BY_DTYPE(c.dtype, l_gn_act_bwd, c.s, c.B, x0.p, x0.xs, x0.C, x1 ? x1->p : x0.p, x1 ? x1->xs : 0, C, HW, dy.p, nw.g, nw.b, mean_rstd, silu, dx0, acc0 ? 1 : 0,
-                 x1 ? dx1 : dx0, acc1 ? 1 : 0, part, part + (size_t)c.B * C, (float2*)slabs, nslab, mab, dgamma, dbeta, acc_param ? 1 : 0);
+        if (dropping)
+            BY_DTYPE(c.dtype, l_gn_act_bwd_drop, c.s, c.B, x0.p, x0.xs, x0.C, x1 ? x1->p : x0.p, x1 ? x1->xs : 0, C, HW, dy.p, nw.g, nw.b, mean_rstd, silu, dx0, acc0 ? 1 : 0,
+                     x1 ? dx1 : dx0, acc1 ? 1 : 0, part, part + (size_t)c.B * C, (float2*)slabs, nslab, mab, dgamma, dbeta, acc_param ? 1 : 0, dropout_args(*drop));
+        else
+            BY_DTYPE(c.dtype, l_gn_act_bwd, c.s, c.B, x0.p, x0.xs, x0.C, x1 ? x1->p : x0.p, x1 ? x1->xs : 0, C, HW, dy.p, nw.g, nw.b, mean_rstd, silu, dx0, acc0 ? 1 : 0,
+                     x1 ? dx1 : dx0, acc1 ? 1 : 0, part, part + (size_t)c.B * C, (float2*)slabs, nslab, mab, dgamma, dbeta, acc_param ? 1 : 0);
         WDM_HIP(hipGetLastError());
     }
     c.ar->free(part);
@@ -981,4 +1014,44 @@ extern "C" int wdm_gn_act_backward(wdm_handle* h, const float* x, int C0, int C,
         if (C1) { Tens o1; o1.p = d1; o1.C = C1; o1.H = H; o1.W = W; o1.xs = C1; WDM_TRY(k_gn_apply(o1, B, sc, sh, C, dfull, C, C0, 0, dtype, c.s)); }
     }
     return k_nhwc_to_nchw(dfull, dx, B, C, H, W, dtype, c.s);
+}
+
+// GroupNorm + SiLU + dropout of ONE (B, C, H, W) tensor, forward and backward, on the kernels the training step launches for a ResnetBlock's norm2:
+// y = factor * silu(GroupNorm(x)); dx, dgamma, dbeta from dy.  The mask is that of (p, seed, step, layer) (wdm_dropout_mask).
+extern "C" int wdm_gn_act_dropout(wdm_handle* h, const float* x, int C, const float* gamma, const float* beta, const float* dy, int B, int H, int W, float p, int64_t seed,
+                                  int64_t step, int layer, float* y, float* dx, float* dgamma, float* dbeta, int dtype, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!h || !x || !gamma || !beta || !dy || !y || !dx || !dgamma || !dbeta || !scratch) WDM_FAIL(WDM_EINVAL, "wdm_gn_act_dropout: null argument");
+    if (C <= 0 || C % 32 || B <= 0 || H <= 0 || W <= 0) WDM_FAIL(WDM_EINVAL, "wdm_gn_act_dropout: bad shape (C must be a multiple of 32)");
+    if (dtype != WDM_F32 && dtype != WDM_BF16) WDM_FAIL(WDM_EINVAL, "wdm_gn_act_dropout: dtype must be f32 or bf16 (the training modes)");
+    if (!(p >= 0.f && p < 1.f)) WDM_FAIL(WDM_EINVAL, "wdm_gn_act_dropout: p = %g outside [0, 1)", (double)p);
+    Arena ar(scratch, scratch_bytes);
+    Ctx c{(hipStream_t)stream, dtype, B, &ar, false};
+    const size_t es = dsize(dtype), n = (size_t)B * H * W * C;
+    const int HW = H * W, ns = gn_default_nslab(HW);
+    Tens tx, tdy, ty;
+    tx.p = ar.alloc(n * es); tx.C = C; tx.H = H; tx.W = W; tx.xs = C;
+    tdy = tx; tdy.p = ar.alloc(n * es);
+    ty = tx; ty.p = ar.alloc(n * es);
+    void* tdx = ar.alloc(n * es);
+    float* mr = (float*)ar.alloc((size_t)B * 64 * sizeof(float));
+    float *sc = (float*)ar.alloc((size_t)B * C * 4), *sh = (float*)ar.alloc((size_t)B * C * 4);
+    float* st = (float*)ar.alloc(gn_stats_bytes(B, ns, C));
+    if (!tx.p || !tdy.p || !ty.p || !tdx || !mr || !sc || !sh || !st) WDM_FAIL(WDM_ENOMEM, "wdm_gn_act_dropout: scratch too small");
+    Dropout d; d.p = p; d.seed = seed; d.layer = layer; d.step = step;
+    NormW nw; nw.g = gamma; nw.b = beta; nw.c = C;
+    WDM_TRY(k_nchw_to_nhwc(x, tx.p, B, C, H, W, dtype, c.s));
+    WDM_TRY(k_nchw_to_nhwc(dy, tdy.p, B, C, H, W, dtype, c.s));
+    WDM_TRY(k_gn_partial(tx, B, st, ns, dtype, c.s));
+    WDM_TRY(k_gn_finalize(B, HW, st, ns, C, nullptr, ns, 0, nw, 1e-6f, 0, sc, sh, c.s, mr));
+    WDM_TRY(k_gn_apply(tx, B, sc, sh, C, ty.p, C, 0, 1, dtype, c.s, &d));
+    WDM_TRY(k_nhwc_to_nchw(ty.p, y, B, C, H, W, dtype, c.s));
+    WDM_TRY(gn_act_backward(c, nw, tx, nullptr, mr, tdy, 1, tdx, false, nullptr, false, dgamma, dbeta, false, &d));
+    return k_nhwc_to_nchw(tdx, dx, B, C, H, W, dtype, c.s);
+}
+
+extern "C" int wdm_dropout_mask(wdm_handle* h, float p, int64_t seed, int64_t step, int layer, int B, int H, int W, int C, float* factor_nchw, void* stream) {
+    if (!h || !factor_nchw) WDM_FAIL(WDM_EINVAL, "wdm_dropout_mask: null argument");
+    if (!(p >= 0.f && p < 1.f)) WDM_FAIL(WDM_EINVAL, "wdm_dropout_mask: p = %g outside [0, 1)", (double)p);
+    Dropout d; d.p = p; d.seed = seed; d.layer = layer; d.step = step;
+    return k_dropout_mask(d, B, H, W, C, factor_nchw, (hipStream_t)stream);
 }

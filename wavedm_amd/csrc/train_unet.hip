@@ -2,7 +2,8 @@
 // (reference: models/ddm_wavelet.py:108-124 loss, :259-272 optimiser step, :34-60 EMAHelper, utils/optimize.py:5-8).
 //
 // The forward pass here is the inference graph un-fused: every GroupNorm+SiLU output, every conv output and the attention
-// intermediates are materialised and kept (dropout is 0 in raindrop_wavelet.yml, so train() and eval() compute the same function);
+// intermediates are materialised and kept (with model.dropout == 0, as in raindrop_wavelet.yml, train() and eval() compute the same function; with dropout the
+// ResnetBlocks' silu(norm2(.)) is masked inside the GroupNorm kernels, forward and backward, from a counter-based generator: dropout.h, wdm_trainer_set_dropout);
 // each op pushes a closure on a tape, the backward pass runs the tape in reverse.  Contractions run on the forward conv kernels
 // (train.hip: dgrad = conv with transposed weights, wgrad = batched pixel-contraction GEMMs).  Parameters, gradients, Adam moments
 // and the EMA shadow are five flat fp32 buffers with one layout (wdm_trainer_param_info), so the optimiser is one elementwise kernel
@@ -207,7 +208,7 @@ namespace {
 struct PInfo { std::string name; int ndim; int64_t shape[4]; size_t off; };
 struct ConvP { size_t w = 0, b = 0; int cin = 0, cout = 0, k = 0; };
 struct NormP { size_t g = 0, b = 0; int c = 0; };
-struct ResP { int cin, cout; NormP n1, n2; ConvP c1, c2, nin; bool has_nin; int temb_row; };
+struct ResP { int cin, cout; NormP n1, n2; ConvP c1, c2, nin; bool has_nin; int temb_row; int layer; };      // layer: position in add_res order (the dropout counter)
 struct AttnP { int c; NormP n; ConvP q, k, v, proj; };
 struct TT { Tens t; void* g = nullptr; bool gset = false; bool needs_grad = true; };
 }  // namespace
@@ -219,6 +220,8 @@ struct wdm_trainer {
     size_t nfloats = 0;
     float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *E = nullptr;
     bool use_mse = false;     // training.use_mse: differentiate the x0-space loss instead of the noise-space one
+    Dropout dropout;          // model.dropout of the next step (wdm_trainer_set_dropout): p, seed and the optimizer step it computes; layer is filled per block
+    int n_res = 0;
     // layers
     size_t d0w, d0b, d1w, d1b, tw, tb;
     ConvP conv_in, conv_out;
@@ -253,7 +256,7 @@ struct wdm_trainer {
     NormP add_norm(const std::string& n, int cc) { NormP p; p.c = cc; p.g = take(n + ".weight", {cc}); p.b = take(n + ".bias", {cc}); return p; }
     std::vector<std::pair<std::string, int>> temb_list;
     ResP add_res(const std::string& n, int cin, int cout) {
-        ResP r; r.cin = cin; r.cout = cout; r.has_nin = cin != cout;
+        ResP r; r.cin = cin; r.cout = cout; r.has_nin = cin != cout; r.layer = n_res++;
         r.n1 = add_norm(n + ".norm1", cin);
         r.c1 = add_conv(n + ".conv1", cin, cout, 3);
         r.temb_row = temb_rows; temb_rows += cout; temb_list.push_back({n + ".temb_proj", cout});
@@ -280,7 +283,7 @@ struct wdm_trainer {
     }
     Tens gtens(TT* t) { Tens d = t->t; d.p = t->g; d.xs = d.C; d.stats = nullptr; return d; }
     int op_conv(const ConvP& p, int mode, TT* x0, TT* x1, int temb_row, TT* res, TT** out);
-    int op_gn_act(const NormP& p, TT* x0, TT* x1, int silu, TT** out);
+    int op_gn_act(const NormP& p, TT* x0, TT* x1, int silu, TT** out, const Dropout* drop = nullptr);
     int op_resblock(const ResP& r, TT* x0, TT* x1, TT** out);
     int op_attn(const AttnP& a, TT* x, TT** out);
     int step(Ctx& cc, const float* x0, const float* t, const float* sa, const float* s1m, const float* e, int c_t0, float* loss, float* out_nchw);
@@ -370,8 +373,8 @@ int wdm_trainer::op_conv(const ConvP& p, int mode, TT* x0, TT* x1, int temb_row,
     return WDM_OK;
 }
 
-// y = act(GroupNorm([x0 | x1]))  (dense)
-int wdm_trainer::op_gn_act(const NormP& p, TT* x0, TT* x1, int silu, TT** out) {
+// y = act(GroupNorm([x0 | x1]))  (dense); drop (single input): y = factor * act(.), the same description to the forward kernel and to the tape entry
+int wdm_trainer::op_gn_act(const NormP& p, TT* x0, TT* x1, int silu, TT** out, const Dropout* drop) {
     Ctx& cx = *c;
     const int C = x0->t.C + (x1 ? x1->t.C : 0), HW = x0->t.H * x0->t.W;
     NormW nw; nw.g = P + p.g; nw.b = P + p.b; nw.c = C;
@@ -390,22 +393,26 @@ int wdm_trainer::op_gn_act(const NormP& p, TT* x0, TT* x1, int silu, TT** out) {
     if (own0) WDM_TRY(k_gn_partial(x0->t, cx.B, st0, ns, cx.dtype, cx.s));
     if (own1) WDM_TRY(k_gn_partial(x1->t, cx.B, st1, ns, cx.dtype, cx.s));
     WDM_TRY(k_gn_finalize(cx.B, HW, st0, ns0, x0->t.C, st1, ns1, x1 ? x1->t.C : 0, nw, 1e-6f, 0, sc, sh, cx.s, mr));
-    WDM_TRY(k_gn_apply(x0->t, cx.B, sc, sh, C, o->t.p, C, 0, silu, cx.dtype, cx.s));
+    if (drop && x1) WDM_FAIL(WDM_EINVAL, "training: dropout behind a GroupNorm over a channel concat is not built");
+    WDM_TRY(k_gn_apply(x0->t, cx.B, sc, sh, C, o->t.p, C, 0, silu, cx.dtype, cx.s, drop));
     if (x1) WDM_TRY(k_gn_apply(x1->t, cx.B, sc + x0->t.C, sh + x0->t.C, C, o->t.p, C, x0->t.C, silu, cx.dtype, cx.s));
     cx.ar->free(sh); cx.ar->free(sc);
     if (own1) cx.ar->free(st1);
     if (own0) cx.ar->free(st0);
     *out = o;
     const NormP pp = p;
+    const bool has_drop = drop != nullptr;
+    const Dropout dd = drop ? *drop : Dropout{};
     tape_rng.push_back({(long long)std::min(pp.g, pp.b), (long long)std::max(pp.g, pp.b) + C});
-    tape.push_back([this, pp, x0, x1, silu, o, mr, C]() -> int {
+    tape.push_back([this, pp, x0, x1, silu, o, mr, C, has_drop, dd]() -> int {
         Ctx& cx = *c;
         if (!o->g) WDM_FAIL(WDM_ESTATE, "backward: GroupNorm output without gradient");
         NormW nw; nw.g = P + pp.g; nw.b = P + pp.b; nw.c = C;
         bool f0 = true, f1 = true;
         WDM_TRY(grad_buf(x0, &f0));
         if (x1) WDM_TRY(grad_buf(x1, &f1));
-        return gn_act_backward(cx, nw, x0->t, x1 ? &x1->t : nullptr, mr, gtens(o), silu, x0->g, !f0, x1 ? x1->g : nullptr, !f1, G + pp.g, G + pp.b, false);
+        return gn_act_backward(cx, nw, x0->t, x1 ? &x1->t : nullptr, mr, gtens(o), silu, x0->g, !f0, x1 ? x1->g : nullptr, !f1, G + pp.g, G + pp.b, false,
+                               has_drop ? &dd : nullptr);
     });
     return WDM_OK;
 }
@@ -414,7 +421,9 @@ int wdm_trainer::op_resblock(const ResP& r, TT* x0, TT* x1, TT** out) {
     TT *a1, *h1, *a2, *sc = nullptr;
     WDM_TRY(op_gn_act(r.n1, x0, x1, 1, &a1));
     WDM_TRY(op_conv(r.c1, MODE_S1, a1, nullptr, r.temb_row, nullptr, &h1));
-    WDM_TRY(op_gn_act(r.n2, h1, nullptr, 1, &a2));
+    Dropout d = dropout;      // h = conv2(dropout(silu(norm2(h)))) (unet.py:129): this block's counters
+    d.layer = r.layer;
+    WDM_TRY(op_gn_act(r.n2, h1, nullptr, 1, &a2, d.p > 0.f ? &d : nullptr));
     if (r.has_nin) WDM_TRY(op_conv(r.nin, MODE_P1, x0, x1, -1, nullptr, &sc));
     else if (x1) WDM_FAIL(WDM_EINVAL, "resblock: identity shortcut cannot take a concat input");
     return op_conv(r.c2, MODE_S1, a2, nullptr, -1, r.has_nin ? sc : x0, out);
@@ -676,6 +685,13 @@ int wdm_trainer_set_buffers(wdm_trainer* t, float* params, float* grads, float* 
 int wdm_trainer_set_objective(wdm_trainer* t, int use_mse) {
     if (!t) WDM_FAIL(WDM_EINVAL, "wdm_trainer_set_objective: null trainer");
     t->use_mse = use_mse != 0;
+    return WDM_OK;
+}
+// model.dropout of the next wdm_trainer_step calls (include/wavedm.h): p, the seed and the optimizer step that is being computed
+int wdm_trainer_set_dropout(wdm_trainer* t, float p, int64_t seed, int64_t step) {
+    if (!t) WDM_FAIL(WDM_EINVAL, "wdm_trainer_set_dropout: null trainer");
+    if (!(p >= 0.f && p < 1.f)) WDM_FAIL(WDM_EINVAL, "wdm_trainer_set_dropout: p = %g outside [0, 1)", (double)p);
+    t->dropout.p = p; t->dropout.seed = seed; t->dropout.step = step; t->dropout.layer = 0;
     return WDM_OK;
 }
 // Gradient buckets (include/wavedm.h): events the next steps record as the flat gradient buffer fills from its end; the bounds of the last step.

@@ -116,6 +116,8 @@ class DenoisingDiffusion_Wavelet(object):
         self.model.load_state_dict(sd, strict=True)
         self.ema_shadow = ckpt.get("ema_helper")
         self.optimizer_state = ckpt.get("optimizer")                            # restored into the trainer (ddm_wavelet.py:186)
+        self.dropout_seed = ckpt.get("dropout_seed")                            # Trainer.save_checkpoint's extra key (None: a checkpoint without it)
+        self._resumed = True
         if ema and self.ema_shadow is not None:                                # EMAHelper.ema, ddm_wavelet.py:55-60
             with torch.no_grad():
                 for name, p in self.model.named_parameters():
@@ -142,7 +144,10 @@ class DenoisingDiffusion_Wavelet(object):
         if osd:                                                                 # --resume: Adam moments and step count (ddm_wavelet.py:186)
             tr.load_optimizer_state_dict(osd)
             tr.step = self.step = max(tr.step, self.step)
+        if getattr(self, "_resumed", False) and "dropout_seed" not in kw:
+            tr.restore_dropout_seed(getattr(self, "dropout_seed", None))        # the masks of step n depend on (seed, n) alone: the resumed run draws what the first would have
         tr.broadcast_state(src=0)                                               # DDP's construction-time broadcast (ddm_wavelet.py:168)
+        tr.announce_dropout_seed()
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and os.environ.get("WAVEDM_GRAD_BUCKETS", "8") != "0":
             # ... and its bucketed gradient all-reduce that overlaps the backward (Trainer.allreduce_grads_overlapped); WAVEDM_GRAD_BUCKETS=0: one flat all-reduce
@@ -208,6 +213,9 @@ class DenoisingDiffusion_Wavelet(object):
         for epoch in range(self.start_epoch, self.config.training.n_epochs):
             for i, (x, y, total) in enumerate(train_loader):
                 loss = self.train_step(x)
+                # what a caller may report when the run ends (device values: no synchronisation in the loop)
+                fin = torch.isfinite(loss)
+                self.last_loss, self.losses_finite = loss, fin if getattr(self, "losses_finite", None) is None else self.losses_finite & fin
                 if self.step % 10 == 0 and rank0:
                     print(f"step: {self.step}, loss: {float(loss)}, loss mean: {float(loss) / npix}")
                 world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1

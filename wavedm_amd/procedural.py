@@ -34,9 +34,9 @@ def dict2namespace(d):
 
 
 def raindrop_wavelet_config(image_size: int = 64, ch: int = 128, ch_mult=(1, 2, 4, 6),
-                            num_res_blocks: int = 2, attn_resolutions=(16,)):
+                            num_res_blocks: int = 2, attn_resolutions=(16,), dropout: float = 0.0):
     """Every key of `configs/raindrop_wavelet.yml` with its values (checked against the reference's file by tests/golden/make_golden.py),
-    except the two deployment-specific ones: data.data_dir ("" here) and data.num_workers (0 here)."""
+    except the two deployment-specific ones: data.data_dir ("" here) and data.num_workers (0 here).  `dropout`: model.dropout, 0.0 in the reference's file."""
     return dict2namespace({
         "data": {"dataset": "RainDrop", "image_size": image_size, "patch_size": image_size * 4,
                  "lap": False, "global_attn": False, "wavelet": True, "wavelet_in_unet": False,
@@ -45,7 +45,7 @@ def raindrop_wavelet_config(image_size: int = 64, ch: int = 128, ch_mult=(1, 2, 
         "model": {"pred_channels": 3, "use_other_channels": True, "other_channels_begin": 3,
                   "use_gt_in_train": True, "in_channels": 48, "out_ch": 3, "ch": ch,
                   "ch_mult": list(ch_mult), "num_res_blocks": num_res_blocks,
-                  "attn_resolutions": list(attn_resolutions), "dropout": 0.0, "ema_rate": 0.999,
+                  "attn_resolutions": list(attn_resolutions), "dropout": float(dropout), "ema_rate": 0.999,
                   "ema": True, "resamp_with_conv": True},
         "diffusion": {"beta_schedule": "linear", "beta_start": 0.0001, "beta_end": 0.02,
                       "num_diffusion_timesteps": 1000},
@@ -56,9 +56,9 @@ def raindrop_wavelet_config(image_size: int = 64, ch: int = 128, ch_mult=(1, 2, 
     })
 
 
-def reduced_config():
+def reduced_config(dropout: float = 0.0):
     """Reduced-width fixture model of SURVEY.md §8c (1.03 M params, attention at res 8)."""
-    return raindrop_wavelet_config(image_size=16, ch=32, ch_mult=(1, 2), attn_resolutions=(8,))
+    return raindrop_wavelet_config(image_size=16, ch=32, ch_mult=(1, 2), attn_resolutions=(8,), dropout=dropout)
 
 
 def variant_config(kind):

@@ -8,7 +8,11 @@ reports (`wdm_trainer_param_info`), and runs the body of the reference's trainin
     trainer.optimizer_step()                    # torch.optim.Adam (utils/optimize.py:5-8) + EMAHelper.update (:48-53)
 
 `state_dict()` / `load_state_dict()` use the reference's keys and shapes, `ema_state_dict()` is `EMAHelper.state_dict()`; a checkpoint
-written by `save_checkpoint` has the reference's dict format (ddm_wavelet.py:282-292) and loads in `DenoisingDiffusion_Wavelet`."""
+written by `save_checkpoint` has the reference's dict format (ddm_wavelet.py:282-292) and loads in `DenoisingDiffusion_Wavelet`.
+
+`model.dropout` (every ResnetBlock's `conv2(dropout(silu(norm2(h))))`, models/unet.py:129): the masks are drawn inside the GroupNorm kernels from a
+counter-based generator (csrc/dropout.h) keyed by `dropout_seed` and counted by (element, block, optimizer step) -- they are not torch's stream, so a
+run matches the reference's in distribution, not bit for bit.  `Trainer.dropout_masks` shows what the next step draws."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,9 +23,19 @@ import torch
 from . import _lib, sampling
 from .unet import _make_config, reference_param_order, resolve_dtype
 
+_MASK63 = (1 << 63) - 1
+
+
+def dropout_rank_seed(base: int, rank: int) -> int:
+    """The dropout seed rank `rank` of a data-parallel run uses: ranks must not share masks (their samples differ, their masks must too), and every rank can
+    derive its own from the one base seed the checkpoint holds.  Rank 0 keeps the base seed; rank r adds r times an odd 63-bit constant (2^63 / golden ratio):
+    multiplication by an odd number is a bijection modulo 2^63, so all ranks of any world below 2^63 differ."""
+    return (int(base) + int(rank) * 0x4F1BBCDCBFA53E0B) & _MASK63
+
+
 
 class Trainer:
-    def __init__(self, config, device=None, dtype=None, lr=None, betas=(0.9, 0.999), eps=None, weight_decay=None, ema_mu=0.9999, use_mse=None):
+    def __init__(self, config, device=None, dtype=None, lr=None, betas=(0.9, 0.999), eps=None, weight_decay=None, ema_mu=0.9999, use_mse=None, dropout=None, dropout_seed=None):
         self.config = config
         self.device = torch.device(device if device is not None else getattr(config, "device", "cuda:0"))
         if self.device.type != "cuda":
@@ -36,9 +50,17 @@ class Trainer:
         self.betas, self.ema_mu = (float(betas[0]), float(betas[1])), float(ema_mu)
         if opt is not None and (getattr(opt, "optimizer", "Adam") != "Adam" or getattr(opt, "amsgrad", False)):
             raise NotImplementedError("wavedm_amd.Trainer implements optim.optimizer: Adam with amsgrad: False (utils/optimize.py:6-8, raindrop_wavelet.yml)")
-        if float(getattr(getattr(config, "model", None), "dropout", 0.0) or 0.0) != 0.0:
-            raise NotImplementedError("wavedm_amd.Trainer: model.dropout != 0 is not built (raindrop_wavelet.yml trains with dropout 0.0; "
-                                      "the backward pass in csrc/train_unet.hip has no dropout mask)")
+        # model.dropout (unet.py:99, :129): masks drawn in the kernels (csrc/dropout.h); the seed is this run's, the masks depend on (seed, rank, step) alone
+        self.dropout = float(dropout if dropout is not None else (getattr(getattr(config, "model", None), "dropout", 0.0) or 0.0))
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"model.dropout = {self.dropout!r}: must lie in [0, 1)")
+        # the base seed: given, or a 63-bit draw from torch's global generator (torch.manual_seed fixes a run) -- drawn only by a trainer that uses dropout, so that
+        # a run without it consumes the random numbers it always did; None until then
+        self.dropout_seed = (int(dropout_seed) & _MASK63) if dropout_seed is not None else None
+        self._dropout_seed_fresh = dropout_seed is None          # (restore_dropout_seed says so once when a resumed checkpoint has no seed)
+        if self.dropout > 0.0:
+            self._ensure_dropout_seed()
+        self._dropout_armed = False                               # the library handle holds p > 0 (wdm_trainer_set_dropout)
         # training.use_mse (ddm_wavelet.py:263-266): back-propagate the x0-space loss instead of the noise-space one
         self.use_mse = bool(use_mse if use_mse is not None else getattr(getattr(config, "training", None), "use_mse", False))
         L = _lib.lib()
@@ -131,6 +153,9 @@ class Trainer:
             if self._ws is None or self._ws.numel() < need:
                 self._ws = None
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if self.dropout > 0.0 or self._dropout_armed:          # (p = 0 on a handle that holds p = 0: the step of a model without dropout, not one call more)
+                _lib.check(_lib.lib().wdm_trainer_set_dropout(self._t, self.dropout, self.rank_dropout_seed(), self.step + 1))
+                self._dropout_armed = self.dropout > 0.0
             for attempt in range(4):
                 ws = self._ws
                 rc = _lib.lib().wdm_trainer_step(self._t, _lib.ptr(x0), _lib.ptr(tf), _lib.ptr(sa), _lib.ptr(s1m), _lib.ptr(e), B, self._c_t0, _lib.ptr(self._loss),
@@ -144,6 +169,44 @@ class Trainer:
                 _lib.check(rc)
                 break
         return (self._loss[0], out) if return_output else self._loss[0]
+
+    # ---- dropout ------------------------------------------------------------------------------------------------------
+    def _ensure_dropout_seed(self):
+        if self.dropout_seed is None:
+            self.dropout_seed = int(torch.randint(0, _MASK63, (1,), dtype=torch.int64).item())
+        return self.dropout_seed
+
+    def rank_dropout_seed(self):
+        """The seed this process draws with: dropout_rank_seed(base seed, rank in the default process group)."""
+        import torch.distributed as dist
+        self._ensure_dropout_seed()
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        return dropout_rank_seed(self.dropout_seed, rank)
+
+    def dropout_blocks(self, R=None):
+        """[(block name, layer index, channels, map side)] of the ResnetBlocks in the library's construction order (down, mid, up) for R x R inputs."""
+        R = int(R if R is not None else self.config.data.image_size)
+        nres = len(self.config.model.ch_mult)
+        out = []
+        for k, (_, shape) in self.layout.items():
+            if k.endswith(".norm2.weight"):
+                name = k[:-len(".norm2.weight")]
+                level = nres - 1 if name.startswith("mid.") else int(name.split(".")[1])
+                out.append((name, len(out), int(shape[0]), R >> level))
+        return out
+
+    def dropout_masks(self, B, R=None):
+        """{block name: (B, C, H, W) tensor of factors, 0 or 1 / (1 - p)} that the NEXT loss_and_grads call of this process applies behind silu(norm2(.)) of each
+        ResnetBlock, from the device function the kernels draw with (wdm_dropout_mask).  Every factor is 1.0 when model.dropout is 0."""
+        L, h = _lib.lib(), _lib.handle(self.device.index or 0)
+        seed = self.rank_dropout_seed() if self.dropout > 0.0 else 0        # (p = 0: every factor is 1 whatever the seed -- and no seed is drawn for looking)
+        out = OrderedDict()
+        with torch.cuda.device(self.device):
+            for name, layer, ch, side in self.dropout_blocks(R):
+                m = torch.empty(int(B), ch, side, side, device=self.device)
+                _lib.check(L.wdm_dropout_mask(h, self.dropout, seed, self.step + 1, layer, int(B), side, side, ch, _lib.ptr(m), _lib.stream_ptr()))
+                out[name] = m
+        return out
 
     def allreduce_grads(self, group=None):
         import torch.distributed as dist
@@ -272,10 +335,29 @@ class Trainer:
         raise RuntimeError("unrecognised optimizer state in the checkpoint")
 
     def save_checkpoint(self, path, epoch=0):
-        """The reference's checkpoint dict (ddm_wavelet.py:282-292): its own `load_ddm_ckpt` (:180-190) reads this file."""
+        """The reference's checkpoint dict (ddm_wavelet.py:282-292): its own `load_ddm_ckpt` (:180-190) reads this file -- it looks up named keys only, so the
+        one key added here, 'dropout_seed' (the BASE seed: a resumed run continues with the masks the uninterrupted run would have drawn), does not disturb it."""
         torch.save({"epoch": epoch, "step": self.step, "state_dict": {k: v.cpu() for k, v in self.state_dict().items()},
                     "optimizer": self.optimizer_state_dict(),
-                    "ema_helper": {k: v.cpu() for k, v in self.ema_state_dict().items()}, "params": None, "config": None}, path)
+                    "ema_helper": {k: v.cpu() for k, v in self.ema_state_dict().items()}, "params": None, "config": None,
+                    "dropout_seed": self.dropout_seed}, path)                 # (None from a trainer that never used dropout: resumes like a file without the key)
+
+    def restore_dropout_seed(self, seed):
+        """--resume: take the checkpoint's base seed; a checkpoint without one (the reference's, or an older one of this package) keeps the fresh seed drawn at
+        construction, and a run that uses dropout says so once."""
+        if seed is not None:
+            self.dropout_seed, self._dropout_seed_fresh = int(seed) & _MASK63, False
+        elif self.dropout > 0.0 and self._dropout_seed_fresh:
+            self._announce_fresh_seed = True                       # said by announce_dropout_seed, once the ranks agree on the seed
+            self._dropout_seed_fresh = False
+
+    def announce_dropout_seed(self):
+        """Behind broadcast_state: rank 0 says -- once -- that the resumed checkpoint held no seed, with the base seed every rank now uses."""
+        import torch.distributed as dist
+        if getattr(self, "_announce_fresh_seed", False):
+            self._announce_fresh_seed = False
+            if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
+                print(f"wavedm_amd.Trainer: the checkpoint holds no 'dropout_seed'; continuing with a fresh one ({self.dropout_seed})")
 
     def broadcast_state(self, src=0, group=None):
         """What DistributedDataParallel does at construction (ddm_wavelet.py:168): every rank starts from rank `src`'s parameters (and here
@@ -284,6 +366,7 @@ class Trainer:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
             for buf in (self.params, self.ema, self.exp_avg, self.exp_avg_sq):
                 dist.broadcast(buf, src=src, group=group)
-            st = torch.tensor([self.step], device=self.device, dtype=torch.int64)
+            st = torch.tensor([self.step, -1 if self.dropout_seed is None else self.dropout_seed], device=self.device, dtype=torch.int64)
             dist.broadcast(st, src=src, group=group)
-            self.step = int(st.item())
+            self.step = int(st[0].item())
+            self.dropout_seed = None if int(st[1].item()) < 0 else int(st[1].item())  # one base seed; each rank draws with dropout_rank_seed(base, its rank)
