@@ -339,6 +339,26 @@ int wdm_trainer_step(wdm_trainer* t, const float* x0, const float* tt, const flo
                      int B, int c_t0, float* loss, float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
 int wdm_trainer_adam_ema(wdm_trainer* t, int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay,
                          float ema_mu, void* stream);
+/* The other optimizers utils/optimize.py:5-14 can build, as torch 2.10's single-tensor rules, each with the EMA update in the same pass over the flat
+ * buffers (fp32, no atomics).  g is the gradient, g += weight_decay * p first (the reference's SGD call passes no weight decay: its callers pass 0):
+ *   WDM_OPT_ADAM     state0 exp_avg, state1 exp_avg_sq                              the rule of wdm_trainer_adam_ema
+ *   WDM_OPT_AMSGRAD  state0 exp_avg, state1 exp_avg_sq, state2 max_exp_avg_sq       vmax = max(vmax, v);
+ *                    p -= lr / (1 - beta1^step) * m / (sqrt(vmax) / sqrt(1 - beta2^step) + eps)
+ *   WDM_OPT_RMSPROP  state0 square_avg          s = beta2 s + (1 - beta2) g^2;  p -= lr g / (sqrt(s) + eps)     (beta2 = RMSprop's alpha; momentum 0, not centered)
+ *   WDM_OPT_SGD      state0 momentum_buffer     buf = g at step 1, beta1 buf + g afterwards;  p -= lr buf       (beta1 = the momentum; dampening 0, no Nesterov)
+ * Arguments a rule does not use are ignored; its state buffers are required.  The hyper-parameters are doubles: 1 - beta, the bias corrections and
+ * lr / (1 - beta1^step) are formed from them as torch forms them from Python floats, then rounded to fp32 once.
+ * wdm_trainer_set_optimizer selects the rule of a trainer and hands over its state buffers (wdm_trainer_num_floats floats each; WDM_OPT_ADAM, the default,
+ * replaces m / v of wdm_trainer_set_buffers); wdm_trainer_optim_step applies it to the trainer's parameters, gradients and EMA shadow.
+ * wdm_optim_step applies one step to caller-owned buffers of n >= 0 floats: 16-byte accesses where every buffer shares one misalignment from a 16-byte
+ * boundary, scalar ends (and scalar throughout where they do not); ema may be NULL. */
+enum { WDM_OPT_ADAM = 0, WDM_OPT_AMSGRAD = 1, WDM_OPT_RMSPROP = 2, WDM_OPT_SGD = 3 };
+int wdm_trainer_set_optimizer(wdm_trainer* t, int rule, float* state0, float* state1, float* state2);
+int wdm_trainer_optim_step(wdm_trainer* t, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           double ema_mu, void* stream);
+int wdm_optim_step(wdm_handle* h, int rule, float* params, const float* grads, float* state0, float* state1, float* state2, float* ema,
+                   int64_t n, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay, double ema_mu,
+                   void* stream);
 /* Gradient buckets for a data-parallel all-reduce that overlaps the backward (the reference wraps the model in DistributedDataParallel, ddm_wavelet.py:168,
  * which all-reduces 25 MB buckets while the backward runs).  The parameters sit in the flat buffers in forward order and the backward runs in reverse, so the
  * gradient buffer fills from its end: with n events set (hipEvent_t handles owned by the caller; n = 0 switches the feature off) every following

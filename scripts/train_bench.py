@@ -22,11 +22,14 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--dropout", type=float, default=0.0, help="model.dropout of the step (masks drawn in the GroupNorm kernels, csrc/dropout.h); 0: the plain step")
+    ap.add_argument("--optimizer", default="Adam", choices=["Adam", "AMSGrad", "RMSProp", "SGD"],
+                    help="optim.optimizer of the step (AMSGrad: Adam with optim.amsgrad: True); utils/optimize.py:5-14")
     ap.add_argument("--prof", action="store_true", help="one more step under the library's per-launch event profiler: per (kernel | shape) rows on stderr")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     cfg = P.raindrop_wavelet_config()
     cfg.device = dev
+    cfg.optim.optimizer, cfg.optim.amsgrad = ("Adam", True) if a.optimizer == "AMSGrad" else (a.optimizer, False)
     sd = P.procedural_state_dict(cfg, seed=61)
     tr = Trainer(cfg, dtype=a.dtype, dropout=a.dropout, dropout_seed=3)
     tr.load_state_dict(sd)
@@ -42,7 +45,8 @@ def main():
         loss = tr.train_step(x0, generator=gd)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.iters
-    out = {"what": "training step (loss + backward + Adam + EMA), raindrop_wavelet UNet 156.5 M params", "batch": a.batch, "dtype": a.dtype, "dropout": a.dropout,
+    out = {"what": f"training step (loss + backward + {a.optimizer} + EMA), raindrop_wavelet UNet 156.5 M params", "batch": a.batch, "dtype": a.dtype, "dropout": a.dropout,
+           "optimizer": a.optimizer,
            "ms_per_step": dt * 1e3, "samples_per_s": a.batch / dt, "loss_first": losses[0], "loss_last": float(loss),
            # forward 80 GFLOP per sample, backward ~2x
            "approx_tflops": a.batch * 79.94e9 * 3 / dt / 1e12}

@@ -14,10 +14,10 @@ from .sampling import get_beta_schedule, compute_alpha, overlapping_grid_indices
 from .datasets import RainDrop, RainDropDataset, HFRMImageFolder
 from .imageio import AsyncImageWriter
 from .metrics import ssim, calculate_ssim
-from .training import Trainer
+from .training import Trainer, optimizer_spec
 from .hfrm_training import HFRMTrainer
 
 __all__ = ["WaveletTransform", "DiffusionUNet", "DiffusionUNet_Global", "DenoisingDiffusion_Wavelet", "DiffusiveRestoration",
            "data_transform", "inverse_data_transform", "torchPSNR", "get_beta_schedule", "compute_alpha",
            "overlapping_grid_indices", "ddim_sample", "HFRM", "RainDrop", "RainDropDataset", "HFRMImageFolder", "AsyncImageWriter", "Trainer", "HFRMTrainer",
-           "ssim", "calculate_ssim"]
+           "ssim", "calculate_ssim", "optimizer_spec"]

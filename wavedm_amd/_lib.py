@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("WAVEDM_LIB") or os.path.join(_HERE, "csrc", "libwaved
 WDM_F32, WDM_BF16, WDM_F32X3, WDM_F16 = 0, 1, 2, 3
 WDM_OK, WDM_EINVAL, WDM_ENOMEM, WDM_EHIP, WDM_ESTATE, WDM_ENOTFOUND = 0, -1, -2, -3, -4, -5
 WDM_IMG_F32_NCHW, WDM_IMG_U8_HWC, WDM_IMG_F32_HWC = 0, 1, 2          # wdm_image_ssim input kinds
+WDM_OPT_ADAM, WDM_OPT_AMSGRAD, WDM_OPT_RMSPROP, WDM_OPT_SGD = 0, 1, 2, 3   # optimizer rules (wdm_optim_step, wdm_trainer_set_optimizer)
 DTYPES = {"f32": WDM_F32, "fp32": WDM_F32, "float32": WDM_F32, "bf16": WDM_BF16, "bfloat16": WDM_BF16, "f32x3": WDM_F32X3, "f16": WDM_F16, "fp16": WDM_F16, "float16": WDM_F16, "half": WDM_F16}
 
 _lib = None
@@ -120,6 +121,9 @@ def lib():
         "wdm_trainer_set_dropout": (i, [vp, f, i64, i64]),
         "wdm_trainer_step": (i, [vp, vp, vp, vp, vp, vp, i, i, vp, vp, vp, sz, vp]),
         "wdm_trainer_adam_ema": (i, [vp, i64, f, f, f, f, f, f, vp]),
+        "wdm_trainer_set_optimizer": (i, [vp, i, vp, vp, vp]),
+        "wdm_trainer_optim_step": (i, [vp, i64] + [C.c_double] * 6 + [vp]),
+        "wdm_optim_step": (i, [vp, i, vp, vp, vp, vp, vp, vp, i64, i64] + [C.c_double] * 6 + [vp]),
         "wdm_trainer_set_grad_events": (i, [vp, C.POINTER(vp), i]),
         "wdm_trainer_grad_buckets": (i, [vp, C.POINTER(i64), i, C.POINTER(i)]),
         "wdm_hfrm_trainer_create": (i, [vp, C.POINTER(HFRMConfig), C.POINTER(vp)]),
@@ -160,7 +164,7 @@ EXPORTED = ["wdm_abi_version", "wdm_last_error", "wdm_create", "wdm_destroy", "w
             "wdm_hfrm_create", "wdm_hfrm_destroy", "wdm_hfrm_num_params", "wdm_hfrm_param_info", "wdm_hfrm_packed_bytes",
             "wdm_hfrm_set_packed", "wdm_hfrm_load_param", "wdm_hfrm_finalize", "wdm_hfrm_workspace_bytes",
             "wdm_hfrm_forward", "wdm_image_sqdiff", "wdm_to_u8_hwc", "wdm_image_ssim_scratch_bytes", "wdm_image_ssim", "wdm_conv_backward", "wdm_gn_act_backward", "wdm_dropout_mask", "wdm_gn_act_dropout", "wdm_trainer_create", "wdm_trainer_destroy", "wdm_trainer_num_params",
-            "wdm_trainer_num_floats", "wdm_trainer_param_info", "wdm_trainer_set_buffers", "wdm_trainer_set_objective", "wdm_trainer_set_dropout", "wdm_trainer_step", "wdm_trainer_adam_ema", "wdm_trainer_set_grad_events", "wdm_trainer_grad_buckets", "wdm_hfrm_trainer_create", "wdm_hfrm_trainer_destroy", "wdm_hfrm_trainer_num_params", "wdm_hfrm_trainer_num_floats",
+            "wdm_trainer_num_floats", "wdm_trainer_param_info", "wdm_trainer_set_buffers", "wdm_trainer_set_objective", "wdm_trainer_set_dropout", "wdm_trainer_step", "wdm_trainer_adam_ema", "wdm_trainer_set_optimizer", "wdm_trainer_optim_step", "wdm_optim_step", "wdm_trainer_set_grad_events", "wdm_trainer_grad_buckets", "wdm_hfrm_trainer_create", "wdm_hfrm_trainer_destroy", "wdm_hfrm_trainer_num_params", "wdm_hfrm_trainer_num_floats",
             "wdm_hfrm_trainer_param_info", "wdm_hfrm_trainer_set_buffers", "wdm_hfrm_trainer_workspace_bytes", "wdm_hfrm_trainer_step", "wdm_hfrm_trainer_adam", "wdm_dwt_fwd_affine", "wdm_dwt_inv_compose", "wdm_conv2d_direct", "wdm_groupnorm", "wdm_cross_attention", "wdm_upsample_add",
             "wdm_prof_enable", "wdm_prof_report", "wdm_env_refresh", "wdm_set_concurrent_streams"]
 

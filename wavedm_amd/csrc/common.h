@@ -294,6 +294,10 @@ int gn_act_backward(Ctx& c, const NormW& nw, const Tens& x0, const Tens* x1, con
 // doubles: 1 - beta and the bias corrections are formed before rounding to fp32 (an fp32 0.999 leaves 1 - beta2 1.3e-5 off torch's value)
 int k_adam_ema(float* P, const float* G, float* M, float* V, float* E, long long n, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay,
                float ema_mu, hipStream_t s);
+// One step of a WDM_OPT_* rule over n floats of any alignment + the EMA update when E != nullptr (train_unet.hip; include/wavedm.h names the state slots).
+// beta1: Adam's beta1 / SGD's momentum; beta2: Adam's beta2 / RMSProp's alpha.  WDM_OPT_ADAM launches k_adam_ema.
+int k_optim_ema(int rule, float* P, const float* G, float* S0, float* S1, float* S2, float* E, long long n, int64_t step, double lr, double beta1, double beta2,
+                double eps, double weight_decay, double ema_mu, hipStream_t s);
 
 }  // namespace wdm
 

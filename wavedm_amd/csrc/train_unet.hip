@@ -165,6 +165,73 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ P, co
     }
 }
 
+// ---- the other optimizers utils/optimize.py can build (torch 2.10's single-tensor rules), each + EMAHelper.update in the same pass ---------------------------
+// One update of one element; s0 / s1 / s2 are the rule's state values (the slots it does not use are never loaded or stored).
+//   WDM_OPT_AMSGRAD  s0 exp_avg, s1 exp_avg_sq, s2 max_exp_avg_sq     p -= step_size * m / (sqrt(max(vmax, v)) / bc2_sqrt + eps)
+//   WDM_OPT_RMSPROP  s0 square_avg (decay b2 = alpha)                  p -= lr * g / (sqrt(s) + eps)           (momentum 0, not centered)
+//   WDM_OPT_SGD      s0 momentum_buffer (decay b1 = momentum)          p -= lr * buf, buf = g on the first step  (dampening 0, no Nesterov)
+struct OptArgs {
+    float* P; const float* G; float* S0; float* S1; float* S2; float* E;
+    long long n, head, nvec;              // head scalar elements up to the first 16-byte boundary, then nvec float4, then the rest scalar
+    float lr, b1, b2, omb1, omb2, eps, wd, step_size, bc2_sqrt, mu;
+    int first;                            // SGD: the step that creates the momentum buffer
+};
+template <int RULE> struct OptSlots { static constexpr int n = RULE == WDM_OPT_AMSGRAD ? 3 : 1; };
+
+template <int RULE>
+__device__ __forceinline__ float opt_update(const OptArgs& a, float p, float g, float& s0, float& s1, float& s2) {
+    if (a.wd != 0.f) g += a.wd * p;
+    if (RULE == WDM_OPT_AMSGRAD) {
+        s0 = a.b1 * s0 + a.omb1 * g;
+        s1 = a.b2 * s1 + a.omb2 * g * g;
+        s2 = fmaxf(s2, s1);
+        return p - a.step_size * (s0 / (sqrtf(s2) / a.bc2_sqrt + a.eps));
+    } else if (RULE == WDM_OPT_RMSPROP) {
+        s0 = a.b2 * s0 + a.omb2 * g * g;
+        return p - a.lr * (g / (sqrtf(s0) + a.eps));
+    } else {
+        s0 = a.first ? g : a.b1 * s0 + g;
+        return p - a.lr * s0;
+    }
+}
+template <int RULE> __device__ __forceinline__ void opt_scalar(const OptArgs& a, long long id) {
+    float s0 = (RULE == WDM_OPT_SGD && a.first) ? 0.f : a.S0[id], s1 = 0.f, s2 = 0.f;
+    if (OptSlots<RULE>::n == 3) { s1 = a.S1[id]; s2 = a.S2[id]; }
+    const float pn = opt_update<RULE>(a, a.P[id], a.G[id], s0, s1, s2);
+    a.S0[id] = s0;
+    if (OptSlots<RULE>::n == 3) { a.S1[id] = s1; a.S2[id] = s2; }
+    a.P[id] = pn;
+    if (a.E) a.E[id] = (1.0f - a.mu) * pn + a.mu * a.E[id];
+}
+union OptF4 { float4 v; float f[4]; };
+// No __restrict__: every stream is read and written at the same index by the same lane, nothing else is shared.
+template <int RULE> __global__ __launch_bounds__(256) void optim_ema_kernel(const OptArgs a) {
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+    for (long long v = tid; v < a.nvec; v += nth) {
+        const long long id = a.head + 4 * v;                          // 16-byte aligned in every buffer (the launcher checked that they share one misalignment)
+        OptF4 p, g, s0, s1, s2, e;
+        p.v = *reinterpret_cast<const float4*>(a.P + id);
+        g.v = *reinterpret_cast<const float4*>(a.G + id);
+        if (RULE == WDM_OPT_SGD && a.first) s0.v = make_float4(0.f, 0.f, 0.f, 0.f);
+        else s0.v = *reinterpret_cast<const float4*>(a.S0 + id);
+        if (OptSlots<RULE>::n == 3) { s1.v = *reinterpret_cast<const float4*>(a.S1 + id); s2.v = *reinterpret_cast<const float4*>(a.S2 + id); }
+        else { s1.v = s2.v = make_float4(0.f, 0.f, 0.f, 0.f); }
+        e.v = a.E ? *reinterpret_cast<const float4*>(a.E + id) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            p.f[k] = opt_update<RULE>(a, p.f[k], g.f[k], s0.f[k], s1.f[k], s2.f[k]);
+            if (a.E) e.f[k] = (1.0f - a.mu) * p.f[k] + a.mu * e.f[k];
+        }
+        *reinterpret_cast<float4*>(a.S0 + id) = s0.v;
+        if (OptSlots<RULE>::n == 3) { *reinterpret_cast<float4*>(a.S1 + id) = s1.v; *reinterpret_cast<float4*>(a.S2 + id) = s2.v; }
+        *reinterpret_cast<float4*>(a.P + id) = p.v;
+        if (a.E) *reinterpret_cast<float4*>(a.E + id) = e.v;
+    }
+    // the scalar ends: `head` elements in front of the vectors, n - head - 4 nvec behind them (all n of them when the buffers' alignments differ)
+    const long long tail0 = a.head + 4 * a.nvec, nsc = a.head + (a.n - tail0);
+    for (long long k = tid; k < nsc; k += nth) opt_scalar<RULE>(a, k < a.head ? k : tail0 + (k - a.head));
+}
+
 template <typename T> static void l_add_into(hipStream_t s, void* dst, const void* src, long long n, int acc) {
     hipLaunchKernelGGL(add_into_kernel<T>, dim3(nb(n, 256)), dim3(256), 0, s, (T*)dst, (const T*)src, n, acc);
 }
@@ -201,6 +268,40 @@ int k_adam_ema(float* P, const float* G, float* M, float* V, float* E, long long
     return WDM_OK;
 }
 
+// One step of `rule` over n floats (common.h).  Every scalar torch forms from its Python floats -- 1 - beta, the bias corrections, lr / bias_correction1 -- is
+// formed here in double and rounded to fp32 once.
+int k_optim_ema(int rule, float* P, const float* G, float* S0, float* S1, float* S2, float* E, long long n, int64_t step, double lr, double beta1, double beta2,
+                double eps, double weight_decay, double ema_mu, hipStream_t s) {
+    if (rule == WDM_OPT_ADAM)
+        return k_adam_ema(P, G, S0, S1, E, n, step, (float)lr, beta1, beta2, (float)eps, (float)weight_decay, (float)ema_mu, s);
+    if (n <= 0) return WDM_OK;
+    OptArgs a{};
+    a.P = P; a.G = G; a.S0 = S0; a.S1 = S1; a.S2 = S2; a.E = E; a.n = n;
+    a.lr = (float)lr; a.b1 = (float)beta1; a.b2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
+    a.eps = (float)eps; a.wd = (float)weight_decay; a.mu = (float)ema_mu; a.first = step == 1;
+    a.step_size = (float)(lr / (1.0 - std::pow(beta1, (double)step)));
+    a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)step));
+    // float4 accesses need one misalignment shared by every buffer the rule touches; buffers that disagree (or are not even 4-byte aligned apart) go scalar
+    const float* bufs[6] = {P, G, S0, rule == WDM_OPT_AMSGRAD ? S1 : nullptr, rule == WDM_OPT_AMSGRAD ? S2 : nullptr, E};
+    const uintptr_t mis = (uintptr_t)P & 15;
+    bool same = (mis & 3) == 0;
+    for (const float* b : bufs) same = same && (!b || ((uintptr_t)b & 15) == mis);
+    a.head = same ? (long long)(((16 - mis) & 15) / 4) : n;
+    if (a.head > n) a.head = n;
+    a.nvec = (n - a.head) / 4;
+    const long long nsc = n - 4 * a.nvec, work = a.nvec > nsc ? a.nvec : nsc;
+    const long long want = (work + 255) / 256;
+    // 512 workgroups = two per CU, grid-stride beyond: fewer waves in flight keep the streams' concurrent windows small, which the HBM rewards -- RMSProp's
+    // loop over 156 M floats took 980 us from 2 048 workgroups, 945 from 1 024, 840 from 512, 815 from 256 (profiles/optimizers_kernel_stats.md)
+    const dim3 grid((unsigned)(want > 512 ? 512 : want)), blk(256);
+    if (rule == WDM_OPT_AMSGRAD) hipLaunchKernelGGL(optim_ema_kernel<WDM_OPT_AMSGRAD>, grid, blk, 0, s, a);
+    else if (rule == WDM_OPT_RMSPROP) hipLaunchKernelGGL(optim_ema_kernel<WDM_OPT_RMSPROP>, grid, blk, 0, s, a);
+    else if (rule == WDM_OPT_SGD) hipLaunchKernelGGL(optim_ema_kernel<WDM_OPT_SGD>, grid, blk, 0, s, a);
+    else WDM_FAIL(WDM_EINVAL, "k_optim_ema: unknown rule %d", rule);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
 }  // namespace wdm
 
 // =====================================================================================================================
@@ -219,6 +320,8 @@ struct wdm_trainer {
     std::vector<PInfo> params;
     size_t nfloats = 0;
     float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *E = nullptr;
+    int opt_rule = WDM_OPT_ADAM;                          // wdm_trainer_set_optimizer: the rule wdm_trainer_optim_step applies, and its state buffers
+    float* S[3] = {nullptr, nullptr, nullptr};            // (WDM_OPT_ADAM keeps M / V of wdm_trainer_set_buffers)
     bool use_mse = false;     // training.use_mse: differentiate the x0-space loss instead of the noise-space one
     Dropout dropout;          // model.dropout of the next step (wdm_trainer_set_dropout): p, seed and the optimizer step it computes; layer is filled per block
     int n_res = 0;
@@ -726,6 +829,37 @@ int wdm_trainer_adam_ema(wdm_trainer* t, int64_t step, float lr, float beta1, fl
     if (!t || !t->P || !t->G || !t->M || !t->V) WDM_FAIL(WDM_ESTATE, "wdm_trainer_adam_ema: buffers not set");
     if (step < 1) WDM_FAIL(WDM_EINVAL, "wdm_trainer_adam_ema: step counts from 1");
     return k_adam_ema(t->P, t->G, t->M, t->V, t->E, (long long)t->nfloats, step, lr, beta1, beta2, eps, weight_decay, ema_mu, (hipStream_t)stream);
+}
+// The rule of wdm_trainer_optim_step and its state buffers (include/wavedm.h: which slots each rule uses).  WDM_OPT_ADAM hands over m / v like wdm_trainer_set_buffers.
+int wdm_trainer_set_optimizer(wdm_trainer* t, int rule, float* state0, float* state1, float* state2) {
+    if (!t) WDM_FAIL(WDM_EINVAL, "wdm_trainer_set_optimizer: null trainer");
+    if (rule < WDM_OPT_ADAM || rule > WDM_OPT_SGD) WDM_FAIL(WDM_EINVAL, "wdm_trainer_set_optimizer: unknown rule %d", rule);
+    const int need = rule == WDM_OPT_AMSGRAD ? 3 : rule == WDM_OPT_ADAM ? 2 : 1;
+    float* st[3] = {state0, state1, state2};
+    for (int k = 0; k < need; ++k)
+        if (!st[k]) WDM_FAIL(WDM_EINVAL, "wdm_trainer_set_optimizer: rule %d needs %d state buffers", rule, need);
+    t->opt_rule = rule;
+    if (rule == WDM_OPT_ADAM) { t->M = state0; t->V = state1; st[0] = st[1] = nullptr; }
+    for (int k = 0; k < 3; ++k) t->S[k] = k < need ? st[k] : nullptr;
+    return WDM_OK;
+}
+int wdm_trainer_optim_step(wdm_trainer* t, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay, double ema_mu, void* stream) {
+    if (!t || !t->P || !t->G) WDM_FAIL(WDM_ESTATE, "wdm_trainer_optim_step: buffers not set");
+    if (step < 1) WDM_FAIL(WDM_EINVAL, "wdm_trainer_optim_step: step counts from 1");
+    const bool adam = t->opt_rule == WDM_OPT_ADAM;
+    if (adam ? (!t->M || !t->V) : !t->S[0]) WDM_FAIL(WDM_ESTATE, "wdm_trainer_optim_step: state buffers not set");
+    return k_optim_ema(t->opt_rule, t->P, t->G, adam ? t->M : t->S[0], adam ? t->V : t->S[1], t->S[2], t->E, (long long)t->nfloats, step, lr, beta1, beta2, eps,
+                       weight_decay, ema_mu, (hipStream_t)stream);
+}
+// One step of a rule over caller-owned flat buffers of any length and alignment (include/wavedm.h)
+int wdm_optim_step(wdm_handle* h, int rule, float* params, const float* grads, float* state0, float* state1, float* state2, float* ema, int64_t n, int64_t step,
+                   double lr, double beta1, double beta2, double eps, double weight_decay, double ema_mu, void* stream) {
+    if (!h || !params || !grads) WDM_FAIL(WDM_EINVAL, "wdm_optim_step: null argument");
+    if (rule < WDM_OPT_ADAM || rule > WDM_OPT_SGD) WDM_FAIL(WDM_EINVAL, "wdm_optim_step: unknown rule %d", rule);
+    if (n < 0 || step < 1) WDM_FAIL(WDM_EINVAL, "wdm_optim_step: n = %lld, step = %lld (step counts from 1)", (long long)n, (long long)step);
+    const int need = rule == WDM_OPT_AMSGRAD ? 3 : rule == WDM_OPT_ADAM ? 2 : 1;
+    if (!state0 || (need >= 2 && !state1) || (need == 3 && !state2)) WDM_FAIL(WDM_EINVAL, "wdm_optim_step: rule %d needs %d state buffers", rule, need);
+    return k_optim_ema(rule, params, grads, state0, state1, state2, ema, (long long)n, step, lr, beta1, beta2, eps, weight_decay, ema_mu, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,11 +1,14 @@
 """Training step of the wavelet-domain UNet on the HIP library.
 
-`Trainer(config)` owns five flat fp32 device buffers -- parameters, gradients, Adam m / v, EMA shadow -- in the layout the library
+`Trainer(config)` owns flat fp32 device buffers -- parameters, gradients, EMA shadow and the state of the configured optimizer (Adam: m / v) -- in the layout the library
 reports (`wdm_trainer_param_info`), and runs the body of the reference's training loop (`models/ddm_wavelet.py:259-272`):
 
     loss = trainer.loss_and_grads(x0, t, e)     # noise_estimation_loss (:108-124) forward + backward
     trainer.allreduce_grads()                   # what DistributedDataParallel does in the reference (:168), one RCCL all-reduce
-    trainer.optimizer_step()                    # torch.optim.Adam (utils/optimize.py:5-8) + EMAHelper.update (:48-53)
+    trainer.optimizer_step()                    # the optimizer of utils/optimize.py:5-14 + EMAHelper.update (:48-53)
+
+`optim.optimizer` / `optim.amsgrad` select one of the four optimizers the reference's `get_optimizer` can build (`optimizer_spec`): Adam, Adam with amsgrad,
+RMSProp, SGD -- torch 2.10's single-tensor update rules, each one HIP kernel over the flat buffers with the EMA update in the same pass.
 
 `state_dict()` / `load_state_dict()` use the reference's keys and shapes, `ema_state_dict()` is `EMAHelper.state_dict()`; a checkpoint
 written by `save_checkpoint` has the reference's dict format (ddm_wavelet.py:282-292) and loads in `DenoisingDiffusion_Wavelet`.
@@ -33,6 +36,83 @@ def dropout_rank_seed(base: int, rank: int) -> int:
     return (int(base) + int(rank) * 0x4F1BBCDCBFA53E0B) & _MASK63
 
 
+# the per-parameter state tensors of each rule, in the order of the library's state slots (include/wavedm.h)
+STATE_NAMES = {"adam": ("exp_avg", "exp_avg_sq"), "amsgrad": ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"), "rmsprop": ("square_avg",), "sgd": ("momentum_buffer",)}
+_RULE_CODES = {"adam": _lib.WDM_OPT_ADAM, "amsgrad": _lib.WDM_OPT_AMSGRAD, "rmsprop": _lib.WDM_OPT_RMSPROP, "sgd": _lib.WDM_OPT_SGD}
+_RULE_TITLES = {"adam": "Adam", "amsgrad": "Adam(amsgrad=True)", "rmsprop": "RMSprop", "sgd": "SGD"}
+
+
+def optimizer_spec(config):
+    """The optimizer `get_optimizer(config, parameters)` of the reference builds (utils/optimize.py:5-14), as {"rule", "lr", "betas", "eps", "weight_decay",
+    "alpha", "momentum"} with rule in adam / amsgrad / rmsprop / sgd and every value what that call hands to torch.optim -- including what it does NOT hand over:
+      RMSProp  optim.RMSprop(parameters, lr, weight_decay): optim.eps is ignored, eps is torch's default 1e-8 (alpha 0.99, momentum 0, not centered)
+      SGD      optim.SGD(parameters, lr, momentum=0.9): optim.weight_decay is ignored, weight decay is 0 (dampening 0, no Nesterov)
+    Keys a rule does not use hold torch's defaults.  A config without an `optim` section, or without some of its keys, gets the values of raindrop_wavelet.yml's
+    optimizer (Adam, amsgrad False, eps 1e-8, weight decay 0) and lr 4e-5.  Needs no GPU."""
+    opt = getattr(config, "optim", None)
+    name = getattr(opt, "optimizer", "Adam")
+    spec = {"rule": "adam", "lr": float(getattr(opt, "lr", 4e-5)), "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.0, "alpha": 0.99, "momentum": 0.0}
+    if name == "Adam":
+        spec.update(rule="amsgrad" if getattr(opt, "amsgrad", False) else "adam", eps=float(getattr(opt, "eps", 1e-8)),
+                    weight_decay=float(getattr(opt, "weight_decay", 0.0)))
+    elif name == "RMSProp":
+        spec.update(rule="rmsprop", weight_decay=float(getattr(opt, "weight_decay", 0.0)))
+    elif name == "SGD":
+        spec.update(rule="sgd", momentum=0.9)
+    else:
+        raise NotImplementedError("Optimizer {} not understood.".format(name))
+    return spec
+
+
+def torch_optimizer(spec, parameters, **kw):
+    """The torch.optim object of an optimizer_spec over `parameters` (what the reference instantiates; the tests' yardstick)."""
+    if spec["rule"] in ("adam", "amsgrad"):
+        return torch.optim.Adam(parameters, lr=spec["lr"], weight_decay=spec["weight_decay"], betas=tuple(spec["betas"]), amsgrad=spec["rule"] == "amsgrad",
+                                eps=spec["eps"], **kw)
+    if spec["rule"] == "rmsprop":
+        return torch.optim.RMSprop(parameters, lr=spec["lr"], alpha=spec["alpha"], eps=spec["eps"], weight_decay=spec["weight_decay"], **kw)
+    return torch.optim.SGD(parameters, lr=spec["lr"], momentum=spec["momentum"], weight_decay=spec["weight_decay"], **kw)
+
+
+def torch_optimizer_state_dict(spec, step, tensors):
+    """`torch.optim.X.state_dict()` of the optimizer of `spec` after `step` steps: tensors = {state name: [one tensor per parameter, in model.parameters() order]}
+    for the names of STATE_NAMES[rule].  The entries and the param_groups keys are the ones torch 2.10 writes, so X.load_state_dict accepts the result."""
+    rule = spec["rule"]
+    names = STATE_NAMES[rule]
+    n = len(tensors[names[0]])
+    state = {}
+    for i in range(n):
+        e = {} if rule == "sgd" else {"step": torch.tensor(float(step))}           # (SGD keeps no step count)
+        for k in names:
+            e[k] = tensors[k][i]
+        state[i] = e
+    if rule in ("adam", "amsgrad"):
+        group = {"lr": spec["lr"], "betas": tuple(spec["betas"]), "eps": spec["eps"], "weight_decay": spec["weight_decay"], "amsgrad": rule == "amsgrad",
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None}
+        if rule == "amsgrad":
+            group["decoupled_weight_decay"] = False
+    elif rule == "rmsprop":
+        group = {"lr": spec["lr"], "momentum": 0.0, "alpha": spec["alpha"], "eps": spec["eps"], "centered": False, "weight_decay": spec["weight_decay"],
+                 "capturable": False, "foreach": None, "maximize": False, "differentiable": False}
+    else:
+        group = {"lr": spec["lr"], "momentum": spec["momentum"], "dampening": 0.0, "weight_decay": spec["weight_decay"], "nesterov": False, "maximize": False,
+                 "foreach": None, "differentiable": False, "fused": None}
+    group["params"] = list(range(n))
+    return {"state": state, "param_groups": [group]}
+
+
+def _checkpoint_rule(osd):
+    """Which of the four optimizers wrote a torch.optim state dict: by the hyper-parameters of its param group, else by the names of its state tensors."""
+    g = osd["param_groups"][0] if osd.get("param_groups") else {}
+    e = next(iter(osd["state"].values()), {}) if osd.get("state") else {}
+    if "betas" in g or "exp_avg" in e:
+        return "amsgrad" if (g.get("amsgrad", False) or "max_exp_avg_sq" in e) else "adam"
+    if "alpha" in g or "square_avg" in e:
+        return "rmsprop"
+    if "nesterov" in g or "dampening" in g or "momentum_buffer" in e:
+        return "sgd"
+    return None
+
 
 class Trainer:
     def __init__(self, config, device=None, dtype=None, lr=None, betas=(0.9, 0.999), eps=None, weight_decay=None, ema_mu=0.9999, use_mse=None, dropout=None, dropout_seed=None):
@@ -43,13 +123,13 @@ class Trainer:
         self._dtype_code = resolve_dtype(config, dtype)
         if self._dtype_code in (_lib.WDM_F32X3, _lib.WDM_F16):      # training has two modes: f32x3 / f16 (inference modes) train in exact fp32
             self._dtype_code = _lib.WDM_F32
-        opt = getattr(config, "optim", None)
-        self.lr = float(lr if lr is not None else getattr(opt, "lr", 4e-5))
-        self.eps = float(eps if eps is not None else getattr(opt, "eps", 1e-8))
-        self.weight_decay = float(weight_decay if weight_decay is not None else getattr(opt, "weight_decay", 0.0))
+        spec = optimizer_spec(config)                   # utils/optimize.py:5-14; the explicit keyword arguments override
+        self.rule = spec["rule"]
+        self.lr = float(lr if lr is not None else spec["lr"])
+        self.eps = float(eps if eps is not None else spec["eps"])
+        self.weight_decay = float(weight_decay if weight_decay is not None else spec["weight_decay"])
         self.betas, self.ema_mu = (float(betas[0]), float(betas[1])), float(ema_mu)
-        if opt is not None and (getattr(opt, "optimizer", "Adam") != "Adam" or getattr(opt, "amsgrad", False)):
-            raise NotImplementedError("wavedm_amd.Trainer implements optim.optimizer: Adam with amsgrad: False (utils/optimize.py:6-8, raindrop_wavelet.yml)")
+        self.alpha, self.momentum = float(spec["alpha"]), float(spec["momentum"])
         # model.dropout (unet.py:99, :129): masks drawn in the kernels (csrc/dropout.h); the seed is this run's, the masks depend on (seed, rank, step) alone
         self.dropout = float(dropout if dropout is not None else (getattr(getattr(config, "model", None), "dropout", 0.0) or 0.0))
         if not 0.0 <= self.dropout < 1.0:
@@ -78,11 +158,19 @@ class Trainer:
         with torch.cuda.device(self.device):
             self.params = torch.zeros(n, device=self.device)
             self.grads = torch.zeros(n, device=self.device)
-            self.exp_avg = torch.zeros(n, device=self.device)
-            self.exp_avg_sq = torch.zeros(n, device=self.device)
+            # only the state the rule needs, under torch's names: exp_avg / exp_avg_sq (/ max_exp_avg_sq), square_avg, momentum_buffer -- also attributes of the trainer
+            self.opt_state = OrderedDict((k, torch.zeros(n, device=self.device)) for k in STATE_NAMES[self.rule])
             self.ema = torch.zeros(n, device=self.device)
+        for k, buf in self.opt_state.items():
+            setattr(self, k, buf)
+        self._momentum_fresh = True                     # SGD: no step has filled the momentum buffer yet (torch creates it from the first gradient)
         _lib.check(L.wdm_trainer_set_objective(t, 1 if self.use_mse else 0))
-        _lib.check(L.wdm_trainer_set_buffers(t, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(self.ema)))
+        if self.rule == "adam":
+            _lib.check(L.wdm_trainer_set_buffers(t, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(self.ema)))
+        else:
+            _lib.check(L.wdm_trainer_set_buffers(t, _lib.ptr(self.params), _lib.ptr(self.grads), None, None, _lib.ptr(self.ema)))
+            slots = [_lib.ptr(b) for b in self.opt_state.values()] + [None] * (3 - len(self.opt_state))
+            _lib.check(L.wdm_trainer_set_optimizer(t, _RULE_CODES[self.rule], *slots))
         betas_t = sampling.get_beta_schedule(beta_schedule=config.diffusion.beta_schedule, beta_start=config.diffusion.beta_start,
                                              beta_end=config.diffusion.beta_end, num_diffusion_timesteps=config.diffusion.num_diffusion_timesteps)
         self.betas_t = torch.from_numpy(betas_t).float().to(self.device)
@@ -269,8 +357,17 @@ class Trainer:
     def optimizer_step(self):
         self.step += 1
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().wdm_trainer_adam_ema(self._t, self.step, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_mu,
-                                                       _lib.stream_ptr()))
+            if self.rule == "adam":
+                _lib.check(_lib.lib().wdm_trainer_adam_ema(self._t, self.step, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_mu,
+                                                           _lib.stream_ptr()))
+                return
+            # the library's first / second decay: Adam's betas, SGD's momentum, RMSProp's alpha (include/wavedm.h)
+            b1, b2 = {"amsgrad": self.betas, "rmsprop": (0.0, self.alpha), "sgd": (self.momentum, 0.0)}[self.rule]
+            step = self.step
+            if self.rule == "sgd":                      # step 1 is the one that creates the buffer, whatever this trainer's count says (torch's SGD keeps none)
+                step = 1 if self._momentum_fresh else max(2, self.step)
+                self._momentum_fresh = False
+            _lib.check(_lib.lib().wdm_trainer_optim_step(self._t, step, self.lr, b1, b2, self.eps, self.weight_decay, self.ema_mu, _lib.stream_ptr()))
 
     def train_step(self, x0, group=None, generator=None):
         """The body of the reference's loop for one batch of wavelet-domain samples x0 (B,Cin,R,R): noise (model.out_ch channels), antithetic timesteps
@@ -292,42 +389,61 @@ class Trainer:
         """Parameter names in the reference's `model.parameters()` order: torch.optim indexes its state by that position."""
         return [k for k, _ in reference_param_order([(k, v[1]) for k, v in self.layout.items()]) if k in self.layout]
 
+    def current_optimizer_spec(self):
+        """This trainer's optimizer in optimizer_spec's form (the configured rule with the hyper-parameters in force)."""
+        return {"rule": self.rule, "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "alpha": self.alpha,
+                "momentum": self.momentum}
+
     def optimizer_state_dict(self):
+        """torch.optim.{Adam, RMSprop, SGD}.state_dict() of the configured optimizer (torch_optimizer_state_dict)."""
         names = self.param_order()
-        state = {i: {"step": torch.tensor(float(self.step)), "exp_avg": self._view(self.exp_avg, k).detach().cpu().clone(),
-                     "exp_avg_sq": self._view(self.exp_avg_sq, k).detach().cpu().clone()} for i, k in enumerate(names)}
-        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(names)))}
-        return {"state": state, "param_groups": [group]}
+        tensors = {s: [self._view(buf, k).detach().cpu().clone() for k in names] for s, buf in self.opt_state.items()}
+        return torch_optimizer_state_dict(self.current_optimizer_spec(), self.step, tensors)
 
     def load_optimizer_state_dict(self, osd):
-        """Accepts torch.optim.Adam.state_dict() (the reference's checkpoints and this trainer's) and this trainer's round-1 flat format."""
+        """Accepts the state_dict() of the torch.optim object the configured optimizer is (the reference's checkpoints and this trainer's) and, for Adam, this
+        trainer's round-1 flat format.  A checkpoint of another optimizer is a ValueError."""
         if not osd:
             return False
         if "state" in osd and "param_groups" in osd:
+            found = _checkpoint_rule(osd)
+            if found is not None and found != self.rule:
+                raise ValueError(f"the checkpoint holds the state of torch.optim.{_RULE_TITLES[found]}, this trainer is configured for torch.optim.{_RULE_TITLES[self.rule]} "
+                                 "(optim.optimizer / optim.amsgrad)")
             names = self.param_order()
             st = osd["state"]
             if len(st) == 0:
                 return False
             if len(st) != len(names):
                 raise RuntimeError(f"optimizer state holds {len(st)} parameters, the model {len(names)}")
+            g = osd["param_groups"][0]
+            if self.rule == "rmsprop" and (float(g.get("momentum", 0.0)) != 0.0 or g.get("centered", False)):
+                raise NotImplementedError("RMSprop with momentum or centered: the reference's call sets neither (utils/optimize.py:10)")
+            if self.rule == "sgd" and (float(g.get("dampening", 0.0)) != 0.0 or g.get("nesterov", False)):
+                raise NotImplementedError("SGD with dampening or Nesterov momentum: the reference's call sets neither (utils/optimize.py:12)")
             step = None
             for i, k in enumerate(names):
                 e = st[i]
-                if tuple(e["exp_avg"].shape) != self.layout[k][1]:
-                    raise RuntimeError(f"optimizer state {i} has shape {tuple(e['exp_avg'].shape)}, parameter {k} {self.layout[k][1]}")
-                self._view(self.exp_avg, k).copy_(e["exp_avg"].to(self.device, torch.float32))
-                self._view(self.exp_avg_sq, k).copy_(e["exp_avg_sq"].to(self.device, torch.float32))
-                step = int(float(e["step"])) if step is None else step
-            g = osd["param_groups"][0]
-            self.lr, self.eps, self.weight_decay = float(g["lr"]), float(g["eps"]), float(g["weight_decay"])
-            self.betas = (float(g["betas"][0]), float(g["betas"][1]))
-            if g.get("amsgrad", False):
-                raise NotImplementedError("amsgrad optimizer state")
+                for s, buf in self.opt_state.items():
+                    if tuple(e[s].shape) != self.layout[k][1]:
+                        raise RuntimeError(f"optimizer state {i} has shape {tuple(e[s].shape)}, parameter {k} {self.layout[k][1]}")
+                    self._view(buf, k).copy_(e[s].to(self.device, torch.float32))
+                if "step" in e:
+                    step = int(float(e["step"])) if step is None else step
+            self.lr, self.weight_decay = float(g["lr"]), float(g["weight_decay"])
+            if self.rule in ("adam", "amsgrad"):
+                self.eps, self.betas = float(g["eps"]), (float(g["betas"][0]), float(g["betas"][1]))
+            elif self.rule == "rmsprop":
+                self.eps, self.alpha = float(g["eps"]), float(g["alpha"])
+            else:
+                self.momentum = float(g["momentum"])
+                self._momentum_fresh = False
             if step is not None:
                 self.step = step
             return True
         if "exp_avg" in osd and "exp_avg_sq" in osd:                # round-1 format of this repository: the two flat buffers
+            if self.rule != "adam":
+                raise ValueError(f"the checkpoint holds flat Adam moments, this trainer is configured for torch.optim.{_RULE_TITLES[self.rule]}")
             self.exp_avg.copy_(osd["exp_avg"].to(self.device))
             self.exp_avg_sq.copy_(osd["exp_avg_sq"].to(self.device))
             self.step = int(osd.get("step", self.step))
@@ -361,12 +477,13 @@ class Trainer:
 
     def broadcast_state(self, src=0, group=None):
         """What DistributedDataParallel does at construction (ddm_wavelet.py:168): every rank starts from rank `src`'s parameters (and here
-        also its EMA shadow and Adam moments, so that a resumed run is identical on every rank)."""
+        also its EMA shadow and optimizer state, so that a resumed run is identical on every rank)."""
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-            for buf in (self.params, self.ema, self.exp_avg, self.exp_avg_sq):
+            for buf in (self.params, self.ema, *self.opt_state.values()):
                 dist.broadcast(buf, src=src, group=group)
-            st = torch.tensor([self.step, -1 if self.dropout_seed is None else self.dropout_seed], device=self.device, dtype=torch.int64)
+            st = torch.tensor([self.step, -1 if self.dropout_seed is None else self.dropout_seed, int(self._momentum_fresh)], device=self.device, dtype=torch.int64)
             dist.broadcast(st, src=src, group=group)
             self.step = int(st[0].item())
+            self._momentum_fresh = bool(st[2].item())
             self.dropout_seed = None if int(st[1].item()) < 0 else int(st[1].item())  # one base seed; each rank draws with dropout_rank_seed(base, its rank)
