@@ -271,6 +271,15 @@ int wdm_hfrm_forward(wdm_hfrm* m, const float* x, int B, int H, int W, float* y,
 int wdm_image_sqdiff(wdm_handle* h, const float* a, const float* b, int B, int H, int W, double* sums, void* stream);
 int wdm_to_u8_hwc(wdm_handle* h, const float* x, int B, int C, int H, int W, uint8_t* y, void* stream);
 
+/* ---- input side of DiffusiveRestoration.restore_folder: photographs at their own size ----------------
+ * wdm_image_ingest: src (B,H,W,3) u8 HWC -> dst (B,3,Hp,Wp) f32 NCHW in [0,1], value (float)u8 / 255.0f as a correctly rounded division (the bits of
+ *   torch.from_numpy(a).float().div(255)); rows H..Hp-1 and columns W..Wp-1 are filled by symmetric extension that is total for any pad length: the source
+ *   row of output row y is s = y mod 2H, s >= H -> 2H-1-s, columns likewise (numpy.pad(mode="symmetric"): [0 1 2] -> [0 1 2 2 1 0 0 1 2 ...]).
+ *   1 <= H <= Hp, 1 <= W <= Wp, B >= 1, Wp a multiple of 4, dst 16-byte aligned (else WDM_EINVAL); 64-bit element offsets.
+ * wdm_to_u8_hwc_crop: x (B,C,Hp,Wp) f32 -> y (B,H,W,C) u8 from the top-left H x W window, wdm_to_u8_hwc's rounding (its bits when H == Hp and W == Wp). */
+int wdm_image_ingest(wdm_handle* h, const uint8_t* src, int B, int H, int W, float* dst, int Hp, int Wp, void* stream);
+int wdm_to_u8_hwc_crop(wdm_handle* h, const float* x, int B, int C, int Hp, int Wp, int H, int W, uint8_t* y, void* stream);
+
 /* wdm_image_ssim: a, b (B images each, layout by `kind`) on the device -> out[B] (device, fp64): SSIM of each pair as calculate_ssim defines it
  * (utils/metrics.py:82-149; Y conversion :152-255) -- 11x11 Gaussian window (sigma 1.5) over the valid (H-10) x (W-10) region, C1 = (0.01*255)^2,
  * C2 = (0.03*255)^2, moments and map in fp64, the map's mean.

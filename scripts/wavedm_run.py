@@ -3,9 +3,13 @@
 
     python scripts/wavedm_run.py eval  --config raindrop_wavelet.yml --resume ckpt.pth.tar --test_set raindrop --sampling_timesteps 25
     python scripts/wavedm_run.py train --config raindrop_wavelet.yml [--resume ckpt.pth.tar]
+    python scripts/wavedm_run.py restore --config raindrop_wavelet.yml --resume ckpt.pth.tar --input photos/ --output restored/ [--recursive]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/wavedm_run.py eval ...      # one rank per GPU
 
 `eval` = eval_diffusion.py (DiffusiveRestoration.restore over the validation loader), `train` = train_diffusion.py (diffusion.train).
+`restore` has no counterpart in the reference: every image file of --input (png jpg jpeg bmp tif tiff webp; sub-folders with --recursive) is restored at ITS
+OWN SIZE, without ground truth and without the evaluation protocol's 720x480 resize (DiffusiveRestoration.restore_folder), and written to
+--output/<same relative name>.png; one line per image, then `restored N images in T s (X img/s)`.  Under torchrun the files are split over the ranks.
 --config is a file name under ./configs or a path.  Under torchrun every rank restores its share of the validation images (the
 loaders use a DistributedSampler) and rank 0 prints the PSNR over all of them; training all-reduces gradients over RCCL.
 Extras: --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train)."""
@@ -26,7 +30,10 @@ from wavedm_amd.config import load_config               # noqa: E402
 
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["eval", "train"])
+    ap.add_argument("mode", choices=["eval", "train", "restore"])
+    ap.add_argument("--input", default=None, help="restore: folder of images to restore")
+    ap.add_argument("--output", default=None, help="restore: folder the restored PNGs are written to")
+    ap.add_argument("--recursive", action="store_true", help="restore: also the sub-folders of --input (mirrored under --output)")
     ap.add_argument("--config", required=True, help="YAML file (name under ./configs, or a path)")
     ap.add_argument("--resume", default="", help="diffusion checkpoint (*.pth.tar) to evaluate / to resume from")
     ap.add_argument("--grid_r", type=int, default=16, help="stride of the overlapping patch grid (wavelet-domain pixels)")
@@ -48,6 +55,8 @@ def parse(argv=None):
     a.rank = int(os.environ.get("RANK", 0))
     a.world_size = int(os.environ.get("WORLD_SIZE", 1))
     a.local_rank = int(os.environ.get("LOCAL_RANK", 0))
+    if a.mode == "restore" and not (a.input and (a.output or a.no_save)):
+        ap.error("restore needs --input DIR and --output DIR (or --no_save)")
     path = a.config if os.path.isfile(a.config) else os.path.join("configs", a.config)
     return a, load_config(path)
 
@@ -67,8 +76,21 @@ def main(argv=None):
     if not getattr(config.data, "wavelet", False):
         raise SystemExit("wavedm_run: only the wavelet-domain model (data.wavelet: True) is built")
     print(f"=> dataset {config.data.dataset}, rank {args.rank} of {args.world_size} on {config.device}")
-    DATASET = datasets.__dict__[config.data.dataset](args, config)
+    DATASET = datasets.__dict__[config.data.dataset](args, config) if args.mode != "restore" else None
     diffusion = wavedm_amd.DenoisingDiffusion_Wavelet(args, config, dtype=args.dtype)
+    if args.mode == "restore":
+        import time
+        if args.ema and args.resume:
+            diffusion.load_ddm_ckpt(args.resume, ema=True)
+        loader = datasets.image_loader(args.input, config.data.num_workers, config, recursive=args.recursive, shard=(args.rank, args.world_size))
+        restorer = wavedm_amd.DiffusiveRestoration(diffusion, args, config, save_images=not args.no_save)
+        t0 = time.perf_counter()
+        done = restorer.restore_folder(loader, args.output, r=args.grid_r)
+        dt = time.perf_counter() - t0
+        print(f"restored {len(done)} images in {dt:.2f} s ({len(done) / max(dt, 1e-9):.2f} img/s)")
+        if args.world_size > 1:
+            dist.destroy_process_group()
+        return 0
     if args.mode == "train":
         # only now do the ranks diverge: noise, timesteps and crop positions differ per rank (the trainer also broadcasts rank 0's
         # parameters when it is built, as DistributedDataParallel does at construction, ddm_wavelet.py:168)

@@ -11,7 +11,7 @@ from .arch import HFRM
 from .ddm_wavelet import DenoisingDiffusion_Wavelet, data_transform, inverse_data_transform
 from .restoration import DiffusiveRestoration, torchPSNR
 from .sampling import get_beta_schedule, compute_alpha, overlapping_grid_indices, ddim_sample
-from .datasets import RainDrop, RainDropDataset, HFRMImageFolder
+from .datasets import RainDrop, RainDropDataset, HFRMImageFolder, ImageFolder, image_loader
 from .imageio import AsyncImageWriter
 from .metrics import ssim, calculate_ssim
 from .training import Trainer, optimizer_spec
@@ -19,5 +19,5 @@ from .hfrm_training import HFRMTrainer
 
 __all__ = ["WaveletTransform", "DiffusionUNet", "DiffusionUNet_Global", "DenoisingDiffusion_Wavelet", "DiffusiveRestoration",
            "data_transform", "inverse_data_transform", "torchPSNR", "get_beta_schedule", "compute_alpha",
-           "overlapping_grid_indices", "ddim_sample", "HFRM", "RainDrop", "RainDropDataset", "HFRMImageFolder", "AsyncImageWriter", "Trainer", "HFRMTrainer",
+           "overlapping_grid_indices", "ddim_sample", "HFRM", "RainDrop", "RainDropDataset", "HFRMImageFolder", "ImageFolder", "image_loader", "AsyncImageWriter", "Trainer", "HFRMTrainer",
            "ssim", "calculate_ssim", "optimizer_spec"]

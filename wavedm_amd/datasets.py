@@ -187,3 +187,74 @@ def hfrm_train_loader(root, batch_size=8, num_workers=8, config=None):
     ds = HFRMImageFolder(root)
     return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=True, num_workers=num_workers, pin_memory=True,
                                        **worker_kwargs(config, num_workers))
+
+
+IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
+
+
+def list_images(root, recursive=False):
+    """Files under `root` with one of IMAGE_EXTENSIONS (any letter case), as POSIX paths relative to it, sorted; sub-folders only with `recursive`."""
+    if not os.path.isdir(root):
+        raise FileNotFoundError(f"ImageFolder: {root!r} is not a directory")
+    names = []
+    for cur, dirs, files in os.walk(root):
+        rel = os.path.relpath(cur, root)
+        for f in files:
+            if os.path.splitext(f)[1].lower() in IMAGE_EXTENSIONS:
+                names.append(f if rel == "." else "/".join(rel.split(os.sep) + [f]))
+        if not recursive:
+            break
+    return sorted(names)
+
+
+def output_names(names):
+    """Input name -> output name: the relative path with its extension replaced by .png.  Two inputs that map to one output (a.jpg and a.png)
+    are a ValueError that names both."""
+    out, seen = [], {}
+    for n in names:
+        o = os.path.splitext(n)[0] + ".png"
+        if o in seen:
+            raise ValueError(f"ImageFolder: {seen[o]!r} and {n!r} would both be written to {o!r}")
+        seen[o] = n
+        out.append(o)
+    return out
+
+
+class ImageFolder(torch.utils.data.Dataset):
+    """A plain folder of photographs, at their own size and without ground truth -- the input of DiffusiveRestoration.restore_folder (no counterpart
+    in the reference, whose loaders resize every evaluation image to 720x480).  Items: (uint8 (H,W,3) tensor, name), the name being the file's POSIX path
+    relative to `root`, extension included; files sorted by that name, `shard=(k, n)` takes files[k::n].  Pixels in, pixels out: the file is decoded
+    with `Image.open(..).convert("RGB")` and nothing else -- EXIF orientation is NOT applied, alpha is dropped, palettes are expanded.  A file PIL
+    cannot decode raises OSError naming it."""
+
+    def __init__(self, root, recursive=False, shard=(0, 1)):
+        super().__init__()
+        k, n = int(shard[0]), int(shard[1])
+        if not 0 <= k < n:
+            raise ValueError(f"ImageFolder: shard {shard!r} (k of n needs 0 <= k < n)")
+        self.root = root
+        self.names = list_images(root, recursive)[k::n]
+
+    def __len__(self):
+        return len(self.names)
+
+    def __getitem__(self, index):
+        from PIL import Image
+        name = self.names[index]
+        path = os.path.join(self.root, *name.split("/"))
+        try:
+            with Image.open(path) as im:
+                a = np.array(im.convert("RGB"))                     # (a copy the tensor may own)
+        except OSError as e:                                       # (PIL.UnidentifiedImageError is one)
+            raise OSError(f"{path}: cannot decode ({e})") from e
+        return torch.from_numpy(a), name
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+
+def image_loader(root, num_workers=0, config=None, recursive=False, shard=(0, 1)):
+    """ImageFolder behind a DataLoader that yields its items one by one (batch_size=None: the sizes differ), decoded by `num_workers` worker
+    processes from the package's fork server (worker_kwargs)."""
+    ds = ImageFolder(root, recursive=recursive, shard=shard)
+    return torch.utils.data.DataLoader(ds, batch_size=None, shuffle=False, num_workers=num_workers, **worker_kwargs(config, num_workers))

@@ -4,7 +4,11 @@
 `AsyncImageWriter.save(img, path)`: quantise on the GPU (wdm_to_u8_hwc: one byte per sample crosses PCIe instead of four),
 copy to a pinned buffer on a side stream, hand the buffer to a worker thread that waits for the copy's event and encodes
 the PNG with PIL.  The sampler's stream never waits for any of it.  `metrics(gt, out)` returns the three PSNRs the
-reference prints, from one device reduction (wdm_image_sqdiff)."""
+reference prints, from one device reduction (wdm_image_sqdiff).
+
+Image input for photographs at their own size (DiffusiveRestoration.restore_folder): `ingest` takes 8-bit HWC images to the float NCHW tensor the
+models read, padded on the device to the sizes they accept (wdm_image_ingest); `to_u8_hwc(.., crop=(H, W))` takes the padding off again
+(wdm_to_u8_hwc_crop)."""
 from __future__ import annotations
 
 import math
@@ -17,10 +21,65 @@ import torch
 from . import _lib
 
 
-def to_u8_hwc(img: torch.Tensor) -> torch.Tensor:
-    """(B,C,H,W) or (C,H,W) f32 on the GPU -> (B,H,W,C) uint8 with torchvision.utils.save_image's rounding."""
+def _check_size(rc):
+    """A size the library refuses (WDM_EINVAL) is the caller's ValueError, with the library's message."""
+    if rc == _lib.WDM_EINVAL:
+        raise ValueError(f"libwavedm_hip: {_lib.lib().wdm_last_error().decode(errors='replace')}")
+    _lib.check(rc)
+
+
+def padded_size(h: int, w: int, multiple: int = 16, min_side: int = 0):
+    """(h, w) -> (hp, wp): each side rounded up to `multiple`, then raised to `min_side` (itself a multiple of `multiple`) if smaller.  Host arithmetic."""
+    h, w, multiple, min_side = int(h), int(w), int(multiple), int(min_side)
+    if h < 1 or w < 1 or multiple < 1 or min_side < 0 or min_side % multiple:
+        raise ValueError(f"padded_size: h={h} w={w} multiple={multiple} min_side={min_side} (sides >= 1, min_side a multiple of multiple)")
+    up = lambda v: max(-(-v // multiple) * multiple, min_side)
+    return up(h), up(w)
+
+
+def ingest(images, multiple: int = 16, min_side: int = 0, device=None) -> torch.Tensor:
+    """(B,H,W,3) uint8 on the host or the device, or a list of same-sized (H,W,3) tensors -> (B,3,Hp,Wp) f32 in [0,1] on the device, (Hp, Wp) =
+    padded_size(H, W, multiple, min_side).  Values are u8 / 255 as ToTensor gives them (`.float().div(255)`, bit for bit); the padding, at the bottom and
+    the right, is the symmetric extension of numpy.pad(mode="symmetric"), periodic when it is longer than the image.  A host tensor goes through pinned
+    memory to `device` (default: the current one) on the current stream; nothing waits."""
+    if isinstance(images, (list, tuple)):
+        if not images or any(t.shape != images[0].shape or t.device != images[0].device for t in images):
+            raise ValueError("ingest: a list needs at least one image, all of one size and on one device")
+        if images[0].is_cuda:
+            images = torch.stack(list(images))
+        else:
+            pinned = _lib.pinned_dontfork(torch.empty((len(images),) + tuple(images[0].shape), dtype=torch.uint8, pin_memory=True))
+            for k, t in enumerate(images):
+                pinned[k].copy_(t)
+            images = pinned
+    if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[-1] == 3):
+        raise TypeError(f"ingest: expected (B,H,W,3) uint8, got {getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))}")
+    if not images.is_cuda:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if not images.is_pinned():
+            images = _lib.pinned_dontfork(torch.empty(images.shape, dtype=torch.uint8, pin_memory=True)).copy_(images)
+        with torch.cuda.device(dev):
+            images = images.to(dev, non_blocking=True)
+    images = images.contiguous()
+    B, H, W, _ = images.shape
+    Hp, Wp = padded_size(H, W, multiple, min_side)
+    out = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=images.device)
+    with torch.cuda.device(images.device):
+        _check_size(_lib.lib().wdm_image_ingest(_lib.handle(images.device.index or 0), _lib.ptr(images), B, H, W, _lib.ptr(out), Hp, Wp, _lib.stream_ptr()))
+    return out
+
+
+def to_u8_hwc(img: torch.Tensor, crop=None) -> torch.Tensor:
+    """(B,C,H,W) or (C,H,W) f32 on the GPU -> (B,H,W,C) uint8 with torchvision.utils.save_image's rounding.  crop=(h, w): only the top-left h x w
+    window, (B,h,w,C) -- what `ingest` padded comes off without a copy of the float tensor."""
     img = _lib.require_cuda_f32(img if img.dim() == 4 else img[None], "to_u8_hwc input")
     B, C, H, W = img.shape
+    if crop is not None:
+        h, w = int(crop[0]), int(crop[1])
+        out = torch.empty(B, max(h, 0), max(w, 0), C, dtype=torch.uint8, device=img.device)
+        with torch.cuda.device(img.device):
+            _check_size(_lib.lib().wdm_to_u8_hwc_crop(_lib.handle(img.device.index or 0), _lib.ptr(img), B, C, H, W, h, w, _lib.ptr(out), _lib.stream_ptr()))
+        return out
     out = torch.empty(B, H, W, C, dtype=torch.uint8, device=img.device)
     with torch.cuda.device(img.device):
         _lib.check(_lib.lib().wdm_to_u8_hwc(_lib.handle(img.device.index or 0), _lib.ptr(img), B, C, H, W, _lib.ptr(out), _lib.stream_ptr()))
@@ -118,7 +177,10 @@ class AsyncImageWriter:
         """img: (1,C,H,W) or (C,H,W) f32 in [0,1] on the GPU (utils/logging.save_image's first image semantics)."""
         if img.dim() == 4:
             img = img[:1]
-        u8 = to_u8_hwc(img)[0]
+        self.save_u8(to_u8_hwc(img)[0], path)
+
+    def save_u8(self, u8: torch.Tensor, path: str):
+        """u8: (H,W,C) uint8 on the GPU, already quantised (to_u8_hwc) -- queued on the current stream."""
         dev = u8.device
         if self._stream is None or self._stream.device != dev:
             self._stream = torch.cuda.Stream(device=dev)

@@ -26,10 +26,17 @@ What makes this call surface as fast as the sampler underneath it -- all of it b
 * a pipeline of depth two over the groups: a feeder thread pulls the loader, pins the group and copies it to the device on a copy stream while the
   previous group samples; the main thread queues a group's whole device work (HFRM, DWTs, sampler, IDWT, metric sums, 8-bit conversion) WITHOUT waiting
   for it, and only then reads the metrics of the group before -- the GPU's queue never runs dry between groups, PNG encoding runs behind in the writer's
-  threads.  Console lines come out in loader order, as before."""
+  threads.  Console lines come out in loader order, as before.
+
+`restore_folder(src, dst)` is the same machinery for what the reference cannot do: a folder of photographs at their own size, without ground truth
+(DESIGN.md §3.5).  Every image is padded on the device to what the models accept (imageio.ingest: multiples of 16, at least one 4p-pixel patch per
+side, symmetric extension at the bottom and the right), restored like restore() restores, cropped back (imageio.to_u8_hwc(crop=)) and written as
+ONE PNG under the input's name.  No 720x480 resize: this path deliberately departs from the reference's evaluation protocol.  The start noise is drawn
+per FILE (file_seed), so a file's result depends on nothing but its pixels, its name and the seed."""
 from __future__ import annotations
 
 import os
+import zlib
 
 import numpy as np
 import torch
@@ -54,6 +61,81 @@ def save_image(img, path):
         a = a[0]
     a = (a * 255 + 0.5).clamp(0, 255).to(torch.uint8).permute(1, 2, 0).numpy()
     Image.fromarray(a).save(path)
+
+
+def file_seed(seed, name):
+    """The seed of one file's start noise in restore_folder: the run's seed in the high word, the CRC-32 of the file's name (POSIX path relative to the
+    input folder, extension included) in the low one -- not the global generator, so that a file's result does not depend on its neighbours, on the
+    order or on the grouping."""
+    return ((int(seed) & 0x7FFFFFFF) << 32) | zlib.crc32(name.encode("utf-8"))
+
+
+_WS_BYTES = {}      # (kind, config bytes, B[, H, W]) -> workspace bytes the library asks for (host computations, a few hundred distinct keys at most)
+
+
+def _workspace_bytes(kind, cfg, *dims):
+    import ctypes as C
+    if len(_WS_BYTES) >= 256:
+        _WS_BYTES.clear()
+    key = (kind, bytes(cfg)) + dims
+    if key not in _WS_BYTES:
+        L, m = _lib.lib(), C.c_void_p()
+        create, query, destroy = ((L.wdm_unet_create, L.wdm_unet_workspace_bytes, L.wdm_unet_destroy) if kind == "unet" else
+                                  (L.wdm_hfrm_create, L.wdm_hfrm_workspace_bytes, L.wdm_hfrm_destroy))
+        _lib.check(create(None, C.byref(cfg), C.byref(m)))
+        try:
+            n = int(query(m, *dims))
+        finally:
+            destroy(m)
+        if n == 0:
+            raise RuntimeError(f"{kind} workspace query failed: " + L.wdm_last_error().decode(errors="replace"))
+        _WS_BYTES[key] = n
+    return _WS_BYTES[key]
+
+
+def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25):
+    """The terms of estimate_restore_bytes, by name."""
+    from .arch import HFRM
+    from .ddm_wavelet import DenoisingDiffusion_Wavelet
+    from .procedural import unet_in_channels
+    from .unet import _make_config, resolve_dtype
+    m, p = config.model, int(config.data.image_size)
+    n_img, mb = int(n_img), int(max_batch or sampling.DEFAULT_MAX_BATCH)
+    pc, cin = int(m.pred_channels), unet_in_channels(config)
+    code = resolve_dtype(config, dtype)
+    elsize = 2 if code in (_lib.WDM_BF16, _lib.WDM_F16) else 4
+    hp, wp = imageio.padded_size(h, w, 16, 4 * p)
+    hl, wl = sampling.overlapping_grid_indices(hp // 4, wp // 4, p, r)
+    n = n_img * len(hl) * len(wl)
+    split = pc < int(m.in_channels)
+    n_other = int(m.in_channels) - int(m.other_channels_begin) if (split and m.use_other_channels) else 0
+    px, px16 = hp * wp, (hp // 4) * (wp // 4)
+    # f32 tensors of the group's size: x, x_cond (48 bands at 1/16 = 3 planes), the output; with an HFRM its image and bands; x_other; the sampler's lists
+    # (start noise, x_t and x0 of every step: sample_image keeps them); the 8-bit input and output
+    full = n_img * (4 * (px * (3 + 3 + 3 + (6 if split else 0)) + px16 * (n_other + pc * (2 * int(steps) + 1))) + 2 * 3 * int(h) * int(w))
+    hfrm = 0
+    if split:
+        # the HFRM runs min(n_img, MAX_PIXELS / (hp wp)) images per call (arch.HFRM.forward); its workspace grows with the pixels of a call, so one image's
+        # bytes times that count -- not rounded down, which keeps the term from falling where one more row halves the images per call -- in the HFRM's
+        # larger (fp32) mode
+        hc = _lib.HFRMConfig()
+        a = DenoisingDiffusion_Wavelet.HFRM_ARGS
+        hc.in_channel, hc.dim, hc.mid_blk_num, hc.n_enc, hc.n_dec, hc.dtype = a["in_channel"], a["dim"], a["mid_blk_num"], len(a["enc_blk_nums"]), len(a["dec_blk_nums"]), _lib.WDM_F32
+        for i, v in enumerate(a["enc_blk_nums"]):
+            hc.enc_blk_nums[i] = v
+        for i, v in enumerate(a["dec_blk_nums"]):
+            hc.dec_blk_nums[i] = v
+        hfrm = int(_workspace_bytes("hfrm", hc, 1, hp, wp) * min(float(n_img), max(1.0, HFRM.MAX_PIXELS / px)))
+    # the UNet's workspace is kept at the largest call's size (DiffusionUNet.workspace); the sampler's calls never exceed min(n, max_batch) patches
+    unet = _workspace_bytes("unet", _make_config(config, code), min(n, mb))
+    return dict(x96=n * p * p * cin * elsize, eps=n * pc * p * p * 4, full=full, hfrm=hfrm, unet=unet)
+
+
+def estimate_restore_bytes(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25):
+    """Device bytes one sampler call of restore_folder needs for `n_img` images of h x w pixels -- host arithmetic, nothing is allocated: the gathered UNet
+    input (n patches x p x p x cin in the compute type), eps (n x pc x p x p f32), the f32 tensors of the group's padded size, the HFRM's workspace and the
+    UNet's for the largest call.  `r`: the patch grid's stride (default 16), `steps`: the DDIM steps.  Non-decreasing in h, w and n_img."""
+    return sum(restore_terms(h, w, n_img, config, max_batch, dtype, r, steps).values())
 
 
 class _StageBudget:
@@ -341,6 +423,208 @@ class DiffusiveRestoration:
         self.last_outputs, self.last_psnrs, self.last_psnrs_y = outputs, acc["torch"], acc["y"]
         self.last_ssims_y = acc["ssim"] if self._ssim else None
         return outputs, acc["torch"]
+
+    # ---- photographs at their own size, without ground truth -----------------------------------------
+    def _feed_folder(self, items, r, q, stop, budget, hungry):
+        """restore_folder's feeder thread: (u8 (H,W,3), name) items -> groups of same-sized images -> pinned -> device (copy stream), one byte per sample.
+        Puts (u8_dev (n,H,W,3), names, copy_done_event, pinned) on q, an exception if one happened, then None."""
+        dev = self.diffusion.device
+        p4 = 4 * self.config.data.image_size
+        try:
+            torch.cuda.set_device(dev)
+            copy_stream = torch.cuda.Stream(device=dev)
+            group, limit = [], 1
+            auto = getattr(self.args, "images_per_call", None) in (None, 0, "auto", "Auto", "AUTO")
+
+            def emit(group):
+                self._mark(f"feeder: group of {len(group)} read")
+                names = [it[1] for it in group]
+                if group[0][0].is_cuda:
+                    x = torch.stack([it[0] for it in group]).contiguous()
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(dev))
+                    q.put((x, names, ev, None))
+                    return
+                xp = _lib.pinned_dontfork(torch.empty((len(group),) + tuple(group[0][0].shape), dtype=torch.uint8, pin_memory=True))
+                for k, it in enumerate(group):
+                    xp[k].copy_(it[0])
+                with torch.cuda.stream(copy_stream):
+                    xd = xp.to(dev, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(copy_stream)
+                budget.acquire(xp.numel())
+                q.put((xd, names, ev, xp))
+
+            for img, name in items:
+                if stop.is_set():
+                    return
+                name = name[0] if isinstance(name, (list, tuple)) else name
+                if not (isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[-1] == 3):
+                    raise TypeError(f"restore_folder: {name!r}: expected a uint8 (H,W,3) tensor, got {getattr(img, 'dtype', type(img))} {tuple(getattr(img, 'shape', ()))}")
+                if group and group[0][0].shape != img.shape:               # only images of equal ORIGINAL size share a call
+                    emit(group)
+                    group = []
+                if not group:
+                    hp, wp = imageio.padded_size(img.shape[0], img.shape[1], 16, p4)
+                    limit = self.images_per_call_for(hp // 4, wp // 4, r)
+                group.append((img, name))
+                if len(group) >= limit or (auto and hungry.is_set()):
+                    emit(group)
+                    group = []
+            if group:
+                emit(group)
+        except BaseException as e:                                             # surfaced by restore_folder()
+            q.put(e)
+        finally:
+            q.put(None)
+
+    def _fits(self, H, W, n, r):
+        """(fits, estimate, limit) of one sampler call over n images of H x W: args.max_restore_bytes if set, else 0.8 of the device memory that is free now
+        (what torch's allocator holds without using counts as free: it is handed out again)."""
+        dev = self.diffusion.device
+        est = estimate_restore_bytes(H, W, n, self.config, self._max_batch(), self.diffusion.model.dtype_name, r, int(self.diffusion.args.sampling_timesteps))
+        limit = getattr(self.args, "max_restore_bytes", None)
+        if not limit:
+            limit = 0.8 * (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
+        return est <= limit, est, limit
+
+    def _launch_folder_group(self, u8, names, r, out_paths, keep_outputs):
+        """One sampler call over same-sized photographs: everything QUEUED, nothing waited for."""
+        cfg, d = self.config, self.diffusion
+        pc, ob, p = cfg.model.pred_channels, cfg.model.other_channels_begin, cfg.data.image_size
+        dev = d.device
+        n, H, W, _ = u8.shape
+        x = imageio.ingest(u8, 16, 4 * p)
+        Hp, Wp = x.shape[-2:]
+        x_cond = d.wavelet_dec.forward_affine(x)
+        split = pc < cfg.model.in_channels
+        use_other = bool(cfg.model.use_other_channels) and split
+        hf_wav = x_other = None
+        if split:                                                              # (as _launch_group: no HFRM call at all when every band is diffused)
+            hf_wav = d.wavelet_dec.forward_affine(d.generator(x).contiguous())
+            if use_other:
+                x_other = hf_wav[:, ob:].contiguous()
+        seed = getattr(self.args, "seed", None)
+        seed = 61 if seed is None else seed
+        noise = torch.cat([torch.randn((1, pc, Hp // 4, Wp // 4), device=dev, generator=torch.Generator(device=dev).manual_seed(file_seed(seed, name)))
+                           for name in names], dim=0)
+        h_list, w_list = sampling.overlapping_grid_indices(Hp // 4, Wp // 4, p, r)
+        corners = [(i, j) for i in h_list for j in w_list]
+        early = bool(getattr(self.args, "early_stop", True))
+        xs, x0_preds = d.sample_image(x_cond, noise, x_other=x_other, last=False, patch_locs=corners, patch_size=p, total=None,
+                                      use_global=False, use_other=use_other, stop_at=-5 if early else None)
+        pred = x0_preds[-5]
+        out = d.wavelet_rec.compose(pred, hf_wav if split else pred, pc)
+        self._mark("main: sampler queued")
+        q8 = imageio.to_u8_hwc(out, crop=(H, W))
+        for k, name in enumerate(names):
+            if out_paths[name] is not None:
+                self.writer.save_u8(q8[k], out_paths[name])
+        kept = [out[k:k + 1, :, :H, :W].clone() for k in range(n)] if keep_outputs else []
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        return dict(names=names, done=done, HW=(H, W), patches=len(corners), kept=kept, keep=(u8, q8))
+
+    def restore_folder(self, src, dst=None, r=None, recursive=False, keep_outputs=False):
+        """Restore photographs at their own size, without ground truth -> [(name, output path or None), ...] in input order.
+
+        src: a directory (datasets.ImageFolder lists it; sub-folders with `recursive`), or any iterable of (uint8 (H,W,3) tensor, name) pairs --
+             an ImageFolder, datasets.image_loader(...) for decoding in worker processes.  `name` is the file's POSIX path relative to the folder.
+        dst: the output folder: one PNG per input at dst/<name with the extension replaced by .png>, sub-folders created; None (or save_images=False)
+             writes nothing.  keep_outputs: keep the cropped f32 (1,3,H,W) outputs in self.last_outputs (off by default: a folder can be large).
+        Per group of same-sized images: imageio.ingest (pad to multiples of 16 and to at least 4 * data.image_size per side) -> DWT -> HFRM, its DWT, x_other
+        -> stitched sampler, x0_preds[-5] -> IDWT -> crop + 8-bit -> writer.  The start noise of a file comes from its own generator, seeded with
+        file_seed(args.seed, name).  A group that estimate_restore_bytes puts over the memory limit (args.max_restore_bytes, else 0.8 of the free device
+        memory) runs one image per call; one image over it is a RuntimeError before any of its kernels is launched."""
+        import queue
+        import threading
+        from . import datasets
+        cfg, d = self.config, self.diffusion
+        if not (cfg.data.wavelet and not cfg.data.wavelet_in_unet):
+            raise NotImplementedError("DiffusiveRestoration.restore_folder: only the data.wavelet / not data.wavelet_in_unet branch (raindrop_wavelet.yml) is accelerated")
+        if getattr(cfg.data, "global_attn", False):
+            raise NotImplementedError("DiffusiveRestoration.restore_folder: data.global_attn needs `total`, the 720x480 view of the reference's loader, which a photograph at its own size does not have")
+        if getattr(d, "patch_group", None) is not None:
+            raise NotImplementedError("DiffusiveRestoration.restore_folder: the patch-sharded mode (patch_group) is not built for folders; shard the FILES over the ranks (ImageFolder(shard=))")
+        if cfg.model.pred_channels > cfg.model.in_channels:
+            raise ValueError(f"model.pred_channels {cfg.model.pred_channels} exceeds the {cfg.model.in_channels} wavelet bands (model.in_channels)")
+        if int(d.args.sampling_timesteps) < 5:
+            raise IndexError("x0_preds[-5] needs at least 5 sampling steps (restoration.py:108)")
+        items = datasets.ImageFolder(src, recursive=recursive) if isinstance(src, (str, os.PathLike)) else src
+        listed = getattr(getattr(items, "dataset", items), "names", None)
+        if listed is not None:
+            datasets.output_names(listed)                                       # two inputs, one output: refused before anything runs
+        write = dst is not None and self.save_images
+        if os.environ.get("WAVEDM_RESTORE_TRACE", "0") == "1":
+            import time
+            self.trace, self._t0 = [], time.perf_counter()
+        if write and self.writer is None:
+            self.writer = imageio.AsyncImageWriter()
+        results, outputs, taken, pending = [], [], {}, []
+        self.last_info = []
+
+        def finish(g):
+            g["done"].synchronize()
+            for name in g["names"]:
+                print(f"{name}: {g['HW'][1]}x{g['HW'][0]}, {g['patches']} patches")
+                self.last_info.append((name, g["HW"], g["patches"]))
+            outputs.extend(g["kept"])
+
+        q, stop = queue.Queue(), threading.Event()
+        budget = _StageBudget(int(getattr(self.args, "prefetch_bytes", 2 << 30)), stop)
+        hungry = threading.Event()
+        feeder = threading.Thread(target=self._feed_folder, args=(items, r, q, stop, budget, hungry), name="wavedm-restore-feeder", daemon=True)
+        feeder.start()
+        try:
+            with torch.no_grad(), torch.cuda.device(d.device):
+                while True:
+                    try:
+                        staged = q.get_nowait()
+                    except queue.Empty:
+                        hungry.set()
+                        staged = q.get()
+                        hungry.clear()
+                    if staged is None:
+                        break
+                    if isinstance(staged, BaseException):
+                        raise staged
+                    u8, names, copied, pinned = staged
+                    budget.release(u8.numel() if pinned is not None else 0)
+                    out_paths = {}
+                    for name in names:
+                        o = os.path.splitext(name)[0] + ".png"
+                        if o in taken:
+                            raise ValueError(f"restore_folder: {taken[o]!r} and {name!r} would both be written to {o!r}")
+                        taken[o] = name
+                        out_paths[name] = os.path.join(dst, *o.split("/")) if write else None
+                        results.append((name, out_paths[name]))
+                    cur = torch.cuda.current_stream(d.device)
+                    cur.wait_event(copied)
+                    u8.record_stream(cur)                                      # (allocated on the feeder's copy stream)
+                    n, H, W = u8.shape[:3]
+                    # a group that does not fit runs one image per call; one image that does not fit is refused before any kernel of it is launched
+                    calls = [(0, n)] if n == 1 or self._fits(H, W, n, r)[0] else [(k, k + 1) for k in range(n)]
+                    for lo, hi in calls:
+                        if hi - lo == 1:
+                            ok, est, limit = self._fits(H, W, 1, r)
+                            if not ok:
+                                raise RuntimeError(f"restore_folder: {names[lo]!r} ({W}x{H}) needs an estimated {est} bytes of device memory, "
+                                                   f"{int(limit)} are available (args.max_restore_bytes, else 0.8 of the free memory)")
+                        g = self._launch_folder_group(u8[lo:hi], names[lo:hi], r, out_paths, keep_outputs)      # group k queued behind group k - 1 ...
+                        self._mark("main: group queued")
+                        pending.append(g)
+                        while len(pending) > 1:
+                            finish(pending.pop(0))                             # ... before the host waits for k - 1
+                while pending:
+                    finish(pending.pop(0))
+        finally:
+            stop.set()
+            budget.wake()
+            feeder.join()
+        if self.writer is not None:
+            self.writer.flush()
+        self.last_outputs = outputs
+        return results
 
     def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None):
         """restoration.py:170-185.  The start noise is drawn image by image (the reference sees one image per call), so a
