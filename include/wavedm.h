@@ -260,6 +260,23 @@ int wdm_hfrm_finalize(wdm_hfrm* m, void* stream);
 size_t wdm_hfrm_workspace_bytes(const wdm_hfrm* m, int B, int H, int W);
 int wdm_hfrm_forward(wdm_hfrm* m, const float* x, int B, int H, int W, float* y, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* Local channel-attention pooling: the reference's test-time local converter (models/arch.py:46-130, replace_layers + Local_Base.convert
+ * with fast_imp=False).  Every ChannelAttn pools over a sliding window instead of the whole map; at level l (maps of H/2^l x W/2^l, l = 0 ..
+ * n_enc) the window is kh_l = (train_h >> l) * base_h / train_h by kw_l likewise (integer divisions: what the converting forward at the
+ * training size freezes).  A map the window covers (kh_l >= h and kw_l >= w) is pooled globally, exactly as without the mode; otherwise
+ * P[i][j] = mean of rows [r0, r0 + k1) x columns [c0, c0 + k2), k1 = min(h, kh_l), k2 = min(w, kw_l), r0 = clamp(i - (k1 - 1) / 2, 0, h - k1),
+ * c0 = clamp(j - (k2 - 1) / 2, 0, w - k2), and the block scales every pixel by chan_conv(P) at that pixel.
+ *   wdm_hfrm_set_local: all four zero -> global pooling (the default).  WDM_EINVAL for a non-positive size, a training size that is no
+ *   multiple of 2^n_enc, or a window that is empty at some level.  Takes effect at the next wdm_hfrm_workspace_bytes / wdm_hfrm_forward (the
+ *   local mode needs more workspace); no re-finalize needed.  In the local mode wdm_hfrm_forward refuses a workspace below wdm_hfrm_workspace_bytes
+ *   with WDM_ENOMEM before its first launch (in the global mode, as before, at the first allocation that does not fit).
+ *   wdm_hfrm_local_kernel: the frozen (kh_l, kw_l) of a level, 0 and 0 in global mode.
+ *   wdm_hfrm_local_pool: the windowed mean alone, for tests: x (B, H, W, d) NHWC in dtype (WDM_F32: d % 4 == 0, WDM_BF16: d % 8 == 0) ->
+ *   compact_out (B, H - k1 + 1, W - k2 + 1, d), same dtype, the mean of every k1 x k2 window (k1 = min(H, kh), k2 = min(W, kw)); fp32 sums in
+ *   a fixed order (no atomics).  Allocates its own scratch and waits for the stream. */
+int wdm_hfrm_set_local(wdm_hfrm* m, int base_h, int base_w, int train_h, int train_w);
+int wdm_hfrm_local_kernel(const wdm_hfrm* m, int level, int* kh, int* kw);
+int wdm_hfrm_local_pool(wdm_handle* h, const void* x, int B, int H, int W, int d, int kh, int kw, int dtype, void* compact_out, void* stream);
 
 /* ---- output side of DiffusiveRestoration.restore ---------------------------------
  * wdm_image_sqdiff: a, b (B,3,H,W) f32 on the device -> sums[B][2] (device, fp64):

@@ -12,7 +12,8 @@ OWN SIZE, without ground truth and without the evaluation protocol's 720x480 res
 --output/<same relative name>.png; one line per image, then `restored N images in T s (X img/s)`.  Under torchrun the files are split over the ranks.
 --config is a file name under ./configs or a path.  Under torchrun every rank restores its share of the validation images (the
 loaders use a DistributedSampler) and rank 0 prints the PSNR over all of them; training all-reduces gradients over RCCL.
-Extras: --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train)."""
+Extras: --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train),
+--hfrm-local [--hfrm-base-size H W] [--hfrm-train-size H W] (eval, restore: the HFRM's channel attention pools over a window instead of the whole image)."""
 import argparse
 import os
 import random
@@ -46,6 +47,15 @@ def parse(argv=None):
     ap.add_argument("--images_per_call", type=int, default=0, help="eval: images per sampler call; 0 = automatic (as many same-sized images as fill the UNet calls), 1 = the reference's loop")
     ap.add_argument("--full_length", action="store_true", help="eval: also run the four DDIM steps behind x0_preds[-5], which restore() never reads (the reference's step count)")
     ap.add_argument("--hfrm_ckpt", default=None)
+    ap.add_argument("--hfrm-local", dest="hfrm_local", action="store_true",
+                    help="eval, restore: the HFRM's channel attention pools over a sliding window of --hfrm-base-size instead of the whole image (the reference's test-time local "
+                         "converter, models/arch.py:46-130, for photographs larger than the HFRM's training images).  A map the window covers is pooled as without the flag: at "
+                         "the evaluation protocol's fixed 480x720 and the default window every level is covered, so `eval --hfrm-local` returns the same bits as `eval`.  The effect "
+                         "on restoration quality has not been measured.")
+    ap.add_argument("--hfrm-base-size", dest="hfrm_base_size", type=int, nargs=2, metavar=("H", "W"), default=None,
+                    help="with --hfrm-local: the pooling window at full resolution (default 720 1080, 1.5 x the training size)")
+    ap.add_argument("--hfrm-train-size", dest="hfrm_train_size", type=int, nargs=2, metavar=("H", "W"), default=None,
+                    help="with --hfrm-local: the size of the HFRM's training images (default 480 720)")
     ap.add_argument("--max_steps", type=int, default=None)
     ap.add_argument("--no_save", action="store_true", help="eval: metrics only, no PNGs")
     ap.add_argument("--ssim", action="store_true", help="eval: also SSIM (Y channel) of every output against its gt, on the device; prints an `ssim all` line")
@@ -55,6 +65,15 @@ def parse(argv=None):
     a.rank = int(os.environ.get("RANK", 0))
     a.world_size = int(os.environ.get("WORLD_SIZE", 1))
     a.local_rank = int(os.environ.get("LOCAL_RANK", 0))
+    if (a.hfrm_base_size or a.hfrm_train_size) and not a.hfrm_local:
+        ap.error("--hfrm-base-size / --hfrm-train-size need --hfrm-local")
+    if a.hfrm_local and a.mode == "train":
+        ap.error("--hfrm-local is a test-time mode (eval, restore)")
+    if a.hfrm_local:                                       # args.hfrm_local: True, or (base_size, train_size) (DenoisingDiffusion_Wavelet)
+        from wavedm_amd.ddm_wavelet import HFRM_LOCAL_DEFAULT
+        train = tuple(a.hfrm_train_size) if a.hfrm_train_size else HFRM_LOCAL_DEFAULT[1][-2:]
+        base = tuple(a.hfrm_base_size) if a.hfrm_base_size else (train[0] * 3 // 2, train[1] * 3 // 2)
+        a.hfrm_local = (base, (1, 3) + tuple(train))
     if a.mode == "restore" and not (a.input and (a.output or a.no_save)):
         ap.error("restore needs --input DIR and --output DIR (or --no_save)")
     path = a.config if os.path.isfile(a.config) else os.path.join("configs", a.config)

@@ -5,7 +5,9 @@ libwavedm_hip.so.
 * same constructor signature and defaults as the reference class, same `state_dict()` keys / shapes / order
   (448 tensors, 15.94 M parameters at the `ddm_wavelet.py:139` configuration), so `lastest.pth` loads with
   `load_state_dict(strict=True)`;
-* `forward(x)`: x (B, 3, H, W) fp32 NCHW on the GPU, H and W multiples of 16 -> (B, 3, H, W) fp32 NCHW.
+* `forward(x)`: x (B, 3, H, W) fp32 NCHW on the GPU, H and W multiples of 16 -> (B, 3, H, W) fp32 NCHW;
+* `convert(base_size, train_size)`: the reference's test-time local converter (`Local_Base.convert`, arch.py:114-130, which the reference
+  ships and never calls): every ChannelAttn pools over a sliding window of `base_size` (at full resolution) instead of the whole map.
 
 The parameter tree comes from the library's own table (wdm_hfrm_param_info)."""
 from __future__ import annotations
@@ -56,6 +58,50 @@ class HFRM(nn.Module):
         self._packed = None
         self._packed_sig = None
         self._ws = {}
+        self._local = None          # ((base_h, base_w), (train_h, train_w)) after convert(), None: global pooling
+
+    # ---- test-time local converter (arch.py:46-130) ---------------------------------------------
+    @staticmethod
+    def local_sizes(base_size, train_size):
+        """(base_h, base_w, train_h, train_w) of a convert() call: `base_size` an int or a pair, `train_size` (1, C, H, W) as in the reference."""
+        if isinstance(base_size, int):
+            base_size = (base_size, base_size)
+        base_size, train_size = tuple(int(v) for v in base_size), tuple(int(v) for v in train_size)
+        if len(base_size) != 2 or len(train_size) < 2:
+            raise ValueError("HFRM.convert: base_size is an int or (h, w), train_size is (1, C, H, W)")
+        return base_size[0], base_size[1], train_size[-2], train_size[-1]
+
+    def convert(self, base_size=None, train_size=None, fast_imp=False):
+        """`Local_Base.convert(base_size, train_size=..., fast_imp=False)`: from now on every ChannelAttn pools over a window -- at level l
+        of `(train_h >> l) * base_h // train_h` rows and likewise columns, what the reference's converting forward at `train_size` freezes --
+        wherever that window does not cover the map, with replicate padding at the borders; a covered map is pooled globally, bit for bit as
+        before.  `convert(None)` returns to global pooling.  Test-time only: the trainer (hfrm_training) never pools locally.  Returns self."""
+        if fast_imp:
+            raise NotImplementedError("HFRM.convert: fast_imp=True is not implemented (the reference calls that path non-equivalent)")
+        L = _lib.lib()
+        if base_size is None:
+            _lib.check(L.wdm_hfrm_set_local(self._m, 0, 0, 0, 0))
+            self._local = None
+        else:
+            if train_size is None:
+                raise ValueError("HFRM.convert: train_size=(1, C, H, W) is required with a base_size")
+            bh, bw, th, tw = self.local_sizes(base_size, train_size)
+            _lib.check(L.wdm_hfrm_set_local(self._m, bh, bw, th, tw))
+            self._local = ((bh, bw), (th, tw))
+        self._ws = {}
+        return self
+
+    @property
+    def local_kernels(self):
+        """[(kh, kw)] of the pools at level 0 .. len(enc_blk_nums) (the last is mid_blks) after convert(); [] while pooling globally."""
+        if self._local is None:
+            return []
+        L, out = _lib.lib(), []
+        kh, kw = C.c_int(), C.c_int()
+        for lv in range(self._cfg.n_enc + 1):
+            _lib.check(L.wdm_hfrm_local_kernel(self._m, lv, C.byref(kh), C.byref(kw)))
+            out.append((kh.value, kw.value))
+        return out
 
     def _register(self, key, shape):
         parts = key.split(".")
@@ -108,7 +154,7 @@ class HFRM(nn.Module):
         return self._packed
 
     def _workspace(self, B, H, W, device):
-        key = (B, H, W, str(device))
+        key = (B, H, W, str(device), self._local)
         if key not in self._ws:
             n = int(_lib.lib().wdm_hfrm_workspace_bytes(self._m, B, H, W))
             if n == 0:

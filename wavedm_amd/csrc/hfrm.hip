@@ -195,6 +195,136 @@ __global__ __launch_bounds__(256) void scale_channels_kernel(T* __restrict__ g, 
     }
 }
 
+// ---- local channel-attention pooling (the reference's test-time local converter, arch.py:46-112, fast_imp=False) ----------
+// The mean over a k1 x k2 window is two 1-D windowed sums: down the columns (model dtype -> f32), then along the rows (f32 -> model
+// dtype, divided by k1 k2).  One body does both (two kernels, so that a trace tells the passes apart by name): a "line" is the walk of one 16-byte channel vector along the summed axis, a thread owns
+// one line and one segment of `seg` consecutive outputs of it (grid.y = segments).  The first output of a segment is the plain sum of its k
+// terms, each further one is (s + entering) - leaving: two loads per output, and the rounding drift of the running sum ends with the
+// segment (local_seg() bounds it at k / 4 steps).  Sums are fp32 in a fixed order, no atomics: the same input gives the same bits, whatever
+// the batch.  line l -> (q, r) = (l / inner_n, l % inner_n): element offset q * q_stride + r * VEC, outputs `step` elements apart.
+//   columns: q = image, r = (column, channel vector), step = W d;  rows: q = (image, output row), r = channel vector, step = d
+template <typename T, bool IN_F32>
+__device__ __forceinline__ void lp_load(const void* __restrict__ p, long long off, float* f) {
+    if constexpr (IN_F32) {
+#pragma unroll
+        for (int v = 0; v < TI<T>::VEC / 4; ++v) TI<float>::unpack(*(const uint4*)((const float*)p + off + 4 * v), f + 4 * v);
+    } else {
+        TI<T>::unpack(*(const uint4*)((const T*)p + off), f);
+    }
+}
+template <typename T, bool IN_F32, bool OUT_F32>
+__device__ __forceinline__ void window_sum(const void* __restrict__ in, void* __restrict__ out, long long lines, long long inner_n, long long in_q,
+                                           long long out_q, long long in_step, long long out_step, int k, int Lo, int seg, float div) {
+    constexpr int VEC = TI<T>::VEC;
+    const long long lid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int o0 = blockIdx.y * seg, o1 = min(o0 + seg, Lo);
+    if (lid >= lines || o0 >= Lo) return;
+    const long long q = lid / inner_n, r = lid - q * inner_n;
+    const long long ib = q * in_q + r * VEC, ob = q * out_q + r * VEC;
+    auto store = [&](int o, const float* s) {
+        if constexpr (OUT_F32) {
+#pragma unroll
+            for (int v = 0; v < VEC / 4; ++v) *(uint4*)((float*)out + ob + o * out_step + 4 * v) = TI<float>::pack(s + 4 * v);
+        } else {
+            float m[VEC];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) m[e] = s[e] / div;
+            *(uint4*)((T*)out + ob + o * out_step) = TI<T>::pack(m);
+        }
+    };
+    float s[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) s[e] = 0.f;
+#pragma unroll 4
+    for (int t = 0; t < k; ++t) {
+        float f[VEC];
+        lp_load<T, IN_F32>(in, ib + (o0 + t) * in_step, f);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s[e] += f[e];
+    }
+    store(o0, s);
+    for (int o = o0 + 1; o < o1; ++o) {
+        float fa[VEC], fb[VEC];
+        lp_load<T, IN_F32>(in, ib + (o + k - 1) * in_step, fa);
+        lp_load<T, IN_F32>(in, ib + (o - 1) * in_step, fb);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s[e] = (s[e] + fa[e]) - fb[e];
+        store(o, s);
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void window_colsum_kernel(const T* __restrict__ in, float* __restrict__ out, long long lines, long long inner_n, long long in_q,
+                                                            long long out_q, long long step, int k, int Lo, int seg) {
+    window_sum<T, false, true>(in, out, lines, inner_n, in_q, out_q, step, step, k, Lo, seg, 1.f);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void window_rowmean_kernel(const float* __restrict__ in, T* __restrict__ out, long long lines, long long inner_n, long long in_q,
+                                                             long long out_q, long long step, int k, int Lo, int seg, float div) {
+    window_sum<T, true, false>(in, out, lines, inner_n, in_q, out_q, step, step, k, Lo, seg, div);
+}
+
+// g[b][i][j][c] *= S[b][clamp(i - p1, 0, Ho - 1)][clamp(j - p2, 0, Wo - 1)][c]: S is the compact map after chan_conv, the clamps are the
+// reference's replicate padding ((k - 1) / 2 before, k / 2 behind)
+template <typename T>
+__global__ __launch_bounds__(256) void scale_local_kernel(T* __restrict__ g, const T* __restrict__ S, long long nvec, int d, int H, int W, int Ho, int Wo,
+                                                          int p1, int p2) {
+    constexpr int VEC = TI<T>::VEC;
+    const int cols = d / VEC;
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < nvec; id += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(id % cols) * VEC;
+        const long long pix = id / cols;
+        const int j = (int)(pix % W), i = (int)((pix / W) % H);
+        const long long b = pix / ((long long)W * H);
+        const int si = min(max(i - p1, 0), Ho - 1), sj = min(max(j - p2, 0), Wo - 1);
+        float f[VEC], s[VEC];
+        TI<T>::unpack(*(const uint4*)(g + pix * d + c), f);
+        TI<T>::unpack(*(const uint4*)(S + ((b * Ho + si) * Wo + sj) * d + c), s);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) f[e] *= s[e];
+        *(uint4*)(g + pix * d + c) = TI<T>::pack(f);
+    }
+}
+
+// Outputs per segment of a windowed sum over k terms with Lo outputs on `lines_img` lines per image.  At most k / 4 running steps: with the
+// k - 1 roundings of the restart and two per step, each relative to a sum of at most k + 1 terms, a stage stays within 1.5 k ulp, both stages
+// and the division within 2 (k1 + k2) 2^-24.  Shorter where an image alone would not fill the chip (65536 threads), but not below 16
+// outputs: every restart reads k terms again.  Depends on the image's shape only, never on the batch: the bits do not either.
+constexpr long long LOCAL_FILL_THREADS = 65536;
+static int local_seg(int k, int Lo, long long lines_img) {
+    const int hi = std::max(1, k / 4), lo = std::min(hi, 16);
+    const long long need = std::max(1LL, (LOCAL_FILL_THREADS + lines_img - 1) / lines_img);
+    const int fill = (int)((Lo + need - 1) / need);
+    return std::min(hi, std::max(lo, fill));
+}
+
+// x (B, H, W, d) NHWC -> compact (B, H - k1 + 1, W - k2 + 1, d), the mean of every k1 x k2 window; colsum: f32 scratch (B, H - k1 + 1, W, d)
+int k_local_pool(const void* x, int B, int H, int W, int d, int k1, int k2, int dtype, float* colsum, void* compact, hipStream_t s) {
+    const int vec = dtype == WDM_BF16 ? 8 : 4, cols = d / vec;
+    const int Ho = H - k1 + 1, Wo = W - k2 + 1;
+    {
+        const long long lines_img = (long long)W * cols, lines = B * lines_img;
+        const int seg = local_seg(k1, Ho, lines_img);
+        // grid.y holds the segments: a walk of more than 65535 of them (a window below 4 on a map that long) is refused rather than given longer
+        // segments, which would leave the error bound -- no map the HFRM can run is that long (the 4 GB descriptor range ends far earlier)
+        if ((Ho + seg - 1) / seg > 65535) WDM_FAIL(WDM_EINVAL, "local pooling: %d output rows in segments of %d exceed the grid", Ho, seg);
+        const dim3 grid((unsigned)nblk(lines, 256), (unsigned)((Ho + seg - 1) / seg));
+        const long long step = (long long)W * d;
+        if (dtype == WDM_BF16) hipLaunchKernelGGL(window_colsum_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)x, colsum, lines, lines_img, H * step, Ho * step, step, k1, Ho, seg);
+        else hipLaunchKernelGGL(window_colsum_kernel<float>, grid, dim3(256), 0, s, (const float*)x, colsum, lines, lines_img, H * step, Ho * step, step, k1, Ho, seg);
+    }
+    {
+        const long long lines_img = (long long)Ho * cols, lines = B * lines_img;
+        const int seg = local_seg(k2, Wo, lines_img);
+        if ((Wo + seg - 1) / seg > 65535) WDM_FAIL(WDM_EINVAL, "local pooling: %d output columns in segments of %d exceed the grid", Wo, seg);
+        const dim3 grid((unsigned)nblk(lines, 256), (unsigned)((Wo + seg - 1) / seg));
+        const float div = (float)((long long)k1 * k2);
+        if (dtype == WDM_BF16) hipLaunchKernelGGL(window_rowmean_kernel<__bf16>, grid, dim3(256), 0, s, (const float*)colsum, (__bf16*)compact, lines, (long long)cols, (long long)W * d, (long long)Wo * d, (long long)d, k2, Wo, seg, div);
+        else hipLaunchKernelGGL(window_rowmean_kernel<float>, grid, dim3(256), 0, s, (const float*)colsum, (float*)compact, lines, (long long)cols, (long long)W * d, (long long)Wo * d, (long long)d, k2, Wo, seg, div);
+    }
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
 // SimpleGate: z[p][c] = x[p][c] * x[p][d + c]
 template <typename T>
 __global__ __launch_bounds__(256) void gate_kernel(const T* __restrict__ x, T* __restrict__ z, long long nvec, int d) {
@@ -315,6 +445,7 @@ struct BlockD {
     int p_beta, p_gamma, p_n1w, p_n1b, p_n2w, p_n2b, p_dww, p_dwb, p_caw, p_cab;   // raw parameter indices
     int p_w[5], p_b[5];                                                            // conv1..conv5 raw indices (conv2 = depthwise)
     GemmD g1, g3, g4, g5;
+    GemmD gca;                       // chan_conv as a GEMM over the compact map (local pooling); global pooling runs it through k_linear on the raw weights
 };
 }  // namespace
 
@@ -333,6 +464,11 @@ struct wdm_hfrm {
     std::vector<BlockD> mid;
     std::vector<int> p_down_w, p_down_b, p_up_w;
     std::vector<GemmD> g_down, g_up;
+    // local channel-attention pooling (wdm_hfrm_set_local): the window and training size as given, and the pools' kernel sizes per level
+    // 0..n_enc as the reference's converting forward freezes them (arch.py:66-72); local == false: every pool is global
+    bool local = false;
+    int base_hw[2] = {0, 0}, train_hw[2] = {0, 0};
+    int lk_h[9] = {0}, lk_w[9] = {0};
 
     size_t take(size_t bytes) { size_t o = packed_bytes; packed_bytes = align_up(packed_bytes + bytes, 256); return o; }
     int add(const std::string& name, std::initializer_list<int64_t> shp) {
@@ -367,7 +503,7 @@ struct wdm_hfrm {
 
     int build();
     int finalize(hipStream_t s);
-    int run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W);
+    int run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W, int level);
     int gemm_rows(Ctx& c, const GemmD& g, const void* x, long long M, const void* res, void* y);
     int forward(Ctx& c, const float* x, int B, int H, int W, float* y);
 };
@@ -397,6 +533,10 @@ int wdm_hfrm::build() {
     }
     p_cout_w = add("conv_out.weight", {cfg.in_channel, dim, 3, 3}); p_cout_b = add("conv_out.bias", {cfg.in_channel});
     cout_w_off = take(conv_packed_bytes(dim, cfg.in_channel, 3, cfg.dtype));
+    // behind everything else: the offsets of the global mode's operands stay where they were
+    for (auto& lv : enc) for (auto& b : lv) b.gca = gemm(b.d, b.d);
+    for (auto& lv : dec) for (auto& b : lv) b.gca = gemm(b.d, b.d);
+    for (auto& b : mid) b.gca = gemm(b.d, b.d);
     return WDM_OK;
 }
 
@@ -421,6 +561,7 @@ int wdm_hfrm::finalize(hipStream_t s) {
         pg(b.g3, b.p_w[2], b.p_b[2], b.p_beta, 1);       // y = x + beta * conv3(.)  ->  beta folded into conv3
         pg(b.g4, b.p_w[3], b.p_b[3], -1, 1);
         pg(b.g5, b.p_w[4], b.p_b[4], b.p_gamma, 1);      // out = y + gamma * conv5(.)
+        pg(b.gca, b.p_caw, b.p_cab, -1, 1);
     };
     for (auto& lv : enc) for (auto& b : lv) pblock(b);
     for (auto& lv : dec) for (auto& b : lv) pblock(b);
@@ -445,7 +586,7 @@ int wdm_hfrm::gemm_rows(Ctx& c, const GemmD& g, const void* x, long long M, cons
     return launch_conv(a, MODE_P1, c.dtype, c.s);
 }
 
-int wdm_hfrm::run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W) {
+int wdm_hfrm::run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W, int level) {
     const int d = b.d, HW = H * W;
     const long long M = (long long)B * HW;
     const size_t es = dsize(c.dtype);
@@ -458,10 +599,19 @@ int wdm_hfrm::run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W) {
     const int ppb = (256 / cols_blk) * 8;                   // pixels per pooling block: 8 per thread
     const int nb = (HW + ppb - 1) / ppb;
     float* part = (float*)A((size_t)B * nb * d * 4);
-    float* pooled = (float*)A((size_t)B * d * 4);
-    float* sc = (float*)A((size_t)B * d * 4);
+    // local pooling at a level whose window does not cover the map: the windowed mean (compact: one value per distinct window), chan_conv on it, a
+    // per-pixel scale; a covered map is the global mean -- the three kernels below, as without the mode (arch.py:78-79)
+    // (`part`, the global pool's partials, is written by dw3x3_gate_kernel at a windowed level too and not read there: 1/8 ... 1/64 of a pixel's bytes
+    // per pixel, left in rather than a second instantiation of that kernel)
+    const bool loc = local && !(lk_h[level] >= H && lk_w[level] >= W);
+    const int k1 = loc ? std::min(H, lk_h[level]) : H, k2 = loc ? std::min(W, lk_w[level]) : W;
+    const int Ho = H - k1 + 1, Wo = W - k2 + 1;
+    const long long Mc = (long long)B * Ho * Wo;
+    float* pooled = loc ? (float*)A((size_t)B * Ho * W * d * 4) : (float*)A((size_t)B * d * 4);      // local: the column sums
+    void* cmp = loc ? A((size_t)Mc * d * es) : nullptr;
+    float* sc = loc ? (float*)A((size_t)Mc * d * es) : (float*)A((size_t)B * d * 4);                  // local: chan_conv(compact), model dtype
     void* y = A((size_t)M * d * es);
-    if (!n1 || !a2 || !g || !part || !pooled || !sc || !y) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block)");
+    if (!n1 || !a2 || !g || !part || !pooled || (loc && !cmp) || !sc || !y) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block)");
     if (!c.dry) {
         const float* n1w = raw(b.p_n1w); const float* n1b = raw(b.p_n1b);
         const int lpp = d / vec, ppw = lpp <= 64 ? 64 / lpp : 1;
@@ -473,12 +623,19 @@ int wdm_hfrm::run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W) {
         const dim3 grid(nb, B, (cols + 255) / 256);
         if (c.dtype == WDM_BF16) hipLaunchKernelGGL(dw3x3_gate_kernel<__bf16>, grid, dim3(256), 0, c.s, (const __bf16*)a2, (__bf16*)g, H, W, d, raw(b.p_dww), raw(b.p_dwb), part, nb, ppb);
         else hipLaunchKernelGGL(dw3x3_gate_kernel<float>, grid, dim3(256), 0, c.s, (const float*)a2, (float*)g, H, W, d, raw(b.p_dww), raw(b.p_dwb), part, nb, ppb);
-        hipLaunchKernelGGL(pool_reduce_kernel, dim3((d + 63) / 64, B), dim3(256), 0, c.s, part, pooled, B, nb, d, 1.0f / (float)HW);
-        WDM_TRY(k_linear(pooled, B, d, raw(b.p_caw), raw(b.p_cab), d, sc, 0, c.s));
         const long long nvec = M * cols;
         const int gg = nblk(nvec, 256) > 16384 ? 16384 : nblk(nvec, 256);
-        if (c.dtype == WDM_BF16) hipLaunchKernelGGL(scale_channels_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (__bf16*)g, sc, nvec, d, HW);
-        else hipLaunchKernelGGL(scale_channels_kernel<float>, dim3(gg), dim3(256), 0, c.s, (float*)g, sc, nvec, d, HW);
+        if (loc) {
+            WDM_TRY(k_local_pool(g, B, H, W, d, k1, k2, c.dtype, pooled, cmp, c.s));
+            WDM_TRY(gemm_rows(c, b.gca, cmp, Mc, nullptr, sc));
+            if (c.dtype == WDM_BF16) hipLaunchKernelGGL(scale_local_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (__bf16*)g, (const __bf16*)sc, nvec, d, H, W, Ho, Wo, (k1 - 1) / 2, (k2 - 1) / 2);
+            else hipLaunchKernelGGL(scale_local_kernel<float>, dim3(gg), dim3(256), 0, c.s, (float*)g, (const float*)sc, nvec, d, H, W, Ho, Wo, (k1 - 1) / 2, (k2 - 1) / 2);
+        } else {
+            hipLaunchKernelGGL(pool_reduce_kernel, dim3((d + 63) / 64, B), dim3(256), 0, c.s, part, pooled, B, nb, d, 1.0f / (float)HW);
+            WDM_TRY(k_linear(pooled, B, d, raw(b.p_caw), raw(b.p_cab), d, sc, 0, c.s));
+            if (c.dtype == WDM_BF16) hipLaunchKernelGGL(scale_channels_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (__bf16*)g, sc, nvec, d, HW);
+            else hipLaunchKernelGGL(scale_channels_kernel<float>, dim3(gg), dim3(256), 0, c.s, (float*)g, sc, nvec, d, HW);
+        }
         WDM_TRY(gemm_rows(c, b.g3, g, M, t.p, y));                                   // y = x + beta*conv3(.)
         const float* n2w = raw(b.p_n2w); const float* n2b = raw(b.p_n2b);
         if (c.dtype == WDM_BF16) hipLaunchKernelGGL(ln2d_kernel<__bf16>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c.s, (const __bf16*)y, (__bf16*)n1, M, d, n2w, n2b, 1e-6f);
@@ -489,7 +646,7 @@ int wdm_hfrm::run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W) {
         WDM_TRY(gemm_rows(c, b.g5, g, M, y, t.p));                                   // out = y + gamma*conv5(.), written over the block input
         WDM_HIP(hipGetLastError());
     }
-    c.ar->free(n1); c.ar->free(a2); c.ar->free(g); c.ar->free(part); c.ar->free(pooled); c.ar->free(sc); c.ar->free(y);
+    c.ar->free(n1); c.ar->free(a2); c.ar->free(g); c.ar->free(part); c.ar->free(pooled); if (cmp) c.ar->free(cmp); c.ar->free(sc); c.ar->free(y);
     return WDM_OK;
 }
 
@@ -511,7 +668,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
     }
     std::vector<Tens> encs;
     for (int i = 0; i < nlev; ++i) {
-        for (auto& b : enc[i]) WDM_TRY(run_block(c, b, t, B, h, w));
+        for (auto& b : enc[i]) WDM_TRY(run_block(c, b, t, B, h, w, i));
         encs.push_back(t);
         // down: space-to-depth + GEMM (4d -> 2d)
         void* u = c.ar->alloc((size_t)B * (h / 2) * (w / 2) * 4 * d * es);
@@ -528,7 +685,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         c.ar->free(u);
         t = nt; d *= 2; h /= 2; w /= 2;
     }
-    for (auto& b : mid) WDM_TRY(run_block(c, b, t, B, h, w));
+    for (auto& b : mid) WDM_TRY(run_block(c, b, t, B, h, w, nlev));
     for (int i = 0; i < cfg.n_dec; ++i) {
         // up: 1x1 (d -> 2d, no bias) + PixelShuffle(2) + skip
         void* p = c.ar->alloc((size_t)B * h * w * 2 * d * es);
@@ -545,7 +702,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         }
         c.ar->free(p); c.ar->free(t.p); c.ar->free(skip.p);
         t = nt; d /= 2; h *= 2; w *= 2;
-        for (auto& b : dec[i]) WDM_TRY(run_block(c, b, t, B, h, w));
+        for (auto& b : dec[i]) WDM_TRY(run_block(c, b, t, B, h, w, nlev - 1 - i));
     }
     // conv_out 3x3 (dim -> 3) + input, NCHW f32 out
     {
@@ -609,6 +766,54 @@ int wdm_hfrm_finalize(wdm_hfrm* m, void* stream) {
     if (!m || !m->packed) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_finalize: no packed buffer");
     return m->finalize((hipStream_t)stream);
 }
+int wdm_hfrm_set_local(wdm_hfrm* m, int base_h, int base_w, int train_h, int train_w) {
+    if (!m) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_local: null argument");
+    if (!base_h && !base_w && !train_h && !train_w) {
+        m->local = false;
+        for (int l = 0; l < 9; ++l) m->lk_h[l] = m->lk_w[l] = 0;
+        m->base_hw[0] = m->base_hw[1] = m->train_hw[0] = m->train_hw[1] = 0;
+        return WDM_OK;
+    }
+    if (base_h <= 0 || base_w <= 0 || train_h <= 0 || train_w <= 0)
+        WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_local: window %d x %d and training size %d x %d must be positive (all zero: global pooling)", base_h, base_w, train_h, train_w);
+    const int n = m->cfg.n_enc;
+    if (train_h % (1 << n) || train_w % (1 << n))
+        WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_local: training size %d x %d must be a multiple of %d (the converting forward runs at it)", train_h, train_w, 1 << n);
+    int kh[9], kw[9];
+    for (int l = 0; l <= n; ++l) {      // arch.py:71-72 on the level-l map of the converting forward, (train >> l): integer divisions
+        const long long a = (long long)(train_h >> l) * base_h / train_h, b = (long long)(train_w >> l) * base_w / train_w;
+        if (a < 1 || b < 1) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_local: window %d x %d is empty at level %d (training size %d x %d)", base_h, base_w, l, train_h, train_w);
+        if (a > 0x7fffffff || b > 0x7fffffff) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_local: window %d x %d too large", base_h, base_w);
+        kh[l] = (int)a; kw[l] = (int)b;
+    }
+    for (int l = 0; l < 9; ++l) { m->lk_h[l] = l <= n ? kh[l] : 0; m->lk_w[l] = l <= n ? kw[l] : 0; }
+    m->base_hw[0] = base_h; m->base_hw[1] = base_w; m->train_hw[0] = train_h; m->train_hw[1] = train_w;
+    m->local = true;
+    return WDM_OK;
+}
+int wdm_hfrm_local_kernel(const wdm_hfrm* m, int level, int* kh, int* kw) {
+    if (!m || level < 0 || level > m->cfg.n_enc) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_local_kernel: level out of range");
+    if (kh) *kh = m->lk_h[level];
+    if (kw) *kw = m->lk_w[level];
+    return WDM_OK;
+}
+/* the windowed mean on its own (unit tests): allocates its f32 column sums itself and waits for the stream -- not a building block of a forward */
+int wdm_hfrm_local_pool(wdm_handle* h, const void* x, int B, int H, int W, int d, int kh, int kw, int dtype, void* compact_out, void* stream) {
+    (void)h;
+    if (!x || !compact_out) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_local_pool: null argument");
+    if (dtype != WDM_BF16 && dtype != WDM_F32) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_local_pool: dtype must be f32 or bf16");
+    const int vec = dtype == WDM_BF16 ? 8 : 4;
+    if (B <= 0 || H <= 0 || W <= 0 || d <= 0 || d % vec || kh <= 0 || kw <= 0) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_local_pool: bad shape (d must be a multiple of %d)", vec);
+    if ((((uintptr_t)x) | ((uintptr_t)compact_out)) & 15) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_local_pool: buffers must be 16-byte aligned");
+    const int k1 = std::min(H, kh), k2 = std::min(W, kw);
+    float* colsum = nullptr;
+    WDM_HIP(hipMalloc((void**)&colsum, (size_t)B * (H - k1 + 1) * W * d * 4));
+    int rc = k_local_pool(x, B, H, W, d, k1, k2, dtype, colsum, compact_out, (hipStream_t)stream);
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    (void)hipFree(colsum);
+    if (rc == WDM_OK && e != hipSuccess) WDM_FAIL(WDM_EHIP, "wdm_hfrm_local_pool: %s", hipGetErrorString(e));
+    return rc;
+}
 size_t wdm_hfrm_workspace_bytes(const wdm_hfrm* m, int B, int H, int W) {
     if (!m || B <= 0) return 0;
     Arena ar = Arena::dry();
@@ -620,6 +825,14 @@ int wdm_hfrm_forward(wdm_hfrm* m, const float* x, int B, int H, int W, float* y,
     if (!m || !x || !y || !workspace) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_forward: null argument");
     if (!m->finalized) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_forward: parameters not loaded / finalized");
     if (((uintptr_t)workspace) & 255) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_forward: workspace must be 256-byte aligned");
+    if (m->local) {
+        // local mode: the size check comes before any launch (a dry run of the allocations): a workspace below wdm_hfrm_workspace_bytes is refused whole,
+        // not part-way through the network.  The global mode is left as it was: the arena refuses at the first allocation that does not fit.
+        if (B <= 0) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_forward: B must be positive");
+        const size_t need = wdm_hfrm_workspace_bytes(m, B, H, W);
+        if (!need) return WDM_EINVAL;                                               // (bad shape: the dry run has set the message)
+        if (workspace_bytes < need) WDM_FAIL(WDM_ENOMEM, "wdm_hfrm_forward: workspace too small (%zu bytes given, wdm_hfrm_workspace_bytes asks for %zu)", workspace_bytes, need);
+    }
     Arena ar(workspace, workspace_bytes);
     Ctx c{(hipStream_t)stream, m->cfg.dtype, B, &ar, false};
     return m->forward(c, x, B, H, W, y);

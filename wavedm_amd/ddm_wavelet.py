@@ -34,6 +34,24 @@ def inverse_data_transform(X):     # ddm_wavelet.py:31-32
     return torch.clamp((X + 1.0) / 2.0, 0.0, 1.0)
 
 
+HFRM_LOCAL_DEFAULT = ((720, 1080), (1, 3, 480, 720))      # args.hfrm_local = True: the HFRM's training size (train_hfrm.py:185) and NAFNet's 1.5x window
+
+
+def resolve_hfrm_local(v):
+    """args.hfrm_local -> None (global pooling) or (base_size, train_size) for HFRM.convert: None / False, True (HFRM_LOCAL_DEFAULT), or a pair
+    (base_size, train_size) with base_size an int or (h, w) and train_size (1, C, H, W) or (H, W)."""
+    if v is None or v is False:
+        return None
+    if v is True:
+        return HFRM_LOCAL_DEFAULT
+    base, train = v
+    base = (int(base), int(base)) if isinstance(base, int) else tuple(int(b) for b in base)
+    train = tuple(int(t) for t in train)
+    if len(base) != 2 or len(train) not in (2, 4):
+        raise ValueError("args.hfrm_local: True, or (base_size, train_size) with base_size an int or (h, w) and train_size (1, C, H, W)")
+    return base, (train if len(train) == 4 else (1, 3) + train)
+
+
 def _identity_generator(x):        # the stand-in for a missing HFRM checkpoint (DenoisingDiffusion_Wavelet._make_generator)
     return x
 
@@ -56,6 +74,16 @@ class DenoisingDiffusion_Wavelet(object):
         # instead of 1.8 at seven images per call, against >= 67 ms of sampling).  A named mode is taken as named for both.
         auto = dtype is None and not getattr(config.model, "hip_dtype", None) and not os.environ.get("WAVEDM_DTYPE")
         self.generator = self._make_generator(generator, "f32" if auto else dtype)
+        # args.hfrm_local: the HFRM pools its channel attention over a window instead of the whole image (HFRM.convert, once, here); self.hfrm_local is the
+        # mode the generator is IN -- None for a generator that cannot be converted (the identity stand-in, a caller's callable)
+        self.hfrm_local = resolve_hfrm_local(getattr(args, "hfrm_local", None))
+        if self.hfrm_local is not None:
+            if hasattr(self.generator, "convert"):
+                self.generator.convert(*self.hfrm_local)
+            else:
+                import warnings
+                warnings.warn("args.hfrm_local is set, but .generator is not an HFRM (the identity stand-in, or a callable): ignored", stacklevel=2)
+                self.hfrm_local = None
 
         if getattr(config.data, "global_attn", False):                          # ddm_wavelet.py:149-152
             from .unet_global import DiffusionUNet_Global

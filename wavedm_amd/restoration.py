@@ -73,17 +73,20 @@ def file_seed(seed, name):
 _WS_BYTES = {}      # (kind, config bytes, B[, H, W]) -> workspace bytes the library asks for (host computations, a few hundred distinct keys at most)
 
 
-def _workspace_bytes(kind, cfg, *dims):
+def _workspace_bytes(kind, cfg, *dims, local=None):
+    """`local`: (base_h, base_w, train_h, train_w) of an HFRM that pools locally (HFRM.convert) -- the throw-away handle is put in the same mode."""
     import ctypes as C
     if len(_WS_BYTES) >= 256:
         _WS_BYTES.clear()
-    key = (kind, bytes(cfg)) + dims
+    key = (kind, bytes(cfg)) + dims + ((tuple(local),) if local else ())
     if key not in _WS_BYTES:
         L, m = _lib.lib(), C.c_void_p()
         create, query, destroy = ((L.wdm_unet_create, L.wdm_unet_workspace_bytes, L.wdm_unet_destroy) if kind == "unet" else
                                   (L.wdm_hfrm_create, L.wdm_hfrm_workspace_bytes, L.wdm_hfrm_destroy))
         _lib.check(create(None, C.byref(cfg), C.byref(m)))
         try:
+            if local:
+                _lib.check(L.wdm_hfrm_set_local(m, *[int(v) for v in local]))
             n = int(query(m, *dims))
         finally:
             destroy(m)
@@ -93,8 +96,9 @@ def _workspace_bytes(kind, cfg, *dims):
     return _WS_BYTES[key]
 
 
-def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25):
-    """The terms of estimate_restore_bytes, by name."""
+def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None):
+    """The terms of estimate_restore_bytes, by name.  `hfrm_local`: what DenoisingDiffusion_Wavelet.hfrm_local holds -- None, or (base_size, train_size)
+    of the HFRM's local pooling, whose workspace is larger."""
     from .arch import HFRM
     from .ddm_wavelet import DenoisingDiffusion_Wavelet
     from .procedural import unet_in_channels
@@ -125,17 +129,19 @@ def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps
             hc.enc_blk_nums[i] = v
         for i, v in enumerate(a["dec_blk_nums"]):
             hc.dec_blk_nums[i] = v
-        hfrm = int(_workspace_bytes("hfrm", hc, 1, hp, wp) * min(float(n_img), max(1.0, HFRM.MAX_PIXELS / px)))
+        local = HFRM.local_sizes(*hfrm_local) if hfrm_local else None
+        hfrm = int(_workspace_bytes("hfrm", hc, 1, hp, wp, local=local) * min(float(n_img), max(1.0, HFRM.MAX_PIXELS / px)))
     # the UNet's workspace is kept at the largest call's size (DiffusionUNet.workspace); the sampler's calls never exceed min(n, max_batch) patches
     unet = _workspace_bytes("unet", _make_config(config, code), min(n, mb))
     return dict(x96=n * p * p * cin * elsize, eps=n * pc * p * p * 4, full=full, hfrm=hfrm, unet=unet)
 
 
-def estimate_restore_bytes(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25):
+def estimate_restore_bytes(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None):
     """Device bytes one sampler call of restore_folder needs for `n_img` images of h x w pixels -- host arithmetic, nothing is allocated: the gathered UNet
     input (n patches x p x p x cin in the compute type), eps (n x pc x p x p f32), the f32 tensors of the group's padded size, the HFRM's workspace and the
-    UNet's for the largest call.  `r`: the patch grid's stride (default 16), `steps`: the DDIM steps.  Non-decreasing in h, w and n_img."""
-    return sum(restore_terms(h, w, n_img, config, max_batch, dtype, r, steps).values())
+    UNet's for the largest call.  `r`: the patch grid's stride (default 16), `steps`: the DDIM steps, `hfrm_local`: the HFRM's local-pooling mode (restore_terms).
+    Non-decreasing in h, w and n_img."""
+    return sum(restore_terms(h, w, n_img, config, max_batch, dtype, r, steps, hfrm_local).values())
 
 
 class _StageBudget:
@@ -482,7 +488,8 @@ class DiffusiveRestoration:
         """(fits, estimate, limit) of one sampler call over n images of H x W: args.max_restore_bytes if set, else 0.8 of the device memory that is free now
         (what torch's allocator holds without using counts as free: it is handed out again)."""
         dev = self.diffusion.device
-        est = estimate_restore_bytes(H, W, n, self.config, self._max_batch(), self.diffusion.model.dtype_name, r, int(self.diffusion.args.sampling_timesteps))
+        est = estimate_restore_bytes(H, W, n, self.config, self._max_batch(), self.diffusion.model.dtype_name, r, int(self.diffusion.args.sampling_timesteps),
+                                     hfrm_local=getattr(self.diffusion, "hfrm_local", None))
         limit = getattr(self.args, "max_restore_bytes", None)
         if not limit:
             limit = 0.8 * (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
@@ -533,7 +540,8 @@ class DiffusiveRestoration:
         dst: the output folder: one PNG per input at dst/<name with the extension replaced by .png>, sub-folders created; None (or save_images=False)
              writes nothing.  keep_outputs: keep the cropped f32 (1,3,H,W) outputs in self.last_outputs (off by default: a folder can be large).
         Per group of same-sized images: imageio.ingest (pad to multiples of 16 and to at least 4 * data.image_size per side) -> DWT -> HFRM, its DWT, x_other
-        -> stitched sampler, x0_preds[-5] -> IDWT -> crop + 8-bit -> writer.  The start noise of a file comes from its own generator, seeded with
+        -> stitched sampler, x0_preds[-5] -> IDWT -> crop + 8-bit -> writer.  With args.hfrm_local the HFRM's pooling windows run over the PADDED image (ingest's
+        symmetric extension included), like every other layer of it.  The start noise of a file comes from its own generator, seeded with
         file_seed(args.seed, name).  A group that estimate_restore_bytes puts over the memory limit (args.max_restore_bytes, else 0.8 of the free device
         memory) runs one image per call; one image over it is a RuntimeError before any of its kernels is launched."""
         import queue
