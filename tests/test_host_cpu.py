@@ -303,3 +303,95 @@ def test_bench_dump_outputs_keeps_the_same_rows_under_its_budget(tmp_path):
     assert a["big"].shape == (len(rows), 3, 512, 512) and np.array_equal(a["big"], np.broadcast_to(rows.reshape(-1, 1, 1, 1), a["big"].shape))
     bench.dump_outputs(str(tmp_path / "c"), {"small": small})
     assert np.array_equal(np.load(tmp_path / "c" / "small.npy"), small.numpy())
+
+
+def _layout_table():
+    """Everything the host-side model descriptions decide, as plain integers and strings: parameter enumerations (the trainers' with offsets), packed / workspace
+    sizes, per config and dtype.  Full-size configs keep one SHA-256 per enumeration beside the totals."""
+    import hashlib
+    import json
+    from wavedm_amd.config import load_config
+    from wavedm_amd.unet import _make_config
+    L = _lib.lib()
+    name, ndim, shape, off = C.c_char_p(), C.c_int(), (C.c_int64 * 4)(), C.c_int64()
+
+    def enum(n, info, obj, with_off):
+        rows = []
+        for i in range(n):
+            _lib.check(info(obj, i, C.byref(name), C.byref(ndim), C.byref(shape), *([C.byref(off)] if with_off else [])))
+            rows.append([name.value.decode(), [int(shape[k]) for k in range(ndim.value)]] + ([int(off.value)] if with_off else []))
+        return rows
+
+    def listed(rows, full):
+        out = {"n": len(rows), "sha256": hashlib.sha256(json.dumps(rows).encode()).hexdigest()}
+        if full:
+            out["rows"] = rows
+        return out
+
+    dtypes = (("bf16", _lib.WDM_BF16), ("f16", _lib.WDM_F16), ("f32", _lib.WDM_F32), ("f32x3", _lib.WDM_F32X3))
+    unet_cfgs = [("reduced", P.reduced_config()), ("raindrop", P.raindrop_wavelet_config()), ("raindrop128", P.raindrop_wavelet_config(image_size=128))]
+    unet_cfgs += [(k, P.variant_config(k)[0]) for k in P.VARIANTS]
+    unet_cfgs += [(k, load_config(os.path.join(REPO, "configs", f"raindrop_wavelet_{k}.yml"))) for k in ("pc12", "pc48")]
+    table = {"unet": {}, "hfrm": {}}
+    for cname, cfg in unet_cfgs:
+        full = cname == "reduced"
+        for dname, code in dtypes:
+            c, u, e = _make_config(cfg, code), C.c_void_p(), {}
+            e["create"] = int(L.wdm_unet_create(None, C.byref(c), C.byref(u)))
+            if e["create"] == 0:
+                e["params"] = listed(enum(L.wdm_unet_num_params(u), L.wdm_unet_param_info, u, False), full)
+                e["packed_bytes"] = int(L.wdm_unet_packed_bytes(u))
+                e["workspace_bytes"] = {str(B): int(L.wdm_unet_workspace_bytes(u, B)) for B in (1, 4)}
+                e["temb_rows"] = int(L.wdm_unet_temb_rows(u))
+                L.wdm_unet_destroy(u)
+            t, tr = C.c_void_p(), {}
+            tr["create"] = int(L.wdm_trainer_create(None, C.byref(c), C.byref(t)))
+            if tr["create"] == 0:
+                tr["params"] = listed(enum(L.wdm_trainer_num_params(t), L.wdm_trainer_param_info, t, True), full)
+                tr["num_floats"] = int(L.wdm_trainer_num_floats(t))
+                L.wdm_trainer_destroy(t)
+            table["unet"][f"{cname}/{dname}"] = {"sampler": e, "trainer": tr}
+    # the default HFRM and the smallest one both engines accept (they refuse any dim but the reference's 32): one block per level, two levels
+    hfrm_cfgs = [("default", dict(mid=6, enc=(2, 2, 2, 4), dec=(2, 2, 2, 2))), ("small", dict(mid=1, enc=(1, 1), dec=(1, 1)))]
+    for cname, k in hfrm_cfgs:
+        full = cname == "small"
+        for dname, code in dtypes:
+            c = _lib.HFRMConfig()
+            c.in_channel, c.dim, c.mid_blk_num, c.n_enc, c.n_dec, c.dtype = 3, 32, k["mid"], len(k["enc"]), len(k["dec"]), code
+            for i, v in enumerate(k["enc"]):
+                c.enc_blk_nums[i] = v
+            for i, v in enumerate(k["dec"]):
+                c.dec_blk_nums[i] = v
+            m, e = C.c_void_p(), {}
+            e["create"] = int(L.wdm_hfrm_create(None, C.byref(c), C.byref(m)))
+            if e["create"] == 0:
+                e["params"] = listed(enum(L.wdm_hfrm_num_params(m), L.wdm_hfrm_param_info, m, False), full)
+                e["packed_bytes"] = int(L.wdm_hfrm_packed_bytes(m))
+                e["workspace_bytes"] = {f"1x{h}x{w}": int(L.wdm_hfrm_workspace_bytes(m, 1, h, w)) for h, w in ((64, 64), (96, 160))}
+                L.wdm_hfrm_destroy(m)
+            t, tr = C.c_void_p(), {}
+            tr["create"] = int(L.wdm_hfrm_trainer_create(None, C.byref(c), C.byref(t)))
+            if tr["create"] == 0:
+                tr["params"] = listed(enum(L.wdm_hfrm_trainer_num_params(t), L.wdm_hfrm_trainer_param_info, t, True), full)
+                tr["num_floats"] = int(L.wdm_hfrm_trainer_num_floats(t))
+                tr["workspace_bytes"] = {f"1x{h}x{w}": int(L.wdm_hfrm_trainer_workspace_bytes(t, 1, h, w)) for h, w in ((64, 64), (96, 160))}
+                L.wdm_hfrm_trainer_destroy(t)
+            table["hfrm"][f"{cname}/{dname}"] = {"sampler": e, "trainer": tr}
+    return table
+
+
+def test_model_layouts_are_the_recorded_ones():
+    """Sampler and trainer of both networks enumerate the same parameters in the same order at the same offsets, and ask for the same packed and workspace
+    bytes, as recorded in tests/golden/layout.json: the packed buffer is broadcast between ranks, the trainers' order is the checkpoint format.  The workspace
+    queries dry-run the forward / training walks, so they also show that every layer record still reaches its consumer.  Integers and strings: equality.
+
+    The file is `json.dump(_layout_table(), f, sort_keys=True, separators=(",", ":"))` run at commit 3290842 ("HFRM: local channel-attention pooling ..."),
+    the last one whose engines each built their own layer list; the reduced UNet and the small HFRM are listed in full, the rest as a SHA-256 per list."""
+    import json
+    want = json.load(open(os.path.join(REPO, "tests", "golden", "layout.json")))
+    got = json.loads(json.dumps(_layout_table()))
+    assert sorted(got) == sorted(want)
+    for net in want:
+        assert sorted(got[net]) == sorted(want[net])
+        for key in want[net]:
+            assert got[net][key] == want[net][key], (net, key)

@@ -9,6 +9,7 @@
 #include "../../include/wavedm.h"
 #include "conv_kernel.h"
 #include "dropout.h"
+#include "model_layout.h"
 
 namespace wdm {
 
@@ -40,6 +41,11 @@ inline bool dtype_valid(int dtype) { return dtype == WDM_F32 || dtype == WDM_BF1
         else { using H16 = __bf16; __VA_ARGS__; }                                 \
     } while (0)
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// ---- launch grids ------------------------------------------------------------------------------
+inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }      // exact: kernels that take one element (or one chunk) per thread
+// grid-stride kernels: enough blocks of bs threads for n elements, at most 16384 (the loop covers the rest)
+inline int grid_capped(long long n, int bs) { const long long g = (n + bs - 1) / bs; return (int)(g > 16384 ? 16384 : g); }
+inline int grid_capped_min1(long long n, int bs) { const int g = grid_capped(n, bs); return g < 1 ? 1 : g; }      // ... and at least one (n may be 0)
 
 // ---- deterministic first-fit arena over a caller-provided buffer -----------------------------
 // In "dry" mode (base == nullptr) it only tracks the high-water mark; the real run repeats the same

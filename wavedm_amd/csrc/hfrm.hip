@@ -19,8 +19,6 @@ using namespace wdm;
 
 namespace wdm {
 
-static inline int nblk(long long n, int bs) { return (int)((n + bs - 1) / bs); }
-
 // ---- LayerNorm2d (arch.py:7-43): per pixel over channels, biased variance --------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void ln2d_kernel(const T* __restrict__ x, T* __restrict__ y, long long M, int C, const float* __restrict__ w,
@@ -307,7 +305,7 @@ int k_local_pool(const void* x, int B, int H, int W, int d, int k1, int k2, int 
         // grid.y holds the segments: a walk of more than 65535 of them (a window below 4 on a map that long) is refused rather than given longer
         // segments, which would leave the error bound -- no map the HFRM can run is that long (the 4 GB descriptor range ends far earlier)
         if ((Ho + seg - 1) / seg > 65535) WDM_FAIL(WDM_EINVAL, "local pooling: %d output rows in segments of %d exceed the grid", Ho, seg);
-        const dim3 grid((unsigned)nblk(lines, 256), (unsigned)((Ho + seg - 1) / seg));
+        const dim3 grid((unsigned)ceil_div(lines, 256), (unsigned)((Ho + seg - 1) / seg));
         const long long step = (long long)W * d;
         if (dtype == WDM_BF16) hipLaunchKernelGGL(window_colsum_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)x, colsum, lines, lines_img, H * step, Ho * step, step, k1, Ho, seg);
         else hipLaunchKernelGGL(window_colsum_kernel<float>, grid, dim3(256), 0, s, (const float*)x, colsum, lines, lines_img, H * step, Ho * step, step, k1, Ho, seg);
@@ -316,7 +314,7 @@ int k_local_pool(const void* x, int B, int H, int W, int d, int k1, int k2, int 
         const long long lines_img = (long long)Ho * cols, lines = B * lines_img;
         const int seg = local_seg(k2, Wo, lines_img);
         if ((Wo + seg - 1) / seg > 65535) WDM_FAIL(WDM_EINVAL, "local pooling: %d output columns in segments of %d exceed the grid", Wo, seg);
-        const dim3 grid((unsigned)nblk(lines, 256), (unsigned)((Wo + seg - 1) / seg));
+        const dim3 grid((unsigned)ceil_div(lines, 256), (unsigned)((Wo + seg - 1) / seg));
         const float div = (float)((long long)k1 * k2);
         if (dtype == WDM_BF16) hipLaunchKernelGGL(window_rowmean_kernel<__bf16>, grid, dim3(256), 0, s, (const float*)colsum, (__bf16*)compact, lines, (long long)cols, (long long)W * d, (long long)Wo * d, (long long)d, k2, Wo, seg, div);
         else hipLaunchKernelGGL(window_rowmean_kernel<float>, grid, dim3(256), 0, s, (const float*)colsum, (float*)compact, lines, (long long)cols, (long long)W * d, (long long)Wo * d, (long long)d, k2, Wo, seg, div);
@@ -438,31 +436,24 @@ __global__ void scale_vec_kernel(const float* __restrict__ b, const float* __res
 // the HFRM object
 // =================================================================================================
 namespace {
-struct HParam { std::string name; int ndim; int64_t shape[4]; size_t raw_off; bool loaded; int64_t numel() const { int64_t n = 1; for (int i = 0; i < ndim; ++i) n *= shape[i]; return n; } };
 struct GemmD { size_t w_off, b_off; int cin, cout, rows_pad; };   // packed GEMM weight [rows_pad][cin] (T) + bias f32
-struct BlockD {
-    int d;
-    int p_beta, p_gamma, p_n1w, p_n1b, p_n2w, p_n2b, p_dww, p_dwb, p_caw, p_cab;   // raw parameter indices
-    int p_w[5], p_b[5];                                                            // conv1..conv5 raw indices (conv2 = depthwise)
-    GemmD g1, g3, g4, g5;
-    GemmD gca;                       // chan_conv as a GEMM over the compact map (local pooling); global pooling runs it through k_linear on the raw weights
-};
+// conv1 / conv3 / conv4 / conv5 of a block, and chan_conv as a GEMM over the compact map (local pooling); global pooling runs it through k_linear on the raw weights
+struct BlockG { GemmD g1, g3, g4, g5, gca; };
 }  // namespace
 
 struct wdm_hfrm {
+    using Block = HfrmLayout::Block;
     wdm_handle* h;
     wdm_hfrm_config cfg;
-    std::vector<HParam> params;
+    HfrmLayout L;
+    std::vector<size_t> raw_off;    // per parameter: byte offset of its fp32 copy at the front of the packed buffer
+    std::vector<bool> loaded;       // per parameter
     std::map<std::string, int> index;
     size_t raw_bytes = 0, packed_bytes = 0;
     char* packed = nullptr;
     bool finalized = false;
-    int p_cin_w, p_cin_b, p_cout_w, p_cout_b;
-    GemmD g_out;                    // conv_out runs on the 3x3 conv kernel: slab layout handled by k_pack_conv
-    size_t cout_w_off = 0;
-    std::vector<std::vector<BlockD>> enc, dec;
-    std::vector<BlockD> mid;
-    std::vector<int> p_down_w, p_down_b, p_up_w;
+    size_t cout_w_off = 0;          // conv_out runs on the 3x3 conv kernel: slab layout handled by k_pack_conv
+    std::vector<BlockG> bg;         // per block (Block::idx)
     std::vector<GemmD> g_down, g_up;
     // local channel-attention pooling (wdm_hfrm_set_local): the window and training size as given, and the pools' kernel sizes per level
     // 0..n_enc as the reference's converting forward freezes them (arch.py:66-72); local == false: every pool is global
@@ -471,104 +462,66 @@ struct wdm_hfrm {
     int lk_h[9] = {0}, lk_w[9] = {0};
 
     size_t take(size_t bytes) { size_t o = packed_bytes; packed_bytes = align_up(packed_bytes + bytes, 256); return o; }
-    int add(const std::string& name, std::initializer_list<int64_t> shp) {
-        HParam p; p.name = name; p.ndim = (int)shp.size(); int i = 0; for (auto v : shp) p.shape[i++] = v; for (; i < 4; ++i) p.shape[i] = 0;
-        p.raw_off = raw_bytes; p.loaded = false;
-        raw_bytes = align_up(raw_bytes + (size_t)p.numel() * 4, 256);
-        index[name] = (int)params.size();
-        params.push_back(p);
-        return (int)params.size() - 1;
-    }
     GemmD gemm(int cin, int cout) {
         GemmD g; g.cin = cin; g.cout = cout; g.rows_pad = conv_rows_pad(cout);
         g.w_off = take((size_t)g.rows_pad * cin * dsize(cfg.dtype)); g.b_off = take((size_t)cout * 4);
         return g;
     }
-    BlockD block(const std::string& n, int d) {
-        BlockD b; b.d = d;
-        b.p_beta = add(n + ".beta", {1, d, 1, 1}); b.p_gamma = add(n + ".gamma", {1, d, 1, 1});
-        const char* cn[5] = {"conv1", "conv2", "conv3", "conv4", "conv5"};
-        const int co[5] = {2 * d, 2 * d, d, 2 * d, d}, ci[5] = {d, 1, d, d, d}, kk[5] = {1, 3, 1, 1, 1};
-        for (int k = 0; k < 3; ++k) { b.p_w[k] = add(n + "." + cn[k] + ".weight", {co[k], ci[k], kk[k], kk[k]}); b.p_b[k] = add(n + "." + cn[k] + ".bias", {co[k]}); }
-        b.p_caw = add(n + ".channel_attn.chan_conv.weight", {d, d, 1, 1}); b.p_cab = add(n + ".channel_attn.chan_conv.bias", {d});
-        for (int k = 3; k < 5; ++k) { b.p_w[k] = add(n + "." + cn[k] + ".weight", {co[k], ci[k], kk[k], kk[k]}); b.p_b[k] = add(n + "." + cn[k] + ".bias", {co[k]}); }
-        b.p_n1w = add(n + ".norm1.weight", {d}); b.p_n1b = add(n + ".norm1.bias", {d});
-        b.p_n2w = add(n + ".norm2.weight", {d}); b.p_n2b = add(n + ".norm2.bias", {d});
-        b.p_dww = b.p_w[1]; b.p_dwb = b.p_b[1];
-        b.g1 = gemm(d, 2 * d); b.g3 = gemm(d, d); b.g4 = gemm(d, 2 * d); b.g5 = gemm(d, d);
-        return b;
-    }
-    const float* raw(int pi) const { return (const float*)(packed + params[pi].raw_off); }
+    const float* raw(int pi) const { return (const float*)(packed + raw_off[pi]); }
     ConvW cw(const GemmD& g) const { ConvW w; w.w = packed + raw_bytes + g.w_off; w.b = (const float*)(packed + raw_bytes + g.b_off); w.cin = g.cin; w.cout = g.cout; w.k = 1; w.rows_pad = g.rows_pad; return w; }
 
     int build();
     int finalize(hipStream_t s);
-    int run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W, int level);
+    int run_block(Ctx& c, const Block& b, Tens& t, int B, int H, int W, int level);
     int gemm_rows(Ctx& c, const GemmD& g, const void* x, long long M, const void* res, void* y);
     int forward(Ctx& c, const float* x, int B, int H, int W, float* y);
 };
 
 int wdm_hfrm::build() {
-    const int dim = cfg.dim;
-    p_cin_w = add("conv_in.weight", {dim, cfg.in_channel, 3, 3}); p_cin_b = add("conv_in.bias", {dim});
-    int d = dim;
-    enc.resize(cfg.n_enc); dec.resize(cfg.n_dec);
-    for (int i = 0; i < cfg.n_enc; ++i) {
-        for (int j = 0; j < cfg.enc_blk_nums[i]; ++j) enc[i].push_back(block("encoders." + std::to_string(i) + "." + std::to_string(j), d));
-        d *= 2;
+    L = hfrm_layout(cfg);
+    for (size_t i = 0; i < L.params.size(); ++i) {
+        raw_off.push_back(raw_bytes);
+        raw_bytes = align_up(raw_bytes + (size_t)L.params[i].numel() * 4, 256);
+        index[L.params[i].name] = (int)i;
     }
-    const int dmid = d;
-    for (int i = 0; i < cfg.n_dec; ++i) {
-        d /= 2;
-        for (int j = 0; j < cfg.dec_blk_nums[i]; ++j) dec[i].push_back(block("decoders." + std::to_string(i) + "." + std::to_string(j), d));
-    }
-    for (int j = 0; j < cfg.mid_blk_num; ++j) mid.push_back(block("mid_blks." + std::to_string(j), dmid));
-    d = dmid;
-    for (int i = 0; i < cfg.n_dec; ++i) { p_up_w.push_back(add("ups." + std::to_string(i) + ".0.weight", {2 * d, d, 1, 1})); g_up.push_back(gemm(d, 2 * d)); d /= 2; }
-    d = dim;
-    for (int i = 0; i < cfg.n_enc; ++i) {
-        p_down_w.push_back(add("downs." + std::to_string(i) + ".weight", {2 * d, d, 2, 2})); p_down_b.push_back(add("downs." + std::to_string(i) + ".bias", {2 * d}));
-        g_down.push_back(gemm(4 * d, 2 * d));
-        d *= 2;
-    }
-    p_cout_w = add("conv_out.weight", {cfg.in_channel, dim, 3, 3}); p_cout_b = add("conv_out.bias", {cfg.in_channel});
-    cout_w_off = take(conv_packed_bytes(dim, cfg.in_channel, 3, cfg.dtype));
+    loaded.assign(L.params.size(), false);
+    bg.resize(L.n_blocks);
+    L.for_each_block([&](const Block& b) { BlockG& g = bg[b.idx]; g.g1 = gemm(b.d, 2 * b.d); g.g3 = gemm(b.d, b.d); g.g4 = gemm(b.d, 2 * b.d); g.g5 = gemm(b.d, b.d); });
+    for (auto& u : L.ups) g_up.push_back(gemm(u.cin, u.cout));
+    for (auto& d : L.downs) g_down.push_back(gemm(4 * d.cin, d.cout));      // (the GEMM behind the space-to-depth gather)
+    cout_w_off = take(conv_packed_bytes(cfg.dim, cfg.in_channel, 3, cfg.dtype));
     // behind everything else: the offsets of the global mode's operands stay where they were
-    for (auto& lv : enc) for (auto& b : lv) b.gca = gemm(b.d, b.d);
-    for (auto& lv : dec) for (auto& b : lv) b.gca = gemm(b.d, b.d);
-    for (auto& b : mid) b.gca = gemm(b.d, b.d);
+    L.for_each_block([&](const Block& b) { bg[b.idx].gca = gemm(b.d, b.d); });
     return WDM_OK;
 }
 
 template <typename T>
 static void pack_gemm(const float* w, const float* rowscale, const float* b, int cout, int cin, int kk, void* wdst, float* bdst, int rows_pad, hipStream_t s) {
     const long long total = (long long)rows_pad * cin * kk;
-    hipLaunchKernelGGL(pack_gemm_w_kernel<T>, dim3(nblk(total, 256) > 4096 ? 4096 : nblk(total, 256)), dim3(256), 0, s, w, rowscale, cout, cin, kk, (T*)wdst, rows_pad);
-    if (b) hipLaunchKernelGGL(scale_vec_kernel, dim3(nblk(cout, 256)), dim3(256), 0, s, b, rowscale, bdst, cout);
+    hipLaunchKernelGGL(pack_gemm_w_kernel<T>, dim3(ceil_div(total, 256) > 4096 ? 4096 : ceil_div(total, 256)), dim3(256), 0, s, w, rowscale, cout, cin, kk, (T*)wdst, rows_pad);
+    if (b) hipLaunchKernelGGL(scale_vec_kernel, dim3(ceil_div(cout, 256)), dim3(256), 0, s, b, rowscale, bdst, cout);
     else (void)hipMemsetAsync(bdst, 0, (size_t)cout * 4, s);
 }
 
 int wdm_hfrm::finalize(hipStream_t s) {
-    for (auto& p : params) if (!p.loaded) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_finalize: parameter '%s' not loaded", p.name.c_str());
+    for (size_t i = 0; i < loaded.size(); ++i) if (!loaded[i]) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_finalize: parameter '%s' not loaded", L.params[i].name.c_str());
     char* pk = packed + raw_bytes;
     auto pg = [&](const GemmD& g, int pw, int pb, int prs, int kk) {
         const int cin_raw = g.cin / kk;
         if (cfg.dtype == WDM_BF16) pack_gemm<__bf16>(raw(pw), prs >= 0 ? raw(prs) : nullptr, pb >= 0 ? raw(pb) : nullptr, g.cout, cin_raw, kk, pk + g.w_off, (float*)(pk + g.b_off), g.rows_pad, s);
         else pack_gemm<float>(raw(pw), prs >= 0 ? raw(prs) : nullptr, pb >= 0 ? raw(pb) : nullptr, g.cout, cin_raw, kk, pk + g.w_off, (float*)(pk + g.b_off), g.rows_pad, s);
     };
-    auto pblock = [&](const BlockD& b) {
-        pg(b.g1, b.p_w[0], b.p_b[0], -1, 1);
-        pg(b.g3, b.p_w[2], b.p_b[2], b.p_beta, 1);       // y = x + beta * conv3(.)  ->  beta folded into conv3
-        pg(b.g4, b.p_w[3], b.p_b[3], -1, 1);
-        pg(b.g5, b.p_w[4], b.p_b[4], b.p_gamma, 1);      // out = y + gamma * conv5(.)
-        pg(b.gca, b.p_caw, b.p_cab, -1, 1);
-    };
-    for (auto& lv : enc) for (auto& b : lv) pblock(b);
-    for (auto& lv : dec) for (auto& b : lv) pblock(b);
-    for (auto& b : mid) pblock(b);
-    for (size_t i = 0; i < g_up.size(); ++i) pg(g_up[i], p_up_w[i], -1, -1, 1);
-    for (size_t i = 0; i < g_down.size(); ++i) pg(g_down[i], p_down_w[i], p_down_b[i], -1, 4);
-    WDM_TRY(k_pack_conv(raw(p_cout_w), cfg.in_channel, cfg.dim, 3, pk + cout_w_off, conv_rows_pad(cfg.in_channel), 0, 1, cfg.dtype, s));
+    L.for_each_block([&](const Block& b) {
+        const BlockG& g = bg[b.idx];
+        pg(g.g1, b.w[0], b.b[0], -1, 1);
+        pg(g.g3, b.w[2], b.b[2], b.beta, 1);       // y = x + beta * conv3(.)  ->  beta folded into conv3
+        pg(g.g4, b.w[3], b.b[3], -1, 1);
+        pg(g.g5, b.w[4], b.b[4], b.gamma, 1);      // out = y + gamma * conv5(.)
+        pg(g.gca, b.caw, b.cab, -1, 1);
+    });
+    for (size_t i = 0; i < g_up.size(); ++i) pg(g_up[i], L.ups[i].w, -1, -1, 1);
+    for (size_t i = 0; i < g_down.size(); ++i) pg(g_down[i], L.downs[i].w, L.downs[i].b, -1, 4);
+    WDM_TRY(k_pack_conv(raw(L.conv_out.w), cfg.in_channel, cfg.dim, 3, pk + cout_w_off, conv_rows_pad(cfg.in_channel), 0, 1, cfg.dtype, s));
     WDM_HIP(hipGetLastError());
     finalized = true;
     return WDM_OK;
@@ -586,8 +539,9 @@ int wdm_hfrm::gemm_rows(Ctx& c, const GemmD& g, const void* x, long long M, cons
     return launch_conv(a, MODE_P1, c.dtype, c.s);
 }
 
-int wdm_hfrm::run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W, int level) {
+int wdm_hfrm::run_block(Ctx& c, const Block& b, Tens& t, int B, int H, int W, int level) {
     const int d = b.d, HW = H * W;
+    const BlockG& bgm = bg[b.idx];
     const long long M = (long long)B * HW;
     const size_t es = dsize(c.dtype);
     const int vec = c.dtype == WDM_BF16 ? 8 : 4;
@@ -613,37 +567,37 @@ int wdm_hfrm::run_block(Ctx& c, const BlockD& b, Tens& t, int B, int H, int W, i
     void* y = A((size_t)M * d * es);
     if (!n1 || !a2 || !g || !part || !pooled || (loc && !cmp) || !sc || !y) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block)");
     if (!c.dry) {
-        const float* n1w = raw(b.p_n1w); const float* n1b = raw(b.p_n1b);
+        const float* n1w = raw(b.n1w); const float* n1b = raw(b.n1b);
         const int lpp = d / vec, ppw = lpp <= 64 ? 64 / lpp : 1;
         const long long waves = (M + ppw - 1) / ppw;
         if (c.dtype == WDM_BF16) hipLaunchKernelGGL(ln2d_kernel<__bf16>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c.s, (const __bf16*)t.p, (__bf16*)n1, M, d, n1w, n1b, 1e-6f);
         else hipLaunchKernelGGL(ln2d_kernel<float>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c.s, (const float*)t.p, (float*)n1, M, d, n1w, n1b, 1e-6f);
-        WDM_TRY(gemm_rows(c, b.g1, n1, M, nullptr, a2));
+        WDM_TRY(gemm_rows(c, bgm.g1, n1, M, nullptr, a2));
         const int cols = d / vec;
         const dim3 grid(nb, B, (cols + 255) / 256);
-        if (c.dtype == WDM_BF16) hipLaunchKernelGGL(dw3x3_gate_kernel<__bf16>, grid, dim3(256), 0, c.s, (const __bf16*)a2, (__bf16*)g, H, W, d, raw(b.p_dww), raw(b.p_dwb), part, nb, ppb);
-        else hipLaunchKernelGGL(dw3x3_gate_kernel<float>, grid, dim3(256), 0, c.s, (const float*)a2, (float*)g, H, W, d, raw(b.p_dww), raw(b.p_dwb), part, nb, ppb);
+        if (c.dtype == WDM_BF16) hipLaunchKernelGGL(dw3x3_gate_kernel<__bf16>, grid, dim3(256), 0, c.s, (const __bf16*)a2, (__bf16*)g, H, W, d, raw(b.w[1]), raw(b.b[1]), part, nb, ppb);
+        else hipLaunchKernelGGL(dw3x3_gate_kernel<float>, grid, dim3(256), 0, c.s, (const float*)a2, (float*)g, H, W, d, raw(b.w[1]), raw(b.b[1]), part, nb, ppb);
         const long long nvec = M * cols;
-        const int gg = nblk(nvec, 256) > 16384 ? 16384 : nblk(nvec, 256);
+        const int gg = ceil_div(nvec, 256) > 16384 ? 16384 : ceil_div(nvec, 256);
         if (loc) {
             WDM_TRY(k_local_pool(g, B, H, W, d, k1, k2, c.dtype, pooled, cmp, c.s));
-            WDM_TRY(gemm_rows(c, b.gca, cmp, Mc, nullptr, sc));
+            WDM_TRY(gemm_rows(c, bgm.gca, cmp, Mc, nullptr, sc));
             if (c.dtype == WDM_BF16) hipLaunchKernelGGL(scale_local_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (__bf16*)g, (const __bf16*)sc, nvec, d, H, W, Ho, Wo, (k1 - 1) / 2, (k2 - 1) / 2);
             else hipLaunchKernelGGL(scale_local_kernel<float>, dim3(gg), dim3(256), 0, c.s, (float*)g, (const float*)sc, nvec, d, H, W, Ho, Wo, (k1 - 1) / 2, (k2 - 1) / 2);
         } else {
             hipLaunchKernelGGL(pool_reduce_kernel, dim3((d + 63) / 64, B), dim3(256), 0, c.s, part, pooled, B, nb, d, 1.0f / (float)HW);
-            WDM_TRY(k_linear(pooled, B, d, raw(b.p_caw), raw(b.p_cab), d, sc, 0, c.s));
+            WDM_TRY(k_linear(pooled, B, d, raw(b.caw), raw(b.cab), d, sc, 0, c.s));
             if (c.dtype == WDM_BF16) hipLaunchKernelGGL(scale_channels_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (__bf16*)g, sc, nvec, d, HW);
             else hipLaunchKernelGGL(scale_channels_kernel<float>, dim3(gg), dim3(256), 0, c.s, (float*)g, sc, nvec, d, HW);
         }
-        WDM_TRY(gemm_rows(c, b.g3, g, M, t.p, y));                                   // y = x + beta*conv3(.)
-        const float* n2w = raw(b.p_n2w); const float* n2b = raw(b.p_n2b);
+        WDM_TRY(gemm_rows(c, bgm.g3, g, M, t.p, y));                                   // y = x + beta*conv3(.)
+        const float* n2w = raw(b.n2w); const float* n2b = raw(b.n2b);
         if (c.dtype == WDM_BF16) hipLaunchKernelGGL(ln2d_kernel<__bf16>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c.s, (const __bf16*)y, (__bf16*)n1, M, d, n2w, n2b, 1e-6f);
         else hipLaunchKernelGGL(ln2d_kernel<float>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c.s, (const float*)y, (float*)n1, M, d, n2w, n2b, 1e-6f);
-        WDM_TRY(gemm_rows(c, b.g4, n1, M, nullptr, a2));
+        WDM_TRY(gemm_rows(c, bgm.g4, n1, M, nullptr, a2));
         if (c.dtype == WDM_BF16) hipLaunchKernelGGL(gate_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (const __bf16*)a2, (__bf16*)g, nvec, d);
         else hipLaunchKernelGGL(gate_kernel<float>, dim3(gg), dim3(256), 0, c.s, (const float*)a2, (float*)g, nvec, d);
-        WDM_TRY(gemm_rows(c, b.g5, g, M, y, t.p));                                   // out = y + gamma*conv5(.), written over the block input
+        WDM_TRY(gemm_rows(c, bgm.g5, g, M, y, t.p));                                   // out = y + gamma*conv5(.), written over the block input
         WDM_HIP(hipGetLastError());
     }
     c.ar->free(n1); c.ar->free(a2); c.ar->free(g); c.ar->free(part); c.ar->free(pooled); if (cmp) c.ar->free(cmp); c.ar->free(sc); c.ar->free(y);
@@ -661,14 +615,14 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
     void* xin = c.ar->alloc((size_t)B * h * w * cfg.in_channel * es);          // NHWC copy of the input for the final residual
     if (!t.p || !xin) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM)");
     if (!c.dry) {
-        const int gg = nblk((long long)B * h * w, 256);
-        if (c.dtype == WDM_BF16) hipLaunchKernelGGL((conv3x3_cin3_kernel<__bf16, 32>), dim3(gg), dim3(256), 0, c.s, x, (__bf16*)t.p, B, h, w, cfg.in_channel, raw(p_cin_w), raw(p_cin_b));
-        else hipLaunchKernelGGL((conv3x3_cin3_kernel<float, 32>), dim3(gg), dim3(256), 0, c.s, x, (float*)t.p, B, h, w, cfg.in_channel, raw(p_cin_w), raw(p_cin_b));
+        const int gg = ceil_div((long long)B * h * w, 256);
+        if (c.dtype == WDM_BF16) hipLaunchKernelGGL((conv3x3_cin3_kernel<__bf16, 32>), dim3(gg), dim3(256), 0, c.s, x, (__bf16*)t.p, B, h, w, cfg.in_channel, raw(L.conv_in.w), raw(L.conv_in.b));
+        else hipLaunchKernelGGL((conv3x3_cin3_kernel<float, 32>), dim3(gg), dim3(256), 0, c.s, x, (float*)t.p, B, h, w, cfg.in_channel, raw(L.conv_in.w), raw(L.conv_in.b));
         WDM_TRY(k_nchw_to_nhwc(x, xin, B, cfg.in_channel, h, w, c.dtype, c.s));
     }
     std::vector<Tens> encs;
     for (int i = 0; i < nlev; ++i) {
-        for (auto& b : enc[i]) WDM_TRY(run_block(c, b, t, B, h, w, i));
+        for (auto& b : L.enc[i]) WDM_TRY(run_block(c, b, t, B, h, w, i));
         encs.push_back(t);
         // down: space-to-depth + GEMM (4d -> 2d)
         void* u = c.ar->alloc((size_t)B * (h / 2) * (w / 2) * 4 * d * es);
@@ -677,7 +631,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         if (!u || !nt.p) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM down)");
         if (!c.dry) {
             const long long total = (long long)B * nt.H * nt.W * 4 * (d / (c.dtype == WDM_BF16 ? 8 : 4));
-            const int gg = nblk(total, 256) > 16384 ? 16384 : nblk(total, 256);
+            const int gg = ceil_div(total, 256) > 16384 ? 16384 : ceil_div(total, 256);
             if (c.dtype == WDM_BF16) hipLaunchKernelGGL(unshuffle2_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (const __bf16*)t.p, (__bf16*)u, B, h, w, d);
             else hipLaunchKernelGGL(unshuffle2_kernel<float>, dim3(gg), dim3(256), 0, c.s, (const float*)t.p, (float*)u, B, h, w, d);
             WDM_TRY(gemm_rows(c, g_down[i], u, (long long)B * nt.H * nt.W, nullptr, nt.p));
@@ -685,7 +639,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         c.ar->free(u);
         t = nt; d *= 2; h /= 2; w /= 2;
     }
-    for (auto& b : mid) WDM_TRY(run_block(c, b, t, B, h, w, nlev));
+    for (auto& b : L.mid) WDM_TRY(run_block(c, b, t, B, h, w, nlev));
     for (int i = 0; i < cfg.n_dec; ++i) {
         // up: 1x1 (d -> 2d, no bias) + PixelShuffle(2) + skip
         void* p = c.ar->alloc((size_t)B * h * w * 2 * d * es);
@@ -696,17 +650,17 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         if (!c.dry) {
             WDM_TRY(gemm_rows(c, g_up[i], t.p, (long long)B * h * w, nullptr, p));
             const long long total = (long long)B * nt.H * nt.W * nt.C;
-            const int gg = nblk(total, 256) > 16384 ? 16384 : nblk(total, 256);
+            const int gg = ceil_div(total, 256) > 16384 ? 16384 : ceil_div(total, 256);
             if (c.dtype == WDM_BF16) hipLaunchKernelGGL(pixel_shuffle_add_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (const __bf16*)p, (const __bf16*)skip.p, (__bf16*)nt.p, B, h, w, nt.C);
             else hipLaunchKernelGGL(pixel_shuffle_add_kernel<float>, dim3(gg), dim3(256), 0, c.s, (const float*)p, (const float*)skip.p, (float*)nt.p, B, h, w, nt.C);
         }
         c.ar->free(p); c.ar->free(t.p); c.ar->free(skip.p);
         t = nt; d /= 2; h *= 2; w *= 2;
-        for (auto& b : dec[i]) WDM_TRY(run_block(c, b, t, B, h, w, nlev - 1 - i));
+        for (auto& b : L.dec[i]) WDM_TRY(run_block(c, b, t, B, h, w, nlev - 1 - i));
     }
     // conv_out 3x3 (dim -> 3) + input, NCHW f32 out
     {
-        ConvW cwo; cwo.w = packed + raw_bytes + cout_w_off; cwo.b = raw(p_cout_b); cwo.cin = cfg.dim; cwo.cout = cfg.in_channel; cwo.k = 3; cwo.rows_pad = conv_rows_pad(cfg.in_channel);
+        ConvW cwo; cwo.w = packed + raw_bytes + cout_w_off; cwo.b = raw(L.conv_out.b); cwo.cin = cfg.dim; cwo.cout = cfg.in_channel; cwo.k = 3; cwo.rows_pad = conv_rows_pad(cfg.in_channel);
         Tens xi; xi.p = xin; xi.C = cfg.in_channel; xi.H = h; xi.W = w; xi.xs = cfg.in_channel;
         Tens dummy;
         Ctx cc = c; cc.B = B;
@@ -733,13 +687,9 @@ int wdm_hfrm_create(wdm_handle* h, const wdm_hfrm_config* cfg, wdm_hfrm** out) {
     return WDM_OK;
 }
 int wdm_hfrm_destroy(wdm_hfrm* m) { delete m; return WDM_OK; }
-int wdm_hfrm_num_params(const wdm_hfrm* m) { return m ? (int)m->params.size() : 0; }
+int wdm_hfrm_num_params(const wdm_hfrm* m) { return m ? (int)m->L.params.size() : 0; }
 int wdm_hfrm_param_info(const wdm_hfrm* m, int i, const char** name, int* ndim, int64_t shape[4]) {
-    if (!m || i < 0 || i >= (int)m->params.size()) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_param_info: index out of range");
-    const HParam& p = m->params[i];
-    if (name) *name = p.name.c_str();
-    if (ndim) *ndim = p.ndim;
-    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
+    if (!m || !param_info(m->L.params, i, name, ndim, shape)) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_param_info: index out of range");
     return WDM_OK;
 }
 size_t wdm_hfrm_packed_bytes(const wdm_hfrm* m) { return m ? m->raw_bytes + m->packed_bytes : 0; }
@@ -748,7 +698,7 @@ int wdm_hfrm_set_packed(wdm_hfrm* m, void* packed, size_t bytes) {
     if (bytes < m->raw_bytes + m->packed_bytes) WDM_FAIL(WDM_ENOMEM, "wdm_hfrm_set_packed: buffer too small");
     if (((uintptr_t)packed) & 255) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_packed: buffer must be 256-byte aligned");
     m->packed = (char*)packed; m->finalized = false;
-    for (auto& p : m->params) p.loaded = false;
+    m->loaded.assign(m->loaded.size(), false);
     return WDM_OK;
 }
 int wdm_hfrm_load_param(wdm_hfrm* m, const char* name, const float* dev_src, int64_t numel, void* stream) {
@@ -756,10 +706,10 @@ int wdm_hfrm_load_param(wdm_hfrm* m, const char* name, const float* dev_src, int
     if (!m->packed) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_load_param: call wdm_hfrm_set_packed first");
     auto it = m->index.find(name);
     if (it == m->index.end()) WDM_FAIL(WDM_ENOTFOUND, "unknown HFRM parameter '%s'", name);
-    HParam& p = m->params[it->second];
+    const ParamDesc& p = m->L.params[it->second];
     if (numel != p.numel()) WDM_FAIL(WDM_EINVAL, "HFRM parameter '%s': %lld elements given, %lld expected", name, (long long)numel, (long long)p.numel());
-    WDM_TRY(k_copy_f32(dev_src, (float*)(m->packed + p.raw_off), numel, (hipStream_t)stream));
-    p.loaded = true; m->finalized = false;
+    WDM_TRY(k_copy_f32(dev_src, (float*)(m->packed + m->raw_off[it->second]), numel, (hipStream_t)stream));
+    m->loaded[it->second] = true; m->finalized = false;
     return WDM_OK;
 }
 int wdm_hfrm_finalize(wdm_hfrm* m, void* stream) {

@@ -19,7 +19,6 @@
 #include <math.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 
 #include "common.h"
@@ -27,8 +26,6 @@
 namespace hft {
 using namespace wdm;
 
-static inline int gridn(long long n, int bs) { long long g = (n + bs - 1) / bs; return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g)); }
-static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 #define GS_LOOP(id, n) for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < (n); id += (long long)gridDim.x * blockDim.x)
 
 __device__ __forceinline__ float team_sum(float v) {      // sum over the 32 lanes of a half wave
@@ -524,89 +521,47 @@ using namespace wdm;
 using namespace hft;
 
 namespace {
-struct TParam { std::string name; int ndim; int64_t shape[4]; int64_t off; int64_t numel; };
 // a layer that runs as a GEMM: forward matrix [rows_f][K] and transposed [rows_t][cout] in the step's pack region
 struct TGemm { int pw = -1, pb = -1; int cout = 0, cin = 0, kk = 1; size_t f_off = 0, t_off = 0;
                int K() const { return cin * kk; } int rows_f() const { return conv_rows_pad(cout); } int rows_t() const { return conv_rows_pad(cin * kk); } };
-struct TBlock {
-    int d;
-    int beta, gamma, n1w, n1b, n2w, n2b, dww, dwb, caw, cab;
-    TGemm g1, g3, g4, g5;
-};
+struct TBlockG { TGemm g1, g3, g4, g5; };      // conv1 / conv3 / conv4 / conv5 of a block
+using TBlock = HfrmLayout::Block;
 struct BSave { float *a1, *a2, *c3, *y, *a4, *c5, *out, *pooled, *sc; };
 }  // namespace
 
 struct wdm_hfrm_trainer {
     wdm_hfrm_config cfg;
-    std::vector<TParam> params;
+    HfrmLayout L;
+    std::vector<int64_t> off;      // per parameter: float offset in the flat buffers, every tensor on a multiple of 64 floats (256-byte aligned views)
     int64_t nfloats = 0;
     size_t pack_bytes = 0;
     float *P = nullptr, *G = nullptr, *Mo = nullptr, *V = nullptr;
-    int p_cin_w, p_cin_b, p_cout_w, p_cout_b;
     size_t cout_off = 0;
-    std::vector<std::vector<TBlock>> enc, dec;
-    std::vector<TBlock> mid;
+    std::vector<TBlockG> bg;       // per block (Block::idx)
     std::vector<TGemm> downs, ups;
     char* pk = nullptr;      // pack region of the current step
 
-    int add(const std::string& name, std::initializer_list<int64_t> shp) {
-        TParam p; p.name = name; p.ndim = (int)shp.size(); int i = 0; p.numel = 1;
-        for (auto v : shp) { p.shape[i++] = v; p.numel *= v; }
-        for (; i < 4; ++i) p.shape[i] = 0;
-        p.off = nfloats;
-        nfloats += (p.numel + 63) / 64 * 64;          // 256-byte aligned views
-        params.push_back(p);
-        return (int)params.size() - 1;
-    }
     size_t take(size_t bytes) { size_t o = pack_bytes; pack_bytes = align_up(pack_bytes + bytes, 256); return o; }
     TGemm gemm(int pw, int pb, int cout, int cin, int kk) {
         TGemm g; g.pw = pw; g.pb = pb; g.cout = cout; g.cin = cin; g.kk = kk;
         g.f_off = take((size_t)g.rows_f() * g.K() * 4); g.t_off = take((size_t)g.rows_t() * cout * 4);
         return g;
     }
-    TBlock block(const std::string& n, int d) {
-        TBlock b; b.d = d;
-        b.beta = add(n + ".beta", {1, d, 1, 1}); b.gamma = add(n + ".gamma", {1, d, 1, 1});
-        const int w1 = add(n + ".conv1.weight", {2 * d, d, 1, 1}), b1 = add(n + ".conv1.bias", {2 * d});
-        b.dww = add(n + ".conv2.weight", {2 * d, 1, 3, 3}); b.dwb = add(n + ".conv2.bias", {2 * d});
-        const int w3 = add(n + ".conv3.weight", {d, d, 1, 1}), b3 = add(n + ".conv3.bias", {d});
-        b.caw = add(n + ".channel_attn.chan_conv.weight", {d, d, 1, 1}); b.cab = add(n + ".channel_attn.chan_conv.bias", {d});
-        const int w4 = add(n + ".conv4.weight", {2 * d, d, 1, 1}), b4 = add(n + ".conv4.bias", {2 * d});
-        const int w5 = add(n + ".conv5.weight", {d, d, 1, 1}), b5 = add(n + ".conv5.bias", {d});
-        b.n1w = add(n + ".norm1.weight", {d}); b.n1b = add(n + ".norm1.bias", {d});
-        b.n2w = add(n + ".norm2.weight", {d}); b.n2b = add(n + ".norm2.bias", {d});
-        b.g1 = gemm(w1, b1, 2 * d, d, 1); b.g3 = gemm(w3, b3, d, d, 1); b.g4 = gemm(w4, b4, 2 * d, d, 1); b.g5 = gemm(w5, b5, d, d, 1);
-        return b;
-    }
-    // the reference's registration order (arch.py:206-233): conv_in, encoders, decoders, mid_blks, ups, downs, conv_out
     void build() {
-        const int dim = cfg.dim;
-        p_cin_w = add("conv_in.weight", {dim, cfg.in_channel, 3, 3}); p_cin_b = add("conv_in.bias", {dim});
-        int d = dim;
-        enc.resize(cfg.n_enc); dec.resize(cfg.n_dec);
-        for (int i = 0; i < cfg.n_enc; ++i) {
-            for (int j = 0; j < cfg.enc_blk_nums[i]; ++j) enc[i].push_back(block("encoders." + std::to_string(i) + "." + std::to_string(j), d));
-            d *= 2;
-        }
-        const int dmid = d;
-        for (int i = 0; i < cfg.n_dec; ++i) {
-            d /= 2;
-            for (int j = 0; j < cfg.dec_blk_nums[i]; ++j) dec[i].push_back(block("decoders." + std::to_string(i) + "." + std::to_string(j), d));
-        }
-        for (int j = 0; j < cfg.mid_blk_num; ++j) mid.push_back(block("mid_blks." + std::to_string(j), dmid));
-        d = dmid;
-        for (int i = 0; i < cfg.n_dec; ++i) { const int pw = add("ups." + std::to_string(i) + ".0.weight", {2 * d, d, 1, 1}); ups.push_back(gemm(pw, -1, 2 * d, d, 1)); d /= 2; }
-        d = dim;
-        for (int i = 0; i < cfg.n_enc; ++i) {
-            const int pw = add("downs." + std::to_string(i) + ".weight", {2 * d, d, 2, 2}), pb = add("downs." + std::to_string(i) + ".bias", {2 * d});
-            downs.push_back(gemm(pw, pb, 2 * d, d, 4));
-            d *= 2;
-        }
-        p_cout_w = add("conv_out.weight", {cfg.in_channel, dim, 3, 3}); p_cout_b = add("conv_out.bias", {cfg.in_channel});
-        cout_off = take(conv_packed_bytes(dim, cfg.in_channel, 3, WDM_F32));
+        L = hfrm_layout(cfg);
+        for (auto& p : L.params) { off.push_back(nfloats); nfloats += (p.numel() + 63) / 64 * 64; }
+        bg.resize(L.n_blocks);
+        L.for_each_block([&](const TBlock& b) {
+            const int d = b.d;
+            TBlockG& g = bg[b.idx];
+            g.g1 = gemm(b.w[0], b.b[0], 2 * d, d, 1); g.g3 = gemm(b.w[2], b.b[2], d, d, 1); g.g4 = gemm(b.w[3], b.b[3], 2 * d, d, 1); g.g5 = gemm(b.w[4], b.b[4], d, d, 1);
+        });
+        for (auto& u : L.ups) ups.push_back(gemm(u.w, -1, u.cout, u.cin, 1));
+        for (auto& d : L.downs) downs.push_back(gemm(d.w, d.b, d.cout, d.cin, 4));
+        cout_off = take(conv_packed_bytes(cfg.dim, cfg.in_channel, 3, WDM_F32));
     }
-    float* prm(int i) const { return P + params[i].off; }
-    float* grd(int i) const { return G + params[i].off; }
+    float* prm(int i) const { return P + off[i]; }
+    float* grd(int i) const { return G + off[i]; }
     const float* wf(const TGemm& g) const { return (const float*)(pk + g.f_off); }
     const float* wt(const TGemm& g) const { return (const float*)(pk + g.t_off); }
 
@@ -692,6 +647,7 @@ int wdm_hfrm_trainer::ln_bwd(Ctx& c, const float* x, const float* dn, const floa
 
 int wdm_hfrm_trainer::fwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, BSave& s) {
     const int d = b.d, HW = H * W;
+    const TBlockG& tg = bg[b.idx];
     const long long M = (long long)B * HW, n1 = M * d;
     auto A = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
     s.a1 = A(2 * n1); s.a2 = A(2 * n1); s.c3 = A(n1); s.y = A(n1); s.a4 = A(2 * n1); s.c5 = A(n1); s.out = A(n1);
@@ -699,11 +655,11 @@ int wdm_hfrm_trainer::fwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
     float* n = A(n1);
     float* g = A(n1);
     if (!s.a1 || !s.a2 || !s.c3 || !s.y || !s.a4 || !s.c5 || !s.out || !s.pooled || !s.sc || !n || !g) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block forward)");
-    const int ge = gridn(n1, 256);
+    const int ge = grid_capped_min1(n1, 256);
     WDM_TRY(ln_fwd(c, X, n, M, d, prm(b.n1w), prm(b.n1b)));
-    WDM_TRY(fwd_gemm(c, b.g1, n, M, s.a1));
+    WDM_TRY(fwd_gemm(c, tg.g1, n, M, s.a1));
     if (!c.dry) {
-        hipLaunchKernelGGL(dw_fwd_kernel, dim3(gridn(2 * n1, 256)), dim3(256), 0, c.s, s.a1, s.a2, H, W, 2 * d, 2 * n1, prm(b.dww), prm(b.dwb));
+        hipLaunchKernelGGL(dw_fwd_kernel, dim3(grid_capped_min1(2 * n1, 256)), dim3(256), 0, c.s, s.a1, s.a2, H, W, 2 * d, 2 * n1, prm(b.w[1]), prm(b.b[1]));
         hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, g, n1, d, (const float*)nullptr, HW);
     }
     WDM_TRY(chan_sums(c, g, nullptr, d, H, W, true, 1.0f / (float)HW, s.pooled));
@@ -711,12 +667,12 @@ int wdm_hfrm_trainer::fwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
         WDM_TRY(k_linear(s.pooled, B, d, prm(b.caw), prm(b.cab), d, s.sc, 0, c.s));
         hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, g, n1, d, (const float*)s.sc, HW);      // channel-scaled gate
     }
-    WDM_TRY(fwd_gemm(c, b.g3, g, M, s.c3));
+    WDM_TRY(fwd_gemm(c, tg.g3, g, M, s.c3));
     if (!c.dry) hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, X, prm(b.beta), s.c3, s.y, n1, d);      // y = x + beta * conv3
     WDM_TRY(ln_fwd(c, s.y, n, M, d, prm(b.n2w), prm(b.n2b)));
-    WDM_TRY(fwd_gemm(c, b.g4, n, M, s.a4));
+    WDM_TRY(fwd_gemm(c, tg.g4, n, M, s.a4));
     if (!c.dry) hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a4, g, n1, d, (const float*)nullptr, HW);
-    WDM_TRY(fwd_gemm(c, b.g5, g, M, s.c5));
+    WDM_TRY(fwd_gemm(c, tg.g5, g, M, s.c5));
     if (!c.dry) {
         hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, s.y, prm(b.gamma), s.c5, s.out, n1, d);  // out = y + gamma * conv5
         WDM_HIP(hipGetLastError());
@@ -728,6 +684,7 @@ int wdm_hfrm_trainer::fwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
 // dO: the gradient of the block output on entry, of its input X on return (in place)
 int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, const BSave& s, float* dO) {
     const int d = b.d, HW = H * W;
+    const TBlockG& tg = bg[b.idx];
     const long long M = (long long)B * HW, n1 = M * d;
     auto A = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
     float* t1 = A(n1);          // dc5, dc3
@@ -739,7 +696,7 @@ int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
     float* sm = A((long long)3 * B * d);      // dsc, dpool
     if (!t1 || !t2 || !t3 || !t4 || !t5 || !t6 || !sm) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block backward)");
     float* dsc = sm; float* dpool = sm + (size_t)B * d;
-    const int ge = gridn(n1, 256);
+    const int ge = grid_capped_min1(n1, 256);
     // out = y + gamma * c5
     WDM_TRY(chan_sums(c, dO, s.c5, d, H, W, false, 1.0f, grd(b.gamma)));
     if (!c.dry) {
@@ -747,13 +704,13 @@ int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
         hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a4, t2, n1, d, (const float*)nullptr, HW);
     }
     // conv5
-    WDM_TRY(wgrad(c, t2, d, t1, d, H, W, grd(b.g5.pw), grd(b.g5.pb)));
-    WDM_TRY(dgrad_gemm(c, b.g5, t1, M, t4));
+    WDM_TRY(wgrad(c, t2, d, t1, d, H, W, grd(tg.g5.pw), grd(tg.g5.pb)));
+    WDM_TRY(dgrad_gemm(c, tg.g5, t1, M, t4));
     // gate, conv4, norm2
     if (!c.dry) hipLaunchKernelGGL(gate_bwd_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.a4, t3, n1, d);
     WDM_TRY(ln_fwd(c, s.y, t2, M, d, prm(b.n2w), prm(b.n2b)));
-    WDM_TRY(wgrad(c, t2, d, t3, 2 * d, H, W, grd(b.g4.pw), grd(b.g4.pb)));
-    WDM_TRY(dgrad_gemm(c, b.g4, t3, M, t4));
+    WDM_TRY(wgrad(c, t2, d, t3, 2 * d, H, W, grd(tg.g4.pw), grd(tg.g4.pb)));
+    WDM_TRY(dgrad_gemm(c, tg.g4, t3, M, t4));
     WDM_TRY(ln_bwd(c, s.y, t4, prm(b.n2w), dO, M, d, grd(b.n2w), grd(b.n2b)));      // dO is now d y
     // y = x + beta * c3
     WDM_TRY(chan_sums(c, dO, s.c3, d, H, W, false, 1.0f, grd(b.beta)));
@@ -763,13 +720,13 @@ int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
         hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, t5, n1, d, (const float*)s.sc, HW);          // g * sc
     }
     // conv3
-    WDM_TRY(wgrad(c, t5, d, t1, d, H, W, grd(b.g3.pw), grd(b.g3.pb)));
-    WDM_TRY(dgrad_gemm(c, b.g3, t1, M, t4));
+    WDM_TRY(wgrad(c, t5, d, t1, d, H, W, grd(tg.g3.pw), grd(tg.g3.pb)));
+    WDM_TRY(dgrad_gemm(c, tg.g3, t1, M, t4));
     // channel attention: sc = W pooled + b, pooled = mean g
     WDM_TRY(chan_sums(c, t4, t2, d, H, W, true, 1.0f, dsc));
     if (!c.dry) {
         const long long nca = (long long)d * d + d + (long long)B * d;
-        hipLaunchKernelGGL(ca_bwd_kernel, dim3(gridn(nca, 256)), dim3(256), 0, c.s, dsc, s.pooled, prm(b.caw), B, d, grd(b.caw), grd(b.cab), dpool);
+        hipLaunchKernelGGL(ca_bwd_kernel, dim3(grid_capped_min1(nca, 256)), dim3(256), 0, c.s, dsc, s.pooled, prm(b.caw), B, d, grd(b.caw), grd(b.cab), dpool);
         hipLaunchKernelGGL(ca_dg_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.sc, dpool, n1, d, HW, 1.0f / (float)HW);
         hipLaunchKernelGGL(gate_bwd_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.a2, t3, n1, d);                         // d a2
     }
@@ -782,16 +739,16 @@ int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
         if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM depthwise wgrad)");
         if (!c.dry) {
             hipLaunchKernelGGL(dw_wgrad_part_kernel, dim3(nk, B, ceil_div(C2, 256)), dim3(256), 0, c.s, t3, s.a1, H, W, C2, chunk, nk, part);
-            hipLaunchKernelGGL(dw_wgrad_final_kernel, dim3(ceil_div(C2 * 10, 256)), dim3(256), 0, c.s, part, B * nk, C2, grd(b.dww), grd(b.dwb));
-            hipLaunchKernelGGL(dw_dgrad_kernel, dim3(gridn(2 * n1, 256)), dim3(256), 0, c.s, t3, t6, H, W, C2, 2 * n1, prm(b.dww));
+            hipLaunchKernelGGL(dw_wgrad_final_kernel, dim3(ceil_div(C2 * 10, 256)), dim3(256), 0, c.s, part, B * nk, C2, grd(b.w[1]), grd(b.b[1]));
+            hipLaunchKernelGGL(dw_dgrad_kernel, dim3(grid_capped_min1(2 * n1, 256)), dim3(256), 0, c.s, t3, t6, H, W, C2, 2 * n1, prm(b.w[1]));
             WDM_HIP(hipGetLastError());
         }
         c.ar->free(part);
     }
     // conv1, norm1
     WDM_TRY(ln_fwd(c, X, t2, M, d, prm(b.n1w), prm(b.n1b)));
-    WDM_TRY(wgrad(c, t2, d, t6, 2 * d, H, W, grd(b.g1.pw), grd(b.g1.pb)));
-    WDM_TRY(dgrad_gemm(c, b.g1, t6, M, t4));
+    WDM_TRY(wgrad(c, t2, d, t6, 2 * d, H, W, grd(tg.g1.pw), grd(tg.g1.pb)));
+    WDM_TRY(dgrad_gemm(c, tg.g1, t6, M, t4));
     WDM_TRY(ln_bwd(c, X, t4, prm(b.n1w), dO, M, d, grd(b.n1w), grd(b.n1b)));        // dO is now d X
     c.ar->free(sm); c.ar->free(t6); c.ar->free(t5); c.ar->free(t4); c.ar->free(t3); c.ar->free(t2); c.ar->free(t1);
     return WDM_OK;
@@ -800,16 +757,13 @@ int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
 int wdm_hfrm_trainer::pack(hipStream_t s) {
     auto pg = [&](const TGemm& g) {
         const long long nf = (long long)g.rows_f() * g.K(), nt = (long long)g.rows_t() * g.cout;
-        hipLaunchKernelGGL(pack_gemm_kernel, dim3(gridn(nf, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 0, (float*)(pk + g.f_off), g.rows_f());
-        hipLaunchKernelGGL(pack_gemm_kernel, dim3(gridn(nt, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 1, (float*)(pk + g.t_off), g.rows_t());
+        hipLaunchKernelGGL(pack_gemm_kernel, dim3(grid_capped_min1(nf, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 0, (float*)(pk + g.f_off), g.rows_f());
+        hipLaunchKernelGGL(pack_gemm_kernel, dim3(grid_capped_min1(nt, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 1, (float*)(pk + g.t_off), g.rows_t());
     };
-    auto pb = [&](const TBlock& b) { pg(b.g1); pg(b.g3); pg(b.g4); pg(b.g5); };
-    for (auto& lv : enc) for (auto& b : lv) pb(b);
-    for (auto& lv : dec) for (auto& b : lv) pb(b);
-    for (auto& b : mid) pb(b);
+    for (auto& b : bg) { pg(b.g1); pg(b.g3); pg(b.g4); pg(b.g5); }
     for (auto& g : ups) pg(g);
     for (auto& g : downs) pg(g);
-    WDM_TRY(k_pack_conv(prm(p_cout_w), cfg.in_channel, cfg.dim, 3, pk + cout_off, conv_rows_pad(cfg.in_channel), 0, 1, WDM_F32, s));
+    WDM_TRY(k_pack_conv(prm(L.conv_out.w), cfg.in_channel, cfg.dim, 3, pk + cout_off, conv_rows_pad(cfg.in_channel), 0, 1, WDM_F32, s));
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }
@@ -828,36 +782,36 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
     std::vector<float*> enc_out(nlev), up_in(cfg.n_dec);
     float* cur = A(M0 * dim);
     if (!cur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer)");
-    if (!c.dry) hipLaunchKernelGGL((conv_in_kernel<32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, cur, B, H, W, nc, prm(p_cin_w), prm(p_cin_b));
+    if (!c.dry) hipLaunchKernelGGL((conv_in_kernel<32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, cur, B, H, W, nc, prm(L.conv_in.w), prm(L.conv_in.b));
     int d = dim, h = H, w = W;
     auto run_blocks = [&](const std::vector<TBlock>& bl) -> int {
         for (auto& b : bl) { BSave s; WDM_TRY(fwd_block(c, b, cur, B, h, w, s)); ins.push_back(cur); saves.push_back(s); cur = s.out; }
         return WDM_OK;
     };
     for (int i = 0; i < nlev; ++i) {
-        WDM_TRY(run_blocks(enc[i]));
+        WDM_TRY(run_blocks(L.enc[i]));
         enc_out[i] = cur;
         const long long Mn = (long long)B * (h / 2) * (w / 2);
         float* u = A(Mn * 4 * d);
         float* nt = A(Mn * 2 * d);
         if (!u || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down)");
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(gridn(Mn * 4 * d, 256)), dim3(256), 0, c.s, cur, u, B, h, w, d, 0);
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(grid_capped_min1(Mn * 4 * d, 256)), dim3(256), 0, c.s, cur, u, B, h, w, d, 0);
         WDM_TRY(fwd_gemm(c, downs[i], u, Mn, nt));
         c.ar->free(u);
         cur = nt; d *= 2; h /= 2; w /= 2;
     }
-    WDM_TRY(run_blocks(mid));
+    WDM_TRY(run_blocks(L.mid));
     for (int i = 0; i < cfg.n_dec; ++i) {
         const long long M = (long long)B * h * w;
         float* p = A(M * 2 * d);
         float* nt = A(M * 2 * d);           // (2h x 2w x d/2)
         if (!p || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up)");
         WDM_TRY(fwd_gemm(c, ups[i], cur, M, p));
-        if (!c.dry) hipLaunchKernelGGL(pixel_shuffle_kernel, dim3(gridn(M * 2 * d, 256)), dim3(256), 0, c.s, p, enc_out[nlev - 1 - i], nt, B, h, w, d / 2);
+        if (!c.dry) hipLaunchKernelGGL(pixel_shuffle_kernel, dim3(grid_capped_min1(M * 2 * d, 256)), dim3(256), 0, c.s, p, enc_out[nlev - 1 - i], nt, B, h, w, d / 2);
         c.ar->free(p);
         up_in[i] = cur;
         cur = nt; d /= 2; h *= 2; w *= 2;
-        WDM_TRY(run_blocks(dec[i]));
+        WDM_TRY(run_blocks(L.dec[i]));
     }
     // conv_out 3x3 + input (run_conv, as the inference forward), NCHW f32
     float* xin = A(M0 * nc);
@@ -867,7 +821,7 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
     if (!xin || !yo || !dY || !lpart) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer output)");
     {
         if (!c.dry) WDM_TRY(k_nchw_to_nhwc(x, xin, B, nc, H, W, WDM_F32, c.s));
-        ConvW cwo; cwo.w = pk + cout_off; cwo.b = prm(p_cout_b); cwo.cin = dim; cwo.cout = nc; cwo.k = 3; cwo.rows_pad = conv_rows_pad(nc);
+        ConvW cwo; cwo.w = pk + cout_off; cwo.b = prm(L.conv_out.b); cwo.cin = dim; cwo.cout = nc; cwo.k = 3; cwo.rows_pad = conv_rows_pad(nc);
         Tens t; t.p = cur; t.C = dim; t.H = H; t.W = W; t.xs = dim;
         Tens xi; xi.p = xin; xi.C = nc; xi.H = H; xi.W = W; xi.xs = nc;
         Tens dummy;
@@ -896,9 +850,9 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
         if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_out wgrad)");
         if (nc != 3) WDM_FAIL(WDM_EINVAL, "HFRM trainer: in_channel must be 3");
         if (!c.dry) {
-            hipLaunchKernelGGL((conv_out_dgrad_kernel<32, 3>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, dY, prm(p_cout_w), dT, B, H, W);
+            hipLaunchKernelGGL((conv_out_dgrad_kernel<32, 3>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, dY, prm(L.conv_out.w), dT, B, H, W);
             hipLaunchKernelGGL((wgrad3_small_part_kernel<32, 3>), dim3(nbk), dim3(256), 0, c.s, cur, dY, B, H, W, -1, chunk, part);
-            hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 0, grd(p_cout_w), grd(p_cout_b));
+            hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 0, grd(L.conv_out.w), grd(L.conv_out.b));
             WDM_HIP(hipGetLastError());
         }
         c.ar->free(part);
@@ -915,7 +869,7 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
     };
     std::vector<float*> dskip(nlev);
     for (int i = cfg.n_dec - 1; i >= 0; --i) {
-        WDM_TRY(back_blocks(dec[i]));
+        WDM_TRY(back_blocks(L.dec[i]));
         // ups[i]: nt = PixelShuffle(W up_in) + skip
         const int dl = 2 * d;                                   // channels of up_in
         const int hl = h / 2, wl = w / 2;
@@ -923,14 +877,14 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
         float* dp = A(M * 2 * dl);
         float* dcur = A(M * dl);
         if (!dp || !dcur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up backward)");
-        if (!c.dry) hipLaunchKernelGGL(pixel_unshuffle_kernel, dim3(gridn(M * 2 * dl, 256)), dim3(256), 0, c.s, dT, dp, B, hl, wl, d);
+        if (!c.dry) hipLaunchKernelGGL(pixel_unshuffle_kernel, dim3(grid_capped_min1(M * 2 * dl, 256)), dim3(256), 0, c.s, dT, dp, B, hl, wl, d);
         dskip[nlev - 1 - i] = dT;
         WDM_TRY(wgrad(c, up_in[i], dl, dp, 2 * dl, hl, wl, grd(ups[i].pw), nullptr));
         WDM_TRY(dgrad_gemm(c, ups[i], dp, M, dcur));
         c.ar->free(dp);
         dT = dcur; d = dl; h = hl; w = wl;
     }
-    WDM_TRY(back_blocks(mid));
+    WDM_TRY(back_blocks(L.mid));
     for (int i = nlev - 1; i >= 0; --i) {
         // downs[i]: level i+1 input = W . unshuffle(enc_out[i]) + b
         const int dl = d / 2, hl = 2 * h, wl = 2 * w;
@@ -938,14 +892,14 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
         float* u = A(Mn * 4 * dl);
         float* gw = A((long long)2 * dl * 4 * dl);
         if (!u || !gw) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down backward)");
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(gridn(Mn * 4 * dl, 256)), dim3(256), 0, c.s, enc_out[i], u, B, hl, wl, dl, 0);
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(grid_capped_min1(Mn * 4 * dl, 256)), dim3(256), 0, c.s, enc_out[i], u, B, hl, wl, dl, 0);
         WDM_TRY(wgrad(c, u, 4 * dl, dT, 2 * dl, h, w, gw, grd(downs[i].pb)));
-        if (!c.dry) hipLaunchKernelGGL(permute_down_grad_kernel, dim3(gridn((long long)2 * dl * 4 * dl, 256)), dim3(256), 0, c.s, gw, grd(downs[i].pw), 2 * dl, dl, 4);
+        if (!c.dry) hipLaunchKernelGGL(permute_down_grad_kernel, dim3(grid_capped_min1((long long)2 * dl * 4 * dl, 256)), dim3(256), 0, c.s, gw, grd(downs[i].pw), 2 * dl, dl, 4);
         WDM_TRY(dgrad_gemm(c, downs[i], dT, Mn, u));           // d u, over u
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(gridn(Mn * 4 * dl, 256)), dim3(256), 0, c.s, dskip[i], u, B, hl, wl, dl, 1);
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(grid_capped_min1(Mn * 4 * dl, 256)), dim3(256), 0, c.s, dskip[i], u, B, hl, wl, dl, 1);
         c.ar->free(gw); c.ar->free(u); c.ar->free(dT);
         dT = dskip[i]; d = dl; h = hl; w = wl;
-        WDM_TRY(back_blocks(enc[i]));
+        WDM_TRY(back_blocks(L.enc[i]));
     }
     {   // conv_in: weight and bias only (the image needs no gradient)
         const int chunk = 2048, nbk = ceil_div(M0, chunk);
@@ -954,7 +908,7 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
         if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_in wgrad)");
         if (!c.dry) {
             hipLaunchKernelGGL((wgrad3_small_part_kernel<32, 3>), dim3(nbk), dim3(256), 0, c.s, dT, x, B, H, W, 1, chunk, part);
-            hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 1, grd(p_cin_w), grd(p_cin_b));
+            hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 1, grd(L.conv_in.w), grd(L.conv_in.b));
             WDM_HIP(hipGetLastError());
         }
         c.ar->free(part);
@@ -981,15 +935,11 @@ int wdm_hfrm_trainer_create(wdm_handle* h, const wdm_hfrm_config* cfg, wdm_hfrm_
     return WDM_OK;
 }
 int wdm_hfrm_trainer_destroy(wdm_hfrm_trainer* t) { delete t; return WDM_OK; }
-int wdm_hfrm_trainer_num_params(const wdm_hfrm_trainer* t) { return t ? (int)t->params.size() : 0; }
+int wdm_hfrm_trainer_num_params(const wdm_hfrm_trainer* t) { return t ? (int)t->L.params.size() : 0; }
 int64_t wdm_hfrm_trainer_num_floats(const wdm_hfrm_trainer* t) { return t ? t->nfloats : 0; }
 int wdm_hfrm_trainer_param_info(const wdm_hfrm_trainer* t, int i, const char** name, int* ndim, int64_t shape[4], int64_t* offset) {
-    if (!t || i < 0 || i >= (int)t->params.size()) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_param_info: index out of range");
-    const TParam& p = t->params[i];
-    if (name) *name = p.name.c_str();
-    if (ndim) *ndim = p.ndim;
-    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
-    if (offset) *offset = p.off;
+    if (!t || !param_info(t->L.params, i, name, ndim, shape)) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_param_info: index out of range");
+    if (offset) *offset = t->off[i];
     return WDM_OK;
 }
 int wdm_hfrm_trainer_set_buffers(wdm_hfrm_trainer* t, float* params, float* grads, float* m, float* v) {

@@ -15,7 +15,6 @@
 
 namespace wdm {
 
-static inline int nblk(long long n, int bs) { long long g = (n + bs - 1) / bs; return (int)(g > 16384 ? 16384 : g); }
 
 // dst[b][c][k] (row length kp, k = oy*Wo + ox; image stride dst_img elements) = src[b][stride*oy + off_y][stride*ox + off_x][c]
 // (0 outside the map / past Ho*Wo), src = the channel concat [src0 (C0 channels) | src1]; rows C <= c < Crows are written as zeros.
@@ -506,13 +505,13 @@ static void gather_t(hipStream_t s, const void* src0, int xs0, int C0, const voi
 #define BY_DTYPE(dtype, FN, ...) do { if ((dtype) == WDM_BF16) FN<__bf16>(__VA_ARGS__); else FN<float>(__VA_ARGS__); } while (0)
 
 template <typename T> static void l_scatter_odd(hipStream_t s, const void* dy, int C, int Ho, int Wo, void* z, long long total) {
-    hipLaunchKernelGGL(scatter_odd_kernel<T>, dim3(nblk(total, 256)), dim3(256), 0, s, (const T*)dy, C, Ho, Wo, (T*)z, total);
+    hipLaunchKernelGGL(scatter_odd_kernel<T>, dim3(grid_capped(total, 256)), dim3(256), 0, s, (const T*)dy, C, Ho, Wo, (T*)z, total);
 }
 template <typename T> static void l_upsample2(hipStream_t s, const void* x, int C, int h, int w, void* y, long long total) {
-    hipLaunchKernelGGL(upsample2_kernel<T>, dim3(nblk(total, 256)), dim3(256), 0, s, (const T*)x, C, h, w, (T*)y, total);
+    hipLaunchKernelGGL(upsample2_kernel<T>, dim3(grid_capped(total, 256)), dim3(256), 0, s, (const T*)x, C, h, w, (T*)y, total);
 }
 template <typename T> static void l_sumpool2(hipStream_t s, const void* dy, int C, int h, int w, void* dx, int acc, long long total) {
-    hipLaunchKernelGGL(sumpool2_kernel<T>, dim3(nblk(total, 256)), dim3(256), 0, s, (const T*)dy, C, h, w, (T*)dx, acc, total);
+    hipLaunchKernelGGL(sumpool2_kernel<T>, dim3(grid_capped(total, 256)), dim3(256), 0, s, (const T*)dy, C, h, w, (T*)dx, acc, total);
 }
 // one pass over OIHW: forward layout dstf[tap][rows_total][cin] (rows >= cout zero) and dgrad layout dstd[KK-1-tap][rows_d][kpad] (transposed)
 template <typename T, int KK>
@@ -586,7 +585,7 @@ template <typename T> static void l_pack_dgrad(hipStream_t s, const float* w, in
     else hipLaunchKernelGGL((pack_dgrad_kernel<T, 1>), grid, dim3(256), 0, s, w, cout, cin, (T*)dst, rows, kpad);
 }
 template <typename T> static void l_pad_channels(hipStream_t s, const void* x, int C, int Cp, void* y, long long total) {
-    hipLaunchKernelGGL(pad_channels_kernel<T>, dim3(nblk(total, 256)), dim3(256), 0, s, (const T*)x, C, Cp, (T*)y, total);
+    hipLaunchKernelGGL(pad_channels_kernel<T>, dim3(grid_capped(total, 256)), dim3(256), 0, s, (const T*)x, C, Cp, (T*)y, total);
 }
 // per-image column sums in ONE launch: out[g][c] = sum over the rows of image g of x[g][row][c].  grid (ceil(C / 64), images), 256 threads = (64 / VEC channel
 // vectors) x (row lanes); a row lane adds its rows in ascending order, the lanes are joined in ascending order.  (colsum_part + colsum_final: two launches.)
@@ -802,7 +801,7 @@ int conv_wgrad(Ctx& c, int mode, const Tens& x0, const Tens* x1, const Tens& dy,
             if (map8) hipLaunchKernelGGL(conv_wgrad_kernel<true>, dim3(w.S * ntile), dim3(512), WgradCfg<true>::LDS_BYTES, c.s, w);
             else hipLaunchKernelGGL(conv_wgrad_kernel<false>, dim3(w.S * ntile), dim3(512), WgradCfg<false>::LDS_BYTES, c.s, w);
             const long long total = (long long)3 * cout * cin;
-            hipLaunchKernelGGL(reduce_wgrad_kernel, dim3(nblk(total, 256)), dim3(256), 0, c.s, part, 9, w.S, rows_g, cout, cin, dw, accumulate ? 1 : 0);
+            hipLaunchKernelGGL(reduce_wgrad_kernel, dim3(grid_capped(total, 256)), dim3(256), 0, c.s, part, 9, w.S, rows_g, cout, cin, dw, accumulate ? 1 : 0);
             WDM_HIP(hipGetLastError());
         }
         c.ar->free(part);
@@ -841,7 +840,7 @@ int conv_wgrad(Ctx& c, int mode, const Tens& x0, const Tens* x1, const Tens& dy,
             }
             if (rc == WDM_OK) {
                 const long long total = (long long)kk * cout * cin;
-                hipLaunchKernelGGL(reduce_wgrad_kernel, dim3(nblk(total, 256)), dim3(256), 0, c.s, part, kk, S, rows_g, cout, cin, dw, accumulate ? 1 : 0);
+                hipLaunchKernelGGL(reduce_wgrad_kernel, dim3(grid_capped(total, 256)), dim3(256), 0, c.s, part, kk, S, rows_g, cout, cin, dw, accumulate ? 1 : 0);
                 WDM_HIP(hipGetLastError());
             }
         }
@@ -871,7 +870,7 @@ int conv_wgrad(Ctx& c, int mode, const Tens& x0, const Tens* x1, const Tens& dy,
         }
         if (rc == WDM_OK) {
             const long long total = (long long)kk * cout * cin;
-            hipLaunchKernelGGL(reduce_wgrad_kernel, dim3(nblk(total, 256)), dim3(256), 0, c.s, part, kk, S, rows_g, cout, cin, dw, accumulate ? 1 : 0);
+            hipLaunchKernelGGL(reduce_wgrad_kernel, dim3(grid_capped(total, 256)), dim3(256), 0, c.s, part, kk, S, rows_g, cout, cin, dw, accumulate ? 1 : 0);
             WDM_HIP(hipGetLastError());
         }
     }

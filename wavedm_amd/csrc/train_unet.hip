@@ -10,7 +10,6 @@
 // and a DDP all-reduce is one collective over the gradient buffer.  Deterministic: no atomics, fixed reduction orders.
 #include <deque>
 #include <functional>
-#include <map>
 #include <string>
 
 #include "common.h"
@@ -18,9 +17,6 @@
 using namespace wdm;
 
 namespace wdm {
-
-static inline int nb(long long n, int bs) { long long g = (n + bs - 1) / bs; return (int)(g > 16384 ? 16384 : g); }      // grid-stride kernels
-static inline int nbu(long long n, int bs) { return (int)((n + bs - 1) / bs); }                                            // one element per thread
 
 // ---- small kernels -------------------------------------------------------------------------------------------------
 // x96[b][p][c] (NHWC, model dtype): c in [c_t0, c_t0 + 3): x0*sa[b] + e*s1m[b]  (q-sample, ddm_wavelet.py:112), else x0
@@ -233,20 +229,20 @@ template <int RULE> __global__ __launch_bounds__(256) void optim_ema_kernel(cons
 }
 
 template <typename T> static void l_add_into(hipStream_t s, void* dst, const void* src, long long n, int acc) {
-    hipLaunchKernelGGL(add_into_kernel<T>, dim3(nb(n, 256)), dim3(256), 0, s, (T*)dst, (const T*)src, n, acc);
+    hipLaunchKernelGGL(add_into_kernel<T>, dim3(grid_capped(n, 256)), dim3(256), 0, s, (T*)dst, (const T*)src, n, acc);
 }
 template <typename T> static void l_split_add(hipStream_t s, const void* src, int C0, int C1, void* d0, int a0, void* d1, int a1, long long total) {
-    hipLaunchKernelGGL(split_add_kernel<T>, dim3(nb(total, 256)), dim3(256), 0, s, (const T*)src, C0, C1, (T*)d0, a0, (T*)d1, a1, total);
+    hipLaunchKernelGGL(split_add_kernel<T>, dim3(grid_capped(total, 256)), dim3(256), 0, s, (const T*)src, C0, C1, (T*)d0, a0, (T*)d1, a1, total);
 }
 template <typename T> static void l_f32_to_t(hipStream_t s, const float* src, void* dst, long long n) {
-    hipLaunchKernelGGL(f32_to_t_kernel<T>, dim3(nb(n, 256)), dim3(256), 0, s, src, (T*)dst, n);
+    hipLaunchKernelGGL(f32_to_t_kernel<T>, dim3(grid_capped(n, 256)), dim3(256), 0, s, src, (T*)dst, n);
 }
 template <typename T> static void l_softmax_bwd(hipStream_t s, const void* P, const float* dP, void* dS, long long rows, int n, float scale) {
     hipLaunchKernelGGL(softmax_bwd_kernel<T>, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, (const T*)P, dP, (T*)dS, rows, n, scale);
 }
 template <typename T> static void l_build_input(hipStream_t s, const float* x0, const float* e, const float* sa, const float* s1m, int C, int HW, int c_t0, int pc, void* x96,
                                                 long long total) {
-    hipLaunchKernelGGL(build_input_kernel<T>, dim3(nb(total, 256)), dim3(256), 0, s, x0, e, sa, s1m, C, HW, c_t0, pc, (T*)x96, total);
+    hipLaunchKernelGGL(build_input_kernel<T>, dim3(grid_capped(total, 256)), dim3(256), 0, s, x0, e, sa, s1m, C, HW, c_t0, pc, (T*)x96, total);
 }
 template <typename T> static void l_loss(hipStream_t s, const float* out, const float* e, int B, int pc, int HW, void* dout, float* loss, float* out_nchw,
                                          const float* sqrt_a, const float* sqrt_1ma, double* partial) {
@@ -262,7 +258,7 @@ void l_colsum_f32(hipStream_t s, const float* x, int C, int rows, float* out, fl
 int k_adam_ema(float* P, const float* G, float* M, float* V, float* E, long long n, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay,
                float ema_mu, hipStream_t s) {
     const float bc1 = 1.0f - (float)std::pow(beta1, (double)step), bc2 = 1.0f - (float)std::pow(beta2, (double)step);
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(nb(n, 256)), dim3(256), 0, s, P, G, M, V, E, n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(grid_capped(n, 256)), dim3(256), 0, s, P, G, M, V, E, n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
                        eps, weight_decay, bc1, std::sqrt(bc2), ema_mu);
     WDM_HIP(hipGetLastError());
     return WDM_OK;
@@ -306,34 +302,25 @@ int k_optim_ema(int rule, float* P, const float* G, float* S0, float* S1, float*
 
 // =====================================================================================================================
 namespace {
-struct PInfo { std::string name; int ndim; int64_t shape[4]; size_t off; };
-struct ConvP { size_t w = 0, b = 0; int cin = 0, cout = 0, k = 0; };
-struct NormP { size_t g = 0, b = 0; int c = 0; };
-struct ResP { int cin, cout; NormP n1, n2; ConvP c1, c2, nin; bool has_nin; int temb_row; int layer; };      // layer: position in add_res order (the dropout counter)
-struct AttnP { int c; NormP n; ConvP q, k, v, proj; };
+using ConvP = UNetLayout::Conv;
+using NormP = UNetLayout::Norm;
+using ResP = UNetLayout::Res;
+using AttnP = UNetLayout::Attn;
 struct TT { Tens t; void* g = nullptr; bool gset = false; bool needs_grad = true; };
 }  // namespace
 
 struct wdm_trainer {
     wdm_unet_config cfg;
-    int temb_ch = 0, temb_rows = 0;
-    std::vector<PInfo> params;
+    UNetLayout L;                 // the network; L.params also lists the temb_proj tail (all weights, then all biases)
+    std::vector<size_t> off;      // per parameter: float offset in the flat buffers, which the parameters tile without gaps in L.params order
     size_t nfloats = 0;
     float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *E = nullptr;
     int opt_rule = WDM_OPT_ADAM;                          // wdm_trainer_set_optimizer: the rule wdm_trainer_optim_step applies, and its state buffers
     float* S[3] = {nullptr, nullptr, nullptr};            // (WDM_OPT_ADAM keeps M / V of wdm_trainer_set_buffers)
     bool use_mse = false;     // training.use_mse: differentiate the x0-space loss instead of the noise-space one
     Dropout dropout;          // model.dropout of the next step (wdm_trainer_set_dropout): p, seed and the optimizer step it computes; layer is filled per block
-    int n_res = 0;
-    // layers
-    size_t d0w, d0b, d1w, d1b, tw, tb;
-    ConvP conv_in, conv_out;
-    NormP norm_out;
-    std::vector<std::vector<ResP>> down_res, up_res;
-    std::vector<std::vector<AttnP>> down_attn, up_attn;
-    std::vector<ConvP> down_ds, up_us;
-    ResP mid1, mid2;
-    AttnP mid_attn;
+    size_t tw = 0, tb = 0;    // all temb_proj layers as ONE [temb_rows][temb_ch] matrix + [temb_rows] bias (rows in block order), like the inference engine
+    std::vector<std::pair<void*, void*>> packed;          // per conv of L.convs: (forward layout, dgrad layout) of this step
     // per-step state
     Ctx* c = nullptr;
     std::deque<TT> acts;
@@ -345,35 +332,14 @@ struct wdm_trainer {
     float* temb_all = nullptr;      // [B][temb_rows] forward values, and its gradient
     float* d_temb_all = nullptr;
 
-    size_t take(const std::string& name, std::initializer_list<int64_t> shp) {
-        PInfo p; p.name = name; p.ndim = (int)shp.size(); int i = 0; size_t n = 1;
-        for (auto v : shp) { p.shape[i++] = v; n *= (size_t)v; }
-        for (; i < 4; ++i) p.shape[i] = 0;
-        p.off = nfloats; nfloats += n;
-        params.push_back(p);
-        return p.off;
+    void build() {
+        L = unet_layout(cfg);
+        const size_t body = L.params.size();
+        for (auto& e : L.temb_proj) L.params.push_back(L.temb_proj_weight(e));
+        for (auto& e : L.temb_proj) L.params.push_back(L.temb_proj_bias(e));
+        for (auto& p : L.params) { off.push_back(nfloats); nfloats += (size_t)p.numel(); }
+        tw = off[body]; tb = off[body + L.temb_proj.size()];
     }
-    std::vector<ConvP> conv_list;                                   // every conv of the model, in construction order (packed together at the start of a step)
-    std::map<size_t, std::pair<void*, void*>> packed;              // weight offset -> (forward layout, dgrad layout) of this step
-    ConvP add_conv(const std::string& n, int cin, int cout, int k) { ConvP p; p.cin = cin; p.cout = cout; p.k = k; p.w = take(n + ".weight", {cout, cin, k, k}); p.b = take(n + ".bias", {cout}); conv_list.push_back(p); return p; }
-    NormP add_norm(const std::string& n, int cc) { NormP p; p.c = cc; p.g = take(n + ".weight", {cc}); p.b = take(n + ".bias", {cc}); return p; }
-    std::vector<std::pair<std::string, int>> temb_list;
-    ResP add_res(const std::string& n, int cin, int cout) {
-        ResP r; r.cin = cin; r.cout = cout; r.has_nin = cin != cout; r.layer = n_res++;
-        r.n1 = add_norm(n + ".norm1", cin);
-        r.c1 = add_conv(n + ".conv1", cin, cout, 3);
-        r.temb_row = temb_rows; temb_rows += cout; temb_list.push_back({n + ".temb_proj", cout});
-        r.n2 = add_norm(n + ".norm2", cout);
-        r.c2 = add_conv(n + ".conv2", cout, cout, 3);
-        if (r.has_nin) r.nin = add_conv(n + ".nin_shortcut", cin, cout, 1);
-        return r;
-    }
-    AttnP add_attn(const std::string& n, int cc) {
-        AttnP a; a.c = cc; a.n = add_norm(n + ".norm", cc);
-        a.q = add_conv(n + ".q", cc, cc, 1); a.k = add_conv(n + ".k", cc, cc, 1); a.v = add_conv(n + ".v", cc, cc, 1); a.proj = add_conv(n + ".proj_out", cc, cc, 1);
-        return a;
-    }
-    void build();
     // ---- graph ops
     TT* new_act() { acts.emplace_back(); return &acts.back(); }
     int grad_buf(TT* t, bool* first) {
@@ -392,79 +358,39 @@ struct wdm_trainer {
     int step(Ctx& cc, const float* x0, const float* t, const float* sa, const float* s1m, const float* e, int c_t0, float* loss, float* out_nchw);
 };
 
-void wdm_trainer::build() {
-    const int ch = cfg.ch, nres = cfg.n_levels, nrb = cfg.num_res_blocks;
-    temb_ch = ch * 4;
-    auto is_attn = [&](int res) { for (int i = 0; i < cfg.n_attn_res; ++i) if (cfg.attn_resolutions[i] == res) return true; return false; };
-    d0w = take("temb.dense.0.weight", {temb_ch, ch}); d0b = take("temb.dense.0.bias", {temb_ch});
-    d1w = take("temb.dense.1.weight", {temb_ch, temb_ch}); d1b = take("temb.dense.1.bias", {temb_ch});
-    conv_in = add_conv("conv_in", cfg.in_channels, ch, 3);
-    int res = cfg.resolution, block_in = ch;
-    down_res.resize(nres); down_attn.resize(nres); down_ds.assign(nres, ConvP{});
-    up_res.resize(nres); up_attn.resize(nres); up_us.assign(nres, ConvP{});
-    for (int l = 0; l < nres; ++l) {
-        block_in = ch * (l == 0 ? 1 : cfg.ch_mult[l - 1]);
-        const int block_out = ch * cfg.ch_mult[l];
-        for (int b = 0; b < nrb; ++b) { down_res[l].push_back(add_res("down." + std::to_string(l) + ".block." + std::to_string(b), block_in, block_out)); block_in = block_out; }
-        if (is_attn(res)) for (int b = 0; b < nrb; ++b) down_attn[l].push_back(add_attn("down." + std::to_string(l) + ".attn." + std::to_string(b), block_out));
-        if (l != nres - 1) { down_ds[l] = add_conv("down." + std::to_string(l) + ".downsample.conv", block_in, block_in, 3); res /= 2; }
-    }
-    mid1 = add_res("mid.block_1", block_in, block_in);
-    mid_attn = add_attn("mid.attn_1", block_in);
-    mid2 = add_res("mid.block_2", block_in, block_in);
-    for (int l = nres - 1; l >= 0; --l) {
-        const int block_out = ch * cfg.ch_mult[l];
-        int skip_in = ch * cfg.ch_mult[l];
-        for (int b = 0; b <= nrb; ++b) {
-            if (b == nrb) skip_in = ch * (l == 0 ? 1 : cfg.ch_mult[l - 1]);
-            up_res[l].push_back(add_res("up." + std::to_string(l) + ".block." + std::to_string(b), block_in + skip_in, block_out));
-            block_in = block_out;
-        }
-        if (is_attn(res)) for (int b = 0; b <= nrb; ++b) up_attn[l].push_back(add_attn("up." + std::to_string(l) + ".attn." + std::to_string(b), block_out));
-        if (l != 0) { up_us[l] = add_conv("up." + std::to_string(l) + ".upsample.conv", block_in, block_in, 3); res *= 2; }
-    }
-    norm_out = add_norm("norm_out", block_in);
-    conv_out = add_conv("conv_out", block_in, cfg.out_ch, 3);
-    // all temb_proj layers as ONE [temb_rows][temb_ch] matrix + [temb_rows] bias (rows in block order), like the inference engine
-    tw = nfloats;
-    for (auto& e : temb_list) take(e.first + ".weight", {e.second, temb_ch});
-    tb = nfloats;
-    for (auto& e : temb_list) take(e.first + ".bias", {e.second});
-}
-
 // y = conv(x0 | x1) + bias (+ temb[b][row + co]) (+ res)
 int wdm_trainer::op_conv(const ConvP& p, int mode, TT* x0, TT* x1, int temb_row, TT* res, TT** out) {
     Ctx& cx = *c;
-    ConvW w; w.cin = p.cin; w.cout = p.cout; w.k = p.k; w.rows_pad = conv_rows_pad(p.cout); w.b = P + p.b;
+    const size_t pw = off[p.w], pb = off[p.b];
+    ConvW w; w.cin = p.cin; w.cout = p.cout; w.k = p.k; w.rows_pad = conv_rows_pad(p.cout); w.b = P + pb;
     // forward and transposed (dgrad) layouts of every conv were written at the start of the step (pack_all): one pass over the fp32 parameters
-    const auto it = packed.find(p.w);
-    if (it == packed.end()) WDM_FAIL(WDM_ESTATE, "training: conv weights were not packed for this step");
-    void* pk = it->second.first;
-    void* wd = x0->needs_grad ? it->second.second : nullptr;
+    if (packed.size() != L.convs.size()) WDM_FAIL(WDM_ESTATE, "training: conv weights were not packed for this step");
+    void* pk = packed[p.idx].first;
+    void* wd = x0->needs_grad ? packed[p.idx].second : nullptr;
     w.w = pk;
     TT* o = new_act();
     // stats: the conv's epilogue also leaves the GroupNorm partial statistics of its output (most conv outputs feed a GroupNorm)
-    WDM_TRY(run_conv(cx, w, mode, {.x0 = &x0->t, .x1 = x1 ? &x1->t : nullptr, .temb = temb_row >= 0 ? temb_all + temb_row : nullptr, .temb_ld = temb_rows, .temb_per_image = 1,
+    WDM_TRY(run_conv(cx, w, mode, {.x0 = &x0->t, .x1 = x1 ? &x1->t : nullptr, .temb = temb_row >= 0 ? temb_all + temb_row : nullptr, .temb_ld = L.temb_rows, .temb_per_image = 1,
                                    .res = res ? &res->t : nullptr, .stats = true}, &o->t));
     *out = o;
     const ConvP pp = p;
-    tape_rng.push_back({(long long)std::min(pp.w, pp.b), (long long)std::max(pp.w + (size_t)pp.cout * pp.cin * pp.k * pp.k, pp.b + (size_t)pp.cout)});
-    tape.push_back([this, pp, mode, x0, x1, temb_row, res, o, wd]() -> int {
+    tape_rng.push_back({(long long)std::min(pw, pb), (long long)std::max(pw + (size_t)pp.cout * pp.cin * pp.k * pp.k, pb + (size_t)pp.cout)});
+    tape.push_back([this, pp, pw, pb, mode, x0, x1, temb_row, res, o, wd]() -> int {
         Ctx& cx = *c;
         if (!o->g) WDM_FAIL(WDM_ESTATE, "backward: conv output without gradient");
         const Tens dy = gtens(o);
         // weight, bias and (ResnetBlock conv1) per-image temb gradients: the column sums come out of the pass that transposes dy
-        WDM_TRY(conv_wgrad(cx, mode, x0->t, x1 ? &x1->t : nullptr, dy, pp.cout, G + pp.w, false, G + pp.b, temb_row >= 0 ? d_temb_all + temb_row : nullptr, temb_rows));
+        WDM_TRY(conv_wgrad(cx, mode, x0->t, x1 ? &x1->t : nullptr, dy, pp.cout, G + pw, false, G + pb, temb_row >= 0 ? d_temb_all + temb_row : nullptr, L.temb_rows));
         const long long n_out = (long long)cx.B * dy.H * dy.W * dy.C;
         if (res && res->needs_grad) { bool first; WDM_TRY(grad_buf(res, &first)); BYT(cx.dtype, l_add_into, cx.s, res->g, o->g, n_out, first ? 0 : 1); }
         if (x0->needs_grad) {
             if (!x1) {
                 bool first; WDM_TRY(grad_buf(x0, &first));
-                WDM_TRY(conv_dgrad(cx, mode, P + pp.w, pp.cin, pp.cout, dy, x0->t.H, x0->t.W, x0->g, !first, wd));
+                WDM_TRY(conv_dgrad(cx, mode, P + pw, pp.cin, pp.cout, dy, x0->t.H, x0->t.W, x0->g, !first, wd));
             } else {
                 void* tmp = cx.ar->alloc((size_t)cx.B * x0->t.H * x0->t.W * pp.cin * dsize(cx.dtype));
                 if (!tmp) WDM_FAIL(WDM_ENOMEM, "training workspace too small (concat dgrad)");
-                WDM_TRY(conv_dgrad(cx, mode, P + pp.w, pp.cin, pp.cout, dy, x0->t.H, x0->t.W, tmp, false, wd));
+                WDM_TRY(conv_dgrad(cx, mode, P + pw, pp.cin, pp.cout, dy, x0->t.H, x0->t.W, tmp, false, wd));
                 bool f0, f1; WDM_TRY(grad_buf(x0, &f0)); WDM_TRY(grad_buf(x1, &f1));
                 BYT(cx.dtype, l_split_add, cx.s, tmp, x0->t.C, x1->t.C, x0->g, f0 ? 0 : 1, x1->g, f1 ? 0 : 1, (long long)cx.B * x0->t.H * x0->t.W * pp.cin);
                 cx.ar->free(tmp);
@@ -480,7 +406,8 @@ int wdm_trainer::op_conv(const ConvP& p, int mode, TT* x0, TT* x1, int temb_row,
 int wdm_trainer::op_gn_act(const NormP& p, TT* x0, TT* x1, int silu, TT** out, const Dropout* drop) {
     Ctx& cx = *c;
     const int C = x0->t.C + (x1 ? x1->t.C : 0), HW = x0->t.H * x0->t.W;
-    NormW nw; nw.g = P + p.g; nw.b = P + p.b; nw.c = C;
+    const size_t pg = off[p.g], pb = off[p.b];
+    NormW nw; nw.g = P + pg; nw.b = P + pb; nw.c = C;
     // partial statistics: taken from the producing conv's epilogue when the tensor carries them, else one pass over the tensor
     const int ns = gn_default_nslab(HW);
     const bool own0 = x0->t.stats == nullptr, own1 = x1 && x1->t.stats == nullptr;
@@ -503,18 +430,17 @@ int wdm_trainer::op_gn_act(const NormP& p, TT* x0, TT* x1, int silu, TT** out, c
     if (own1) cx.ar->free(st1);
     if (own0) cx.ar->free(st0);
     *out = o;
-    const NormP pp = p;
     const bool has_drop = drop != nullptr;
     const Dropout dd = drop ? *drop : Dropout{};
-    tape_rng.push_back({(long long)std::min(pp.g, pp.b), (long long)std::max(pp.g, pp.b) + C});
-    tape.push_back([this, pp, x0, x1, silu, o, mr, C, has_drop, dd]() -> int {
+    tape_rng.push_back({(long long)std::min(pg, pb), (long long)std::max(pg, pb) + C});
+    tape.push_back([this, pg, pb, x0, x1, silu, o, mr, C, has_drop, dd]() -> int {
         Ctx& cx = *c;
         if (!o->g) WDM_FAIL(WDM_ESTATE, "backward: GroupNorm output without gradient");
-        NormW nw; nw.g = P + pp.g; nw.b = P + pp.b; nw.c = C;
+        NormW nw; nw.g = P + pg; nw.b = P + pb; nw.c = C;
         bool f0 = true, f1 = true;
         WDM_TRY(grad_buf(x0, &f0));
         if (x1) WDM_TRY(grad_buf(x1, &f1));
-        return gn_act_backward(cx, nw, x0->t, x1 ? &x1->t : nullptr, mr, gtens(o), silu, x0->g, !f0, x1 ? x1->g : nullptr, !f1, G + pp.g, G + pp.b, false,
+        return gn_act_backward(cx, nw, x0->t, x1 ? &x1->t : nullptr, mr, gtens(o), silu, x0->g, !f0, x1 ? x1->g : nullptr, !f1, G + pg, G + pb, false,
                                has_drop ? &dd : nullptr);
     });
     return WDM_OK;
@@ -598,6 +524,12 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
     c = &cc;
     acts.clear(); tape.clear(); tape_rng.clear();
     const int nres = cfg.n_levels, nrb = cfg.num_res_blocks, R = cfg.resolution, B = cc.B;
+    const int temb_ch = L.temb_ch, temb_rows = L.temb_rows;
+    const size_t d0w = off[L.d0w], d0b = off[L.d0b], d1w = off[L.d1w], d1b = off[L.d1b];
+    const auto &down_res = L.down_res, &up_res = L.up_res;
+    const auto &down_attn = L.down_attn, &up_attn = L.up_attn;
+    const ConvP& conv_out = L.conv_out;
+    const size_t cout_w = off[conv_out.w], cout_b = off[conv_out.b];
     const size_t es = dsize(cc.dtype);
     auto af = [&](size_t n) -> float* { return (float*)cc.ar->alloc(n * 4); };
     // ---- temb MLP (fp32), values kept for the backward pass
@@ -607,9 +539,9 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
     if (!emb || !pre0 || !t0 || !t1 || !s1 || !temb_all || !d_temb_all) WDM_FAIL(WDM_ENOMEM, "training workspace too small (temb)");
     WDM_TRY(k_timestep_embedding(t, B, cfg.ch, emb, cc.s));
     WDM_TRY(k_linear(emb, B, cfg.ch, P + d0w, P + d0b, temb_ch, pre0, 0, cc.s));
-    hipLaunchKernelGGL(silu_f32_kernel, dim3(nbu((long long)B * temb_ch, 256)), dim3(256), 0, cc.s, pre0, t0, (long long)B * temb_ch);
+    hipLaunchKernelGGL(silu_f32_kernel, dim3(ceil_div((long long)B * temb_ch, 256)), dim3(256), 0, cc.s, pre0, t0, (long long)B * temb_ch);
     WDM_TRY(k_linear(t0, B, temb_ch, P + d1w, P + d1b, temb_ch, t1, 0, cc.s));
-    hipLaunchKernelGGL(silu_f32_kernel, dim3(nbu((long long)B * temb_ch, 256)), dim3(256), 0, cc.s, t1, s1, (long long)B * temb_ch);
+    hipLaunchKernelGGL(silu_f32_kernel, dim3(ceil_div((long long)B * temb_ch, 256)), dim3(256), 0, cc.s, t1, s1, (long long)B * temb_ch);
     WDM_TRY(k_linear(s1, B, temb_ch, P + tw, P + tb, temb_rows, temb_all, 0, cc.s));
     WDM_HIP(hipMemsetAsync(d_temb_all, 0, (size_t)B * temb_rows * 4, cc.s));
     // ---- forward and dgrad weight layouts of all convs (the parameters changed in the last optimiser step): a dozen launches for ~90 layers
@@ -617,18 +549,18 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
     {
         size_t bytes = 0;
         auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        for (const ConvP& q : conv_list) bytes += up(conv_packed_bytes(q.cin, q.cout, q.k, cc.dtype)) + up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
+        for (const ConvP& q : L.convs) bytes += up(conv_packed_bytes(q.cin, q.cout, q.k, cc.dtype)) + up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
         pack_region = (char*)cc.ar->alloc(bytes);
         if (!pack_region) WDM_FAIL(WDM_ENOMEM, "training workspace too small (packed weights)");
-        packed.clear();
+        packed.assign(L.convs.size(), {nullptr, nullptr});
         std::vector<PackDesc> d3, d1;
-        size_t off = 0;
-        for (const ConvP& q : conv_list) {
+        size_t at = 0;
+        for (const ConvP& q : L.convs) {
             PackDesc d{};
-            d.w = P + q.w; d.cout = q.cout; d.cin = q.cin; d.rows_total = conv_rows_pad(q.cout);
-            d.dstf = pack_region + off; off += up(conv_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
-            d.dstd = pack_region + off; off += up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
-            packed[q.w] = {d.dstf, d.dstd};
+            d.w = P + off[q.w]; d.cout = q.cout; d.cin = q.cin; d.rows_total = conv_rows_pad(q.cout);
+            d.dstf = pack_region + at; at += up(conv_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
+            d.dstd = pack_region + at; at += up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
+            packed[q.idx] = {d.dstf, d.dstd};
             (q.k == 3 ? d3 : d1).push_back(d);
         }
         if (!cc.dry) {
@@ -645,7 +577,7 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
     // ---- forward
     std::vector<TT*> hs;
     TT* h;
-    WDM_TRY(op_conv(conv_in, MODE_S1, xin, nullptr, -1, nullptr, &h));
+    WDM_TRY(op_conv(L.conv_in, MODE_S1, xin, nullptr, -1, nullptr, &h));
     hs.push_back(h);
     for (int l = 0; l < nres; ++l) {
         for (int b = 0; b < nrb; ++b) {
@@ -654,12 +586,12 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
             if (!down_attn[l].empty()) { TT* o2; WDM_TRY(op_attn(down_attn[l][b], o, &o2)); o = o2; }
             hs.push_back(o);
         }
-        if (l != nres - 1) { TT* o; WDM_TRY(op_conv(down_ds[l], MODE_S2, hs.back(), nullptr, -1, nullptr, &o)); hs.push_back(o); }
+        if (l != nres - 1) { TT* o; WDM_TRY(op_conv(L.down_ds[l], MODE_S2, hs.back(), nullptr, -1, nullptr, &o)); hs.push_back(o); }
     }
     TT *m1, *m2;
-    WDM_TRY(op_resblock(mid1, hs.back(), nullptr, &m1));
-    WDM_TRY(op_attn(mid_attn, m1, &m2));
-    WDM_TRY(op_resblock(mid2, m2, nullptr, &h));
+    WDM_TRY(op_resblock(L.mid1, hs.back(), nullptr, &m1));
+    WDM_TRY(op_attn(L.mid_attn, m1, &m2));
+    WDM_TRY(op_resblock(L.mid2, m2, nullptr, &h));
     for (int l = nres - 1; l >= 0; --l) {
         for (int b = 0; b <= nrb; ++b) {
             TT* skip = hs.back(); hs.pop_back();
@@ -668,16 +600,16 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
             h = o;
             if (!up_attn[l].empty()) { TT* o2; WDM_TRY(op_attn(up_attn[l][b], h, &o2)); h = o2; }
         }
-        if (l != 0) { TT* o; WDM_TRY(op_conv(up_us[l], MODE_UPS, h, nullptr, -1, nullptr, &o)); h = o; }
+        if (l != 0) { TT* o; WDM_TRY(op_conv(L.up_us[l], MODE_UPS, h, nullptr, -1, nullptr, &o)); h = o; }
     }
     TT* an;
-    WDM_TRY(op_gn_act(norm_out, h, nullptr, 1, &an));
+    WDM_TRY(op_gn_act(L.norm_out, h, nullptr, 1, &an));
     // conv_out in fp32 NHWC for the loss
     float* outf = af((size_t)B * R * R * pc);
     if (!outf) WDM_FAIL(WDM_ENOMEM, "training workspace too small (output)");
     {
-        ConvW w; w.cin = conv_out.cin; w.cout = pc; w.k = 3; w.rows_pad = conv_rows_pad(pc); w.b = P + conv_out.b;
-        w.w = packed.at(conv_out.w).first;
+        ConvW w; w.cin = conv_out.cin; w.cout = pc; w.k = 3; w.rows_pad = conv_rows_pad(pc); w.b = P + cout_b;
+        w.w = packed[conv_out.idx].first;
         Tens dummy;
         WDM_TRY(run_conv(cc, w, MODE_S1, {.x0 = &an->t, .y_mode = Y_NHWC_F32, .y_ext = outf}, &dummy));
     }
@@ -693,10 +625,10 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
     // ---- backward: conv_out by hand, then the tape in reverse
     {
         Tens dy; dy.p = dout; dy.C = pc; dy.H = R; dy.W = R; dy.xs = pc;
-        WDM_TRY(colsum(cc, dy, G + conv_out.b, false, false));
-        WDM_TRY(conv_wgrad(cc, MODE_S1, an->t, nullptr, dy, pc, G + conv_out.w, false));
+        WDM_TRY(colsum(cc, dy, G + cout_b, false, false));
+        WDM_TRY(conv_wgrad(cc, MODE_S1, an->t, nullptr, dy, pc, G + cout_w, false));
         bool f; WDM_TRY(grad_buf(an, &f));
-        WDM_TRY(conv_dgrad(cc, MODE_S1, P + conv_out.w, conv_out.cin, pc, dy, R, R, an->g, false, packed.at(conv_out.w).second));
+        WDM_TRY(conv_dgrad(cc, MODE_S1, P + cout_w, conv_out.cin, pc, dy, R, R, an->g, false, packed[conv_out.idx].second));
     }
     // The tape runs in reverse; the parameters sit in the flat buffers in forward order, so the gradient buffer fills from its END.  With events set
     // (wdm_trainer_set_grad_events) the range finished so far is cut into buckets and an event is recorded behind each: the caller's all-reduce of a bucket
@@ -706,8 +638,8 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
     {
         std::vector<long long> prefix_hi(tape.size() + 1, 0);
         for (size_t i = 0; i < tape.size(); ++i) prefix_hi[i + 1] = std::max(prefix_hi[i], tape_rng[i].second);
-        long long run_lo = (long long)std::min(conv_out.w, conv_out.b);
-        const long long body_hi = (long long)std::max(conv_out.w + (size_t)pc * conv_out.cin * 9, conv_out.b + (size_t)pc);
+        long long run_lo = (long long)std::min(cout_w, cout_b);
+        const long long body_hi = (long long)std::max(cout_w + (size_t)pc * conv_out.cin * 9, cout_b + (size_t)pc);
         long long body_lo = run_lo;
         for (size_t i = 0; i < tape.size(); ++i) if (tape_rng[i].first >= 0) body_lo = std::min(body_lo, tape_rng[i].first);
         const size_t nev = gev.size();
@@ -733,17 +665,17 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
         const long long n4 = (long long)B * temb_ch;
         float *d_s1 = af(n4), *d_t1 = af(n4), *d_t0 = af(n4), *d_pre0 = af(n4), *csc = af((size_t)4 * temb_rows), *xpart = af((size_t)64 * n4);
         if (!d_s1 || !d_t1 || !d_t0 || !d_pre0 || !csc || !xpart) WDM_FAIL(WDM_ENOMEM, "training workspace too small (temb backward)");
-        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(nbu((long long)temb_rows * temb_ch, 256)), dim3(256), 0, cc.s, d_temb_all, s1, B, temb_rows, temb_ch, G + tw);
+        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_rows * temb_ch, 256)), dim3(256), 0, cc.s, d_temb_all, s1, B, temb_rows, temb_ch, G + tw);
         l_colsum_f32(cc.s, d_temb_all, temb_rows, B, G + tb, csc);
-        hipLaunchKernelGGL(lin_bwd_x_part_kernel, dim3(nbu(n4, 256), 64), dim3(256), 0, cc.s, d_temb_all, P + tw, B, temb_rows, temb_ch, xpart);
-        hipLaunchKernelGGL(lin_bwd_x_final_kernel, dim3(nbu(n4, 256)), dim3(256), 0, cc.s, xpart, n4, d_s1);
-        hipLaunchKernelGGL(silu_bwd_f32_kernel, dim3(nbu(n4, 256)), dim3(256), 0, cc.s, t1, d_s1, d_t1, n4);
-        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(nbu((long long)temb_ch * temb_ch, 256)), dim3(256), 0, cc.s, d_t1, t0, B, temb_ch, temb_ch, G + d1w);
+        hipLaunchKernelGGL(lin_bwd_x_part_kernel, dim3(ceil_div(n4, 256), 64), dim3(256), 0, cc.s, d_temb_all, P + tw, B, temb_rows, temb_ch, xpart);
+        hipLaunchKernelGGL(lin_bwd_x_final_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, xpart, n4, d_s1);
+        hipLaunchKernelGGL(silu_bwd_f32_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, t1, d_s1, d_t1, n4);
+        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_ch * temb_ch, 256)), dim3(256), 0, cc.s, d_t1, t0, B, temb_ch, temb_ch, G + d1w);
         l_colsum_f32(cc.s, d_t1, temb_ch, B, G + d1b, csc);
-        hipLaunchKernelGGL(lin_bwd_x_part_kernel, dim3(nbu(n4, 256), 64), dim3(256), 0, cc.s, d_t1, P + d1w, B, temb_ch, temb_ch, xpart);
-        hipLaunchKernelGGL(lin_bwd_x_final_kernel, dim3(nbu(n4, 256)), dim3(256), 0, cc.s, xpart, n4, d_t0);
-        hipLaunchKernelGGL(silu_bwd_f32_kernel, dim3(nbu(n4, 256)), dim3(256), 0, cc.s, pre0, d_t0, d_pre0, n4);
-        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(nbu((long long)temb_ch * cfg.ch, 256)), dim3(256), 0, cc.s, d_pre0, emb, B, temb_ch, cfg.ch, G + d0w);
+        hipLaunchKernelGGL(lin_bwd_x_part_kernel, dim3(ceil_div(n4, 256), 64), dim3(256), 0, cc.s, d_t1, P + d1w, B, temb_ch, temb_ch, xpart);
+        hipLaunchKernelGGL(lin_bwd_x_final_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, xpart, n4, d_t0);
+        hipLaunchKernelGGL(silu_bwd_f32_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, pre0, d_t0, d_pre0, n4);
+        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_ch * cfg.ch, 256)), dim3(256), 0, cc.s, d_pre0, emb, B, temb_ch, cfg.ch, G + d0w);
         l_colsum_f32(cc.s, d_pre0, temb_ch, B, G + d0b, csc);
         WDM_HIP(hipGetLastError());
     }
@@ -769,15 +701,11 @@ int wdm_trainer_create(wdm_handle* h, const wdm_unet_config* cfg, wdm_trainer** 
     return WDM_OK;
 }
 int wdm_trainer_destroy(wdm_trainer* t) { delete t; return WDM_OK; }
-int wdm_trainer_num_params(const wdm_trainer* t) { return t ? (int)t->params.size() : 0; }
+int wdm_trainer_num_params(const wdm_trainer* t) { return t ? (int)t->L.params.size() : 0; }
 int64_t wdm_trainer_num_floats(const wdm_trainer* t) { return t ? (int64_t)t->nfloats : 0; }
 int wdm_trainer_param_info(const wdm_trainer* t, int i, const char** name, int* ndim, int64_t shape[4], int64_t* offset) {
-    if (!t || i < 0 || i >= (int)t->params.size()) WDM_FAIL(WDM_EINVAL, "wdm_trainer_param_info: index out of range");
-    const PInfo& p = t->params[i];
-    if (name) *name = p.name.c_str();
-    if (ndim) *ndim = p.ndim;
-    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
-    if (offset) *offset = (int64_t)p.off;
+    if (!t || !param_info(t->L.params, i, name, ndim, shape)) WDM_FAIL(WDM_EINVAL, "wdm_trainer_param_info: index out of range");
+    if (offset) *offset = (int64_t)t->off[i];
     return WDM_OK;
 }
 int wdm_trainer_set_buffers(wdm_trainer* t, float* params, float* grads, float* m, float* v, float* ema) {

@@ -18,10 +18,8 @@ namespace {
 
 enum ParamKind { PK_CONV, PK_F32 };
 
+// where a parameter of the layout lands in the packed buffer (wdm_unet::slots, parallel to the layout's parameter list)
 struct ParamSlot {
-    std::string name;
-    int ndim = 0;
-    int64_t shape[4] = {0, 0, 0, 0};
     ParamKind kind = PK_F32;
     size_t off = 0;       // byte offset of the destination matrix / vector in the packed buffer
     int rows_total = 0;   // PK_CONV: rows of the destination matrix (fused qk: 2C)
@@ -32,13 +30,11 @@ struct ParamSlot {
     size_t up4_off = 0;      // PK_CONV of an Upsample conv (bf16): second destination, the 16 sub-pixel taps (k_pack_up4); 0 = none
     bool loaded = false;
     int fold = -1, fold_role = -1;   // tensor of an AttnBlock whose folded operands are rebuilt when it is loaded (16-bit modes): index into wdm_unet::folds, FR_* role
-    int64_t numel() const { int64_t n = 1; for (int i = 0; i < ndim; ++i) n *= shape[i]; return n; }
 };
+inline ParamSlot slot_at(ParamKind kind, size_t off, int rows_total = 0, int row_off = 0) { ParamSlot s; s.kind = kind; s.off = off; s.rows_total = rows_total; s.row_off = row_off; return s; }
 
+// a conv's operands in the packed buffer (wdm_unet::convd, parallel to the layout's conv list; q and k of an AttnBlock share the fused [2C][C] matrix)
 struct ConvD { size_t w_off, b_off; int cin, cout, k, rows_pad; size_t up4_off, sm_off; };
-struct NormD { size_t g_off, b_off; int c; };
-struct ResD { int cin, cout; NormD n1, n2; ConvD c1, c2, nin; bool has_nin; int temb_row; };
-struct AttnD { int c; NormD n; ConvD qk, v, proj, qf, pf; int fold; };
 // folded AttnBlock operands (common.h: k_attn_fold): the fp32 originals of the four matrices are kept ([Wq | Wk | Wv | Wp] at stage_off) so that any one tensor can be
 // reloaded; the biases' fp32 copies are the ones the unfolded convs use
 enum { FR_QW = 0, FR_KW, FR_VW, FR_PW, FR_QB, FR_VB, FR_PB, FR_N };
@@ -47,9 +43,15 @@ struct FoldD { int c; size_t stage_off; ConvD qk, v, proj, qf, pf; int slot[FR_N
 }  // namespace
 
 struct wdm_unet {
+    using Conv = UNetLayout::Conv;
+    using Norm = UNetLayout::Norm;
+    using Res = UNetLayout::Res;
+    using Attn = UNetLayout::Attn;
     wdm_handle* h;
     wdm_unet_config cfg;
-    std::vector<ParamSlot> params;
+    UNetLayout L;                   // the network; L.params also lists the temb_proj tail (weight, bias per layer)
+    std::vector<ParamSlot> slots;   // per parameter
+    std::vector<ConvD> convd;       // per conv
     std::map<std::string, int> index;
     size_t packed_bytes = 0;
     size_t range_flag_off = 0;      // WDM_F16 only
@@ -57,122 +59,88 @@ struct wdm_unet {
     size_t fold_tmp_floats = 0, fold_tmp_off = 0;
     char* packed = nullptr;
     bool all_loaded = false;
-    int temb_ch = 0, temb_rows = 0;   // rows of the concatenated temb_proj matrix
-    size_t temb_w_off = 0, temb_b_off = 0, d0w = 0, d0b = 0, d1w = 0, d1b = 0;
-    ConvD conv_in, conv_out;
-    NormD norm_out;
-    std::vector<std::vector<ResD>> down_res, up_res;
-    std::vector<std::vector<AttnD>> down_attn, up_attn;
-    std::vector<ConvD> down_ds, up_us;   // per level (unused entries have cin == 0)
-    ResD mid1, mid2;
-    AttnD mid_attn;
+    size_t temb_w_off = 0, temb_b_off = 0;
 
-    // ---- construction helpers
+    // ---- the packed buffer, laid out in one pass over the layout (the order of the take() calls IS the buffer's format: it is broadcast between ranks)
     size_t take(size_t bytes) { size_t o = packed_bytes; packed_bytes = align_up(packed_bytes + bytes, 256); return o; }
-    void add_param(const std::string& name, std::initializer_list<int64_t> shp, ParamKind kind, size_t off, int rows_total, int row_off) {
-        ParamSlot p;
-        p.name = name; p.kind = kind; p.off = off; p.rows_total = rows_total; p.row_off = row_off;
-        p.ndim = (int)shp.size();
-        int i = 0;
-        for (auto v : shp) p.shape[i++] = v;
-        index[name] = (int)params.size();
-        params.push_back(p);
-    }
+    void place_f32(int pi) { slots[pi] = slot_at(PK_F32, take((size_t)L.params[pi].numel() * 4)); }
     // cin_pad > cin: the kernels' K dimension is padded with zero columns (conv_in of a model whose input width is not a multiple of 32)
     // s1: the conv gets the slab-major weight copy: stride-1 convs, and since round 5 the Downsample convs of the 16-bit modes (conv_s2_kernel.h); Upsample convs
     // never read theirs (their sub-pixel taps are slab-major themselves: k_pack_up4): less to pack after every trainer sync, a smaller weight broadcast
-    ConvD add_conv(const std::string& name, int cin, int cout, int k, int cin_pad = 0, bool s1 = true) {
+    ConvD& place_conv(const Conv& c, int cin_pad = 0, bool s1 = true) {
         ConvD d{};
-        if (cin_pad <= 0) cin_pad = cin;
-        d.cin = cin_pad; d.cout = cout; d.k = k; d.rows_pad = conv_rows_pad(cout);
-        d.w_off = take(conv_packed_bytes(cin_pad, cout, k, cfg.dtype));
-        d.b_off = take((size_t)cout * 4);
-        add_param(name + ".weight", {cout, cin, k, k}, PK_CONV, d.w_off, d.rows_pad, 0);
-        params.back().cin_dst = cin_pad != cin ? cin_pad : 0;
-        if (s1 && cin_pad == cin && conv_sm_eligible(cfg.dtype, k, cin)) {
-            d.sm_off = take(conv_packed_bytes(cin, cout, k, cfg.dtype));
-            params.back().sm_off = d.sm_off;
-        }
-        add_param(name + ".bias", {cout}, PK_F32, d.b_off, 0, 0);
-        return d;
+        if (cin_pad <= 0) cin_pad = c.cin;
+        d.cin = cin_pad; d.cout = c.cout; d.k = c.k; d.rows_pad = conv_rows_pad(c.cout);
+        d.w_off = take(conv_packed_bytes(cin_pad, c.cout, c.k, cfg.dtype));
+        d.b_off = take((size_t)c.cout * 4);
+        slots[c.w] = slot_at(PK_CONV, d.w_off, d.rows_pad);
+        slots[c.w].cin_dst = cin_pad != c.cin ? cin_pad : 0;
+        if (s1 && cin_pad == c.cin && conv_sm_eligible(cfg.dtype, c.k, c.cin)) slots[c.w].sm_off = d.sm_off = take(conv_packed_bytes(c.cin, c.cout, c.k, cfg.dtype));
+        slots[c.b] = slot_at(PK_F32, d.b_off);
+        return convd[c.idx] = d;
     }
-    NormD add_norm(const std::string& name, int c) {
-        NormD d{};
-        d.c = c;
-        d.g_off = take((size_t)c * 4);
-        d.b_off = take((size_t)c * 4);
-        add_param(name + ".weight", {c}, PK_F32, d.g_off, 0, 0);
-        add_param(name + ".bias", {c}, PK_F32, d.b_off, 0, 0);
-        return d;
+    void place_norm(const Norm& n) { place_f32(n.g); place_f32(n.b); }
+    void place_res(const Res& r) {
+        place_norm(r.n1); place_conv(r.c1);
+        place_norm(r.n2); place_conv(r.c2);
+        if (r.has_nin) place_conv(r.nin);
     }
-    ResD add_res(const std::string& name, int cin, int cout, std::vector<std::pair<std::string, int>>& temb_list) {
-        ResD r{};
-        r.cin = cin; r.cout = cout;
-        r.n1 = add_norm(name + ".norm1", cin);
-        r.c1 = add_conv(name + ".conv1", cin, cout, 3);
-        r.temb_row = temb_rows;
-        temb_list.push_back({name + ".temb_proj", cout});
-        temb_rows += cout;
-        r.n2 = add_norm(name + ".norm2", cout);
-        r.c2 = add_conv(name + ".conv2", cout, cout, 3);
-        r.has_nin = cin != cout;
-        if (r.has_nin) r.nin = add_conv(name + ".nin_shortcut", cin, cout, 1);
-        return r;
-    }
-    AttnD add_attn(const std::string& name, int c) {
-        AttnD a{};
-        a.c = c;
-        a.n = add_norm(name + ".norm", c);
+    void place_attn(const Attn& a) {
+        const int c = a.c;
+        place_norm(a.n);
         // q and k are fused into one [2C][C] matrix: one pass over the normalised input produces both
         ConvD qk{};
         qk.cin = c; qk.cout = 2 * c; qk.k = 1; qk.rows_pad = conv_rows_pad(2 * c);
         qk.w_off = take(conv_packed_bytes(c, 2 * c, 1, cfg.dtype));
         qk.b_off = take((size_t)2 * c * 4);
-        add_param(name + ".q.weight", {c, c, 1, 1}, PK_CONV, qk.w_off, qk.rows_pad, 0);
-        params.back().zero_tail = false;   // the k slot below owns the rows behind q
-        add_param(name + ".q.bias", {c}, PK_F32, qk.b_off, 0, 0);
-        add_param(name + ".k.weight", {c, c, 1, 1}, PK_CONV, qk.w_off, qk.rows_pad, c);
-        add_param(name + ".k.bias", {c}, PK_F32, qk.b_off, 0, c);
-        a.qk = qk;
-        a.v = add_conv(name + ".v", c, c, 1);
-        a.proj = add_conv(name + ".proj_out", c, c, 1);
-        a.fold = -1;
+        slots[a.q.w] = slot_at(PK_CONV, qk.w_off, qk.rows_pad, 0);
+        slots[a.q.w].zero_tail = false;   // the k slot below owns the rows behind q
+        slots[a.q.b] = slot_at(PK_F32, qk.b_off, 0, 0);
+        slots[a.k.w] = slot_at(PK_CONV, qk.w_off, qk.rows_pad, c);
+        slots[a.k.b] = slot_at(PK_F32, qk.b_off, 0, c);
+        convd[a.q.idx] = convd[a.k.idx] = qk;
+        place_conv(a.v);
+        place_conv(a.proj);
         if (is_h16(cfg.dtype)) {
             // the folded operands the fused core runs on (blocks.hip: run_attn), rebuilt by wdm_unet_load_param whenever one of the seven tensors behind them arrives
             FoldD f{};
             f.c = c;
             auto plain = [&](ConvD& d) { d = ConvD{}; d.cin = c; d.cout = c; d.k = 1; d.rows_pad = conv_rows_pad(c); d.w_off = take(conv_packed_bytes(c, c, 1, cfg.dtype)); d.b_off = take((size_t)c * 4);
                                         if (c % 32 == 0) d.sm_off = take(conv_packed_bytes(c, c, 1, cfg.dtype)); };      // + the slab-major copy the fused core streams (attn_fused_kernel.h)
-            plain(a.qf); plain(a.pf);
+            plain(f.qf); plain(f.pf);
             f.stage_off = take((size_t)4 * c * c * 4);
-            f.qk = a.qk; f.v = a.v; f.proj = a.proj; f.qf = a.qf; f.pf = a.pf;
-            const char* names[FR_N] = {".q.weight", ".k.weight", ".v.weight", ".proj_out.weight", ".q.bias", ".v.bias", ".proj_out.bias"};
+            f.qk = qk; f.v = convd[a.v.idx]; f.proj = convd[a.proj.idx];
+            const int role_slot[FR_N] = {a.q.w, a.k.w, a.v.w, a.proj.w, a.q.b, a.v.b, a.proj.b};
             for (int r = 0; r < FR_N; ++r) {
-                f.slot[r] = index.at(name + names[r]);
-                params[f.slot[r]].fold = (int)folds.size();
-                params[f.slot[r]].fold_role = r;
+                f.slot[r] = role_slot[r];
+                slots[f.slot[r]].fold = (int)folds.size();
+                slots[f.slot[r]].fold_role = r;
             }
             fold_tmp_floats = std::max(fold_tmp_floats, (size_t)c * c);
-            a.fold = (int)folds.size();
             folds.push_back(f);
         }
-        return a;
     }
 
     int build();
     ConvW cw(const ConvD& d) const { ConvW w; w.w = packed + d.w_off; w.w_up4 = d.up4_off ? packed + d.up4_off : nullptr; w.w_sm = d.sm_off ? packed + d.sm_off : nullptr; w.b = (const float*)(packed + d.b_off); w.cin = d.cin; w.cout = d.cout; w.k = d.k; w.rows_pad = d.rows_pad; return w; }
-    NormW nw(const NormD& d) const { NormW n; n.g = (const float*)(packed + d.g_off); n.b = (const float*)(packed + d.b_off); n.c = d.c; return n; }
-    ResW rw(const ResD& d, const float* temb_all, int n_t) const {
+    ConvW cw(const Conv& c) const { return cw(convd[c.idx]); }
+    NormW nw(const Norm& d) const { NormW n; n.g = (const float*)(packed + slots[d.g].off); n.b = (const float*)(packed + slots[d.b].off); n.c = d.c; return n; }
+    ResW rw(const Res& d, const float* temb_all, int n_t) const {
         ResW r;
         r.cin = d.cin; r.cout = d.cout; r.n1 = nw(d.n1); r.n2 = nw(d.n2); r.c1 = cw(d.c1); r.c2 = cw(d.c2);
         r.has_nin = d.has_nin;
         if (d.has_nin) r.nin = cw(d.nin);
         r.temb = temb_all ? temb_all + d.temb_row : nullptr;
-        r.temb_ld = temb_rows;
+        r.temb_ld = L.temb_rows;
         r.temb_per_image = n_t > 1;
         return r;
     }
-    AttnW aw(const AttnD& d) const { AttnW a; a.c = d.c; a.n = nw(d.n); a.qk = cw(d.qk); a.v = cw(d.v); a.proj = cw(d.proj); if (d.fold >= 0) { a.qf = cw(d.qf); a.pf = cw(d.pf); } return a; }
+    AttnW aw(const Attn& d) const {
+        AttnW a; a.c = d.c; a.n = nw(d.n); a.qk = cw(d.q); a.v = cw(d.v); a.proj = cw(d.proj);
+        const int fold = slots[d.q.w].fold;
+        if (fold >= 0) { a.qf = cw(folds[fold].qf); a.pf = cw(folds[fold].pf); }
+        return a;
+    }
 
     int refold(const ParamSlot& p, const float* dev_src, hipStream_t s);
     int check_f16_range(const float* dev, int64_t n, const char* what, hipStream_t s, float limit = 65504.0f);
@@ -181,73 +149,43 @@ struct wdm_unet {
 };
 
 int wdm_unet::build() {
-    const int ch = cfg.ch, nres = cfg.n_levels, nrb = cfg.num_res_blocks;
-    temb_ch = ch * 4;
-    auto is_attn = [&](int res) { for (int i = 0; i < cfg.n_attn_res; ++i) if (cfg.attn_resolutions[i] == res) return true; return false; };
-    std::vector<std::pair<std::string, int>> temb_list;
-
-    d0w = take((size_t)temb_ch * ch * 4); d0b = take((size_t)temb_ch * 4);
-    add_param("temb.dense.0.weight", {temb_ch, ch}, PK_F32, d0w, 0, 0);
-    add_param("temb.dense.0.bias", {temb_ch}, PK_F32, d0b, 0, 0);
-    d1w = take((size_t)temb_ch * temb_ch * 4); d1b = take((size_t)temb_ch * 4);
-    add_param("temb.dense.1.weight", {temb_ch, temb_ch}, PK_F32, d1w, 0, 0);
-    add_param("temb.dense.1.bias", {temb_ch}, PK_F32, d1b, 0, 0);
-    conv_in = add_conv("conv_in", cfg.in_channels, ch, 3, (int)align_up((size_t)cfg.in_channels, 32));
-
-    int res = cfg.resolution;
-    int block_in = ch;
-    down_res.resize(nres); down_attn.resize(nres); down_ds.assign(nres, ConvD{});
-    up_res.resize(nres); up_attn.resize(nres); up_us.assign(nres, ConvD{});
+    const int nres = cfg.n_levels;
+    L = unet_layout(cfg);
+    slots.assign(L.params.size(), ParamSlot{});
+    convd.assign(L.convs.size(), ConvD{});
+    place_f32(L.d0w); place_f32(L.d0b); place_f32(L.d1w); place_f32(L.d1b);
+    place_conv(L.conv_in, (int)align_up((size_t)cfg.in_channels, 32));
     for (int l = 0; l < nres; ++l) {
-        block_in = ch * (l == 0 ? 1 : cfg.ch_mult[l - 1]);
-        const int block_out = ch * cfg.ch_mult[l];
-        for (int b = 0; b < nrb; ++b) {
-            down_res[l].push_back(add_res("down." + std::to_string(l) + ".block." + std::to_string(b), block_in, block_out, temb_list));
-            block_in = block_out;
-        }
-        if (is_attn(res))
-            for (int b = 0; b < nrb; ++b) down_attn[l].push_back(add_attn("down." + std::to_string(l) + ".attn." + std::to_string(b), block_out));
-        if (l != nres - 1) {
-            down_ds[l] = add_conv("down." + std::to_string(l) + ".downsample.conv", block_in, block_in, 3, 0, is_h16(cfg.dtype));      // (16-bit: conv_s2_kernel.h streams the slab-major copy)
-            res /= 2;
-        }
+        for (auto& r : L.down_res[l]) place_res(r);
+        for (auto& a : L.down_attn[l]) place_attn(a);
+        if (l != nres - 1) place_conv(L.down_ds[l], 0, is_h16(cfg.dtype));      // (16-bit: conv_s2_kernel.h streams the slab-major copy)
     }
-    mid1 = add_res("mid.block_1", block_in, block_in, temb_list);
-    mid_attn = add_attn("mid.attn_1", block_in);
-    mid2 = add_res("mid.block_2", block_in, block_in, temb_list);
+    place_res(L.mid1); place_attn(L.mid_attn); place_res(L.mid2);
     for (int l = nres - 1; l >= 0; --l) {
-        const int block_out = ch * cfg.ch_mult[l];
-        int skip_in = ch * cfg.ch_mult[l];
-        for (int b = 0; b <= nrb; ++b) {
-            if (b == nrb) skip_in = ch * (l == 0 ? 1 : cfg.ch_mult[l - 1]);
-            up_res[l].push_back(add_res("up." + std::to_string(l) + ".block." + std::to_string(b), block_in + skip_in, block_out, temb_list));
-            block_in = block_out;
-        }
-        if (is_attn(res))
-            for (int b = 0; b <= nrb; ++b) up_attn[l].push_back(add_attn("up." + std::to_string(l) + ".attn." + std::to_string(b), block_out));
+        for (auto& r : L.up_res[l]) place_res(r);
+        for (auto& a : L.up_attn[l]) place_attn(a);
         if (l != 0) {
-            up_us[l] = add_conv("up." + std::to_string(l) + ".upsample.conv", block_in, block_in, 3, 0, false);
-            if ((is_h16(cfg.dtype) || cfg.dtype == WDM_F32X3) && block_in % 32 == 0 && block_in >= 128) {       // sub-pixel taps for conv_up4_kernel.h / conv_up4x3_kernel.h, next to the 3x3 ones
-                up_us[l].up4_off = take((size_t)16 * up_us[l].rows_pad * block_in * dsize(cfg.dtype));
-                params[index["up." + std::to_string(l) + ".upsample.conv.weight"]].up4_off = up_us[l].up4_off;
-            }
-            res *= 2;
+            const Conv& us = L.up_us[l];
+            ConvD& d = place_conv(us, 0, false);
+            if ((is_h16(cfg.dtype) || cfg.dtype == WDM_F32X3) && us.cin % 32 == 0 && us.cin >= 128)       // sub-pixel taps for conv_up4_kernel.h / conv_up4x3_kernel.h, next to the 3x3 ones
+                slots[us.w].up4_off = d.up4_off = take((size_t)16 * d.rows_pad * us.cin * dsize(cfg.dtype));
         }
     }
-    norm_out = add_norm("norm_out", block_in);
-    conv_out = add_conv("conv_out", block_in, cfg.out_ch, 3);
+    place_norm(L.norm_out);
+    place_conv(L.conv_out);
 
     // all temb_proj Linear layers concatenated into one [sum(cout)][temb_ch] fp32 matrix: one GEMV launch per step
     if (fold_tmp_floats) fold_tmp_off = take(fold_tmp_floats * 4);      // one C x C fp32 product of the AttnBlock folding, before it is packed
     if (cfg.dtype == WDM_F16) range_flag_off = take(256);      // device int the weight loader's fp16 range check writes (wdm_unet_load_param)
-    temb_w_off = take((size_t)temb_rows * temb_ch * 4);
-    temb_b_off = take((size_t)temb_rows * 4);
+    temb_w_off = take((size_t)L.temb_rows * L.temb_ch * 4);
+    temb_b_off = take((size_t)L.temb_rows * 4);
     int row = 0;
-    for (auto& e : temb_list) {
-        add_param(e.first + ".weight", {e.second, temb_ch}, PK_F32, temb_w_off, 0, row * temb_ch);
-        add_param(e.first + ".bias", {e.second}, PK_F32, temb_b_off, 0, row);
-        row += e.second;
+    for (auto& e : L.temb_proj) {
+        L.params.push_back(L.temb_proj_weight(e)); slots.push_back(slot_at(PK_F32, temb_w_off, 0, row * L.temb_ch));
+        L.params.push_back(L.temb_proj_bias(e)); slots.push_back(slot_at(PK_F32, temb_b_off, 0, row));
+        row += e.cout;
     }
+    for (size_t i = 0; i < L.params.size(); ++i) index[L.params[i].name] = (int)i;
     return WDM_OK;
 }
 
@@ -272,7 +210,7 @@ int wdm_unet::refold(const ParamSlot& p, const float* dev_src, hipStream_t s) {
     float* stage = (float*)(packed + f.stage_off);
     if (p.fold_role <= FR_PW) WDM_TRY(k_copy_f32(dev_src, stage + p.fold_role * cc, (long long)cc, s));
     const bool qk_side = p.fold_role == FR_QW || p.fold_role == FR_KW || p.fold_role == FR_QB;
-    auto have = [&](std::initializer_list<int> roles) { for (int r : roles) if (!params[f.slot[r]].loaded) return false; return true; };
+    auto have = [&](std::initializer_list<int> roles) { for (int r : roles) if (!slots[f.slot[r]].loaded) return false; return true; };
     float* tmp = (float*)(packed + fold_tmp_off);
     const ConvD& dst = qk_side ? f.qf : f.pf;
     if (qk_side) {
@@ -295,13 +233,15 @@ int wdm_unet::temb_table(Ctx& c, const float* t, int n_t, float* temb_all) {
     float *emb, *t0, *t1;
     auto af = [&](size_t n, float** p) -> int { *p = (float*)c.ar->alloc(n * 4); if (!*p) WDM_FAIL(WDM_ENOMEM, "workspace too small"); return WDM_OK; };
     WDM_TRY(af((size_t)n_t * cfg.ch, &emb));
-    WDM_TRY(af((size_t)n_t * temb_ch, &t0));
-    WDM_TRY(af((size_t)n_t * temb_ch, &t1));
+    WDM_TRY(af((size_t)n_t * L.temb_ch, &t0));
+    WDM_TRY(af((size_t)n_t * L.temb_ch, &t1));
     if (!c.dry) {
         WDM_TRY(k_timestep_embedding(t, n_t, cfg.ch, emb, c.s));
-        WDM_TRY(k_linear(emb, n_t, cfg.ch, (const float*)(packed + d0w), (const float*)(packed + d0b), temb_ch, t0, 2, c.s));
-        WDM_TRY(k_linear(t0, n_t, temb_ch, (const float*)(packed + d1w), (const float*)(packed + d1b), temb_ch, t1, 0, c.s));
-        WDM_TRY(k_linear(t1, n_t, temb_ch, (const float*)(packed + temb_w_off), (const float*)(packed + temb_b_off), temb_rows, temb_all, 1, c.s));
+        const int temb_ch = L.temb_ch;
+        auto pf = [&](int pi) { return (const float*)(packed + slots[pi].off); };
+        WDM_TRY(k_linear(emb, n_t, cfg.ch, pf(L.d0w), pf(L.d0b), temb_ch, t0, 2, c.s));
+        WDM_TRY(k_linear(t0, n_t, temb_ch, pf(L.d1w), pf(L.d1b), temb_ch, t1, 0, c.s));
+        WDM_TRY(k_linear(t1, n_t, temb_ch, (const float*)(packed + temb_w_off), (const float*)(packed + temb_b_off), L.temb_rows, temb_all, 1, c.s));
     }
     c.ar->free(emb); c.ar->free(t0); c.ar->free(t1);
     return WDM_OK;
@@ -309,12 +249,17 @@ int wdm_unet::temb_table(Ctx& c, const float* t, int n_t, float* temb_all) {
 
 int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* eps_out, const float* temb_pre) {
     const int nres = cfg.n_levels, nrb = cfg.num_res_blocks, R = cfg.resolution;
+    const auto &down_res = L.down_res, &up_res = L.up_res;
+    const auto &down_attn = L.down_attn, &up_attn = L.up_attn;
+    const Res &mid1 = L.mid1, &mid2 = L.mid2;
+    const Attn& mid_attn = L.mid_attn;
+    const int cin_pad = convd[L.conv_in.idx].cin;      // conv_in's K dimension in the packed matrix
     // ---- timestep embedding MLP + every block's temb projection (depends only on t): computed here, or taken from a table the caller made for
     // all the timesteps of a sampling run at once (temb_pre: one row, shared by the images)
     float* temb_all = nullptr;
     if (temb_pre) { temb_all = const_cast<float*>(temb_pre); n_t = 1; }
     else {
-        temb_all = (float*)c.ar->alloc((size_t)n_t * temb_rows * 4);
+        temb_all = (float*)c.ar->alloc((size_t)n_t * L.temb_rows * 4);
         if (!temb_all) WDM_FAIL(WDM_ENOMEM, "workspace too small");
         WDM_TRY(temb_table(c, t, n_t, temb_all));
     }
@@ -322,15 +267,15 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
     Tens x;
     x.p = (void*)x96; x.C = cfg.in_channels; x.H = R; x.W = R; x.xs = cfg.in_channels;
     void* xpad = nullptr;
-    if (conv_in.cin != cfg.in_channels) {      // input width not a multiple of the K slab: zero-padded copy (the weights carry zero columns)
-        xpad = c.ar->alloc((size_t)c.B * R * R * conv_in.cin * dsize(c.dtype));
+    if (cin_pad != cfg.in_channels) {      // input width not a multiple of the K slab: zero-padded copy (the weights carry zero columns)
+        xpad = c.ar->alloc((size_t)c.B * R * R * cin_pad * dsize(c.dtype));
         if (!xpad) WDM_FAIL(WDM_ENOMEM, "workspace too small (padded input)");
-        if (!c.dry) WDM_TRY(k_pad_channels(x96, cfg.in_channels, conv_in.cin, xpad, (long long)c.B * R * R, c.dtype, c.s));
-        x.p = xpad; x.C = conv_in.cin; x.xs = conv_in.cin;
+        if (!c.dry) WDM_TRY(k_pad_channels(x96, cfg.in_channels, cin_pad, xpad, (long long)c.B * R * R, c.dtype, c.s));
+        x.p = xpad; x.C = cin_pad; x.xs = cin_pad;
     }
     std::vector<Tens> hs;
     Tens h;
-    WDM_TRY(run_conv(c, cw(conv_in), MODE_S1, {.x0 = &x, .stats = true}, &h));
+    WDM_TRY(run_conv(c, cw(L.conv_in), MODE_S1, {.x0 = &x, .stats = true}, &h));
     if (xpad) c.ar->free(xpad);
     hs.push_back(h);
     for (int l = 0; l < nres; ++l) {
@@ -356,7 +301,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
         }
         if (l != nres - 1) {
             Tens o;
-            WDM_TRY(run_conv(c, cw(down_ds[l]), MODE_S2, {.x0 = &hs.back(), .stats = true}, &o));
+            WDM_TRY(run_conv(c, cw(L.down_ds[l]), MODE_S2, {.x0 = &hs.back(), .stats = true}, &o));
             hs.push_back(o);
         }
     }
@@ -389,7 +334,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
         }
         if (l != 0) {
             Tens o;
-            WDM_TRY(run_conv(c, cw(up_us[l]), MODE_UPS, {.x0 = &h, .stats = true}, &o));
+            WDM_TRY(run_conv(c, cw(L.up_us[l]), MODE_UPS, {.x0 = &h, .stats = true}, &o));
             free_tens(c, h);
             h = o;
         }
@@ -397,9 +342,9 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
     // ---- norm_out -> SiLU -> conv_out, written as NCHW fp32 (the reference's output layout)
     {
         float *sc, *sh;
-        WDM_TRY(run_gn(c, nw(norm_out), h, nullptr, 1, &sc, &sh));
+        WDM_TRY(run_gn(c, nw(L.norm_out), h, nullptr, 1, &sc, &sh));
         Tens dummy;
-        WDM_TRY(run_conv(c, cw(conv_out), MODE_S1, {.x0 = &h, .scale = sc, .shift = sh, .y_mode = Y_NCHW_F32, .y_ext = eps_out}, &dummy));
+        WDM_TRY(run_conv(c, cw(L.conv_out), MODE_S1, {.x0 = &h, .scale = sc, .shift = sh, .y_mode = Y_NCHW_F32, .y_ext = eps_out}, &dummy));
         c.ar->free(sc); c.ar->free(sh);
     }
     free_tens(c, h);
@@ -447,13 +392,9 @@ int wdm_unet_create(wdm_handle* h, const wdm_unet_config* cfg, wdm_unet** out) {
     return WDM_OK;
 }
 int wdm_unet_destroy(wdm_unet* u) { delete u; return WDM_OK; }
-int wdm_unet_num_params(const wdm_unet* u) { return u ? (int)u->params.size() : 0; }
+int wdm_unet_num_params(const wdm_unet* u) { return u ? (int)u->L.params.size() : 0; }
 int wdm_unet_param_info(const wdm_unet* u, int i, const char** name, int* ndim, int64_t shape[4]) {
-    if (!u || i < 0 || i >= (int)u->params.size()) WDM_FAIL(WDM_EINVAL, "wdm_unet_param_info: index %d out of range", i);
-    const ParamSlot& p = u->params[i];
-    if (name) *name = p.name.c_str();
-    if (ndim) *ndim = p.ndim;
-    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
+    if (!u || !param_info(u->L.params, i, name, ndim, shape)) WDM_FAIL(WDM_EINVAL, "wdm_unet_param_info: index %d out of range", i);
     return WDM_OK;
 }
 size_t wdm_unet_packed_bytes(const wdm_unet* u) { return u ? u->packed_bytes : 0; }
@@ -462,7 +403,7 @@ int wdm_unet_set_packed(wdm_unet* u, void* packed, size_t bytes) {
     if (bytes < u->packed_bytes) WDM_FAIL(WDM_ENOMEM, "wdm_unet_set_packed: %zu bytes given, %zu needed", bytes, u->packed_bytes);
     if (((uintptr_t)packed) & 255) WDM_FAIL(WDM_EINVAL, "wdm_unet_set_packed: buffer must be 256-byte aligned");
     u->packed = (char*)packed;
-    for (auto& p : u->params) p.loaded = false;
+    for (auto& p : u->slots) p.loaded = false;
     u->all_loaded = false;
     return WDM_OK;
 }
@@ -471,11 +412,12 @@ int wdm_unet_load_param(wdm_unet* u, const char* name, const float* dev_src, int
     if (!u->packed) WDM_FAIL(WDM_ESTATE, "wdm_unet_load_param: call wdm_unet_set_packed first");
     auto it = u->index.find(name);
     if (it == u->index.end()) WDM_FAIL(WDM_ENOTFOUND, "unknown parameter '%s'", name);
-    ParamSlot& p = u->params[it->second];
-    if (numel != p.numel()) WDM_FAIL(WDM_EINVAL, "parameter '%s': %lld elements given, %lld expected", name, (long long)numel, (long long)p.numel());
+    ParamSlot& p = u->slots[it->second];
+    const ParamDesc& desc = u->L.params[it->second];
+    if (numel != desc.numel()) WDM_FAIL(WDM_EINVAL, "parameter '%s': %lld elements given, %lld expected", name, (long long)numel, (long long)desc.numel());
     hipStream_t s = (hipStream_t)stream;
     if (p.kind == PK_CONV) {
-        const int cout = (int)p.shape[0], cin = (int)p.shape[1], k = (int)p.shape[2];
+        const int cout = (int)desc.shape[0], cin = (int)desc.shape[1], k = (int)desc.shape[2];
         // (an Upsample conv is ALSO packed as pre-summed sub-pixel taps, up to four weights each, k_pack_up4: a quarter of the range keeps every sum inside it -- ADVICE r5)
         if (u->cfg.dtype == WDM_F16) WDM_TRY(u->check_f16_range(dev_src, numel, name, s, p.up4_off ? 65504.0f / 4 : 65504.0f));
         WDM_TRY(k_pack_conv(dev_src, cout, cin, k, u->packed + p.off, p.rows_total, p.row_off, p.zero_tail ? 1 : 0, u->cfg.dtype, s, p.cin_dst));
@@ -494,13 +436,13 @@ int wdm_unet_load_param(wdm_unet* u, const char* name, const float* dev_src, int
         }
     }
     bool all = true;
-    for (auto& q : u->params) all = all && q.loaded;
+    for (auto& q : u->slots) all = all && q.loaded;
     u->all_loaded = all;
     return WDM_OK;
 }
 int wdm_unet_mark_loaded(wdm_unet* u) {
     if (!u || !u->packed) WDM_FAIL(WDM_ESTATE, "wdm_unet_mark_loaded: no packed buffer");
-    for (auto& p : u->params) p.loaded = true;
+    for (auto& p : u->slots) p.loaded = true;
     u->all_loaded = true;
     return WDM_OK;
 }
@@ -511,10 +453,10 @@ size_t wdm_unet_workspace_bytes(const wdm_unet* u, int B) {
     int rc = const_cast<wdm_unet*>(u)->forward(c, (const void*)(uintptr_t)4096, nullptr, 1, nullptr);
     // n_t = B needs B-1 more rows of temb scratch than n_t = 1: account for the larger case
     if (rc != WDM_OK) return 0;
-    const size_t extra = (size_t)(B - 1) * (u->cfg.ch + 2 * (size_t)u->temb_ch + u->temb_rows) * 4 + 4096;
+    const size_t extra = (size_t)(B - 1) * (u->cfg.ch + 2 * (size_t)u->L.temb_ch + u->L.temb_rows) * 4 + 4096;
     return ar.peak() + align_up(extra, 256);
 }
-int wdm_unet_temb_rows(const wdm_unet* u) { return u ? u->temb_rows : 0; }
+int wdm_unet_temb_rows(const wdm_unet* u) { return u ? u->L.temb_rows : 0; }
 int wdm_unet_temb_table(wdm_unet* u, const float* t, int n, float* temb_out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!u || !t || !temb_out || !workspace || n <= 0) WDM_FAIL(WDM_EINVAL, "wdm_unet_temb_table: null argument");
     if (!u->all_loaded) WDM_FAIL(WDM_ESTATE, "wdm_unet_temb_table: parameters not loaded");
