@@ -398,13 +398,20 @@ int wdm_trainer_grad_buckets(const wdm_trainer* t, int64_t* bounds, int max_boun
 /* ---- HFRM training step -------------------------------------------------------------------------------
  * Replaces the body of train_hfrm.py's loop (train_hfrm.py:240-268): HFRM forward, the back-propagated loss
  * 2 * mean|255 out - 255 target| = 510 * mean|out - target| (the perceptual terms are commented out there) and its backward, and
- * torch.optim.Adam with no EMA.  Exact fp32 only (cfg->dtype = WDM_F32), the reference's HFRM widths (dim 32, in_channel 3, <= 4 levels).
+ * torch.optim.Adam with no EMA.  cfg->dtype = WDM_F32 only (the type of the parameters and the optimizer state), the reference's HFRM widths
+ * (dim 32, in_channel 3, <= 4 levels).
  * Parameters, gradients and the Adam moments are four caller-allocated flat fp32 DEVICE buffers of wdm_hfrm_trainer_num_floats floats sharing one
  * layout: wdm_hfrm_trainer_param_info gives name, shape and float offset of every state_dict entry, in the reference's registration order.
  *   x (B, 3, H, W) NCHW f32, H and W multiples of 16; pass exactly one of target (B, 3, H, W) -- the reference loss, *loss (device float) is
  *   written -- or dy (B, 3, H, W), an upstream gradient of the output (the loss is not computed, loss may be NULL).  The step writes every entry of
  *   the gradient buffer (not accumulated); out (optional, B x 3 x H x W) receives the forward output.  Deterministic: no float atomics.
- *   wdm_hfrm_trainer_workspace_bytes: the exact workspace of a step at (B, H, W) (a dry run of the step's allocations); 0 on a bad shape. */
+ *   wdm_hfrm_trainer_workspace_bytes: the exact workspace of a step at (B, H, W) (a dry run of the step's allocations); 0 on a bad shape.  The step
+ *   checks workspace_bytes against that figure before its first launch (WDM_ENOMEM, "workspace too small").
+ *   wdm_hfrm_trainer_set_precision: the storage type of activations and activation gradients.  WDM_F32 (the state after create): exact fp32.
+ *   WDM_BF16: mixed precision -- activations, saved tensors and activation gradients in bf16 (round to nearest even), the 1x1 / downs GEMMs and their
+ *   weight gradients on the bf16 MFMA path with fp32 accumulation; parameters, gradients, Adam moments, partial sums, the loss and all other arithmetic
+ *   stay fp32, so the four buffers, their layout and wdm_hfrm_trainer_adam are the same in both modes.  No loss scaling (bf16 has fp32's exponent
+ *   range); WDM_F16 is refused for that reason, anything else is WDM_EINVAL.  Legal between steps; workspace_bytes and step follow the setting. */
 typedef struct wdm_hfrm_trainer wdm_hfrm_trainer;
 int wdm_hfrm_trainer_create(wdm_handle* h, const wdm_hfrm_config* cfg, wdm_hfrm_trainer** out);
 int wdm_hfrm_trainer_destroy(wdm_hfrm_trainer* t);
@@ -412,6 +419,7 @@ int wdm_hfrm_trainer_num_params(const wdm_hfrm_trainer* t);
 int64_t wdm_hfrm_trainer_num_floats(const wdm_hfrm_trainer* t);
 int wdm_hfrm_trainer_param_info(const wdm_hfrm_trainer* t, int i, const char** name, int* ndim, int64_t shape[4], int64_t* offset);
 int wdm_hfrm_trainer_set_buffers(wdm_hfrm_trainer* t, float* params, float* grads, float* m, float* v);
+int wdm_hfrm_trainer_set_precision(wdm_hfrm_trainer* t, int act_dtype);
 size_t wdm_hfrm_trainer_workspace_bytes(const wdm_hfrm_trainer* t, int B, int H, int W);
 int wdm_hfrm_trainer_step(wdm_hfrm_trainer* t, const float* x, const float* target, const float* dy, int B, int H, int W, float* loss, float* out,
                           void* workspace, size_t workspace_bytes, void* stream);

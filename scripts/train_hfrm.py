@@ -8,7 +8,11 @@ Reads <data_dir>/<dataset_name>/train/{input,gt} (the reference's myImageFloder 
 --epoch N > 0, from <save_dir>/<dataset_name>/best.pth, weights only) with the reference's loss 2 * mean|255 out - 255 gt|, Adam
 (b1, b2) and lr = lr * 0.5 ** (step / 100000), and writes <save_dir>/<dataset_name>/lastest.pth every epoch and best.pth whenever the
 epoch PSNR beats the best so far.  Both hold the plain state_dict.  The forward, backward and Adam run on libwavedm_hip.so
-(wavedm_amd.HFRMTrainer); there is no torch autograd and no CPU path."""
+(wavedm_amd.HFRMTrainer); there is no torch autograd and no CPU path.
+
+--dtype bf16-mixed trains with bf16 activations over the same fp32 parameters and optimizer state (the checkpoints are the same files);
+--sample_interval N writes the reference's sample_images sheet [input | prediction | target] of the batch's first image to
+<sample_dir>/%03d_%06d.png % (epoch, i) whenever i % N == 0 (the reference: N = 1000, ./train_result)."""
 import argparse
 import datetime
 import os
@@ -20,7 +24,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from wavedm_amd import datasets                                     # noqa: E402
-from wavedm_amd.hfrm_training import HFRM_DEFAULTS, HFRMTrainer     # noqa: E402
+from wavedm_amd.hfrm_training import HFRM_DEFAULTS, HFRMTrainer, sample_sheet     # noqa: E402
+from wavedm_amd.imageio import AsyncImageWriter                     # noqa: E402
 
 
 def parse_args(argv=None):
@@ -39,6 +44,10 @@ def parse_args(argv=None):
     p.add_argument("--max_steps", type=int, default=0, help="stop after this many optimizer steps (0: run all epochs)")
     p.add_argument("--best_psnr", type=float, default=31.0, help="epoch PSNR best.pth has to beat first (the reference starts at 31)")
     p.add_argument("--seed", type=int, default=0, help="seed of the conv biases' default init")
+    p.add_argument("--dtype", type=str, default="f32", choices=("f32", "bf16-mixed"),
+                   help="f32: exact fp32; bf16-mixed: bf16 activations and GEMMs over fp32 parameters, gradients and Adam state")
+    p.add_argument("--sample_interval", type=int, default=0, help="write a sample sheet every this many batches of an epoch (0: none; the reference uses 1000)")
+    p.add_argument("--sample_dir", type=str, default="train_result", help="directory of the sample sheets")
     return p.parse_args(argv)
 
 
@@ -47,7 +56,8 @@ def main(argv=None):
     print(opt)
     out_dir = os.path.join(opt.save_dir, opt.dataset_name)
     os.makedirs(out_dir, exist_ok=True)
-    trainer = HFRMTrainer(**HFRM_DEFAULTS, lr=opt.lr, betas=(opt.b1, opt.b2))
+    trainer = HFRMTrainer(**HFRM_DEFAULTS, lr=opt.lr, betas=(opt.b1, opt.b2), dtype=opt.dtype)
+    writer = AsyncImageWriter(workers=1) if opt.sample_interval > 0 else None
     print("HFRM parameters:", sum(int(np.prod(s)) for _, s in trainer.layout.values()))
     if opt.epoch != 0:
         trainer.load_state_dict(torch.load(os.path.join(out_dir, "best.pth"), map_location="cpu"), strict=True)
@@ -63,7 +73,9 @@ def main(argv=None):
         for i, (real_A, real_B) in enumerate(loader):
             real_A = real_A.to(trainer.device, non_blocking=True)
             real_B = real_B.to(trainer.device, non_blocking=True)
-            loss, psnr = trainer.train_step(real_A, real_B)
+            loss, psnr, fake_B = trainer.train_step(real_A, real_B, return_output=True)
+            if writer is not None and i % opt.sample_interval == 0:
+                writer.save_u8(sample_sheet(real_A, fake_B, real_B), os.path.join(opt.sample_dir, "%03d_%06d.png" % (epoch, i)))
             epoch_psnr.append(psnr.mean().item())
             print("PSNR this: %f", epoch_psnr[-1])
             batches_done = epoch * len(loader) + i
@@ -85,6 +97,8 @@ def main(argv=None):
         trainer.save(os.path.join(out_dir, "lastest.pth"))
         if done:
             break
+    if writer is not None:
+        writer.close()
     return 0
 
 

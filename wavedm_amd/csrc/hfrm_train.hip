@@ -1,6 +1,8 @@
 // HFRM training step (reference: train_hfrm.py:254-268 over models/arch.py:132-253): a training forward that keeps what the
 // backward needs, the backward of every layer, the reference's loss 2 * mean|255 out - 255 target| = 510 * mean|out - target|, and
-// Adam without EMA (train_unet.hip's update, k_adam_ema with no shadow) over one flat fp32 parameter / gradient / moment buffer set.  Exact fp32 only.
+// Adam without EMA (train_unet.hip's update, k_adam_ema with no shadow) over one flat fp32 parameter / gradient / moment buffer set.
+// Two precisions (wdm_hfrm_trainer_set_precision): exact fp32, or "bf16-mixed" -- activations and activation gradients stored in bf16, GEMMs on the bf16
+// MFMA path with fp32 accumulation, every parameter, gradient, moment, partial sum and all arithmetic outside the MFMAs in fp32 (see T below).
 //
 // Contractions reuse the existing primitives: every 1x1 conv (and the 2x2 stride-2 `downs`, after a space-to-depth gather) runs
 // forward AND dgrad on the MFMA conv kernel as a GEMM over the flattened pixels (MODE_P1, the path wdm_hfrm::gemm_rows drives: no
@@ -28,6 +30,15 @@ using namespace wdm;
 
 #define GS_LOOP(id, n) for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < (n); id += (long long)gridDim.x * blockDim.x)
 
+// T is the storage type of an activation or activation gradient: float (the exact mode: plain loads and stores, the code the fp32 trainer has always run) or
+// __bf16 (the mixed mode: converted to fp32 on load, rounded to nearest even on store; all arithmetic and every reduction in fp32 in the same fixed order).
+// The streaming kernels move 16 bytes per lane in the bf16 instantiation (8 channels: every channel count of the network is a multiple of 32).
+template <typename T> __device__ __forceinline__ float ldv(const T* p, long long i) { return TI<T>::ld(p, i); }
+template <typename T> __device__ __forceinline__ void stv(T* p, long long i, float v) { TI<T>::st(p, i, v); }
+template <typename T> __device__ __forceinline__ void ld8(const T* p, long long i, float* f) { TI<T>::unpack(*(const uint4*)(p + i), f); }
+template <typename T> __device__ __forceinline__ void st8(T* p, long long i, const float* f) { *(uint4*)(p + i) = TI<T>::pack(f); }
+template <typename T> constexpr bool H16 = sizeof(T) == 2;
+
 __device__ __forceinline__ float team_sum(float v) {      // sum over the 32 lanes of a half wave
 #pragma unroll
     for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o);
@@ -36,31 +47,128 @@ __device__ __forceinline__ float team_sum(float v) {      // sum over the 32 lan
 
 // ---- LayerNorm2d (arch.py:7-43), a team of 32 lanes per pixel, channel c = lane + 32 j --------------------------------
 constexpr int LN_TEAMS = 8;
-template <int NJ>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long long M, const float* __restrict__ w,
+// bf16: a lane owns 8 consecutive channels (16 bytes), a team of C / 8 lanes (at most 32; two vectors per lane at C = 512) a pixel
+template <int C> struct Ln16 { static constexpr int TEAM = C / 8 < 32 ? C / 8 : 32, NV = C / (8 * TEAM), PPB = 256 / TEAM; };
+template <int TEAM> __device__ __forceinline__ float team_sum_n(float v) {
+#pragma unroll
+    for (int o = TEAM / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+template <typename T, int NJ>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, long long M, const float* __restrict__ w,
                                                      const float* __restrict__ b) {
     constexpr int C = 32 * NJ;
+    if constexpr (H16<T>) {
+        constexpr int TEAM = Ln16<C>::TEAM, NV = Ln16<C>::NV, PPB = Ln16<C>::PPB;
+        const int tl = threadIdx.x % TEAM;
+        for (long long p = (long long)blockIdx.x * PPB + threadIdx.x / TEAM; p < M; p += (long long)gridDim.x * PPB) {
+            float f[NV][8], s = 0.f;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                ld8(x, p * C + (tl + TEAM * v) * 8, f[v]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s += f[v][e];
+            }
+            const float mu = team_sum_n<TEAM>(s) / (float)C;
+            float q = 0.f;
+#pragma unroll
+            for (int v = 0; v < NV; ++v)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float dd = f[v][e] - mu; q += dd * dd; }
+            const float rstd = 1.0f / sqrtf(team_sum_n<TEAM>(q) / (float)C + 1e-6f);
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const int c = (tl + TEAM * v) * 8;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) f[v][e] = (f[v][e] - mu) * rstd * w[c + e] + b[c + e];
+                st8(y, p * C + c, f[v]);
+            }
+        }
+        return;
+    }
     const int lane = threadIdx.x & 31;
     for (long long p = (long long)blockIdx.x * LN_TEAMS + (threadIdx.x >> 5); p < M; p += (long long)gridDim.x * LN_TEAMS) {
         float f[NJ], s = 0.f;
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) { f[j] = x[p * C + lane + 32 * j]; s += f[j]; }
+        for (int j = 0; j < NJ; ++j) { f[j] = ldv(x, p * C + lane + 32 * j); s += f[j]; }
         const float mu = team_sum(s) / (float)C;
         float q = 0.f;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) { const float dd = f[j] - mu; q += dd * dd; }
         const float rstd = 1.0f / sqrtf(team_sum(q) / (float)C + 1e-6f);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) { const int c = lane + 32 * j; y[p * C + c] = (f[j] - mu) * rstd * w[c] + b[c]; }
+        for (int j = 0; j < NJ; ++j) { const int c = lane + 32 * j; stv(y, p * C + c, (f[j] - mu) * rstd * w[c] + b[c]); }
     }
 }
 
 // LayerNormFunction.backward (arch.py:19-31): g = dn w, dx = rstd (g - xh mean(g xh) - mean(g)); dx = dres + that (dres may alias dx);
 // part[block][0][C] = sum dn xh, part[block][1][C] = sum dn over the block's pixels (teams joined in ascending order)
-template <int NJ>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dn, const float* __restrict__ w, const float* dres,
-                                                     float* dx, long long M, float* __restrict__ part) {
+template <typename T, int NJ>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dn, const float* __restrict__ w, const T* dres,
+                                                     T* dx, long long M, float* __restrict__ part) {
     constexpr int C = 32 * NJ;
+    if constexpr (H16<T>) {
+        constexpr int TEAM = Ln16<C>::TEAM, NV = Ln16<C>::NV, PPB = Ln16<C>::PPB;
+        __shared__ float red16[PPB][2][C];
+        const int tl = threadIdx.x % TEAM, tm = threadIdx.x / TEAM;
+        float aw[NV][8], ab[NV][8];
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { aw[v][e] = 0.f; ab[v][e] = 0.f; }
+        for (long long p = (long long)blockIdx.x * PPB + tm; p < M; p += (long long)gridDim.x * PPB) {
+            float f[NV][8], g[NV][8], s = 0.f;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                ld8(x, p * C + (tl + TEAM * v) * 8, f[v]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s += f[v][e];
+            }
+            const float mu = team_sum_n<TEAM>(s) / (float)C;
+            float q = 0.f;
+#pragma unroll
+            for (int v = 0; v < NV; ++v)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float dd = f[v][e] - mu; q += dd * dd; }
+            const float rstd = 1.0f / sqrtf(team_sum_n<TEAM>(q) / (float)C + 1e-6f);
+            float sg = 0.f, sgy = 0.f;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const int c = (tl + TEAM * v) * 8;
+                float d[8];
+                ld8(dn, p * C + c, d);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    f[v][e] = (f[v][e] - mu) * rstd;                      // xh
+                    g[v][e] = d[e] * w[c + e];
+                    sg += g[v][e]; sgy += g[v][e] * f[v][e];
+                    aw[v][e] += d[e] * f[v][e]; ab[v][e] += d[e];
+                }
+            }
+            const float mg = team_sum_n<TEAM>(sg) / (float)C, mgy = team_sum_n<TEAM>(sgy) / (float)C;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const long long i = p * C + (tl + TEAM * v) * 8;
+                float r[8];
+                ld8(dres, i, r);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) r[e] += rstd * (g[v][e] - f[v][e] * mgy - mg);
+                st8(dx, i, r);
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { red16[tm][0][(tl + TEAM * v) * 8 + e] = aw[v][e]; red16[tm][1][(tl + TEAM * v) * 8 + e] = ab[v][e]; }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * C; i += 256) {
+            const int k = i / C, c = i % C;
+            float s = 0.f;
+            for (int t = 0; t < PPB; ++t) s += red16[t][k][c];
+            part[(long long)blockIdx.x * 2 * C + i] = s;
+        }
+        return;
+    }
     __shared__ float red[LN_TEAMS][2][C];
     const int lane = threadIdx.x & 31, team = threadIdx.x >> 5;
     float aw[NJ], ab[NJ];
@@ -69,7 +177,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
     for (long long p = (long long)blockIdx.x * LN_TEAMS + team; p < M; p += (long long)gridDim.x * LN_TEAMS) {
         float f[NJ], g[NJ], s = 0.f;
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) { f[j] = x[p * C + lane + 32 * j]; s += f[j]; }
+        for (int j = 0; j < NJ; ++j) { f[j] = ldv(x, p * C + lane + 32 * j); s += f[j]; }
         const float mu = team_sum(s) / (float)C;
         float q = 0.f;
 #pragma unroll
@@ -79,7 +187,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int c = lane + 32 * j;
-            const float d = dn[p * C + c];
+            const float d = ldv(dn, p * C + c);
             f[j] = (f[j] - mu) * rstd;                      // xh
             g[j] = d * w[c];
             sg += g[j]; sgy += g[j] * f[j];
@@ -89,7 +197,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const long long i = p * C + lane + 32 * j;
-            dx[i] = dres[i] + rstd * (g[j] - f[j] * mgy - mg);
+            stv(dx, i, ldv(dres, i) + rstd * (g[j] - f[j] * mgy - mg));
         }
     }
 #pragma unroll
@@ -105,8 +213,43 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
 
 // ---- per-channel sums: part[(b * nk + k) * C + c] = sum over chunk k of image b of a[p][c] (* m[p][c]) ---------------------------
 // grid (nk, B, ceil(C / 256)); 256 threads = (channels) x (pixel rows); rows joined in ascending order
-__global__ __launch_bounds__(256) void chan_part_kernel(const float* __restrict__ a, const float* __restrict__ m, int C, int HW, int chunk, int nk,
+template <typename T>
+__global__ __launch_bounds__(256) void chan_part_kernel(const T* __restrict__ a, const T* __restrict__ m, int C, int HW, int chunk, int nk,
                                                         float* __restrict__ part) {
+    if constexpr (H16<T>) {      // a thread sums 8 channels of every (256 / (cols / 8))-th pixel row; the rows are then joined in ascending order
+        __shared__ float red16[256 * 8];
+        const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
+        const int cols = min(C - cb * 256, 256), colsv = cols / 8, rows = 256 / colsv;
+        const int col = threadIdx.x % colsv, r = threadIdx.x / colsv, c = cb * 256 + col * 8;
+        float s[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = 0.f;
+        if (r < rows) {
+            const int p1 = min((k + 1) * chunk, HW);
+            for (int p = k * chunk + r; p < p1; p += rows) {
+                const long long i = ((long long)b * HW + p) * C + c;
+                float f[8], g[8];
+                ld8(a, i, f);
+                if (m) {
+                    ld8(m, i, g);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s[e] += f[e] * g[e];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s[e] += f[e];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) red16[r * cols + col * 8 + e] = s[e];
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < cols) {
+            float t = 0.f;
+            for (int rr = 0; rr < rows; ++rr) t += red16[rr * cols + threadIdx.x];
+            part[((long long)b * nk + k) * C + cb * 256 + threadIdx.x] = t;
+        }
+        return;
+    }
     __shared__ float red[256];
     const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
     const int cols = min(C - cb * 256, 256), rows = 256 / cols;
@@ -116,7 +259,7 @@ __global__ __launch_bounds__(256) void chan_part_kernel(const float* __restrict_
         const int p1 = min((k + 1) * chunk, HW);
         for (int p = k * chunk + r; p < p1; p += rows) {
             const long long i = ((long long)b * HW + p) * C + c;
-            s += m ? a[i] * m[i] : a[i];
+            s += m ? ldv(a, i) * ldv(m, i) : ldv(a, i);
         }
     }
     red[threadIdx.x] = s;
@@ -145,39 +288,93 @@ __global__ __launch_bounds__(256) void chan_final_kernel(const float* __restrict
 
 // ---- elementwise ----------------------------------------------------------------------------------------------------------
 // SimpleGate (arch.py:132-141): g[p][c] = a[p][c] * a[p][d + c]  (* sc[b][c] when sc is given)
-__global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ a, float* __restrict__ g, long long n, int d, const float* __restrict__ sc, int HW) {
-    GS_LOOP(id, n) {
-        const long long p = id / d;
-        const int c = (int)(id % d);
-        float v = a[p * 2 * d + c] * a[p * 2 * d + d + c];
-        if (sc) v *= sc[(p / HW) * d + c];
-        g[id] = v;
+template <typename T>
+__global__ __launch_bounds__(256) void gate_kernel(const T* __restrict__ a, T* __restrict__ g, long long n, int d, const float* __restrict__ sc, int HW) {
+    if constexpr (H16<T>) {
+        GS_LOOP(iv, n / 8) {
+            const long long id = iv * 8, p = id / d;
+            const int c = (int)(id % d);
+            float u[8], v[8];
+            ld8(a, p * 2 * d + c, u); ld8(a, p * 2 * d + d + c, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { v[e] *= u[e]; if (sc) v[e] *= sc[(p / HW) * d + c + e]; }
+            st8(g, id, v);
+        }
+    } else {
+        GS_LOOP(id, n) {
+            const long long p = id / d;
+            const int c = (int)(id % d);
+            float v = a[p * 2 * d + c] * a[p * 2 * d + d + c];
+            if (sc) v *= sc[(p / HW) * d + c];
+            g[id] = v;
+        }
     }
 }
-__global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__ dg, const float* __restrict__ a, float* __restrict__ da, long long n, int d) {
-    GS_LOOP(id, n) {
-        const long long p = id / d;
-        const int c = (int)(id % d);
-        const float g = dg[id];
-        da[p * 2 * d + c] = g * a[p * 2 * d + d + c];
-        da[p * 2 * d + d + c] = g * a[p * 2 * d + c];
+template <typename T>
+__global__ __launch_bounds__(256) void gate_bwd_kernel(const T* __restrict__ dg, const T* __restrict__ a, T* __restrict__ da, long long n, int d) {
+    if constexpr (H16<T>) {
+        GS_LOOP(iv, n / 8) {
+            const long long id = iv * 8, p = id / d;
+            const int c = (int)(id % d);
+            float g[8], u[8], v[8];
+            ld8(dg, id, g); ld8(a, p * 2 * d + c, u); ld8(a, p * 2 * d + d + c, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float t = g[e] * v[e]; v[e] = g[e] * u[e]; u[e] = t; }
+            st8(da, p * 2 * d + c, u); st8(da, p * 2 * d + d + c, v);
+        }
+    } else {
+        GS_LOOP(id, n) {
+            const long long p = id / d;
+            const int c = (int)(id % d);
+            const float g = dg[id];
+            da[p * 2 * d + c] = g * a[p * 2 * d + d + c];
+            da[p * 2 * d + d + c] = g * a[p * 2 * d + c];
+        }
     }
 }
 // out[p][c] = x[p][c] + s[c] * v[p][c]   (x == nullptr: s[c] * v[p][c])
-__global__ __launch_bounds__(256) void axpy_chan_kernel(const float* __restrict__ x, const float* __restrict__ s, const float* __restrict__ v, float* __restrict__ out,
+template <typename T>
+__global__ __launch_bounds__(256) void axpy_chan_kernel(const T* __restrict__ x, const float* __restrict__ s, const T* __restrict__ v, T* __restrict__ out,
                                                         long long n, int C) {
-    GS_LOOP(id, n) {
-        const float t = s[id % C] * v[id];
-        out[id] = x ? x[id] + t : t;
+    if constexpr (H16<T>) {
+        GS_LOOP(iv, n / 8) {
+            const long long id = iv * 8;
+            const int c = (int)(id % C);
+            float f[8], xf[8];
+            ld8(v, id, f);
+            if (x) ld8(x, id, xf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float t = s[c + e] * f[e]; f[e] = x ? xf[e] + t : t; }
+            st8(out, id, f);
+        }
+    } else {
+        GS_LOOP(id, n) {
+            const float t = s[id % C] * v[id];
+            out[id] = x ? x[id] + t : t;
+        }
     }
 }
 // channel attention backward, pixel side: dg = dgs * sc[b][c] + dpool[b][c] / HW (in place)
-__global__ __launch_bounds__(256) void ca_dg_kernel(float* __restrict__ dg, const float* __restrict__ sc, const float* __restrict__ dpool, long long n, int d, int HW,
+template <typename T>
+__global__ __launch_bounds__(256) void ca_dg_kernel(T* __restrict__ dg, const float* __restrict__ sc, const float* __restrict__ dpool, long long n, int d, int HW,
                                                     float inv_hw) {
-    GS_LOOP(id, n) {
-        const int c = (int)(id % d);
-        const long long b = id / d / HW;
-        dg[id] = dg[id] * sc[b * d + c] + dpool[b * d + c] * inv_hw;
+    if constexpr (H16<T>) {
+        GS_LOOP(iv, n / 8) {
+            const long long id = iv * 8;
+            const int c = (int)(id % d);
+            const long long b = id / d / HW;
+            float f[8];
+            ld8(dg, id, f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = f[e] * sc[b * d + c + e] + dpool[b * d + c + e] * inv_hw;
+            st8(dg, id, f);
+        }
+    } else {
+        GS_LOOP(id, n) {
+            const int c = (int)(id % d);
+            const long long b = id / d / HW;
+            dg[id] = dg[id] * sc[b * d + c] + dpool[b * d + c] * inv_hw;
+        }
     }
 }
 // channel attention backward, vector side (sc = W pooled + bias, B x d): dW[o][i] = sum_b dsc[b][o] pooled[b][i], db[o] = sum_b dsc[b][o],
@@ -206,8 +403,31 @@ __global__ __launch_bounds__(256) void ca_bwd_kernel(const float* __restrict__ d
 }
 
 // ---- depthwise 3x3, pad 1, on C channels (ResidualBlock.conv2, groups = 2d): forward, dgrad, wgrad ---------------------------
-__global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W, int C, long long n, const float* __restrict__ w,
+template <typename T>
+__global__ __launch_bounds__(256) void dw_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int H, int W, int C, long long n, const float* __restrict__ w,
                                                      const float* __restrict__ bias) {
+    if constexpr (H16<T>) {
+        GS_LOOP(iv, n / 8) {
+            const long long id = iv * 8;
+            const int c = (int)(id % C);
+            const long long p = id / C;
+            const int px = (int)(p % W), py = (int)((p / W) % H);
+            const long long img = p - (long long)py * W - px;
+            float s[8], f[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] = bias[c + e];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                    ld8(x, (img + (long long)yy * W + xx) * C + c, f);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s[e] += f[e] * w[(c + e) * 9 + t];
+                }
+            }
+            st8(y, id, s);
+        }
+    } else
     GS_LOOP(id, n) {
         const int c = (int)(id % C);
         const long long p = id / C;
@@ -223,7 +443,30 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ x
     }
 }
 // dx[q][c] = sum_t w[c][t] dy[q - (t / 3 - 1, t % 3 - 1)][c]
-__global__ __launch_bounds__(256) void dw_dgrad_kernel(const float* __restrict__ dy, float* __restrict__ dx, int H, int W, int C, long long n, const float* __restrict__ w) {
+template <typename T>
+__global__ __launch_bounds__(256) void dw_dgrad_kernel(const T* __restrict__ dy, T* __restrict__ dx, int H, int W, int C, long long n, const float* __restrict__ w) {
+    if constexpr (H16<T>) {
+        GS_LOOP(iv, n / 8) {
+            const long long id = iv * 8;
+            const int c = (int)(id % C);
+            const long long p = id / C;
+            const int px = (int)(p % W), py = (int)((p / W) % H);
+            const long long img = p - (long long)py * W - px;
+            float s[8], f[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] = 0.f;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = py - (t / 3 - 1), xx = px - (t % 3 - 1);
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                    ld8(dy, (img + (long long)yy * W + xx) * C + c, f);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s[e] += f[e] * w[(c + e) * 9 + t];
+                }
+            }
+            st8(dx, id, s);
+        }
+    } else
     GS_LOOP(id, n) {
         const int c = (int)(id % C);
         const long long p = id / C;
@@ -239,8 +482,59 @@ __global__ __launch_bounds__(256) void dw_dgrad_kernel(const float* __restrict__
     }
 }
 // part[(b * nk + k)][c][10]: sum over chunk k of image b of dy[p][c] x[p + tap][c] (taps 0..8) and of dy[p][c] (slot 9)
-__global__ __launch_bounds__(256) void dw_wgrad_part_kernel(const float* __restrict__ dy, const float* __restrict__ x, int H, int W, int C, int chunk, int nk,
+template <typename T>
+__global__ __launch_bounds__(256) void dw_wgrad_part_kernel(const T* __restrict__ dy, const T* __restrict__ x, int H, int W, int C, int chunk, int nk,
                                                             float* __restrict__ part) {
+    if constexpr (H16<T>) {      // a thread holds the ten sums of 8 channels; the pixel rows are joined through LDS five slots at a time, in ascending order
+        __shared__ float red16[256 * 8 * 5];
+        const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
+        const int HW = H * W;
+        const int cols = min(C - cb * 256, 256), colsv = cols / 8, rows = 256 / colsv;
+        const int col = threadIdx.x % colsv, r = threadIdx.x / colsv, c = cb * 256 + col * 8;
+        float acc[10][8];
+#pragma unroll
+        for (int t = 0; t < 10; ++t)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[t][e] = 0.f;
+        if (r < rows) {
+            const long long img = (long long)b * HW;
+            const int p1 = min((k + 1) * chunk, HW);
+            for (int p = k * chunk + r; p < p1; p += rows) {
+                const int py = p / W, px = p - py * W;
+                float g[8], f[8];
+                ld8(dy, (img + p) * C + c, g);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[9][e] += g[e];
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+                    if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                        ld8(x, (img + (long long)yy * W + xx) * C + c, f);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) acc[t][e] += g[e] * f[e];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            if (half) __syncthreads();
+            if (r < rows) {
+#pragma unroll
+                for (int t = 0; t < 5; ++t)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) red16[(r * 5 + t) * cols + col * 8 + e] = acc[half * 5 + t][e];
+            }
+            __syncthreads();
+            for (int o = threadIdx.x; o < 5 * cols; o += 256) {
+                const int t = o / cols, ch = o % cols;
+                float sum = 0.f;
+                for (int rr = 0; rr < rows; ++rr) sum += red16[(rr * 5 + t) * cols + ch];
+                part[(((long long)b * nk + k) * C + cb * 256 + ch) * 10 + half * 5 + t] = sum;
+            }
+        }
+        return;
+    }
     __shared__ float red[256 * 10];
     const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
     const int HW = H * W;
@@ -254,12 +548,12 @@ __global__ __launch_bounds__(256) void dw_wgrad_part_kernel(const float* __restr
         const int p1 = min((k + 1) * chunk, HW);
         for (int p = k * chunk + r; p < p1; p += rows) {
             const int py = p / W, px = p - py * W;
-            const float g = dy[(img + p) * C + c];
+            const float g = ldv(dy, (img + p) * C + c);
             acc[9] += g;
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) acc[t] += g * x[(img + (long long)yy * W + xx) * C + c];
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) acc[t] += g * ldv(x, (img + (long long)yy * W + xx) * C + c);
             }
         }
     }
@@ -286,9 +580,30 @@ __global__ __launch_bounds__(256) void dw_wgrad_final_kernel(const float* __rest
 
 // ---- 2x2 stride-2 conv (downs) and PixelShuffle(2) (ups) --------------------------------------------------------------------
 // space-to-depth: u[b][y][x][(i*2+j)*d + c] = x[b][2y+i][2x+j][c]; add != 0: the adjoint, x[...] += u[...]
-__global__ __launch_bounds__(256) void unshuffle2_kernel(float* __restrict__ x, float* __restrict__ u, int B, int H, int W, int d, int add) {
+template <typename T>
+__global__ __launch_bounds__(256) void unshuffle2_kernel(T* __restrict__ x, T* __restrict__ u, int B, int H, int W, int d, int add) {
     const int h2 = H / 2, w2 = W / 2;
     const long long n = (long long)B * h2 * w2 * 4 * d;
+    if constexpr (H16<T>) {
+        GS_LOOP(iv, n / 8) {
+            const long long id = iv * 8;
+            const int c = (int)(id % d);
+            const int ij = (int)((id / d) % 4);
+            const long long op = id / (4 * d);
+            const int ox = (int)(op % w2), oy = (int)((op / w2) % h2);
+            const long long b = op / ((long long)w2 * h2);
+            const long long xi = ((b * H + 2 * oy + (ij >> 1)) * W + 2 * ox + (ij & 1)) * d + c;
+            float f[8], g[8];
+            if (add) {
+                ld8(x, xi, f); ld8(u, id, g);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) f[e] += g[e];
+                st8(x, xi, f);
+            } else {
+                *(uint4*)(u + id) = *(const uint4*)(x + xi);
+            }
+        }
+    } else
     GS_LOOP(id, n) {
         const int c = (int)(id % d);
         const int ij = (int)((id / d) % 4);
@@ -301,7 +616,8 @@ __global__ __launch_bounds__(256) void unshuffle2_kernel(float* __restrict__ x, 
     }
 }
 // forward: out[b][2y+i][2x+j][c] = p[b][y][x][c*4 + i*2 + j] + skip[...];  adjoint: dp[b][y][x][c*4 + i*2 + j] = dout[b][2y+i][2x+j][c]
-__global__ __launch_bounds__(256) void pixel_shuffle_kernel(const float* __restrict__ p, const float* __restrict__ skip, float* __restrict__ out, int B, int h, int w,
+template <typename T>
+__global__ __launch_bounds__(256) void pixel_shuffle_kernel(const T* __restrict__ p, const T* __restrict__ skip, T* __restrict__ out, int B, int h, int w,
                                                             int dout) {
     const long long n = (long long)B * 4 * h * w * dout;
     GS_LOOP(id, n) {
@@ -309,10 +625,11 @@ __global__ __launch_bounds__(256) void pixel_shuffle_kernel(const float* __restr
         const long long op = id / dout;
         const int X = (int)(op % (2 * w)), Y = (int)((op / (2 * w)) % (2 * h));
         const long long b = op / ((long long)4 * w * h);
-        out[id] = p[((b * h + (Y >> 1)) * w + (X >> 1)) * (4LL * dout) + c * 4 + (Y & 1) * 2 + (X & 1)] + skip[id];
+        stv(out, id, ldv(p, ((b * h + (Y >> 1)) * w + (X >> 1)) * (4LL * dout) + c * 4 + (Y & 1) * 2 + (X & 1)) + ldv(skip, id));
     }
 }
-__global__ __launch_bounds__(256) void pixel_unshuffle_kernel(const float* __restrict__ dout, float* __restrict__ dp, int B, int h, int w, int dch) {
+template <typename T>
+__global__ __launch_bounds__(256) void pixel_unshuffle_kernel(const T* __restrict__ dout, T* __restrict__ dp, int B, int h, int w, int dch) {
     const long long n = (long long)B * h * w * 4 * dch;
     GS_LOOP(id, n) {
         const int k = (int)(id % (4 * dch));
@@ -320,7 +637,7 @@ __global__ __launch_bounds__(256) void pixel_unshuffle_kernel(const float* __res
         const int x = (int)(q % w), y = (int)((q / w) % h);
         const long long b = q / ((long long)w * h);
         const int c = k >> 2, i = (k >> 1) & 1, j = k & 1;
-        dp[id] = dout[((b * 2 * h + 2 * y + i) * (2 * w) + 2 * x + j) * dch + c];
+        stv(dp, id, ldv(dout, ((b * 2 * h + 2 * y + i) * (2 * w) + 2 * x + j) * dch + c));
     }
 }
 // GEMM-order weight gradient [cout][(i*2+j)*cin + c] -> OIHW [cout][cin][2][2]
@@ -335,7 +652,8 @@ __global__ __launch_bounds__(256) void permute_down_grad_kernel(const float* __r
 }
 // OIHW [cout][cin][k][k] f32 -> GEMM matrix, K index kc = (i*k + j) * cin + c:  forward [rows][K] (rows >= cout zero) or transposed
 // [rows][cout] (row = kc, rows >= K zero): the dgrad GEMM's weights
-__global__ __launch_bounds__(256) void pack_gemm_kernel(const float* __restrict__ w, int cout, int cin, int kk, int transposed, float* __restrict__ dst, int rows) {
+template <typename T>
+__global__ __launch_bounds__(256) void pack_gemm_kernel(const float* __restrict__ w, int cout, int cin, int kk, int transposed, T* __restrict__ dst, int rows) {
     const int K = cin * kk;
     const long long n = (long long)rows * (transposed ? cout : K);
     GS_LOOP(id, n) {
@@ -344,13 +662,13 @@ __global__ __launch_bounds__(256) void pack_gemm_kernel(const float* __restrict_
         else { o = (int)(id / K); kc = (int)(id % K); }
         float v = 0.f;
         if (o < cout && kc < K) v = w[((long long)o * cin + kc % cin) * kk + kc / cin];
-        dst[id] = v;
+        stv(dst, id, v);
     }
 }
 
 // ---- conv_in (3 -> 32, 3x3) forward on the NCHW image, as in the inference forward (hfrm.hip) -----------------------------------
-template <int DIM>
-__global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int cin, const float* __restrict__ w,
+template <typename T, int DIM>
+__global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ x, T* __restrict__ y, int B, int H, int W, int cin, const float* __restrict__ w,
                                                       const float* __restrict__ bias) {
     __shared__ float ws[16 * 9 * DIM + DIM];
     for (int i = threadIdx.x; i < cin * 9 * DIM; i += 256) {
@@ -379,13 +697,18 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ 
             for (int o = 0; o < DIM; ++o) acc[o] += v * wr[o];
         }
     }
+    if constexpr (H16<T>) {
 #pragma unroll
-    for (int o = 0; o < DIM; ++o) y[pix * DIM + o] = acc[o];
+        for (int o = 0; o < DIM; o += 8) st8(y, pix * DIM + o, acc + o);
+    } else {
+#pragma unroll
+        for (int o = 0; o < DIM; ++o) y[pix * DIM + o] = acc[o];
+    }
 }
 
 // conv_out (DIM -> NC, 3x3 pad 1) dgrad: dt[q][ci] = sum_{co, tap} w[co][ci][tap] dy[b][co][q - tap offset]  (dy NCHW, dt NHWC)
-template <int DIM, int NC>
-__global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dt, int B, int H, int W) {
+template <typename T, int DIM, int NC>
+__global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w, T* __restrict__ dt, int B, int H, int W) {
     __shared__ float ws[NC * DIM * 9];
     for (int i = threadIdx.x; i < NC * DIM * 9; i += 256) ws[i] = w[i];
     __syncthreads();
@@ -408,8 +731,13 @@ __global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __rest
             for (int ci = 0; ci < DIM; ++ci) acc[ci] += v * ws[(co * DIM + ci) * 9 + t];
         }
     }
+    if constexpr (H16<T>) {
 #pragma unroll
-    for (int ci = 0; ci < DIM; ++ci) dt[pix * DIM + ci] = acc[ci];
+        for (int ci = 0; ci < DIM; ci += 8) st8(dt, pix * DIM + ci, acc + ci);
+    } else {
+#pragma unroll
+        for (int ci = 0; ci < DIM; ++ci) dt[pix * DIM + ci] = acc[ci];
+    }
 }
 
 // Weight gradient of a 3x3 pad-1 conv between a DIM-channel NHWC map A ("wide") and an NC-channel NCHW map N ("narrow"):
@@ -417,8 +745,8 @@ __global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __rest
 //   conv_in:  A = dy (co), N = x (ci), sgn = +1  ->  dW[co][ci][tap], bias = sum A
 //   conv_out: A = t (ci),  N = dy (co), sgn = -1 ->  dW[co][ci][tap], bias = sum N
 // part[blk][DIM * NC * 9 + DIM + NC] over a chunk of pixels per workgroup; 256 threads = DIM channels x (256 / DIM) pixel rows
-template <int DIM, int NC>
-__global__ __launch_bounds__(256) void wgrad3_small_part_kernel(const float* __restrict__ A, const float* __restrict__ Nn, int B, int H, int W, int sgn, int chunk,
+template <typename T, int DIM, int NC>
+__global__ __launch_bounds__(256) void wgrad3_small_part_kernel(const T* __restrict__ A, const float* __restrict__ Nn, int B, int H, int W, int sgn, int chunk,
                                                                 float* __restrict__ part) {
     constexpr int ROWS = 256 / DIM, NA = NC * 9 + 1 + NC, NOUT = DIM * NC * 9 + DIM + NC;
     __shared__ float red[256 * NA];
@@ -431,7 +759,7 @@ __global__ __launch_bounds__(256) void wgrad3_small_part_kernel(const float* __r
     for (long long p = p0 + r; p < p1; p += ROWS) {
         const int px = (int)(p % W), py = (int)((p / W) % H);
         const long long b = p / HW;
-        const float a = A[p * DIM + c];
+        const float a = ldv(A, p * DIM + c);
         acc[NC * 9] += a;
 #pragma unroll
         for (int n = 0; n < NC; ++n) {
@@ -526,7 +854,7 @@ struct TGemm { int pw = -1, pb = -1; int cout = 0, cin = 0, kk = 1; size_t f_off
                int K() const { return cin * kk; } int rows_f() const { return conv_rows_pad(cout); } int rows_t() const { return conv_rows_pad(cin * kk); } };
 struct TBlockG { TGemm g1, g3, g4, g5; };      // conv1 / conv3 / conv4 / conv5 of a block
 using TBlock = HfrmLayout::Block;
-struct BSave { float *a1, *a2, *c3, *y, *a4, *c5, *out, *pooled, *sc; };
+template <typename T> struct BSave { T *a1, *a2, *c3, *y, *a4, *c5, *out; float *pooled, *sc; };
 }  // namespace
 
 struct wdm_hfrm_trainer {
@@ -540,6 +868,8 @@ struct wdm_hfrm_trainer {
     std::vector<TBlockG> bg;       // per block (Block::idx)
     std::vector<TGemm> downs, ups;
     char* pk = nullptr;      // pack region of the current step
+    int act = WDM_F32;       // storage type of activations and their gradients: WDM_F32, or WDM_BF16 (the mixed mode; the pack region keeps its fp32-sized slots)
+    int chk_key[4] = {0, 0, 0, 0}; size_t chk_need = 0;      // the last shape / precision a step was sized for, and its workspace
 
     size_t take(size_t bytes) { size_t o = pack_bytes; pack_bytes = align_up(pack_bytes + bytes, 256); return o; }
     TGemm gemm(int pw, int pb, int cout, int cin, int kk) {
@@ -562,49 +892,60 @@ struct wdm_hfrm_trainer {
     }
     float* prm(int i) const { return P + off[i]; }
     float* grd(int i) const { return G + off[i]; }
-    const float* wf(const TGemm& g) const { return (const float*)(pk + g.f_off); }
-    const float* wt(const TGemm& g) const { return (const float*)(pk + g.t_off); }
+    // the pack region in bf16: the same slots at half their fp32 size (offsets stay 128-byte aligned)
+    size_t poff(size_t o) const { return act == WDM_BF16 ? o / 2 : o; }
+    const void* wf(const TGemm& g) const { return pk + poff(g.f_off); }
+    const void* wt(const TGemm& g) const { return pk + poff(g.t_off); }
 
-    int gemm_run(Ctx& c, const float* w, int rows, int K, int N, const float* bias, const float* x, long long M, float* y);
-    int fwd_gemm(Ctx& c, const TGemm& g, const float* x, long long M, float* y) { return gemm_run(c, wf(g), g.rows_f(), g.K(), g.cout, g.pb >= 0 ? prm(g.pb) : nullptr, x, M, y); }
-    int dgrad_gemm(Ctx& c, const TGemm& g, const float* dy, long long M, float* dx) { return gemm_run(c, wt(g), g.rows_t(), g.cout, g.K(), nullptr, dy, M, dx); }
-    int wgrad(Ctx& c, const float* x, int cin, const float* dy, int cout, int H, int W, float* dw, float* db);
-    int chan_sums(Ctx& c, const float* a, const float* m, int C, int H, int W, bool per_image, float scale, float* o0, float* o1 = nullptr, int split = 1 << 30);
-    int ln_fwd(Ctx& c, const float* x, float* y, long long M, int d, const float* w, const float* b);
-    int ln_bwd(Ctx& c, const float* x, const float* dn, const float* w, float* dio, long long M, int d, float* dw, float* db);
-    int fwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, BSave& s);
-    int bwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, const BSave& s, float* dO);
-    int pack(hipStream_t s);
-    int step(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out);
+    // x, y, dy, dx below: activations in the step's storage type (c.dtype: fp32 or bf16); the weights were packed in the same type
+    int gemm_run(Ctx& c, const void* w, int rows, int K, int N, const float* bias, const void* x, long long M, void* y);
+    int fwd_gemm(Ctx& c, const TGemm& g, const void* x, long long M, void* y) { return gemm_run(c, wf(g), g.rows_f(), g.K(), g.cout, g.pb >= 0 ? prm(g.pb) : nullptr, x, M, y); }
+    int dgrad_gemm(Ctx& c, const TGemm& g, const void* dy, long long M, void* dx) { return gemm_run(c, wt(g), g.rows_t(), g.cout, g.K(), nullptr, dy, M, dx); }
+    int wgrad(Ctx& c, const void* x, int cin, const void* dy, int cout, int H, int W, float* dw, float* db);
+    template <typename T> int chan_sums(Ctx& c, const T* a, const T* m, int C, int H, int W, bool per_image, float scale, float* o0, float* o1 = nullptr, int split = 1 << 30);
+    template <typename T> int ln_fwd(Ctx& c, const T* x, T* y, long long M, int d, const float* w, const float* b);
+    template <typename T> int ln_bwd(Ctx& c, const T* x, const T* dn, const float* w, T* dio, long long M, int d, float* dw, float* db);
+    template <typename T> int fwd_block(Ctx& c, const TBlock& b, const T* X, int B, int H, int W, BSave<T>& s);
+    template <typename T> int bwd_block(Ctx& c, const TBlock& b, const T* X, int B, int H, int W, const BSave<T>& s, T* dO);
+    template <typename T> int pack(hipStream_t s);
+    template <typename T> int step_t(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out);
+    int step(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out) {
+        c.dtype = act;
+        return act == WDM_BF16 ? step_t<__bf16>(c, x, target, dyext, B, H, W, loss, out) : step_t<float>(c, x, target, dyext, B, H, W, loss, out);
+    }
 };
 
-int wdm_hfrm_trainer::gemm_run(Ctx& c, const float* w, int rows, int K, int N, const float* bias, const float* x, long long M, float* y) {
+// elements of a streaming kernel's grid-stride loop: one per lane in fp32, eight (16 bytes) in bf16
+template <typename T> static int egrid(long long n) { return grid_capped_min1(sizeof(T) == 2 ? n / 8 : n, 256); }
+
+int wdm_hfrm_trainer::gemm_run(Ctx& c, const void* w, int rows, int K, int N, const float* bias, const void* x, long long M, void* y) {
     if (c.dry) return WDM_OK;
     const int Hp = (int)align_up((size_t)((M + 15) / 16), 16);
-    ConvArgs a = gemm_args(1, Hp, 16, x, K, K, w, K, 0, rows, N, y, Y_NHWC, 4);
+    ConvArgs a = gemm_args(1, Hp, 16, x, K, K, w, K, 0, rows, N, y, Y_NHWC, dsize(c.dtype));
     a.bias = bias;
     a.m_valid = M;
-    return launch_conv(a, MODE_P1, WDM_F32, c.s);
+    return launch_conv(a, MODE_P1, c.dtype, c.s);
 }
 
 // dw [cout][cin] (the GEMM view of the layer) = sum over pixels dy[p][co] x[p][ci]  (conv_wgrad, mode 3); db = colsum(dy)
-int wdm_hfrm_trainer::wgrad(Ctx& c, const float* x, int cin, const float* dy, int cout, int H, int W, float* dw, float* db) {
+int wdm_hfrm_trainer::wgrad(Ctx& c, const void* x, int cin, const void* dy, int cout, int H, int W, float* dw, float* db) {
     Tens tx, tdy;
-    tx.p = const_cast<float*>(x); tx.C = cin; tx.H = H; tx.W = W; tx.xs = cin;
-    tdy.p = const_cast<float*>(dy); tdy.C = cout; tdy.H = H; tdy.W = W; tdy.xs = cout;
+    tx.p = const_cast<void*>(x); tx.C = cin; tx.H = H; tx.W = W; tx.xs = cin;
+    tdy.p = const_cast<void*>(dy); tdy.C = cout; tdy.H = H; tdy.W = W; tdy.xs = cout;
     WDM_TRY(conv_wgrad(c, MODE_P1, tx, nullptr, tdy, cout, dw, false));
     if (db) WDM_TRY(colsum(c, tdy, db, false, false));
     return WDM_OK;
 }
 
-int wdm_hfrm_trainer::chan_sums(Ctx& c, const float* a, const float* m, int C, int H, int W, bool per_image, float scale, float* o0, float* o1, int split) {
+template <typename T>
+int wdm_hfrm_trainer::chan_sums(Ctx& c, const T* a, const T* m, int C, int H, int W, bool per_image, float scale, float* o0, float* o1, int split) {
     const int HW = H * W;
     const int nk = std::max(1, std::min(256, ceil_div(HW, 1024)));
     const int chunk = ceil_div(HW, nk);
     float* part = (float*)c.ar->alloc((size_t)c.B * nk * C * 4);
     if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM channel sums)");
     if (!c.dry) {
-        hipLaunchKernelGGL(chan_part_kernel, dim3(nk, c.B, ceil_div(C, 256)), dim3(256), 0, c.s, a, m, C, HW, chunk, nk, part);
+        hipLaunchKernelGGL(chan_part_kernel<T>, dim3(nk, c.B, ceil_div(C, 256)), dim3(256), 0, c.s, a, m, C, HW, chunk, nk, part);
         hipLaunchKernelGGL(chan_final_kernel, dim3(ceil_div((long long)(per_image ? c.B : 1) * C, 256)), dim3(256), 0, c.s, part, c.B, nk, C, per_image ? 1 : 0, scale,
                            o0, o1, split);
         WDM_HIP(hipGetLastError());
@@ -613,7 +954,11 @@ int wdm_hfrm_trainer::chan_sums(Ctx& c, const float* a, const float* m, int C, i
     return WDM_OK;
 }
 
-static int ln_grid(long long M) { return (int)std::min<long long>(1024, (M + LN_TEAMS * 4 - 1) / (LN_TEAMS * 4)); }
+// pixels a workgroup normalises at a time: 8 teams of 32 lanes in fp32, 256 / (d / 8) teams (at least 8) in bf16
+template <typename T> static int ln_grid(long long M, int d) {
+    const int ppb = sizeof(T) == 2 ? 256 / std::min(d / 8, 32) : LN_TEAMS;
+    return (int)std::min<long long>(1024, (M + ppb * 4 - 1) / (ppb * 4));
+}
 
 #define LN_SWITCH(d, K, ...)                                                  \
     switch (d) {                                                              \
@@ -625,19 +970,21 @@ static int ln_grid(long long M) { return (int)std::min<long long>(1024, (M + LN_
         default: WDM_FAIL(WDM_EINVAL, "HFRM trainer: LayerNorm over %d channels unsupported", d); \
     }
 
-int wdm_hfrm_trainer::ln_fwd(Ctx& c, const float* x, float* y, long long M, int d, const float* w, const float* b) {
+template <typename T>
+int wdm_hfrm_trainer::ln_fwd(Ctx& c, const T* x, T* y, long long M, int d, const float* w, const float* b) {
     if (c.dry) return WDM_OK;
-    LN_SWITCH(d, NJ, hipLaunchKernelGGL(ln_fwd_kernel<NJ>, dim3(ln_grid(M)), dim3(256), 0, c.s, x, y, M, w, b));
+    LN_SWITCH(d, NJ, hipLaunchKernelGGL((ln_fwd_kernel<T, NJ>), dim3(ln_grid<T>(M, d)), dim3(256), 0, c.s, x, y, M, w, b));
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }
 // dio (+)= LayerNorm backward of dn (dio holds the residual gradient on entry); dw / db = weight / bias gradients
-int wdm_hfrm_trainer::ln_bwd(Ctx& c, const float* x, const float* dn, const float* w, float* dio, long long M, int d, float* dw, float* db) {
-    const int g = ln_grid(M);
+template <typename T>
+int wdm_hfrm_trainer::ln_bwd(Ctx& c, const T* x, const T* dn, const float* w, T* dio, long long M, int d, float* dw, float* db) {
+    const int g = ln_grid<T>(M, d);
     float* part = (float*)c.ar->alloc((size_t)g * 2 * d * 4);
     if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM LayerNorm backward)");
     if (!c.dry) {
-        LN_SWITCH(d, NJ, hipLaunchKernelGGL(ln_bwd_kernel<NJ>, dim3(g), dim3(256), 0, c.s, x, dn, w, dio, dio, M, part));
+        LN_SWITCH(d, NJ, hipLaunchKernelGGL((ln_bwd_kernel<T, NJ>), dim3(g), dim3(256), 0, c.s, x, dn, w, (const T*)dio, dio, M, part));
         hipLaunchKernelGGL(chan_final_kernel, dim3(ceil_div(2 * d, 256)), dim3(256), 0, c.s, part, 1, g, 2 * d, 0, 1.0f, dw, db, d);
         WDM_HIP(hipGetLastError());
     }
@@ -645,36 +992,38 @@ int wdm_hfrm_trainer::ln_bwd(Ctx& c, const float* x, const float* dn, const floa
     return WDM_OK;
 }
 
-int wdm_hfrm_trainer::fwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, BSave& s) {
+template <typename T>
+int wdm_hfrm_trainer::fwd_block(Ctx& c, const TBlock& b, const T* X, int B, int H, int W, BSave<T>& s) {
     const int d = b.d, HW = H * W;
     const TBlockG& tg = bg[b.idx];
     const long long M = (long long)B * HW, n1 = M * d;
-    auto A = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
+    auto A = [&](long long elems) { return (T*)c.ar->alloc((size_t)elems * sizeof(T)); };
+    auto AF = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
     s.a1 = A(2 * n1); s.a2 = A(2 * n1); s.c3 = A(n1); s.y = A(n1); s.a4 = A(2 * n1); s.c5 = A(n1); s.out = A(n1);
-    s.pooled = A((long long)B * d); s.sc = A((long long)B * d);
-    float* n = A(n1);
-    float* g = A(n1);
+    s.pooled = AF((long long)B * d); s.sc = AF((long long)B * d);
+    T* n = A(n1);
+    T* g = A(n1);
     if (!s.a1 || !s.a2 || !s.c3 || !s.y || !s.a4 || !s.c5 || !s.out || !s.pooled || !s.sc || !n || !g) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block forward)");
-    const int ge = grid_capped_min1(n1, 256);
+    const int ge = egrid<T>(n1);
     WDM_TRY(ln_fwd(c, X, n, M, d, prm(b.n1w), prm(b.n1b)));
     WDM_TRY(fwd_gemm(c, tg.g1, n, M, s.a1));
     if (!c.dry) {
-        hipLaunchKernelGGL(dw_fwd_kernel, dim3(grid_capped_min1(2 * n1, 256)), dim3(256), 0, c.s, s.a1, s.a2, H, W, 2 * d, 2 * n1, prm(b.w[1]), prm(b.b[1]));
-        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, g, n1, d, (const float*)nullptr, HW);
+        hipLaunchKernelGGL(dw_fwd_kernel<T>, dim3(egrid<T>(2 * n1)), dim3(256), 0, c.s, s.a1, s.a2, H, W, 2 * d, 2 * n1, prm(b.w[1]), prm(b.b[1]));
+        hipLaunchKernelGGL(gate_kernel<T>, dim3(ge), dim3(256), 0, c.s, s.a2, g, n1, d, (const float*)nullptr, HW);
     }
-    WDM_TRY(chan_sums(c, g, nullptr, d, H, W, true, 1.0f / (float)HW, s.pooled));
+    WDM_TRY(chan_sums<T>(c, g, nullptr, d, H, W, true, 1.0f / (float)HW, s.pooled));
     if (!c.dry) {
         WDM_TRY(k_linear(s.pooled, B, d, prm(b.caw), prm(b.cab), d, s.sc, 0, c.s));
-        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, g, n1, d, (const float*)s.sc, HW);      // channel-scaled gate
+        hipLaunchKernelGGL(gate_kernel<T>, dim3(ge), dim3(256), 0, c.s, s.a2, g, n1, d, (const float*)s.sc, HW);      // channel-scaled gate
     }
     WDM_TRY(fwd_gemm(c, tg.g3, g, M, s.c3));
-    if (!c.dry) hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, X, prm(b.beta), s.c3, s.y, n1, d);      // y = x + beta * conv3
+    if (!c.dry) hipLaunchKernelGGL(axpy_chan_kernel<T>, dim3(ge), dim3(256), 0, c.s, X, prm(b.beta), s.c3, s.y, n1, d);      // y = x + beta * conv3
     WDM_TRY(ln_fwd(c, s.y, n, M, d, prm(b.n2w), prm(b.n2b)));
     WDM_TRY(fwd_gemm(c, tg.g4, n, M, s.a4));
-    if (!c.dry) hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a4, g, n1, d, (const float*)nullptr, HW);
+    if (!c.dry) hipLaunchKernelGGL(gate_kernel<T>, dim3(ge), dim3(256), 0, c.s, s.a4, g, n1, d, (const float*)nullptr, HW);
     WDM_TRY(fwd_gemm(c, tg.g5, g, M, s.c5));
     if (!c.dry) {
-        hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, s.y, prm(b.gamma), s.c5, s.out, n1, d);  // out = y + gamma * conv5
+        hipLaunchKernelGGL(axpy_chan_kernel<T>, dim3(ge), dim3(256), 0, c.s, s.y, prm(b.gamma), s.c5, s.out, n1, d);  // out = y + gamma * conv5
         WDM_HIP(hipGetLastError());
     }
     c.ar->free(g); c.ar->free(n);
@@ -682,65 +1031,67 @@ int wdm_hfrm_trainer::fwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
 }
 
 // dO: the gradient of the block output on entry, of its input X on return (in place)
-int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, int H, int W, const BSave& s, float* dO) {
+template <typename T>
+int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const T* X, int B, int H, int W, const BSave<T>& s, T* dO) {
     const int d = b.d, HW = H * W;
     const TBlockG& tg = bg[b.idx];
     const long long M = (long long)B * HW, n1 = M * d;
-    auto A = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
-    float* t1 = A(n1);          // dc5, dc3
-    float* t2 = A(n1);          // g2, n2, g, n1
-    float* t3 = A(2 * n1);      // da4, da2
-    float* t4 = A(n1);          // dg2, dn2, dgs / dg, dn1
-    float* t5 = A(n1);          // g * sc
-    float* t6 = A(2 * n1);      // da1
-    float* sm = A((long long)3 * B * d);      // dsc, dpool
+    auto A = [&](long long elems) { return (T*)c.ar->alloc((size_t)elems * sizeof(T)); };
+    auto AF = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
+    T* t1 = A(n1);          // dc5, dc3
+    T* t2 = A(n1);          // g2, n2, g, n1
+    T* t3 = A(2 * n1);      // da4, da2
+    T* t4 = A(n1);          // dg2, dn2, dgs / dg, dn1
+    T* t5 = A(n1);          // g * sc
+    T* t6 = A(2 * n1);      // da1
+    float* sm = AF((long long)3 * B * d);      // dsc, dpool
     if (!t1 || !t2 || !t3 || !t4 || !t5 || !t6 || !sm) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM block backward)");
     float* dsc = sm; float* dpool = sm + (size_t)B * d;
-    const int ge = grid_capped_min1(n1, 256);
+    const int ge = egrid<T>(n1);
     // out = y + gamma * c5
-    WDM_TRY(chan_sums(c, dO, s.c5, d, H, W, false, 1.0f, grd(b.gamma)));
+    WDM_TRY(chan_sums<T>(c, dO, s.c5, d, H, W, false, 1.0f, grd(b.gamma)));
     if (!c.dry) {
-        hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, (const float*)nullptr, prm(b.gamma), dO, t1, n1, d);
-        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a4, t2, n1, d, (const float*)nullptr, HW);
+        hipLaunchKernelGGL(axpy_chan_kernel<T>, dim3(ge), dim3(256), 0, c.s, (const T*)nullptr, prm(b.gamma), dO, t1, n1, d);
+        hipLaunchKernelGGL(gate_kernel<T>, dim3(ge), dim3(256), 0, c.s, s.a4, t2, n1, d, (const float*)nullptr, HW);
     }
     // conv5
     WDM_TRY(wgrad(c, t2, d, t1, d, H, W, grd(tg.g5.pw), grd(tg.g5.pb)));
     WDM_TRY(dgrad_gemm(c, tg.g5, t1, M, t4));
     // gate, conv4, norm2
-    if (!c.dry) hipLaunchKernelGGL(gate_bwd_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.a4, t3, n1, d);
+    if (!c.dry) hipLaunchKernelGGL(gate_bwd_kernel<T>, dim3(ge), dim3(256), 0, c.s, t4, s.a4, t3, n1, d);
     WDM_TRY(ln_fwd(c, s.y, t2, M, d, prm(b.n2w), prm(b.n2b)));
     WDM_TRY(wgrad(c, t2, d, t3, 2 * d, H, W, grd(tg.g4.pw), grd(tg.g4.pb)));
     WDM_TRY(dgrad_gemm(c, tg.g4, t3, M, t4));
     WDM_TRY(ln_bwd(c, s.y, t4, prm(b.n2w), dO, M, d, grd(b.n2w), grd(b.n2b)));      // dO is now d y
     // y = x + beta * c3
-    WDM_TRY(chan_sums(c, dO, s.c3, d, H, W, false, 1.0f, grd(b.beta)));
+    WDM_TRY(chan_sums<T>(c, dO, s.c3, d, H, W, false, 1.0f, grd(b.beta)));
     if (!c.dry) {
-        hipLaunchKernelGGL(axpy_chan_kernel, dim3(ge), dim3(256), 0, c.s, (const float*)nullptr, prm(b.beta), dO, t1, n1, d);
-        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, t2, n1, d, (const float*)nullptr, HW);       // g
-        hipLaunchKernelGGL(gate_kernel, dim3(ge), dim3(256), 0, c.s, s.a2, t5, n1, d, (const float*)s.sc, HW);          // g * sc
+        hipLaunchKernelGGL(axpy_chan_kernel<T>, dim3(ge), dim3(256), 0, c.s, (const T*)nullptr, prm(b.beta), dO, t1, n1, d);
+        hipLaunchKernelGGL(gate_kernel<T>, dim3(ge), dim3(256), 0, c.s, s.a2, t2, n1, d, (const float*)nullptr, HW);       // g
+        hipLaunchKernelGGL(gate_kernel<T>, dim3(ge), dim3(256), 0, c.s, s.a2, t5, n1, d, (const float*)s.sc, HW);          // g * sc
     }
     // conv3
     WDM_TRY(wgrad(c, t5, d, t1, d, H, W, grd(tg.g3.pw), grd(tg.g3.pb)));
     WDM_TRY(dgrad_gemm(c, tg.g3, t1, M, t4));
     // channel attention: sc = W pooled + b, pooled = mean g
-    WDM_TRY(chan_sums(c, t4, t2, d, H, W, true, 1.0f, dsc));
+    WDM_TRY(chan_sums<T>(c, t4, t2, d, H, W, true, 1.0f, dsc));
     if (!c.dry) {
         const long long nca = (long long)d * d + d + (long long)B * d;
         hipLaunchKernelGGL(ca_bwd_kernel, dim3(grid_capped_min1(nca, 256)), dim3(256), 0, c.s, dsc, s.pooled, prm(b.caw), B, d, grd(b.caw), grd(b.cab), dpool);
-        hipLaunchKernelGGL(ca_dg_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.sc, dpool, n1, d, HW, 1.0f / (float)HW);
-        hipLaunchKernelGGL(gate_bwd_kernel, dim3(ge), dim3(256), 0, c.s, t4, s.a2, t3, n1, d);                         // d a2
+        hipLaunchKernelGGL(ca_dg_kernel<T>, dim3(ge), dim3(256), 0, c.s, t4, s.sc, dpool, n1, d, HW, 1.0f / (float)HW);
+        hipLaunchKernelGGL(gate_bwd_kernel<T>, dim3(ge), dim3(256), 0, c.s, t4, s.a2, t3, n1, d);                         // d a2
     }
     // depthwise conv2
     {
         const int C2 = 2 * d;
         const int nk = std::max(1, std::min(256, ceil_div(HW, 1024)));
         const int chunk = ceil_div(HW, nk);
-        float* part = A((long long)B * nk * C2 * 10);
+        float* part = AF((long long)B * nk * C2 * 10);
         if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM depthwise wgrad)");
         if (!c.dry) {
-            hipLaunchKernelGGL(dw_wgrad_part_kernel, dim3(nk, B, ceil_div(C2, 256)), dim3(256), 0, c.s, t3, s.a1, H, W, C2, chunk, nk, part);
+            hipLaunchKernelGGL(dw_wgrad_part_kernel<T>, dim3(nk, B, ceil_div(C2, 256)), dim3(256), 0, c.s, t3, s.a1, H, W, C2, chunk, nk, part);
             hipLaunchKernelGGL(dw_wgrad_final_kernel, dim3(ceil_div(C2 * 10, 256)), dim3(256), 0, c.s, part, B * nk, C2, grd(b.w[1]), grd(b.b[1]));
-            hipLaunchKernelGGL(dw_dgrad_kernel, dim3(grid_capped_min1(2 * n1, 256)), dim3(256), 0, c.s, t3, t6, H, W, C2, 2 * n1, prm(b.w[1]));
+            hipLaunchKernelGGL(dw_dgrad_kernel<T>, dim3(egrid<T>(2 * n1)), dim3(256), 0, c.s, t3, t6, H, W, C2, 2 * n1, prm(b.w[1]));
             WDM_HIP(hipGetLastError());
         }
         c.ar->free(part);
@@ -754,48 +1105,51 @@ int wdm_hfrm_trainer::bwd_block(Ctx& c, const TBlock& b, const float* X, int B, 
     return WDM_OK;
 }
 
+template <typename T>
 int wdm_hfrm_trainer::pack(hipStream_t s) {
     auto pg = [&](const TGemm& g) {
         const long long nf = (long long)g.rows_f() * g.K(), nt = (long long)g.rows_t() * g.cout;
-        hipLaunchKernelGGL(pack_gemm_kernel, dim3(grid_capped_min1(nf, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 0, (float*)(pk + g.f_off), g.rows_f());
-        hipLaunchKernelGGL(pack_gemm_kernel, dim3(grid_capped_min1(nt, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 1, (float*)(pk + g.t_off), g.rows_t());
+        hipLaunchKernelGGL(pack_gemm_kernel<T>, dim3(grid_capped_min1(nf, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 0, (T*)(pk + poff(g.f_off)), g.rows_f());
+        hipLaunchKernelGGL(pack_gemm_kernel<T>, dim3(grid_capped_min1(nt, 256)), dim3(256), 0, s, prm(g.pw), g.cout, g.cin, g.kk, 1, (T*)(pk + poff(g.t_off)), g.rows_t());
     };
     for (auto& b : bg) { pg(b.g1); pg(b.g3); pg(b.g4); pg(b.g5); }
     for (auto& g : ups) pg(g);
     for (auto& g : downs) pg(g);
-    WDM_TRY(k_pack_conv(prm(L.conv_out.w), cfg.in_channel, cfg.dim, 3, pk + cout_off, conv_rows_pad(cfg.in_channel), 0, 1, WDM_F32, s));
+    WDM_TRY(k_pack_conv(prm(L.conv_out.w), cfg.in_channel, cfg.dim, 3, pk + poff(cout_off), conv_rows_pad(cfg.in_channel), 0, 1, sizeof(T) == 2 ? WDM_BF16 : WDM_F32, s));
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }
 
-int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out) {
+template <typename T>
+int wdm_hfrm_trainer::step_t(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out) {
     const int nlev = cfg.n_enc, dim = cfg.dim, nc = cfg.in_channel;
     if (H % (1 << nlev) || W % (1 << nlev) || H % 16 || W % 16) WDM_FAIL(WDM_EINVAL, "HFRM trainer: H=%d W=%d must be multiples of 16 and of %d", H, W, 1 << nlev);
-    auto A = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
-    pk = (char*)c.ar->alloc(pack_bytes);
+    auto A = [&](long long elems) { return (T*)c.ar->alloc((size_t)elems * sizeof(T)); };
+    auto AF = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
+    pk = (char*)c.ar->alloc(poff(pack_bytes));
     if (!pk) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer weights)");
-    if (!c.dry) WDM_TRY(pack(c.s));
+    if (!c.dry) WDM_TRY(pack<T>(c.s));
     const long long M0 = (long long)B * H * W;
     // ---- forward, keeping what the backward reads
-    std::vector<const float*> ins;          // block inputs in execution order
-    std::vector<BSave> saves;
-    std::vector<float*> enc_out(nlev), up_in(cfg.n_dec);
-    float* cur = A(M0 * dim);
+    std::vector<const T*> ins;          // block inputs in execution order
+    std::vector<BSave<T>> saves;
+    std::vector<T*> enc_out(nlev), up_in(cfg.n_dec);
+    T* cur = A(M0 * dim);
     if (!cur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer)");
-    if (!c.dry) hipLaunchKernelGGL((conv_in_kernel<32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, cur, B, H, W, nc, prm(L.conv_in.w), prm(L.conv_in.b));
+    if (!c.dry) hipLaunchKernelGGL((conv_in_kernel<T, 32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, cur, B, H, W, nc, prm(L.conv_in.w), prm(L.conv_in.b));
     int d = dim, h = H, w = W;
     auto run_blocks = [&](const std::vector<TBlock>& bl) -> int {
-        for (auto& b : bl) { BSave s; WDM_TRY(fwd_block(c, b, cur, B, h, w, s)); ins.push_back(cur); saves.push_back(s); cur = s.out; }
+        for (auto& b : bl) { BSave<T> s; WDM_TRY(fwd_block<T>(c, b, cur, B, h, w, s)); ins.push_back(cur); saves.push_back(s); cur = s.out; }
         return WDM_OK;
     };
     for (int i = 0; i < nlev; ++i) {
         WDM_TRY(run_blocks(L.enc[i]));
         enc_out[i] = cur;
         const long long Mn = (long long)B * (h / 2) * (w / 2);
-        float* u = A(Mn * 4 * d);
-        float* nt = A(Mn * 2 * d);
+        T* u = A(Mn * 4 * d);
+        T* nt = A(Mn * 2 * d);
         if (!u || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down)");
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(grid_capped_min1(Mn * 4 * d, 256)), dim3(256), 0, c.s, cur, u, B, h, w, d, 0);
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * d)), dim3(256), 0, c.s, cur, u, B, h, w, d, 0);
         WDM_TRY(fwd_gemm(c, downs[i], u, Mn, nt));
         c.ar->free(u);
         cur = nt; d *= 2; h /= 2; w /= 2;
@@ -803,25 +1157,25 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
     WDM_TRY(run_blocks(L.mid));
     for (int i = 0; i < cfg.n_dec; ++i) {
         const long long M = (long long)B * h * w;
-        float* p = A(M * 2 * d);
-        float* nt = A(M * 2 * d);           // (2h x 2w x d/2)
+        T* p = A(M * 2 * d);
+        T* nt = A(M * 2 * d);           // (2h x 2w x d/2)
         if (!p || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up)");
         WDM_TRY(fwd_gemm(c, ups[i], cur, M, p));
-        if (!c.dry) hipLaunchKernelGGL(pixel_shuffle_kernel, dim3(grid_capped_min1(M * 2 * d, 256)), dim3(256), 0, c.s, p, enc_out[nlev - 1 - i], nt, B, h, w, d / 2);
+        if (!c.dry) hipLaunchKernelGGL(pixel_shuffle_kernel<T>, dim3(grid_capped_min1(M * 2 * d, 256)), dim3(256), 0, c.s, p, enc_out[nlev - 1 - i], nt, B, h, w, d / 2);
         c.ar->free(p);
         up_in[i] = cur;
         cur = nt; d /= 2; h *= 2; w *= 2;
         WDM_TRY(run_blocks(L.dec[i]));
     }
     // conv_out 3x3 + input (run_conv, as the inference forward), NCHW f32
-    float* xin = A(M0 * nc);
-    float* yo = out ? out : A(M0 * nc);
-    float* dY = A(M0 * nc);
-    float* lpart = A(LOSS_BLOCKS);
+    T* xin = A(M0 * nc);
+    float* yo = out ? out : AF(M0 * nc);
+    float* dY = AF(M0 * nc);
+    float* lpart = AF(LOSS_BLOCKS);
     if (!xin || !yo || !dY || !lpart) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer output)");
     {
-        if (!c.dry) WDM_TRY(k_nchw_to_nhwc(x, xin, B, nc, H, W, WDM_F32, c.s));
-        ConvW cwo; cwo.w = pk + cout_off; cwo.b = prm(L.conv_out.b); cwo.cin = dim; cwo.cout = nc; cwo.k = 3; cwo.rows_pad = conv_rows_pad(nc);
+        if (!c.dry) WDM_TRY(k_nchw_to_nhwc(x, xin, B, nc, H, W, c.dtype, c.s));
+        ConvW cwo; cwo.w = pk + poff(cout_off); cwo.b = prm(L.conv_out.b); cwo.cin = dim; cwo.cout = nc; cwo.k = 3; cwo.rows_pad = conv_rows_pad(nc);
         Tens t; t.p = cur; t.C = dim; t.H = H; t.W = W; t.xs = dim;
         Tens xi; xi.p = xin; xi.C = nc; xi.H = H; xi.W = W; xi.xs = nc;
         Tens dummy;
@@ -841,17 +1195,17 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
         WDM_HIP(hipGetLastError());
     }
     // ---- backward
-    float* dT = A(M0 * dim);
+    T* dT = A(M0 * dim);
     if (!dT) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer backward)");
     {
         const int chunk = 2048, nbk = ceil_div(M0, chunk);
         constexpr int NOUT = 32 * 3 * 9 + 32 + 3;
-        float* part = A((long long)nbk * NOUT);
+        float* part = AF((long long)nbk * NOUT);
         if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_out wgrad)");
         if (nc != 3) WDM_FAIL(WDM_EINVAL, "HFRM trainer: in_channel must be 3");
         if (!c.dry) {
-            hipLaunchKernelGGL((conv_out_dgrad_kernel<32, 3>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, dY, prm(L.conv_out.w), dT, B, H, W);
-            hipLaunchKernelGGL((wgrad3_small_part_kernel<32, 3>), dim3(nbk), dim3(256), 0, c.s, cur, dY, B, H, W, -1, chunk, part);
+            hipLaunchKernelGGL((conv_out_dgrad_kernel<T, 32, 3>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, dY, prm(L.conv_out.w), dT, B, H, W);
+            hipLaunchKernelGGL((wgrad3_small_part_kernel<T, 32, 3>), dim3(nbk), dim3(256), 0, c.s, cur, dY, B, H, W, -1, chunk, part);
             hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 0, grd(L.conv_out.w), grd(L.conv_out.b));
             WDM_HIP(hipGetLastError());
         }
@@ -861,23 +1215,23 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
     auto back_blocks = [&](const std::vector<TBlock>& bl) -> int {
         for (int j = (int)bl.size() - 1; j >= 0; --j) {
             --k;
-            WDM_TRY(bwd_block(c, bl[j], ins[k], B, h, w, saves[k], dT));
-            const BSave& s = saves[k];
+            WDM_TRY(bwd_block<T>(c, bl[j], ins[k], B, h, w, saves[k], dT));
+            const BSave<T>& s = saves[k];
             c.ar->free(s.sc); c.ar->free(s.pooled); c.ar->free(s.c5); c.ar->free(s.a4); c.ar->free(s.y); c.ar->free(s.c3); c.ar->free(s.a2); c.ar->free(s.a1);
         }
         return WDM_OK;
     };
-    std::vector<float*> dskip(nlev);
+    std::vector<T*> dskip(nlev);
     for (int i = cfg.n_dec - 1; i >= 0; --i) {
         WDM_TRY(back_blocks(L.dec[i]));
         // ups[i]: nt = PixelShuffle(W up_in) + skip
         const int dl = 2 * d;                                   // channels of up_in
         const int hl = h / 2, wl = w / 2;
         const long long M = (long long)B * hl * wl;
-        float* dp = A(M * 2 * dl);
-        float* dcur = A(M * dl);
+        T* dp = A(M * 2 * dl);
+        T* dcur = A(M * dl);
         if (!dp || !dcur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up backward)");
-        if (!c.dry) hipLaunchKernelGGL(pixel_unshuffle_kernel, dim3(grid_capped_min1(M * 2 * dl, 256)), dim3(256), 0, c.s, dT, dp, B, hl, wl, d);
+        if (!c.dry) hipLaunchKernelGGL(pixel_unshuffle_kernel<T>, dim3(grid_capped_min1(M * 2 * dl, 256)), dim3(256), 0, c.s, dT, dp, B, hl, wl, d);
         dskip[nlev - 1 - i] = dT;
         WDM_TRY(wgrad(c, up_in[i], dl, dp, 2 * dl, hl, wl, grd(ups[i].pw), nullptr));
         WDM_TRY(dgrad_gemm(c, ups[i], dp, M, dcur));
@@ -889,14 +1243,14 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
         // downs[i]: level i+1 input = W . unshuffle(enc_out[i]) + b
         const int dl = d / 2, hl = 2 * h, wl = 2 * w;
         const long long Mn = (long long)B * h * w;
-        float* u = A(Mn * 4 * dl);
-        float* gw = A((long long)2 * dl * 4 * dl);
+        T* u = A(Mn * 4 * dl);
+        float* gw = AF((long long)2 * dl * 4 * dl);
         if (!u || !gw) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down backward)");
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(grid_capped_min1(Mn * 4 * dl, 256)), dim3(256), 0, c.s, enc_out[i], u, B, hl, wl, dl, 0);
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * dl)), dim3(256), 0, c.s, enc_out[i], u, B, hl, wl, dl, 0);
         WDM_TRY(wgrad(c, u, 4 * dl, dT, 2 * dl, h, w, gw, grd(downs[i].pb)));
         if (!c.dry) hipLaunchKernelGGL(permute_down_grad_kernel, dim3(grid_capped_min1((long long)2 * dl * 4 * dl, 256)), dim3(256), 0, c.s, gw, grd(downs[i].pw), 2 * dl, dl, 4);
         WDM_TRY(dgrad_gemm(c, downs[i], dT, Mn, u));           // d u, over u
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel, dim3(grid_capped_min1(Mn * 4 * dl, 256)), dim3(256), 0, c.s, dskip[i], u, B, hl, wl, dl, 1);
+        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * dl)), dim3(256), 0, c.s, dskip[i], u, B, hl, wl, dl, 1);
         c.ar->free(gw); c.ar->free(u); c.ar->free(dT);
         dT = dskip[i]; d = dl; h = hl; w = wl;
         WDM_TRY(back_blocks(L.enc[i]));
@@ -904,10 +1258,10 @@ int wdm_hfrm_trainer::step(Ctx& c, const float* x, const float* target, const fl
     {   // conv_in: weight and bias only (the image needs no gradient)
         const int chunk = 2048, nbk = ceil_div(M0, chunk);
         constexpr int NOUT = 32 * 3 * 9 + 32 + 3;
-        float* part = A((long long)nbk * NOUT);
+        float* part = AF((long long)nbk * NOUT);
         if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_in wgrad)");
         if (!c.dry) {
-            hipLaunchKernelGGL((wgrad3_small_part_kernel<32, 3>), dim3(nbk), dim3(256), 0, c.s, dT, x, B, H, W, 1, chunk, part);
+            hipLaunchKernelGGL((wgrad3_small_part_kernel<T, 32, 3>), dim3(nbk), dim3(256), 0, c.s, (const T*)dT, x, B, H, W, 1, chunk, part);
             hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 1, grd(L.conv_in.w), grd(L.conv_in.b));
             WDM_HIP(hipGetLastError());
         }
@@ -947,10 +1301,20 @@ int wdm_hfrm_trainer_set_buffers(wdm_hfrm_trainer* t, float* params, float* grad
     t->P = params; t->G = grads; t->Mo = m; t->V = v;
     return WDM_OK;
 }
+int wdm_hfrm_trainer_set_precision(wdm_hfrm_trainer* t, int act_dtype) {
+    if (!t) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_set_precision: null trainer");
+    if (act_dtype == WDM_F16)
+        WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_set_precision: fp16 activations are refused: the mixed mode has no loss scaling, and fp16's exponent range "
+                             "(max 65504) does not hold the activation gradients; use WDM_BF16 (fp32's exponent range)");
+    if (act_dtype != WDM_F32 && act_dtype != WDM_BF16)
+        WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_set_precision: activation dtype %d unsupported (WDM_F32: exact fp32, WDM_BF16: bf16 activations over fp32 master state)", act_dtype);
+    t->act = act_dtype;
+    return WDM_OK;
+}
 size_t wdm_hfrm_trainer_workspace_bytes(const wdm_hfrm_trainer* t, int B, int H, int W) {
     if (!t || B <= 0) return 0;
     Arena ar = Arena::dry();
-    Ctx c{nullptr, WDM_F32, B, &ar, true};
+    Ctx c{nullptr, t->act, B, &ar, true};
     if (const_cast<wdm_hfrm_trainer*>(t)->step(c, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr) != WDM_OK) return 0;
     return ar.peak() + 4096;
 }
@@ -960,8 +1324,16 @@ int wdm_hfrm_trainer_step(wdm_hfrm_trainer* t, const float* x, const float* targ
     if ((target == nullptr) == (dy == nullptr)) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_step: pass exactly one of target and dy");
     if (!t->P || !t->G) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_trainer_step: call wdm_hfrm_trainer_set_buffers first");
     if (((uintptr_t)workspace) & 255) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_step: workspace must be 256-byte aligned");
+    // sized before the first launch: a short workspace fails here, not half-way through the step with the gradient buffer partly written
+    if (t->chk_key[0] != B || t->chk_key[1] != H || t->chk_key[2] != W || t->chk_key[3] != t->act || !t->chk_need) {
+        const size_t need = wdm_hfrm_trainer_workspace_bytes(t, B, H, W);
+        if (!need) return WDM_EINVAL;      // (the dry run has set the message)
+        t->chk_key[0] = B; t->chk_key[1] = H; t->chk_key[2] = W; t->chk_key[3] = t->act; t->chk_need = need;
+    }
+    if (workspace_bytes < t->chk_need)
+        WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer step: %zu bytes given, wdm_hfrm_trainer_workspace_bytes reports %zu)", workspace_bytes, t->chk_need);
     Arena ar(workspace, workspace_bytes);
-    Ctx c{(hipStream_t)stream, WDM_F32, B, &ar, false};
+    Ctx c{(hipStream_t)stream, t->act, B, &ar, false};
     return t->step(c, x, target, dy, B, H, W, loss, out);
 }
 int wdm_hfrm_trainer_adam(wdm_hfrm_trainer* t, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay, void* stream) {

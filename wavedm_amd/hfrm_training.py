@@ -8,7 +8,11 @@
     trainer.optimizer_step()                    # torch.optim.Adam(betas=(0.5, 0.999)), lr = 2e-4 * 0.5 ** (step / 1e5), no EMA
 
 `state_dict()` uses the reference's keys, shapes and order; `save(path)` writes the plain state_dict that `wavedm_amd.HFRM` and the
-reference's `DenoisingDiffusion_Wavelet` load with strict=True.  Exact fp32 only."""
+reference's `DenoisingDiffusion_Wavelet` load with strict=True.
+
+Two precisions: exact fp32 (the default) and `dtype="bf16-mixed"` -- activations and activation gradients stored in bf16, GEMMs on the
+bf16 MFMA path with fp32 accumulation, the four flat buffers (and so every checkpoint) unchanged fp32.  `sample_sheet` builds the
+reference's `sample_images` sheet [input | prediction | target] on the device."""
 from __future__ import annotations
 
 import ctypes as C
@@ -34,13 +38,31 @@ def batch_psnr(target, pred):
     return 20 * torch.log10(1 / rmse)
 
 
+MIXED = "bf16-mixed"      # a name of this module alone (not in _lib.DTYPES): no other class learns it
+
+
 def _resolve_train_dtype(dtype):
+    """The activation storage type of a training step: WDM_BF16 for "bf16-mixed", WDM_F32 for everything else that is accepted."""
     name = dtype or "f32"
+    if name == MIXED:
+        return _lib.WDM_BF16
     if name not in _lib.DTYPES:
-        raise ValueError(f"unknown compute dtype {name!r} (use 'f32'; 'f32x3' and 'f16' train in exact fp32 as well)")
+        raise ValueError(f"unknown compute dtype {name!r} (use 'f32' or 'bf16-mixed'; 'f32x3' and 'f16' train in exact fp32 as well)")
     if _lib.DTYPES[name] == _lib.WDM_BF16:
-        raise NotImplementedError("HFRMTrainer: bf16 training is not built; the HFRM trains in exact fp32 (dtype='f32')")
+        raise NotImplementedError("HFRMTrainer: true bf16 training (bf16 parameters and optimizer state) is not built; "
+                                  "dtype='bf16-mixed' trains with bf16 activations over fp32 master state, dtype='f32' in exact fp32")
     return _lib.WDM_F32
+
+
+def sample_sheet(inp, out, gt):
+    """The reference's sample_images sheet (train_hfrm.py:199-220) of batch element 0: an (H, 3W, 3) uint8 tensor [input | prediction |
+    target], values x * 255 in fp32 -- the prediction clamped to [0, 255] first -- truncated toward zero as the reference's .int() does
+    (not the rounding of wdm_to_u8_hwc).  Computed where the tensors live."""
+    a = inp[0].detach().float() * 255
+    p = torch.clamp(out[0].detach().float() * 255, 0, 255)
+    t = gt[0].detach().float() * 255
+    sheet = torch.cat([a, p, t], dim=2).permute(1, 2, 0)
+    return sheet.to(torch.int32).to(torch.uint8).contiguous()
 
 
 def reference_init_state_dict(shapes, seed: int = 0):
@@ -79,7 +101,8 @@ def reference_init_state_dict(shapes, seed: int = 0):
 class HFRMTrainer:
     def __init__(self, in_channel=3, dim=32, mid_blk_num=6, enc_blk_nums=(2, 2, 2, 4), dec_blk_nums=(2, 2, 2, 2), device=None, dtype=None,
                  lr=2e-4, betas=(0.5, 0.999), eps=1e-8):
-        self._dtype_code = _resolve_train_dtype(dtype)
+        self._act_code = _resolve_train_dtype(dtype)
+        self._dtype_code = _lib.WDM_F32                 # parameters and optimizer state: fp32 in both precisions
         if len(enc_blk_nums) != len(dec_blk_nums):
             raise ValueError("HFRMTrainer: enc_blk_nums and dec_blk_nums must have the same length")
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -101,6 +124,7 @@ class HFRMTrainer:
         t = C.c_void_p()
         _lib.check(L.wdm_hfrm_trainer_create(None, C.byref(cfg), C.byref(t)))
         self._t = t
+        _lib.check(L.wdm_hfrm_trainer_set_precision(t, self._act_code))
         self.layout = OrderedDict()                     # name -> (offset, shape)
         name, ndim, shape, off = C.c_char_p(), C.c_int(), (C.c_int64 * 4)(), C.c_int64()
         for i in range(L.wdm_hfrm_trainer_num_params(t)):
@@ -161,9 +185,20 @@ class HFRMTrainer:
         """The plain state_dict (train_hfrm.py:303-305 saves generator.module.state_dict(): no `module.` prefix, no optimizer state)."""
         torch.save(OrderedDict((k, v.cpu()) for k, v in self.state_dict().items()), path)
 
+    # ---- precision ---------------------------------------------------------------------------------------------------
+    @property
+    def precision(self):
+        return MIXED if self._act_code == _lib.WDM_BF16 else "f32"
+
+    def set_precision(self, dtype):
+        """Switch between "f32" and "bf16-mixed" between steps; parameters, moments and the step count stay."""
+        code = _resolve_train_dtype(dtype)
+        _lib.check(_lib.lib().wdm_hfrm_trainer_set_precision(self._t, code))
+        self._act_code = code
+
     # ---- one step ----------------------------------------------------------------------------------------------------
     def _workspace(self, B, H, W):
-        key = (B, H, W)
+        key = (B, H, W, self._act_code)
         if self._ws_key != key:
             n = int(_lib.lib().wdm_hfrm_trainer_workspace_bytes(self._t, B, H, W))
             if n == 0:
@@ -209,9 +244,10 @@ class HFRMTrainer:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().wdm_hfrm_trainer_adam(self._t, self.step, lr, self.betas[0], self.betas[1], self.eps, 0.0, _lib.stream_ptr()))
 
-    def train_step(self, inp, gt):
-        """One iteration of train_hfrm.py's loop: loss, backward, Adam.  Returns (loss, per-image PSNR of this step's output), both on the device."""
+    def train_step(self, inp, gt, return_output=False):
+        """One iteration of train_hfrm.py's loop: loss, backward, Adam.  Returns (loss, per-image PSNR of this step's output), both on the device
+        (and that output when asked: the sample sheet is drawn from it)."""
         loss, out = self.loss_and_grads(inp, gt, return_output=True)
         loss, psnr = loss.clone(), batch_psnr(gt, out)
         self.optimizer_step()
-        return loss, psnr
+        return (loss, psnr, out) if return_output else (loss, psnr)
