@@ -132,6 +132,25 @@ int wdm_patch_accumulate_c(wdm_handle* h, const float* eps, const int32_t* patch
 int wdm_ddim_from_sums_c(wdm_handle* h, const float* acc_cnt, const float* x_t, int channels, int nimg, int H, int W, float sqrt_1m_at,
                          float sqrt_at, float sqrt_at_next, float c2, float* x0_out, float* x_next_out, void* stream);
 
+/* ---- images of DIFFERENT sizes in one call: the ragged layout -----------------
+ * A ragged C-channel tensor of nimg images is ONE flat f32 buffer: image i occupies the contiguous elements
+ * [C * pix_off[i], C * pix_off[i+1]) as a plain (C, H_i, W_i) NCHW block, pix_off = the prefix sum of H_i * W_i.  One set of tables therefore serves
+ * x_cond (48 channels), x_t / x0 / x_next (pred_channels) and x_other; every W_i is a multiple of 4, so every block starts 16-byte aligned for every C.
+ * Device tables (read-only, built by the caller -- wavedm_amd.sampling.RaggedLayout validates them; the library checks only what the host can see):
+ *   img_tab  int32[nimg][4]  : H_i, W_i, patch_lo_i, patch_hi_i -- [patch_lo, patch_hi) is image i's slice of the patch list, which must be image-major
+ *                              (all of image 0's triples, then image 1's, ...), every window inside its image;
+ *   blk_tab  int32[nimg + 1] : the first 256-pixel block of image i, blocks counted per image (ceil(H_i W_i / 256) each); blk_tab[nimg] = nblk, all blocks;
+ *   pix_off  int64[nimg + 1] : the pixel offsets above.
+ * wdm_pack_channels_ragged: wdm_pack_channels with `src` ragged (nch channels); p <= 128 and nch <= 48 (one workgroup per patch row).
+ * wdm_ddim_update_ragged:   wdm_ddim_update_c (eta = 0) with x_t / x0_out / x_next_out ragged (`channels` channels); eps (n, channels, p, p) as before.
+ * Per image both return the bits of the plain entry points on that image alone (wdm_ddim_update's at channels = 3): the same sums in patch-list order,
+ * the same expression, 0/0 = NaN where no patch covers a pixel.  Bad arguments: WDM_EINVAL, nothing launched. */
+int wdm_pack_channels_ragged(wdm_handle* h, const float* src, int nch, const int32_t* img_tab, const int64_t* pix_off, int nimg,
+                             const int32_t* patches, int n, int p, void* x96, int c_total, int c_off, int dtype, void* stream);
+int wdm_ddim_update_ragged(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t,
+                           const int32_t* img_tab, const int32_t* blk_tab, const int64_t* pix_off, int nimg, int nblk, float sqrt_1m_at,
+                           float sqrt_at, float sqrt_at_next, float c2, float* x0_out, float* x_next_out, void* stream);
+
 /* NCHW f32 (B,C,H,W) -> NHWC dtype (B,H,W,C) and back (used by the drop-in model(x, t) call). */
 int wdm_nchw_to_nhwc(wdm_handle* h, const float* src, void* dst, int B, int C, int H, int W, int dtype,
                      void* stream);

@@ -5,6 +5,8 @@
                                                                                         # the same N as [degraded | gt] pairs through restore()
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/restore_folder_bench.py --kernels
     python scripts/restore_folder_bench.py --summarize DIR                              # the trace -> a table: time and bytes/s per kernel and size
+    python scripts/restore_folder_bench.py --mixed [--n 32] [--steps 25] [--dtype f16]  # args.mix_sizes off / on / on / off: a folder of mixed sizes, the
+                                                                                        # uniform folder (profiles/restore_folder_mixed.md)
 
 Procedural weights (UNet and HFRM), raindrop_wavelet.yml's model; both paths with and without their PNG output."""
 import argparse
@@ -85,6 +87,56 @@ def rates(a):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def mixed(a):
+    """args.mix_sizes against the default grouping (profiles/restore_folder_mixed.md): a seeded folder of N synthetic pictures with sides drawn from 200 ... 900
+    pixels, and the uniform folder (N x 480x720), each through restore_folder with the mode off, on, on, off in ONE process, every leg repeated three times.
+    No PNGs are written (the encoder is not what the mode changes).  One line per leg: img/s per repeat, sampler calls, mean patches per call."""
+    import numpy as np
+    import torch
+    from PIL import Image
+    import wavedm_amd
+    from wavedm_amd import procedural as P
+    torch.set_grad_enabled(False)
+    dev = torch.device("cuda", 0)
+    cfg = P.raindrop_wavelet_config()
+    cfg.device = dev
+    base = SimpleNamespace(resume="", sampling_timesteps=a.steps, local_rank=0, image_folder="", test_set="raindrop", grid_r=16, seed=61)
+    d = wavedm_amd.DenoisingDiffusion_Wavelet(base, cfg, generator="procedural", dtype=a.dtype or "f16")
+    d.model.load_state_dict(P.procedural_state_dict(cfg, seed=61), strict=True)
+    tmp = tempfile.mkdtemp(prefix="wdm_rfm_")
+    try:
+        rng = np.random.default_rng(a.seed)
+        folders = {}
+        for tag in ("mixed", "uniform"):
+            src = os.path.join(tmp, tag)
+            os.makedirs(src)
+            for k in range(a.n):
+                h, w = (int(rng.integers(200, 901)), int(rng.integers(200, 901))) if tag == "mixed" else (480, 720)
+                Image.fromarray(picture(h, w, seed=4 + k)).save(os.path.join(src, f"img{k:03d}.png"))
+            folders[tag] = src
+        print(f"{a.n} images per folder, {a.steps} steps, mode {d.model.dtype_name}, max_batch {wavedm_amd.sampling.DEFAULT_MAX_BATCH}, folder seed {a.seed}")
+        for tag in (["uniform"] if a.uniform_only else ["mixed", "uniform"] if a.folder == "both" else [a.folder]):
+            for leg, mix in enumerate(([False] if a.uniform_only else [False, True, True, False])):
+                args = SimpleNamespace(**vars(base))
+                args.mix_sizes = mix
+                rest = wavedm_amd.DiffusiveRestoration(d, args, cfg, save_images=False)
+                rates_ = []
+                for rep in range(3 + (1 if leg == 0 else 0)):                 # the folder's first pass of all warms the allocator and the workspaces up
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    with contextlib.redirect_stdout(io.StringIO()):
+                        rest.restore_folder(folders[tag], None, r=16)
+                    torch.cuda.synchronize()
+                    rates_.append(a.n / (time.perf_counter() - t0))
+                if leg == 0:
+                    rates_ = rates_[1:]
+                calls = getattr(rest, "last_calls", None)
+                per_call = "" if calls is None else f"   {len(calls)} sampler calls, {sum(i[2] for i in rest.last_info) / len(calls):.1f} patches per call"
+                print(f"{tag:8s} mix_sizes {'on ' if mix else 'off'}: {'  '.join(f'{v:.3f}' for v in rates_)} img/s{per_call}", flush=True)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def kernels(a):
     """Each kernel REPS times per size, the sizes one after the other (the summary tells them apart by their grids)."""
     import torch
@@ -130,12 +182,18 @@ if __name__ == "__main__":
     ap.add_argument("--n", type=int, default=32)
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--dtype", default=None, choices=["f16", "bf16", "f32x3", "f32"], help="default: the package's automatic mode (f16 sampler, fp32 HFRM)")
+    ap.add_argument("--mixed", action="store_true", help="args.mix_sizes off / on / on / off over a folder of mixed sizes and over the uniform folder")
+    ap.add_argument("--uniform-only", dest="uniform_only", action="store_true", help="with --mixed: the uniform folder with the mode off only (runs on a build without the mode)")
+    ap.add_argument("--folder", default="both", choices=["both", "mixed", "uniform"], help="with --mixed: which folder(s)")
+    ap.add_argument("--seed", type=int, default=7, help="with --mixed: the seed of the folder's sizes")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--summarize", default=None, metavar="DIR")
     a = ap.parse_args()
     if a.summarize:
         summarize(a.summarize)
+    elif a.mixed:
+        mixed(a)
     elif a.kernels:
         kernels(a)
     else:

@@ -45,6 +45,9 @@ def parse(argv=None):
     ap.add_argument("--ema", action="store_true", help="eval: load the EMA weights of the checkpoint")
     ap.add_argument("--dtype", default=None, choices=["f16", "bf16", "f32x3", "f32"])
     ap.add_argument("--images_per_call", type=int, default=0, help="eval: images per sampler call; 0 = automatic (as many same-sized images as fill the UNet calls), 1 = the reference's loop")
+    ap.add_argument("--mix-sizes", dest="mix_sizes", action="store_true",
+                    help="restore: images of DIFFERENT sizes share a sampler call (as many consecutive files as fill the UNet calls, or --images_per_call of them); "
+                         "every file's result is the one it gets alone, bit for bit.  Off by default: only files of equal size share a call")
     ap.add_argument("--full_length", action="store_true", help="eval: also run the four DDIM steps behind x0_preds[-5], which restore() never reads (the reference's step count)")
     ap.add_argument("--hfrm_ckpt", default=None)
     ap.add_argument("--hfrm-local", dest="hfrm_local", action="store_true",

@@ -121,6 +121,18 @@ int wdm_ddim_from_sums_c(wdm_handle* h, const float* acc_cnt, const float* x_t, 
     if (!h || !acc_cnt || !x_t || !x0_out || !x_next_out || channels <= 0) WDM_FAIL(WDM_EINVAL, "wdm_ddim_from_sums_c: null argument");
     return k_ddim_from_sums(acc_cnt, x_t, nimg, H, W, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out, (hipStream_t)stream, channels);
 }
+int wdm_pack_channels_ragged(wdm_handle* h, const float* src, int nch, const int32_t* img_tab, const int64_t* pix_off, int nimg, const int32_t* patches, int n,
+                             int p, void* x96, int c_total, int c_off, int dtype, void* stream) {
+    if (!h || !src || !img_tab || !pix_off || !patches || !x96) WDM_FAIL(WDM_EINVAL, "wdm_pack_channels_ragged: null argument");
+    return k_pack_channels_ragged(src, nch, img_tab, pix_off, nimg, patches, n, p, x96, c_total, c_off, dtype, (hipStream_t)stream);
+}
+int wdm_ddim_update_ragged(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t, const int32_t* img_tab,
+                           const int32_t* blk_tab, const int64_t* pix_off, int nimg, int nblk, float sqrt_1m_at, float sqrt_at, float sqrt_at_next, float c2,
+                           float* x0_out, float* x_next_out, void* stream) {
+    if (!h || !eps || !patches || !x_t || !img_tab || !blk_tab || !pix_off || !x0_out || !x_next_out) WDM_FAIL(WDM_EINVAL, "wdm_ddim_update_ragged: null argument");
+    return k_ddim_update_ragged(eps, patches, n, p, channels, x_t, img_tab, blk_tab, pix_off, nimg, nblk, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out,
+                                (hipStream_t)stream);
+}
 int wdm_nchw_to_nhwc(wdm_handle* h, const float* src, void* dst, int B, int C, int H, int W, int dtype, void* stream) {
     if (!h || !src || !dst) WDM_FAIL(WDM_EINVAL, "wdm_nchw_to_nhwc: null argument");
     return k_nchw_to_nhwc(src, dst, B, C, H, W, dtype, (hipStream_t)stream);

@@ -145,6 +145,11 @@ int k_ddim_from_sums(const float* acc_cnt, const float* x_t, int nimg, int H, in
 int k_ddim_update_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, int nimg, int H, int W,
                     float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s, const float* noise = nullptr, float c1 = 0.f);
 int k_patch_accumulate_c(const float* eps, const int32_t* patches, int n, int p, int C, int nimg, int H, int W, float* acc_cnt, hipStream_t s);
+// images of different sizes in one call (the ragged layout, include/wavedm.h): the gather and the eta = 0 scatter-mean + DDIM update
+int k_pack_channels_ragged(const float* src, int nch, const int32_t* img_tab, const int64_t* pix_off, int nimg, const int32_t* patches, int n, int p, void* x96,
+                           int c_total, int c_off, int dtype, hipStream_t s);
+int k_ddim_update_ragged(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, const int32_t* img_tab, const int32_t* blk_tab,
+                         const int64_t* pix_off, int nimg, int nblk, float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s);
 int k_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, int dtype, hipStream_t s);
 int k_nhwc_to_nchw(const void* src, float* dst, int B, int C, int H, int W, int dtype, hipStream_t s);
 // GroupNorm(32, eps): partial statistics float4[B][nslab][C] = (pivot, sum(x-K), sum((x-K)^2), n) and their finalisation

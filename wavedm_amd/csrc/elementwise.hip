@@ -376,6 +376,110 @@ int k_patch_accumulate_c(const float* eps, const int32_t* patches, int n, int p,
     return launch_scatter_c<true>(eps, patches, n, p, C, nullptr, nimg, H, W, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, 0.f, acc_cnt, s);
 }
 
+// ---- images of DIFFERENT sizes in one call: the ragged layout (include/wavedm.h).  A ragged C-channel tensor is one flat f32 buffer, image i
+// the plain (C, H_i, W_i) block at element C * pix_off[i]; img_tab holds (H, W, patch_lo, patch_hi) per image -- [patch_lo, patch_hi) is the image's slice of the
+// image-major patch list --, blk_tab the first 256-pixel block of each image (blk_tab[nimg] = all blocks), pix_off the 64-bit prefix sum of H_i W_i.  The two
+// kernels that cross image boundaries are the plain ones with H, W and the base pointer looked up instead of passed: the same reads, the same sums in the same
+// order, the same expression -- per image the bits of the plain kernels on that image alone.
+template <typename T>
+__global__ __launch_bounds__(256) void pack_channels_rows_ragged_kernel(const float* __restrict__ src, int nch, const int32_t* __restrict__ img_tab,
+                                                                        const int64_t* __restrict__ pix_off, const int32_t* __restrict__ patches, int p,
+                                                                        T* __restrict__ x96, int c_total, int c_off) {
+    h16_mode_init<T>();
+    __shared__ float tile[PACK_MAX_CH * (PACK_MAX_P + 1)];
+    const int k = (int)(blockIdx.x / (unsigned)p), yy = (int)(blockIdx.x - (unsigned)k * (unsigned)p);
+    const int img = patches[3 * k], hi = patches[3 * k + 1], wi = patches[3 * k + 2];
+    const int H = img_tab[4 * img], W = img_tab[4 * img + 1];
+    const int ld = p + 1, tot = nch * p;
+    const float* row0 = src + (long long)nch * pix_off[img] + (long long)(hi + yy) * W + wi;
+    for (int id = threadIdx.x; id < tot; id += 256) {
+        const int c = id / p, xx = id - c * p;
+        tile[c * ld + xx] = row0[(long long)c * H * W + xx];
+    }
+    __syncthreads();
+    T* out = x96 + ((long long)k * p + yy) * p * c_total + c_off;
+    for (int id = threadIdx.x; id < tot; id += 256) {
+        const int xx = id / nch, c = id - xx * nch;
+        TI<T>::st(out, (long long)xx * c_total + c, tile[c * ld + xx]);
+    }
+}
+
+int k_pack_channels_ragged(const float* src, int nch, const int32_t* img_tab, const int64_t* pix_off, int nimg, const int32_t* patches, int n, int p, void* x96,
+                           int c_total, int c_off, int dtype, hipStream_t s) {
+    if (nimg < 1 || n < 1 || p < 1 || nch < 1 || c_off < 0 || c_off + nch > c_total) WDM_FAIL(WDM_EINVAL, "pack_channels_ragged: bad arguments");
+    if (p > PACK_MAX_P || nch > PACK_MAX_CH || (long long)n * p >= 2147483647LL)
+        WDM_FAIL(WDM_EINVAL, "pack_channels_ragged: %d patches of %d x %d with %d channels exceed the row kernel (p <= %d, channels <= %d)", n, p, p, nch, PACK_MAX_P, PACK_MAX_CH);
+    if (is_h16(dtype)) WDM_H16_SWITCH(dtype, hipLaunchKernelGGL(pack_channels_rows_ragged_kernel<H16>, dim3(n * p), dim3(256), 0, s, src, nch, img_tab, pix_off, patches, p, (H16*)x96, c_total, c_off));
+    else hipLaunchKernelGGL(pack_channels_rows_ragged_kernel<float>, dim3(n * p), dim3(256), 0, s, src, nch, img_tab, pix_off, patches, p, (float*)x96, c_total, c_off);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
+// scatter_update_c_kernel over the ragged layout, eta = 0.  Workgroup = 256 consecutive pixels of ONE image, found by a binary search of blk_tab on the block
+// index -- uniform per workgroup, a few scalar loads --; the image's span of the patch list comes from img_tab (no scan).  One writer per element, no atomics.
+template <int CH>
+__global__ __launch_bounds__(256) void scatter_update_ragged_kernel(const float* __restrict__ eps, const int32_t* __restrict__ patches, int n, int p, int C,
+                                                                    const float* __restrict__ x_t, const int32_t* __restrict__ img_tab,
+                                                                    const int32_t* __restrict__ blk_tab, const int64_t* __restrict__ pix_off, int nimg, float s1m,
+                                                                    float sa, float san, float c2, float* __restrict__ x0o, float* __restrict__ xno,
+                                                                    const float* __restrict__ noise, float c1) {
+    const int blk = blockIdx.x, c0 = blockIdx.y * CH;
+    int a = 0, b = nimg;                       // blk_tab[a] <= blk < blk_tab[b]
+    while (b - a > 1) {
+        const int m = (a + b) >> 1;
+        if (blk_tab[m] <= blk) a = m; else b = m;
+    }
+    const int img = a;
+    const int H = img_tab[4 * img], W = img_tab[4 * img + 1];
+    const int lo = max(img_tab[4 * img + 2], 0), hi = min(img_tab[4 * img + 3], n);
+    const int HW = H * W;
+    const int pix = (blk - blk_tab[img]) * 256 + threadIdx.x;
+    if (pix >= HW) return;
+    const int yy = pix / W, xx = pix - yy * W;
+    float acc[CH], cnt = 0.f;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) acc[j] = 0.f;
+    const long long pp = (long long)p * p;
+    for (int k = lo; k < hi; ++k) {
+        const int pi = patches[3 * k], hi_ = patches[3 * k + 1], wi = patches[3 * k + 2];
+        if (pi == img && (unsigned)(yy - hi_) < (unsigned)p && (unsigned)(xx - wi) < (unsigned)p) {
+            const float* e = eps + ((long long)k * C + c0) * pp + (long long)(yy - hi_) * p + (xx - wi);
+#pragma unroll
+            for (int j = 0; j < CH; ++j)
+                if (c0 + j < C) acc[j] += e[j * pp];
+            cnt += 1.f;
+        }
+    }
+    const long long base = (long long)C * pix_off[img];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        if (c0 + j >= C) continue;
+        const long long id = base + (long long)(c0 + j) * HW + pix;
+        const float et = acc[j] / cnt;
+        const float xt = x_t[id];
+        const float x0 = (xt - et * s1m) / sa;
+        x0o[id] = x0;
+        xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;      // scatter_update_c_kernel's line, character for character; noise is always null here (eta = 0)
+    }
+}
+
+int k_ddim_update_ragged(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, const int32_t* img_tab, const int32_t* blk_tab,
+                         const int64_t* pix_off, int nimg, int nblk, float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s) {
+    if (nimg < 1 || n < 1 || p < 1 || C < 1 || nblk < 1) WDM_FAIL(WDM_EINVAL, "ddim_update_ragged: bad arguments");
+    if (C > 65535) WDM_FAIL(WDM_EINVAL, "ddim_update_ragged: %d channels exceed the launch grid", C);
+    // channels per thread: launch_scatter_c's rule, counted over all images' pixel blocks
+    int ch = 4;
+    while (ch > 1 && (long long)nblk * ((C + ch - 1) / ch) < 1024) ch >>= 1;
+    const dim3 grid(nblk, (C + ch - 1) / ch);
+#define WDM_SCATTER_R(CH_) hipLaunchKernelGGL((scatter_update_ragged_kernel<CH_>), grid, dim3(256), 0, s, eps, patches, n, p, C, x_t, img_tab, blk_tab, pix_off, nimg, s1m, sa, san, c2, x0, xn, (const float*)nullptr, 0.f)
+    if (ch == 1) WDM_SCATTER_R(1);
+    else if (ch == 2) WDM_SCATTER_R(2);
+    else WDM_SCATTER_R(4);
+#undef WDM_SCATTER_R
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
 // =================================================================================================
 // layout conversion at the drop-in model(x, t) boundary
 // =================================================================================================

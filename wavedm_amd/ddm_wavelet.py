@@ -292,6 +292,27 @@ class DenoisingDiffusion_Wavelet(object):
             xs = xs[0][-1]
         return xs
 
+    def sample_image_ragged(self, x_cond, x, layout, x_other=None, use_other=False, stop_at=None):
+        """sample_image(last=False, patch_locs=<each image's grid>) for images of DIFFERENT sizes in one sampler call: x_cond, x (the start noise) and x_other are
+        ragged tensors of `layout` (sampling.RaggedLayout).  eta = 0, one device, not captured into a hipGraph; every image's lists hold the bits it gets alone
+        (sampling.ddim_sample_ragged).  -> (xs, x0_preds), lists of flat tensors."""
+        self._require_plain_unet("sample_image_ragged")
+        if getattr(self, "patch_group", None) is not None:
+            raise NotImplementedError("sample_image_ragged: the patch-sharded mode (patch_group) is not built for ragged calls")
+        skip = self.config.diffusion.num_diffusion_timesteps // self.args.sampling_timesteps
+        seq = range(0, self.config.diffusion.num_diffusion_timesteps, skip)
+        if not use_other:
+            x_other = None
+        if not self.config.data.begin_from_noise:                              # ddm_wavelet.py:445-447, image by image: the same element-wise expression
+            a = (1 - self.betas).cumprod(dim=0)[self.num_timesteps - 1]
+            pc, nc = x.numel() // layout.pix_off[-1], x_cond.numel() // layout.pix_off[-1]
+            x0 = torch.empty_like(x)
+            for i in range(layout.nimg):
+                layout.view(x0, pc, i).copy_(layout.view(x_cond, nc, i)[:, :pc] * a.sqrt() + layout.view(x, pc, i) * (1.0 - a).sqrt())
+            x = x0
+        return sampling.ddim_sample_ragged(self.model, x, x_cond, x_other, layout, list(seq), self.betas,
+                                           max_batch=getattr(self.args, "max_batch", None) or sampling.DEFAULT_MAX_BATCH, stop_at=stop_at)
+
     def generalized_steps_overlapping(self, x, x_cond, seq, model, b, eta=0., corners=None, p_size=None,
                                       manual_batching=True, total=None, x_other=None, use_global=False, use_other=False, stop_at=None):
         """ddm_wavelet.py:437-506 on the device (eta != 0 included: :500-502, one randn_like(x) per step from the device generator)."""

@@ -144,6 +144,52 @@ def estimate_restore_bytes(h, w, n_img, config, max_batch=None, dtype=None, r=No
     return sum(restore_terms(h, w, n_img, config, max_batch, dtype, r, steps, hfrm_local).values())
 
 
+def folder_patch_count(h, w, p, r=None):
+    """Patches of one h x w photograph in restore_folder: the grid over its padded wavelet-domain size (p = data.image_size, r = the grid's stride)."""
+    hp, wp = imageio.padded_size(h, w, 16, 4 * int(p))
+    hl, wl = sampling.overlapping_grid_indices(hp // 4, wp // 4, int(p), r)
+    return len(hl) * len(wl)
+
+
+def estimate_restore_bytes_mixed(sizes, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None):
+    """estimate_restore_bytes for ONE sampler call over photographs of different sizes (args.mix_sizes), `sizes` a list of (h, w) in pixels: every image's
+    own x96, eps and full terms (all three are linear in the images), the LARGEST HFRM term -- the HFRM runs over one run of equal-sized images at a time;
+    each image's term is taken as if the whole group had its size, the most any run of it can need, which also keeps the estimate from falling when an image
+    grows out of a run --, and the UNet's workspace for min(total patches, max_batch).  Equal to estimate_restore_bytes(h, w, n, ...) for n equal sizes;
+    non-decreasing when an image is added or enlarged."""
+    from .unet import _make_config, resolve_dtype
+    sizes = [(int(h), int(w)) for (h, w) in sizes]
+    if not sizes:
+        raise ValueError("estimate_restore_bytes_mixed: no images")
+    mb, p = int(max_batch or sampling.DEFAULT_MAX_BATCH), int(config.data.image_size)
+    total, hfrm, n = 0, 0, 0
+    for (h, w) in sizes:
+        t = restore_terms(h, w, 1, config, mb, dtype, r, steps, hfrm_local)
+        total += t["x96"] + t["eps"] + t["full"]
+        n += folder_patch_count(h, w, p, r)
+        hfrm = max(hfrm, restore_terms(h, w, len(sizes), config, mb, dtype, r, steps, hfrm_local)["hfrm"])
+    return total + hfrm + _workspace_bytes("unet", _make_config(config, resolve_dtype(config, dtype)), min(n, mb))
+
+
+MIX_MAX_IMAGES = 64      # images per sampler call of the automatic mixed-size grouping, at most
+
+
+def mix_group_step(counts, nxt, max_batch, images_per_call=None):
+    """The grouping rule of args.mix_sizes, host arithmetic: the open group holds images of `counts` patches each (input order), the next image has `nxt`.
+    -> (before, after): close the open group BEFORE the image joins (it then opens a new one), close the group AFTER it joined.
+    images_per_call = N: N images per call whatever their sizes.  Automatic (None, 0, "auto"): a group is closed when the next image would push its patches
+    over max_batch -- one UNet call per step carries the whole group --, and at MIX_MAX_IMAGES images; an image of more than max_batch patches is a group of
+    its own.  (The feeder adds today's rule on top: with automatic grouping, what is there goes at once while the sampler waits for input.)"""
+    counts, nxt, mb = list(counts), int(nxt), int(max_batch)
+    if images_per_call not in (None, 0, "auto", "Auto", "AUTO"):
+        return False, len(counts) + 1 >= max(1, int(images_per_call))
+    if nxt > mb:
+        return bool(counts), True
+    if counts and sum(counts) + nxt > mb:
+        return True, False
+    return False, len(counts) + 1 >= MIX_MAX_IMAGES
+
+
 class _StageBudget:
     """Bytes of staged input (pinned host + device copies) the feeder may hold ahead of the sampler."""
 
@@ -461,12 +507,47 @@ class DiffusiveRestoration:
                 budget.acquire(xp.numel())
                 q.put((xd, names, ev, xp))
 
+            def emit_mixed(group):
+                """args.mix_sizes: the group's images, of any sizes, in ONE flat pinned u8 buffer (image k at offs[k], H_k * W_k * 3 bytes) and one H2D copy."""
+                self._mark(f"feeder: mixed group of {len(group)} read")
+                names, shapes = [it[1] for it in group], [tuple(it[0].shape[:2]) for it in group]
+                if group[0][0].is_cuda:
+                    x = torch.cat([it[0].reshape(-1) for it in group])
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(dev))
+                    q.put((x, names, ev, None, shapes))
+                    return
+                xp = _lib.pinned_dontfork(torch.empty(sum(3 * h * w for (h, w) in shapes), dtype=torch.uint8, pin_memory=True))
+                o = 0
+                for it in group:
+                    xp[o:o + it[0].numel()].copy_(it[0].reshape(-1))
+                    o += it[0].numel()
+                with torch.cuda.stream(copy_stream):
+                    xd = xp.to(dev, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(copy_stream)
+                budget.acquire(xp.numel())
+                q.put((xd, names, ev, xp, shapes))
+
+            mix, counts = bool(getattr(self.args, "mix_sizes", False)), []
             for img, name in items:
                 if stop.is_set():
                     return
                 name = name[0] if isinstance(name, (list, tuple)) else name
                 if not (isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[-1] == 3):
                     raise TypeError(f"restore_folder: {name!r}: expected a uint8 (H,W,3) tensor, got {getattr(img, 'dtype', type(img))} {tuple(getattr(img, 'shape', ()))}")
+                if mix:                                                     # images of any sizes share a call, in input order: mix_group_step
+                    cnt = folder_patch_count(img.shape[0], img.shape[1], p4 // 4, r)
+                    before, after = mix_group_step(counts, cnt, self._max_batch(), getattr(self.args, "images_per_call", None))
+                    if before and group:
+                        emit_mixed(group)
+                        group, counts = [], []
+                    group.append((img, name))
+                    counts.append(cnt)
+                    if after or (auto and hungry.is_set()):
+                        emit_mixed(group)
+                        group, counts = [], []
+                    continue
                 if group and group[0][0].shape != img.shape:               # only images of equal ORIGINAL size share a call
                     emit(group)
                     group = []
@@ -478,7 +559,7 @@ class DiffusiveRestoration:
                     emit(group)
                     group = []
             if group:
-                emit(group)
+                (emit_mixed if mix else emit)(group)
         except BaseException as e:                                             # surfaced by restore_folder()
             q.put(e)
         finally:
@@ -532,6 +613,72 @@ class DiffusiveRestoration:
         done.record(torch.cuda.current_stream(dev))
         return dict(names=names, done=done, HW=(H, W), patches=len(corners), kept=kept, keep=(u8, q8))
 
+    def _fits_mixed(self, shapes, r):
+        """_fits for one sampler call over photographs of different sizes (estimate_restore_bytes_mixed)."""
+        dev = self.diffusion.device
+        est = estimate_restore_bytes_mixed(shapes, self.config, self._max_batch(), self.diffusion.model.dtype_name, r, int(self.diffusion.args.sampling_timesteps),
+                                           hfrm_local=getattr(self.diffusion, "hfrm_local", None))
+        limit = getattr(self.args, "max_restore_bytes", None)
+        if not limit:
+            limit = 0.8 * (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
+        return est <= limit, est, limit
+
+    def _launch_mixed_group(self, imgs, names, r, out_paths, keep_outputs):
+        """args.mix_sizes: one sampler call over photographs of DIFFERENT sizes (imgs: (1,H,W,3) u8 on the device): everything QUEUED, nothing waited for.
+        x_cond, the start noise and x_other are ragged tensors (sampling.RaggedLayout); ingest, DWT, HFRM and its DWT run per run of consecutive images of equal
+        padded size and write views of them, compose / crop / 8-bit conversion run per image -- all with the kernels of _launch_folder_group, so every file's
+        bits are the ones it gets there."""
+        cfg, d = self.config, self.diffusion
+        pc, ob, p = cfg.model.pred_channels, cfg.model.other_channels_begin, cfg.data.image_size
+        dev = d.device
+        n = len(imgs)
+        x_in = [imageio.ingest(u, 16, 4 * p) for u in imgs]
+        layout = sampling.RaggedLayout([(x.shape[-2] // 4, x.shape[-1] // 4) for x in x_in], p, r)
+        split = pc < cfg.model.in_channels
+        use_other = bool(cfg.model.use_other_channels) and split
+        n_other = cfg.model.in_channels - ob
+        x_cond = torch.empty(layout.numel(48), device=dev, dtype=torch.float32)
+        x_other = torch.empty(layout.numel(n_other), device=dev, dtype=torch.float32) if use_other else None
+        noise = torch.empty(layout.numel(pc), device=dev, dtype=torch.float32)
+        run_view = lambda flat, C, i0, i1: flat[C * layout.pix_off[i0]:C * layout.pix_off[i1]].view((i1 - i0, C) + layout.sizes[i0])
+        hf_wav = [None] * n
+        i0 = 0
+        while i0 < n:
+            i1 = i0 + 1
+            while i1 < n and layout.sizes[i1] == layout.sizes[i0]:
+                i1 += 1
+            x = x_in[i0] if i1 - i0 == 1 else torch.cat(x_in[i0:i1], dim=0)
+            d.wavelet_dec.forward_affine(x, out=run_view(x_cond, 48, i0, i1))
+            if split:                                                          # (as _launch_folder_group: no HFRM call at all when every band is diffused)
+                hw = d.wavelet_dec.forward_affine(d.generator(x).contiguous())
+                for k in range(i0, i1):
+                    hf_wav[k] = hw[k - i0:k - i0 + 1]
+                if use_other:
+                    run_view(x_other, n_other, i0, i1).copy_(hw[:, ob:])
+            i0 = i1
+        seed = getattr(self.args, "seed", None)
+        seed = 61 if seed is None else seed
+        for k, name in enumerate(names):
+            layout.view(noise, pc, k).copy_(torch.randn((1, pc) + layout.sizes[k], device=dev, generator=torch.Generator(device=dev).manual_seed(file_seed(seed, name))))
+        early = bool(getattr(self.args, "early_stop", True))
+        xs, x0_preds = d.sample_image_ragged(x_cond, noise, layout, x_other=x_other, use_other=use_other, stop_at=-5 if early else None)
+        pred = x0_preds[-5]
+        self._mark("main: sampler queued")
+        q8s, kept = [], []
+        for k, name in enumerate(names):
+            H, W = imgs[k].shape[1:3]
+            lo = layout.view(pred, pc, k)
+            out = d.wavelet_rec.compose(lo, hf_wav[k] if split else lo, pc)
+            q8 = imageio.to_u8_hwc(out, crop=(H, W))
+            if out_paths[name] is not None:
+                self.writer.save_u8(q8[0], out_paths[name])
+            q8s.append(q8)
+            if keep_outputs:
+                kept.append(out[:, :, :H, :W].clone())
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        return dict(names=names, done=done, HW=[tuple(u.shape[1:3]) for u in imgs], patches=list(layout.patch_counts), kept=kept, keep=(imgs, q8s))
+
     def restore_folder(self, src, dst=None, r=None, recursive=False, keep_outputs=False):
         """Restore photographs at their own size, without ground truth -> [(name, output path or None), ...] in input order.
 
@@ -543,7 +690,11 @@ class DiffusiveRestoration:
         -> stitched sampler, x0_preds[-5] -> IDWT -> crop + 8-bit -> writer.  With args.hfrm_local the HFRM's pooling windows run over the PADDED image (ingest's
         symmetric extension included), like every other layer of it.  The start noise of a file comes from its own generator, seeded with
         file_seed(args.seed, name).  A group that estimate_restore_bytes puts over the memory limit (args.max_restore_bytes, else 0.8 of the free device
-        memory) runs one image per call; one image over it is a RuntimeError before any of its kernels is launched."""
+        memory) runs one image per call; one image over it is a RuntimeError before any of its kernels is launched.
+        args.mix_sizes (default False): consecutive files of DIFFERENT sizes share a sampler call as well -- `images_per_call` of them, or
+        automatically as many as fill one UNet call (mix_group_step) --, on the ragged layout of sampling.RaggedLayout; files are never reordered, and every
+        file's result, the printed lines, last_info, last_outputs and the returned list are what the mode gives switched off, bit for bit.  self.last_calls
+        holds one tuple of names per sampler call of the last run, in either mode."""
         import queue
         import threading
         from . import datasets
@@ -570,12 +721,15 @@ class DiffusiveRestoration:
             self.writer = imageio.AsyncImageWriter()
         results, outputs, taken, pending = [], [], {}, []
         self.last_info = []
+        self.last_calls = []                                                    # one tuple of names per sampler call, in order
 
         def finish(g):
             g["done"].synchronize()
-            for name in g["names"]:
-                print(f"{name}: {g['HW'][1]}x{g['HW'][0]}, {g['patches']} patches")
-                self.last_info.append((name, g["HW"], g["patches"]))
+            for k, name in enumerate(g["names"]):
+                mixed = isinstance(g["patches"], list)                         # a mixed-size call: every image has its own size and patch count
+                HW, patches = (g["HW"][k], g["patches"][k]) if mixed else (g["HW"], g["patches"])
+                print(f"{name}: {HW[1]}x{HW[0]}, {patches} patches")
+                self.last_info.append((name, HW, patches))
             outputs.extend(g["kept"])
 
         q, stop = queue.Queue(), threading.Event()
@@ -596,7 +750,8 @@ class DiffusiveRestoration:
                         break
                     if isinstance(staged, BaseException):
                         raise staged
-                    u8, names, copied, pinned = staged
+                    u8, names, copied, pinned = staged[:4]
+                    shapes = staged[4] if len(staged) > 4 else None            # args.mix_sizes: a flat buffer of images of these (H, W)
                     budget.release(u8.numel() if pinned is not None else 0)
                     out_paths = {}
                     for name in names:
@@ -609,16 +764,33 @@ class DiffusiveRestoration:
                     cur = torch.cuda.current_stream(d.device)
                     cur.wait_event(copied)
                     u8.record_stream(cur)                                      # (allocated on the feeder's copy stream)
-                    n, H, W = u8.shape[:3]
+                    if shapes is None:
+                        n, H, W = u8.shape[:3]
+                        image = lambda k: u8[k:k + 1]
+                        shape = lambda k: (H, W)
+                        together = n == 1 or self._fits(H, W, n, r)[0]
+                    else:
+                        n = len(names)
+                        offs = [sum(3 * h * w for (h, w) in shapes[:k]) for k in range(n)]
+                        image = lambda k: u8[offs[k]:offs[k] + 3 * shapes[k][0] * shapes[k][1]].view((1,) + tuple(shapes[k]) + (3,))
+                        shape = lambda k: shapes[k]
+                        together = n == 1 or self._fits_mixed(shapes, r)[0]
                     # a group that does not fit runs one image per call; one image that does not fit is refused before any kernel of it is launched
-                    calls = [(0, n)] if n == 1 or self._fits(H, W, n, r)[0] else [(k, k + 1) for k in range(n)]
+                    calls = [(0, n)] if together else [(k, k + 1) for k in range(n)]
                     for lo, hi in calls:
                         if hi - lo == 1:
+                            H, W = shape(lo)
                             ok, est, limit = self._fits(H, W, 1, r)
                             if not ok:
                                 raise RuntimeError(f"restore_folder: {names[lo]!r} ({W}x{H}) needs an estimated {est} bytes of device memory, "
                                                    f"{int(limit)} are available (args.max_restore_bytes, else 0.8 of the free memory)")
-                        g = self._launch_folder_group(u8[lo:hi], names[lo:hi], r, out_paths, keep_outputs)      # group k queued behind group k - 1 ...
+                        self.last_calls.append(tuple(names[lo:hi]))
+                        if shapes is None:
+                            g = self._launch_folder_group(u8[lo:hi], names[lo:hi], r, out_paths, keep_outputs)      # group k queued behind group k - 1 ...
+                        elif hi - lo == 1:                                     # one image: the plain path (the same bits either way)
+                            g = self._launch_folder_group(image(lo), names[lo:hi], r, out_paths, keep_outputs)
+                        else:
+                            g = self._launch_mixed_group([image(k) for k in range(lo, hi)], names[lo:hi], r, out_paths, keep_outputs)
                         self._mark("main: group queued")
                         pending.append(g)
                         while len(pending) > 1:

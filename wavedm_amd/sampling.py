@@ -200,6 +200,163 @@ class scatter_update_fns:
             _lib.check(self.L.wdm_ddim_from_sums_c(self.h, acc_cnt, xt, self.pc, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
 
 
+class RaggedLayout:
+    """Images of DIFFERENT sizes in one sampler call (include/wavedm.h): a ragged C-channel tensor is one flat f32 buffer in which image i
+    is the plain (C, h_i, w_i) block at element C * pix_off[i], pix_off the prefix sum of h_i * w_i -- one layout for x_cond, x_t / x0 / x_next and x_other.
+
+    sizes: wavelet-domain (h, w) per image, each side >= p, every width a multiple of 4 (so that every block starts 16-byte aligned for every C).
+    The patch list is image-major: `overlapping_grid_indices(h_i, w_i, p, r)` per image, in the order ddim_sample gives one image's corner list.
+    `RaggedLayout.from_patches(sizes, p, patches)` takes an explicit list of (img, hi, wi) instead (image-major, every window inside its image).
+    Everything here is host arithmetic; `tables(dev)` uploads the device tables once per distinct content (_device_const)."""
+    BLOCK = 256         # pixels per workgroup of wdm_ddim_update_ragged
+
+    def __init__(self, sizes, p, r=None, patches=None):
+        self.p = p = int(p)
+        self.sizes = tuple((int(h), int(w)) for (h, w) in sizes)
+        if not self.sizes or p < 1:
+            raise ValueError(f"RaggedLayout: {len(self.sizes)} images, patch size {p}")
+        for i, (h, w) in enumerate(self.sizes):
+            if h < p or w < p:
+                raise ValueError(f"RaggedLayout: image {i} ({h}x{w}) is smaller than one {p}x{p} patch")
+            if w % 4:
+                raise ValueError(f"RaggedLayout: image {i}'s width {w} is not a multiple of 4")
+            if h * w > 2 ** 31 - 1 - self.BLOCK:
+                raise ValueError(f"RaggedLayout: image {i} ({h}x{w}) exceeds 2^31 pixels")
+        nimg = len(self.sizes)
+        if patches is None:
+            tri = []
+            for i, (h, w) in enumerate(self.sizes):
+                hl, wl = overlapping_grid_indices(h, w, p, r)
+                tri += [(i, a, b) for a in hl for b in wl]
+        else:
+            tri = [tuple(int(v) for v in c) for c in patches]
+            if not tri or any(len(c) != 3 for c in tri):
+                raise ValueError("RaggedLayout: the patch list needs at least one (img, hi, wi) triple")
+            for k, (im, hi, wi) in enumerate(tri):
+                if not 0 <= im < nimg:
+                    raise ValueError(f"RaggedLayout: patch {k} names image {im} of {nimg}")
+                if k and im < tri[k - 1][0]:
+                    raise ValueError(f"RaggedLayout: the patch list is not image-major (patch {k} of image {im} follows image {tri[k - 1][0]}'s)")
+                h, w = self.sizes[im]
+                if not (0 <= hi and hi + p <= h and 0 <= wi and wi + p <= w):
+                    raise ValueError(f"RaggedLayout: patch {(im, hi, wi)} of size {p} leaves its {h}x{w} image")
+        if len(tri) * p >= 2 ** 31 - 1:
+            raise ValueError(f"RaggedLayout: {len(tri)} patches of {p} rows exceed the launch grid")
+        self.patches = tuple(tri)
+        self.n = len(tri)
+        counts = [0] * nimg
+        for (im, _, _) in tri:
+            counts[im] += 1
+        self.patch_counts = tuple(counts)
+        self.patch_lo = tuple(sum(counts[:i]) for i in range(nimg))
+        self.pix_off = tuple(sum(h * w for (h, w) in self.sizes[:i]) for i in range(nimg + 1))
+        blocks = [-(-(h * w) // self.BLOCK) for (h, w) in self.sizes]
+        self.blk_off = tuple(sum(blocks[:i]) for i in range(nimg + 1))
+        if self.blk_off[-1] > 2 ** 31 - 1:
+            raise ValueError("RaggedLayout: the group exceeds 2^31 pixel blocks")
+        assert all(o % 4 == 0 for o in self.pix_off), "every image's block starts 16-byte aligned for every channel count"
+        self.img_tab = tuple((h, w, lo, lo + c) for (h, w), lo, c in zip(self.sizes, self.patch_lo, self.patch_counts))
+
+    @classmethod
+    def from_patches(cls, sizes, p, patches):
+        return cls(sizes, p, patches=patches)
+
+    @property
+    def nimg(self):
+        return len(self.sizes)
+
+    def numel(self, C):
+        """Elements of a ragged C-channel tensor."""
+        return int(C) * self.pix_off[-1]
+
+    def view(self, flat, C, i):
+        """Image i of a ragged C-channel tensor as an ordinary (1, C, h_i, w_i) view."""
+        h, w = self.sizes[i]
+        C = int(C)
+        return flat[C * self.pix_off[i]:C * self.pix_off[i + 1]].view(1, C, h, w)
+
+    def tables(self, dev):
+        """(patches int32 (n,3), img_tab int32 (nimg,4), blk_tab int32 (nimg+1), pix_off int64 (nimg+1)) on `dev`."""
+        return (_device_const(dev, "patches", self.patches, torch.int32), _device_const(dev, "ragged_img", self.img_tab, torch.int32),
+                _device_const(dev, "ragged_blk", self.blk_off, torch.int32), _device_const(dev, "ragged_pix", self.pix_off, torch.int64))
+
+
+def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=64, keep="all", stop_at=None):
+    """ddim_sample's plain loop (one stream, unsharded, eta = 0) for images of DIFFERENT sizes in one call.
+
+    x (pc channels), x_cond (48) and x_other (or None) are ragged tensors of `layout` (RaggedLayout): flat fp32 buffers on the GPU.  The patches of all
+    images form one list, gathered into one UNet input and run in the same equal-sized UNet calls (`call_b`) as ddim_sample's -- a call may hold the end of one
+    image and the start of the next, which changes nothing (per-patch results do not depend on the batch, tests/test_gpu_unet.py) --, with the same temb table;
+    `wdm_pack_channels_ragged` and `wdm_ddim_update_ragged` are the plain kernels with the image's size looked up.  Every image's result is therefore, bit for
+    bit, what ddim_sample returns for that image alone (tests/test_gpu_ragged.py).  `keep` and `stop_at` as in ddim_sample; returns (xs, x0_preds), lists of
+    flat tensors (layout.view gives an image's block).  With WAVEDM_GRAPH=1 a ragged call still launches directly: it is not captured."""
+    x = _lib.require_cuda_f32(x, "x")
+    x_cond = _lib.require_cuda_f32(x_cond, "x_cond")
+    if x_other is not None:
+        x_other = _lib.require_cuda_f32(x_other, "x_other")
+    dev = x.device
+    L, h = _lib.lib(), _lib.handle(dev.index or 0)
+    if hasattr(unet, "pack_weights"):
+        unet.pack_weights()
+    npix, p, n = layout.pix_off[-1], layout.p, layout.n
+    if x.dim() != 1 or x_cond.dim() != 1 or (x_other is not None and x_other.dim() != 1):
+        raise ValueError("ddim_sample_ragged: x, x_cond and x_other are flat ragged tensors")
+    if x.numel() < npix or x.numel() % npix or x_cond.numel() % npix or (x_other is not None and x_other.numel() % npix):
+        raise ValueError(f"ddim_sample_ragged: tensors of {x.numel()} / {x_cond.numel()} elements do not hold whole channels of the layout's {npix} pixels")
+    pc, ncond, nother = x.numel() // npix, x_cond.numel() // npix, (x_other.numel() // npix if x_other is not None else 0)
+    cin = unet.in_channels
+    assert ncond + pc + nother == cin, f"channel split {ncond}+{pc}+{nother} != UNet in_channels {cin}"
+    assert p == unet.resolution, "patch size must equal config.data.image_size (unet.py:351)"
+    with torch.cuda.device(dev):
+        patches, img_tab, blk_tab, pix_off = layout.tables(dev)
+        pptr, iptr, bptr, optr = _lib.ptr(patches), _lib.ptr(img_tab), _lib.ptr(blk_tab), _lib.ptr(pix_off)
+        nimg, nblk = layout.nimg, layout.blk_off[-1]
+        seq = list(seq)
+        seq_next = [-1] + seq[:-1]
+        abar = alpha_bar_table(betas)
+        t_dev = _device_const(dev, "timesteps", tuple(float(v) for v in reversed(seq)), torch.float32)
+        n_run = len(seq) if stop_at is None else len(seq) + int(stop_at) + 1
+        assert 1 <= n_run <= len(seq), f"stop_at={stop_at} out of range for {len(seq)} steps"
+        keep_set = None if keep == "all" else frozenset(int(v) for v in keep)
+        n_calls = max(1, -(-n // max_batch))                                    # ddim_sample's equal-sized calls
+        call_b = -(-n // n_calls) if os.environ.get("WAVEDM_EVEN_CALLS", "1") != "0" else max_batch
+        st = _lib.stream_ptr()
+        x96 = torch.empty(n, p, p, cin, device=dev, dtype=unet._torch_dtype)
+        _lib.check(L.wdm_pack_channels_ragged(h, _lib.ptr(x_cond), ncond, iptr, optr, nimg, pptr, n, p, _lib.ptr(x96), cin, 0, unet._dtype_code, st))
+        if nother:
+            _lib.check(L.wdm_pack_channels_ragged(h, _lib.ptr(x_other), nother, iptr, optr, nimg, pptr, n, p, _lib.ptr(x96), cin, ncond + pc, unet._dtype_code, st))
+        eps = torch.empty(n, pc, p, p, device=dev, dtype=torch.float32)
+        temb = unet.temb_table(t_dev, B=min(n, call_b)) if os.environ.get("WAVEDM_TEMB_TABLE", "1") != "0" else None
+        S = len(seq)
+        xs, x0_preds = [x], []
+        xt = x
+        for k, (i_t, j_t) in enumerate(zip(reversed(seq), reversed(seq_next))):
+            if _TRACE is not None:
+                _TRACE(f"sampler: step {k}")
+            if k >= n_run:
+                x0_preds.append(None)
+                xs.append(None)
+                continue
+            at, at_next = abar[i_t + 1], abar[j_t + 1]
+            s1m, sa = float((1 - at).sqrt()), float(at.sqrt())
+            san, c2 = float(at_next.sqrt()), float((1 - at_next).sqrt())
+            x0 = torch.empty_like(x)
+            xn = torch.empty_like(x)
+            _lib.check(L.wdm_pack_channels_ragged(h, _lib.ptr(xt), pc, iptr, optr, nimg, pptr, n, p, _lib.ptr(x96), cin, ncond, unet._dtype_code, st))
+            for i in range(0, n, call_b):
+                unet.forward_nhwc(x96[i:i + call_b], t_dev[k:k + 1], eps[i:i + call_b], temb_row=None if temb is None else temb[k])
+            _lib.check(L.wdm_ddim_update_ragged(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), iptr, bptr, optr, nimg, nblk, s1m, sa, san, c2,
+                                                _lib.ptr(x0), _lib.ptr(xn), st))
+            x0_preds.append(x0 if keep_set is None or (k - S) in keep_set else None)
+            xs.append(xn)
+            if keep_set is not None and len(xs) >= 3:
+                xs[-2] = xs[-2] if (len(xs) - 2 - (S + 1)) in keep_set else None
+            xt = xn
+        if keep != "all":
+            x0_preds = [t if (i - S) in keep else None for i, t in enumerate(x0_preds)]
+        return xs, x0_preds
+
+
 def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None, max_batch=64, keep="all", stop_at=None,
                 patch_group=None, streams=None, eta=0.0):
     """DDIM over `seq` (ascending list of timesteps) for NIMG images; eta = 0 (what every caller in the reference passes) is the deterministic sampler.

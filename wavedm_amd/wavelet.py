@@ -41,14 +41,17 @@ class WaveletTransform(nn.Module):
         self.scale, self.dec, self.transpose = scale, dec, transpose
         self.conv = _FrozenConv()
 
-    def forward_affine(self, x, scale=2.0, shift=-1.0):
-        """dec only: DWT(scale * x + shift) in one kernel -- `wavelet_dec(data_transform(x))` of the reference (restoration.py:88-96)."""
+    def forward_affine(self, x, scale=2.0, shift=-1.0, out=None):
+        """dec only: DWT(scale * x + shift) in one kernel -- `wavelet_dec(data_transform(x))` of the reference (restoration.py:88-96).
+        `out`: a contiguous (B,48,H/4,W/4) f32 tensor to write (a view of a ragged buffer, sampling.RaggedLayout) instead of a new one."""
         assert self.dec
         x = _lib.require_cuda_f32(x, "WaveletTransform input")
         B, C, H, W = x.shape
         if C != 3 or H % 4 or W % 4:
             raise ValueError(f"WaveletTransform(dec): expected (B,3,4h,4w), got {tuple(x.shape)}")
-        y = torch.empty(B, 48, H // 4, W // 4, device=x.device, dtype=torch.float32)
+        if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 48, H // 4, W // 4)):
+            raise ValueError(f"WaveletTransform(dec): out must be a contiguous f32 {(B, 48, H // 4, W // 4)} tensor on the GPU")
+        y = torch.empty(B, 48, H // 4, W // 4, device=x.device, dtype=torch.float32) if out is None else out
         if B:
             with torch.cuda.device(x.device):
                 _lib.check(_lib.lib().wdm_dwt_fwd_affine(_lib.handle(x.device.index or 0), _lib.ptr(x), float(scale), float(shift), _lib.ptr(y), B, H, W,
