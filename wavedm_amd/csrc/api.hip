@@ -172,6 +172,7 @@ int wdm_resblock_forward(wdm_handle* h, const wdm_resblock_params* p, const floa
 int wdm_attn_forward(wdm_handle* h, const wdm_attn_params* p, const float* x, int B, int H, int W, float* y, int dtype, void* scratch,
                      size_t scratch_bytes, void* stream) {
     if (!h || !p || !x || !y || !scratch) WDM_FAIL(WDM_EINVAL, "wdm_attn_forward: null argument");
+    WDM_TRY(attn_tokens_check(H, W));       // before the weights are packed: a refused map launches nothing
     Scratch sc(scratch, scratch_bytes);
     Ctx c{(hipStream_t)stream, dtype, B, &sc.ar, false};
     const int C = p->c;

@@ -1,9 +1,10 @@
-// Launcher of the fused attention core (attn_fused_kernel.h).
+// Launchers of the fused attention core (attn_fused_kernel.h) and of the streaming core for maps beyond 512 tokens (attn_stream_kernel.h).
 #include <atomic>
 #include <type_traits>
 
 #include "common.h"
 #include "attn_fused_kernel.h"
+#include "attn_stream_kernel.h"
 
 namespace wdm {
 
@@ -66,6 +67,61 @@ int launch_attn_fused(const AttnOperands& in, void* o, int B, int C, hipStream_t
     if (dtype == WDM_F16) return in.v_tok ? launch_attn_fused_t<f16_t, true>(in, o, B, C, s, vbias, proj) : launch_attn_fused_t<f16_t, false>(in, o, B, C, s, vbias, proj);
     if (dtype == WDM_BF16) return in.v_tok ? launch_attn_fused_t<__bf16, true>(in, o, B, C, s, vbias, proj) : launch_attn_fused_t<__bf16, false>(in, o, B, C, s, vbias, proj);
     WDM_FAIL(WDM_EINVAL, "attn(fused): 16-bit modes only");
+}
+
+// ---- streaming core (attn_stream_kernel.h): maps beyond 512 tokens, 16-bit modes, C = 128 ... 1024 in steps of 128 -----------------------------------
+bool attn_stream_eligible(int dtype, int N, int C) {
+    return env_cfg().attn_stream && is_h16(dtype) && N > 512 && N % AttnStreamCfg::KB == 0 && N <= WDM_ATTN_MAX_TOKENS && C % AttnStreamCfg::CK == 0 && C >= AttnStreamCfg::CK &&
+           C <= AttnStreamCfg::MAX_C;
+}
+template <typename T, int NCB>
+static void launch_attn_stream_n(const AttnStreamArgs& a, int grid, hipStream_t s) {
+    hipLaunchKernelGGL((attn_stream_kernel<T, NCB>), dim3(grid), dim3(AttnStreamCfg::NTHREADS), 0, s, a);
+}
+template <typename T>
+static int launch_attn_stream_t(const AttnStreamArgs& a, int grid, hipStream_t s) {
+    switch (a.C / AttnStreamCfg::CK) {
+        case 1: launch_attn_stream_n<T, 1>(a, grid, s); break;
+        case 2: launch_attn_stream_n<T, 2>(a, grid, s); break;
+        case 3: launch_attn_stream_n<T, 3>(a, grid, s); break;
+        case 4: launch_attn_stream_n<T, 4>(a, grid, s); break;
+        case 5: launch_attn_stream_n<T, 5>(a, grid, s); break;
+        case 6: launch_attn_stream_n<T, 6>(a, grid, s); break;
+        case 7: launch_attn_stream_n<T, 7>(a, grid, s); break;
+        case 8: launch_attn_stream_n<T, 8>(a, grid, s); break;
+        default: WDM_FAIL(WDM_EINVAL, "attn(stream): C = %d unsupported (multiple of 128, <= %d)", a.C, AttnStreamCfg::MAX_C);
+    }
+    return WDM_OK;
+}
+int launch_attn_stream(const AttnOperands& in, void* o, int B, int N, int C, hipStream_t s, const float* vbias, int dtype) {
+    using Cf = AttnStreamCfg;
+    if (!in.q || !in.k || !in.v || !o || B <= 0) WDM_FAIL(WDM_EINVAL, "attn(stream): bad argument");
+    if (!is_h16(dtype)) WDM_FAIL(WDM_EINVAL, "attn(stream): 16-bit modes only");
+    if (N % Cf::KB || N <= 0 || N > WDM_ATTN_MAX_TOKENS || C % Cf::CK || C <= 0 || C > Cf::MAX_C)
+        WDM_FAIL(WDM_EINVAL, "attn(stream): %d tokens x %d channels unsupported (tokens: multiple of 64, <= %d; channels: multiple of 128, <= %d)", N, C, WDM_ATTN_MAX_TOKENS, Cf::MAX_C);
+    if (in.v_tok || in.bdiag || in.qw) WDM_FAIL(WDM_EINVAL, "attn(stream): takes q, k token-major and V^T channel-major");
+    if (in.q_ld < C || in.k_ld < C || (in.q_ld | in.k_ld) % 8 || (((uintptr_t)in.q | (uintptr_t)in.k | (uintptr_t)in.v) & 15) || ((uintptr_t)o & 7) || (vbias && ((uintptr_t)vbias & 15)))
+        WDM_FAIL(WDM_EINVAL, "attn(stream): row strides must be multiples of 8 elements >= C and the operands 16-byte aligned");
+    const long long grid = (long long)B * (N / Cf::QB);
+    if (grid > 2147483647LL) WDM_FAIL(WDM_EINVAL, "attn(stream): %lld workgroups exceed the launch grid", grid);
+    AttnStreamArgs a{};
+    a.q = in.q; a.k = in.k; a.vt = in.v; a.o = o; a.vbias = vbias;
+    a.B = B; a.N = N; a.C = C; a.q_ld = in.q_ld; a.k_ld = in.k_ld;
+    a.alpha2 = (float)(std::pow((double)C, -0.5) * 1.4426950408889634);
+    a.xcd_groups = grid % 8 == 0 ? 1 : 0;
+    const bool prof = prof_enabled();
+    if (prof) {
+        char name[96];
+        snprintf(name, sizeof(name), "attn_stream_q64k64_%s|%d tokens C=%d", dtype == WDM_F16 ? "f16" : "bf16", N, C);
+        prof_begin(s, name, 4.0 * B * N * (double)N * C, (double)B * N * C * 2.0 * 4.0);
+    }
+    int rc;
+    if (dtype == WDM_F16) rc = launch_attn_stream_t<f16_t>(a, (int)grid, s);
+    else rc = launch_attn_stream_t<__bf16>(a, (int)grid, s);
+    if (prof) prof_end(s);
+    WDM_TRY(rc);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
 }
 
 }  // namespace wdm

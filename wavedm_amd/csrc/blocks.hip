@@ -95,7 +95,7 @@ void env_cfg_refresh() {
     auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
     c->conv_dma = flag("WDM_CONV_DMA", 1); c->gemm = flag("WDM_GEMM", 1); c->bn256 = num("WDM_BN256", 1);
     c->gn_tile = num("WDM_GN_TILE", 2); c->gn_inline = flag("WDM_GN_INLINE", 1); c->attn_fused = num("WDM_ATTN_FUSED", 3); c->attn_fold = num("WDM_ATTN_FOLD", 1);
-    c->up4 = flag("WDM_UP4", 1); c->attn_sm = flag("WDM_ATTN_SM", 1); c->wgrad_bg = num("WDM_WGRAD_BG", 0);
+    c->up4 = flag("WDM_UP4", 1); c->attn_sm = flag("WDM_ATTN_SM", 1); c->attn_stream = flag("WDM_ATTN_STREAM", 1); c->wgrad_bg = num("WDM_WGRAD_BG", 0);
     std::lock_guard<std::mutex> lk(g_env_mu);
     g_env.store(c, std::memory_order_release);
 }
@@ -393,6 +393,41 @@ static int run_attn_folded(Ctx& c, const AttnW& w, const Tens& x, Tens& hn, bool
     return WDM_OK;
 }
 
+// Maps beyond 512 tokens, every compute mode: Q.K^T, softmax and P.V per block of query rows, so that only one block's score rows per image ever exist (a 64 x 64 map's
+// whole score matrix is 64 MB per image in fp32).  The block is a function of N alone -- 256 rows as a 16 x 16 "map" of the GEMM kernels where that divides N, else 128 (8 x 16)
+// or 64 (8 x 8) -- so an image's bits depend on neither the batch nor its size.  The GEMMs address a block inside the image through Hin: the input grid is the whole image
+// (N / gw rows of gw tokens), the output grid the block, and the base pointer the block's first row (the launcher's descriptor extent, B x Hin x Win rows from that base,
+// then ends q0 rows behind the tensor: it is a bound, not an access -- the rows read are (image, y < Hout), all inside).  o: dense [B][N][C].
+static int attn_query_block(int N) { return N % 256 == 0 ? 256 : N % 128 == 0 ? 128 : 64; }
+static int attn_core_blocked(Ctx& c, const Tens& qk, const void* vT, const float* vbias, int C, int N, Tens& o) {
+    const size_t es = dsize(c.dtype);
+    const int QB = attn_query_block(N), gw = QB == 64 ? 8 : 16, gh = QB / gw;
+    float* S = nullptr;
+    WDM_TRY(alloc_f32(c, (size_t)c.B * QB * N, &S));
+    void* P = c.ar->alloc((size_t)c.B * QB * N * es);
+    void* ob = c.ar->alloc((size_t)c.B * QB * C * es);
+    if (!P || !ob) WDM_FAIL(WDM_ENOMEM, "workspace too small (attention: one query block's P and O)");
+    if (!c.dry) {
+        const void* k = (const char*)qk.p + (size_t)C * es;
+        for (int q0 = 0; q0 < N; q0 += QB) {
+            // S[b][i][j] = C^-1/2 * sum_c q[b][q0 + i][c] k[b][j][c]
+            ConvArgs a = gemm_args(c.B, gh, gw, (const char*)qk.p + (size_t)q0 * qk.xs * es, qk.xs, C, k, qk.xs, (long long)N * qk.xs, N, N, S, Y_NHWC_F32, es,
+                                   (float)std::pow((double)C, -0.5));
+            a.Hin = N / gw;
+            a.w_bytes = (unsigned)(((size_t)N * qk.xs - C) * es);
+            WDM_TRY(launch_conv(a, MODE_P1, c.dtype, c.s));
+            WDM_TRY(k_softmax_rows(S, P, (long long)c.B * QB, N, c.dtype, c.s));
+            // O[b][q0 + i][c] = sum_j P[b][i][j] V^T[b][c][j]
+            ConvArgs p = gemm_args(c.B, gh, gw, P, N, N, vT, N, (long long)C * N, C, C, ob, Y_NHWC, es);
+            p.bias = vbias;
+            WDM_TRY(launch_conv(p, MODE_P1, c.dtype, c.s));
+            WDM_TRY(k_copy_token_rows(ob, o.p, c.B, QB, N, q0, (size_t)C * es, c.s));
+        }
+    }
+    c.ar->free(S); c.ar->free(P); c.ar->free(ob);
+    return WDM_OK;
+}
+
 // Unfolded form: the q|k GEMM and V^T, then the fused core or the three launches Q.K^T, softmax, P.V.  Frees hn.
 static int run_attn_unfolded(Ctx& c, const AttnW& w, const Tens& x, Tens& hn, bool fused, Tens* out) {
     const int C = w.c, N = x.H * x.W;
@@ -435,6 +470,15 @@ static int run_attn_unfolded(Ctx& c, const AttnW& w, const Tens& x, Tens& hn, bo
         WDM_TRY(alloc_tens(c, C, x.H, x.W, &o));
         if (!c.dry) WDM_TRY(launch_attn_fused(in, o.p, c.B, C, c.s, vbias, nullptr, c.dtype));
         c.ar->free(vT);
+    } else if (N > 512) {
+        WDM_TRY(alloc_tens(c, C, x.H, x.W, &o));
+        if (attn_stream_eligible(c.dtype, N, C)) {
+            // streaming core (attn_stream_kernel.h): K and V^T pass through LDS in key blocks, running maximum and sum per query, P never leaves the CU
+            if (!c.dry) WDM_TRY(launch_attn_stream(in, o.p, c.B, N, C, c.s, vbias, c.dtype));
+        } else {
+            WDM_TRY(attn_core_blocked(c, qk, vT, vbias, C, N, o));
+        }
+        c.ar->free(vT);
     } else {
         float* S = nullptr;
         WDM_TRY(alloc_f32(c, (size_t)c.B * N * N, &S));
@@ -460,12 +504,21 @@ static int run_attn_unfolded(Ctx& c, const AttnW& w, const Tens& x, Tens& hn, bo
     return WDM_OK;
 }
 
+// the token counts an AttnBlock takes; the entry points ask before their first launch (a UNet call for every level that has attention), run_attn asks again
+int attn_tokens_check(int H, int W) {
+    const long long N = (long long)H * W;
+    if (H <= 0 || W <= 0 || N % 64 || N > WDM_ATTN_MAX_TOKENS)
+        WDM_FAIL(WDM_EINVAL, "attn: %lld tokens unsupported (a %dx%d map; multiple of 64, <= %d)", N, H, W, WDM_ATTN_MAX_TOKENS);
+    return WDM_OK;
+}
+
 int run_attn(Ctx& c, const AttnW& w, const Tens& x, Tens* out) {
     const int C = w.c, N = x.H * x.W;
     if (x.C != C) WDM_FAIL(WDM_EINVAL, "attn: input has %d channels, block expects %d", x.C, C);
-    if (N % 64 || N > 512) WDM_FAIL(WDM_EINVAL, "attn: %d tokens unsupported (multiple of 64, <= 512)", N);
+    WDM_TRY(attn_tokens_check(x.H, x.W));
     Tens hn;
     WDM_TRY(materialize_gn(c, w.n, x, nullptr, 0, &hn));
+    if (N > 512) return run_attn_unfolded(c, w, x, hn, false, out);      // per query block, or the streaming core (16-bit modes, C a multiple of 128)
     const bool fused = attn_fused_eligible(c.dtype, N, C);
     // the 8 x 8 maps' block (64 tokens): the fused core in its block-diagonal form -- four images per 256-row "image" of the kernel, scores outside an image's own block masked
     // (attn_fused_kernel.h: bdiag) -- on the folded operands; any batch size (a ragged last group is skipped per query block), so an image's bits do not depend on the batch

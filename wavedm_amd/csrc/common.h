@@ -57,6 +57,7 @@ class Arena {
     void* alloc(size_t bytes);
     void free(void* p);
     size_t peak() const { return peak_; }
+    size_t capacity() const { return cap_; }
     bool failed() const { return failed_; }
     bool is_dry() const { return base_ == nullptr; }
 
@@ -170,7 +171,11 @@ int k_gn_finalize_apply(int B, const Tens& x0, const Tens* x1, const float* st0,
 int k_gn_apply(const Tens& x, int B, const float* scale, const float* shift, int sc_ld, void* y, int y_stride, int y_choff, int silu, int dtype,
                hipStream_t s, const Dropout* drop = nullptr);
 int k_dropout_mask(const Dropout& drop, int B, int H, int W, int C, float* factor_nchw, hipStream_t s);      // fp32 (B, C, H, W): 0 or the scale, every element
-int k_softmax_rows(const float* S, void* P, long long rows, int n, int dtype, hipStream_t s);
+// Largest AttnBlock map: 64 x 64 (the shipped model's top level).  Token counts are multiples of 64; up to 512 the score matrix of the whole batch is one tensor
+// (or never leaves the CU: attn_fused_kernel.h), beyond that attention runs per block of query rows (blocks.hip) or on the streaming core (attn_stream_kernel.h)
+constexpr int WDM_ATTN_MAX_TOKENS = 4096;
+int k_softmax_rows(const float* S, void* P, long long rows, int n, int dtype, hipStream_t s);      // n a multiple of 64, <= WDM_ATTN_MAX_TOKENS
+int k_copy_token_rows(const void* src, void* dst, int B, int rows, int dst_rows, int row0, size_t row_bytes, hipStream_t s);      // dst[b][row0 + r] = src[b][r]
 int k_timestep_embedding(const float* t, int n_t, int dim, float* emb, hipStream_t s);
 // out[n][o] = post( W[o][:] . pre(in[n][:]) + b[o] );  act: 0 none, 1 SiLU on input, 2 SiLU on output
 int k_linear(const float* in, int n, int k, const float* W, const float* b, int o, float* out, int act, hipStream_t s);
@@ -221,6 +226,10 @@ struct AttnOperands {
 // proj != nullptr (C <= 512): proj_out fused in as a third phase; *proj = the 1x1 conv's arguments as run_conv builds them (weights, bias, residual, output,
 // statistics); o is then unused
 int launch_attn_fused(const AttnOperands& in, void* o, int B, int C, hipStream_t s, const float* vbias = nullptr, const ConvArgs* proj = nullptr, int dtype = WDM_BF16);
+// ---- streaming attention core (attn.hip / attn_stream_kernel.h): maps beyond 512 tokens, 16-bit modes, C a multiple of 128 up to 1024; q, k token-major as above,
+// in.v = V^T [B][C][N] -> o [B][N][C].  Online softmax over key blocks taken in ascending order: no score tensor, the same bits on every call
+bool attn_stream_eligible(int dtype, int N, int C);
+int launch_attn_stream(const AttnOperands& in, void* o, int B, int N, int C, hipStream_t s, const float* vbias = nullptr, int dtype = WDM_BF16);
 // AttnBlock operand folding (elementwise.hip), fp32 in / out, fp64 sums: M = Wk^T Wq, cq = Wk^T bq (scores: (Wq h_i + bq).(Wk h_j + bk) = (M h_i + cq).h_j + terms constant
 // in j, which the softmax cancels); Wvp = Wp Wv, bvp = Wp bv + bp (proj_out(P.(Wv h + bv)) = Wvp (P.h) + bvp: the rows of P sum to one)        (models/unet.py:176-191)
 int k_attn_fold(const float* wq, const float* bq, const float* wk, const float* wv, const float* bv, const float* wp, const float* bp, int C, float* M, float* cq, float* Wvp,
@@ -241,6 +250,7 @@ struct EnvCfg {
     int attn_fused = 3;   // WDM_ATTN_FUSED=0: attention core as three launches (Q.K^T, softmax, P.V); 1: fused core, proj_out as its own GEMM; 2: proj_out fused in as well;
                           // 3 (default): the folded block's query projection too (C = 128 ... 512 on 16 x 16 maps): the AttnBlock behind its GroupNorm is one launch
     int attn_sm = 1;      // WDM_ATTN_SM=0: the fused attention core streams Wk^T Wq / Wp Wv from the plain [row][cin] matrices (64-byte half lines per row) instead of their slab-major copies
+    int attn_stream = 1;  // WDM_ATTN_STREAM=0: AttnBlocks beyond 512 tokens per block of query rows in the 16-bit modes too (blocks.hip: attn_core_blocked), not on the streaming core
     int up4 = 1;          // WDM_UP4=0: 9-tap Upsample conv everywhere (no sub-pixel form)
     int wgrad_bg = 0;     // WDM_WGRAD_BG=<n>: the batched-GEMM form of the weight gradient everywhere, n images per group (0: direct kernel for 3x3 stride-1 layers, training)
 };
@@ -281,6 +291,7 @@ int run_gn(Ctx& c, const NormW& nw, const Tens& x0, const Tens* x1, int for_silu
 // next_n: the norm of the consumer of *out when that consumer normalises in a pass of its own (an AttnBlock, an 8 x 8 ResnetBlock): conv2 writes it (run_conv: on)
 int run_resblock(Ctx& c, const ResW& w, const Tens& x0, const Tens* x1, Tens* out, const NormW* next_n = nullptr, int next_silu = 0);
 int run_attn(Ctx& c, const AttnW& w, const Tens& x, Tens* out);
+int attn_tokens_check(int H, int W);      // WDM_EINVAL, with the limit in the message, for a map an AttnBlock does not take (tokens: multiple of 64, <= WDM_ATTN_MAX_TOKENS)
 int alloc_tens(Ctx& c, int C, int H, int W, Tens* t);
 void free_tens(Ctx& c, Tens& t);
 

@@ -826,11 +826,53 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     for (int i = 0; i < 8; ++i)
         if (i < per) TI<T>::st(P, row * n + lane + i * 64, v[i] * inv);
 }
+// rows beyond 512 keys (AttnBlocks on maps above 16 x 16, up to WDM_ATTN_MAX_TOKENS): the same wave-per-row scheme -- lane l holds keys l, l + 64, ... and reduces them in
+// ascending order before the wavefront shuffles, fp32 throughout -- with the row read three times (it is 2 - 16 KB: the second and third reads are cache hits)
+// instead of held in 8 registers.  The order is fixed, so a row's bits depend on the row alone.
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_rows_long_kernel(const float* __restrict__ S, T* __restrict__ P, long long rows, int n) {
+    h16_mode_init<T>();
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* src = S + row * n;
+    float mx = -INFINITY;
+    for (int j = lane; j < n; j += 64) mx = fmaxf(mx, src[j]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float sum = 0.f;
+    for (int j = lane; j < n; j += 64) sum += expf(src[j] - mx);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
+    const float inv = 1.0f / sum;
+    for (int j = lane; j < n; j += 64) TI<T>::st(P, row * n + j, expf(src[j] - mx) * inv);
+}
 int k_softmax_rows(const float* S, void* P, long long rows, int n, int dtype, hipStream_t s) {
-    if (n % 64 || n > 512 || n <= 0) WDM_FAIL(WDM_EINVAL, "softmax: row length %d must be a multiple of 64 and <= 512", n);
+    if (n % 64 || n > WDM_ATTN_MAX_TOKENS || n <= 0) WDM_FAIL(WDM_EINVAL, "softmax: row length %d must be a multiple of 64 and <= %d", n, WDM_ATTN_MAX_TOKENS);
+    if ((rows + 3) / 4 > 2147483647LL) WDM_FAIL(WDM_EINVAL, "softmax: %lld rows exceed the launch grid", rows);
     const int g = (int)((rows + 3) / 4);
-    if (is_h16(dtype)) WDM_H16_SWITCH(dtype, hipLaunchKernelGGL(softmax_rows_kernel<H16>, dim3(g), dim3(256), 0, s, S, (H16*)P, rows, n));
+    if (n > 512) {
+        if (is_h16(dtype)) WDM_H16_SWITCH(dtype, hipLaunchKernelGGL(softmax_rows_long_kernel<H16>, dim3(g), dim3(256), 0, s, S, (H16*)P, rows, n));
+        else hipLaunchKernelGGL(softmax_rows_long_kernel<float>, dim3(g), dim3(256), 0, s, S, (float*)P, rows, n);
+    } else if (is_h16(dtype)) WDM_H16_SWITCH(dtype, hipLaunchKernelGGL(softmax_rows_kernel<H16>, dim3(g), dim3(256), 0, s, S, (H16*)P, rows, n));
     else hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3(g), dim3(256), 0, s, S, (float*)P, rows, n);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
+// dst[b][row0 + r][:] = src[b][r][:] for r < rows: a query block's rows of O into the image's token-major tensor (blocks.hip: run_attn_unfolded beyond 512 tokens).
+// 16-byte vectors; row_v = vectors per row, dst images dst_rows rows apart
+__global__ __launch_bounds__(256) void copy_token_rows_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, long long n, int rows, int dst_rows, int row0, int row_v) {
+    const long long per_img = (long long)rows * row_v;
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (long long)gridDim.x * blockDim.x) {
+        const long long b = id / per_img, r = id - b * per_img;
+        dst[(b * dst_rows + row0) * row_v + r] = src[id];
+    }
+}
+int k_copy_token_rows(const void* src, void* dst, int B, int rows, int dst_rows, int row0, size_t row_bytes, hipStream_t s) {
+    if (row_bytes % 16 || ((uintptr_t)src | (uintptr_t)dst) & 15 || row0 < 0 || row0 + rows > dst_rows) WDM_FAIL(WDM_EINVAL, "copy_token_rows: rows of %zu bytes at %d (+%d of %d) unsupported", row_bytes, row0, rows, dst_rows);
+    const long long n = (long long)B * rows * (long long)(row_bytes / 16);
+    hipLaunchKernelGGL(copy_token_rows_kernel, dim3(grid_capped_min1(n, 256)), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, n, rows, dst_rows, row0, (int)(row_bytes / 16));
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }

@@ -469,6 +469,7 @@ int wdm_trainer::op_attn(const AttnP& a, TT* x, TT** out) {
     const int C = a.c, N = x->t.H * x->t.W, B = cx.B;
     const size_t es = dsize(cx.dtype);
     const float scale = (float)std::pow((double)C, -0.5);
+    WDM_TRY(attn_tokens_check(x->t.H, x->t.W));
     TT *hn, *q, *k, *v;
     WDM_TRY(op_gn_act(a.n, x, nullptr, 0, &hn));
     WDM_TRY(op_conv(a.q, MODE_P1, hn, nullptr, -1, nullptr, &q));
@@ -532,6 +533,20 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
     const size_t cout_w = off[conv_out.w], cout_b = off[conv_out.b];
     const size_t es = dsize(cc.dtype);
     auto af = [&](size_t n) -> float* { return (float*)cc.ar->alloc(n * 4); };
+    for (int l = 0; l < nres; ++l)      // every map that carries an AttnBlock, before the first launch
+        if (!down_attn[l].empty() || !up_attn[l].empty() || l == nres - 1) WDM_TRY(attn_tokens_check(R >> l, R >> l));
+    {   // ... and what op_attn alone will ask of the arena: every block's softmax matrix, kept for the backward pass, plus the largest block's transients (fp32 dP,
+        // dS and two transposed operands).  On a 64 x 64 map that is 1/2 GB per image: a workspace that cannot hold it fails here, not after half a forward pass
+        size_t kept = 0, transient = 0;
+        for (int l = 0; l < nres; ++l) {
+            const size_t nblk = down_attn[l].size() + up_attn[l].size() + (l == nres - 1 ? 1 : 0), nn = (size_t)(R >> l) * (R >> l) * (R >> l) * (R >> l);
+            if (!nblk) continue;
+            kept += nblk * B * nn * es;
+            transient = std::max(transient, (size_t)B * nn * (4 + 3 * es));
+        }
+        if (kept + transient > cc.ar->capacity())
+            WDM_FAIL(WDM_ENOMEM, "training workspace too small (attention: %zu bytes of kept softmax matrices and backward transients, %zu given)", kept + transient, cc.ar->capacity());
+    }
     // ---- temb MLP (fp32), values kept for the backward pass
     float *emb = af((size_t)B * cfg.ch), *pre0 = af((size_t)B * temb_ch), *t0 = af((size_t)B * temb_ch), *t1 = af((size_t)B * temb_ch), *s1 = af((size_t)B * temb_ch);
     temb_all = af((size_t)B * temb_rows);

@@ -254,6 +254,9 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
     const Res &mid1 = L.mid1, &mid2 = L.mid2;
     const Attn& mid_attn = L.mid_attn;
     const int cin_pad = convd[L.conv_in.idx].cin;      // conv_in's K dimension in the packed matrix
+    // every map that carries an AttnBlock, before the first launch (and in the dry run, so the workspace query of such a config fails with the same message)
+    for (int l = 0; l < nres; ++l)
+        if (!down_attn[l].empty() || !up_attn[l].empty() || l == nres - 1) WDM_TRY(attn_tokens_check(R >> l, R >> l));
     // ---- timestep embedding MLP + every block's temb projection (depends only on t): computed here, or taken from a table the caller made for
     // all the timesteps of a sampling run at once (temb_pre: one row, shared by the images)
     float* temb_all = nullptr;

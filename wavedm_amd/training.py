@@ -114,6 +114,25 @@ def _checkpoint_rule(osd):
     return None
 
 
+def attn_long_workspace_bytes(model, B: int, R: int, dsize: int) -> int:
+    """What the AttnBlocks on maps beyond 512 tokens add to a training step's workspace (train_unet.hip: op_attn): the softmax matrix P of every such block, kept
+    for the backward pass (B N^2 elements each), and at the largest of them the transients of one block -- fp32 scores S or dP, dS, and the two transposed operands.
+    Blocks of up to 512 tokens are covered by the per-pixel term of the caller, as before.  Counting them here means a workspace that is too small is enlarged before
+    the first launch of a step instead of by the double-and-retry path in the middle of one."""
+    nlev, nrb = len(model.ch_mult), int(model.num_res_blocks)
+    attn = [int(a) for a in model.attn_resolutions]
+    kept, transient = 0, 0
+    for lvl in range(nlev):
+        res = R >> lvl
+        n = res * res
+        blocks = (2 * nrb + 1 if res in attn else 0) + (1 if lvl == nlev - 1 else 0)      # down + up blocks of the level; mid.attn_1 on the coarsest map
+        if n <= 512 or not blocks:
+            continue
+        kept += blocks * B * n * n * dsize
+        transient = max(transient, B * n * n * (4 + 3 * dsize))
+    return kept + transient
+
+
 class Trainer:
     def __init__(self, config, device=None, dtype=None, lr=None, betas=(0.9, 0.999), eps=None, weight_decay=None, ema_mu=0.9999, use_mse=None, dropout=None, dropout_seed=None):
         self.config = config
@@ -237,7 +256,7 @@ class Trainer:
             # ... plus the forward AND dgrad weight layouts of every conv, packed at the start of the step and kept for its whole length (train_unet.hip: pack_region):
             # about twice the parameter bytes in the model dtype -- without this term small batches took the double-and-retry path on every first step
             dsize = 2 if self._dtype_code == _lib.WDM_BF16 else 4
-            need = B * Cc * R * R * 4 * 160 + 2 * self._n_floats * dsize + (1 << 28)
+            need = B * Cc * R * R * 4 * 160 + 2 * self._n_floats * dsize + (1 << 28) + attn_long_workspace_bytes(self.config.model, B, R, dsize)
             if self._ws is None or self._ws.numel() < need:
                 self._ws = None
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
