@@ -22,6 +22,7 @@
 // The first V^T chunks are fetched while the softmax runs.  LDS: phase 1 3 x 40 KB; phase 2 P 32 KB + 3 x 32 KB; + 1 KB of statistics.
 #pragma once
 #include "conv_kernel.h"
+#include "lds_dma.h"
 
 namespace wdm {
 
@@ -94,20 +95,8 @@ __global__ __launch_bounds__(512, 2) void attn_fused_kernel(const AttnFusedArgs 
     if (a.bdiag && b * 4 + qb >= a.nimg) return;                      // (ragged last group: this query block is no image)
     const int Cc = a.C;
 
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    auto make_q = [](const void* p, unsigned bytes) __attribute__((always_inline)) {
-        const unsigned long long v = (unsigned long long)p;
-        return i32x4{(int)(unsigned)v, (int)((unsigned)(v >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-    };
     const i32x4 q_q = make_q(a.q, a.q_bytes), q_k = make_q(a.k, a.k_bytes), q_vt = make_q(a.v, a.v_bytes);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-    auto dma16 = [&](const i32x4& rsrc, unsigned lds_addr, unsigned voff, int soff) __attribute__((always_inline)) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff), "s"(lds_addr), "s"(rsrc), "s"(soff)
-                     : "memory");
-    };
 
     // ---- phase-1 DMA geometry: 40 pieces of 8 rows x 128 B per step, five per wave; pieces 0-31 = key rows, 32-39 = query rows
     unsigned v1[5];
@@ -158,10 +147,10 @@ __global__ __launch_bounds__(512, 2) void attn_fused_kernel(const AttnFusedArgs 
             const int r = off / rowb, s16 = (off - r * rowb) >> 4;
             const int sp = s16 >> 1, f = (r & 3) + 4 * ((r >> 3) & 1);
             const int bseg = (sp & ~7) | ((sp - f) & 7);
-            v2[j] = piece < p2 ? (unsigned)((((long long)b * N + r) * a.v_ld) * 2 + (bseg * 2 + (s16 & 1)) * 16) : 0xFFFF0000u;
+            v2[j] = piece < p2 ? (unsigned)((((long long)b * N + r) * a.v_ld) * 2 + (bseg * 2 + (s16 & 1)) * 16) : DMA_OOB;
         } else {
             const int row = piece * 16 + (lane >> 2);                  // channel of the pass
-            v2[j] = piece < p2 ? (unsigned)((((long long)b * Cc + row) * N) * 2 + un2 * 16) : 0xFFFF0000u;
+            v2[j] = piece < p2 ? (unsigned)((((long long)b * Cc + row) * N) * 2 + un2 * 16) : DMA_OOB;
         }
     }
     auto issue2 = [&](int pass, int chunk, int buf) __attribute__((always_inline)) {
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(512, 2) void attn_fused_kernel(const AttnFusedArgs 
         for (int j = 0; j < 4; ++j) {
             const int row = (wave * 4 + j) * 16 + (lane >> 2);         // output channel
             // slab-major copy: a 1 KB piece (16 rows x 64 B) is one contiguous run of whole cache lines; the plain matrix gives 16 half lines a kilobyte apart
-            v0[j] = row < Cc ? (unsigned)((a.qw_slab ? row * 32 : row * a.qw_ld) * 2 + un2 * 16) : 0xFFFF0000u;
+            v0[j] = row < Cc ? (unsigned)((a.qw_slab ? row * 32 : row * a.qw_ld) * 2 + un2 * 16) : DMA_OOB;
         }
         const int qstep = a.qw_slab ? a.qw_slab * 2 : 64;             // bytes between 32-channel chunks
         auto issue0 = [&](int chunk, int buf) __attribute__((always_inline)) {
@@ -458,7 +447,7 @@ __global__ __launch_bounds__(512, 2) void attn_fused_kernel(const AttnFusedArgs 
         for (int j = 0; j < 4; ++j) {
             const int piece = wave * 4 + j;
             const int row = piece * 16 + (lane >> 2);                      // output channel
-            v3[j] = row < pe.w_rows && row < Cc ? (unsigned)((sm3 ? row * 32 : row * pe.w_row_stride) * 2 + un2 * 16) : 0xFFFF0000u;
+            v3[j] = row < pe.w_rows && row < Cc ? (unsigned)((sm3 ? row * 32 : row * pe.w_row_stride) * 2 + un2 * 16) : DMA_OOB;
         }
         const int wstep = sm3 ? pe.w_rows * 64 : 64;                      // bytes between 32-channel chunks
         auto issue3 = [&](int chunk, int buf) __attribute__((always_inline)) {

@@ -127,6 +127,102 @@ static bool out_norm_shape_ok(const ConvArgs& a, int bn) {
     const int gw = a.Cout / 32;
     return a.Cout % 32 == 0 && gw > 0 && gw <= 64 && bn % gw == 0 && a.Cout % bn == 0 && a.y_mode == Y_NHWC && a.m_valid == 0 && !a.up4;
 }
+// ---- the tilings both LDS-DMA families have (the 16-bit kernels, the f32x3 ones): one launcher each, over the kernel KERN, its configuration C and the family
+// F (H16Family / X3Family below, next to the kernels they serve: a translation unit sees one family's kernels).  F holds what differs:
+//   ES, SC_KSTEP    element bytes; channels per K step of the fused shortcut's phase
+//   TAG, DT         "" / "x3" behind the kernel's name in a profile name, the dtype at its end;  DMA8, UP4, S2: the launcher's name in error messages
+//   dma8_rejects, up4_rejects        the operands this family's kernel does not take on top of the common list
+//   copy_weights, s2_weights, up4_weights, up4_weight_bytes     which weight copy a launch reads and how its extent is bounded
+// `static std::atomic` in a function template: one per instantiation, i.e. per kernel.
+// (launch_dma / launch_dmax3 and launch_gemm / launch_gemmx3 stay apart: different binaries per launch, rejection lists and statistics-slab rules -- more traits than shared lines.)
+// 3x3 stride-1 on 8 x 8 maps, two images per tile (conv_dma8_kernel.h, conv_dma8x3_kernel.h), no prologue
+template <class F, class C, auto KERN>
+static int launch_dma8_as(const ConvArgs& a0, hipStream_t s) {
+    ConvArgs a = a0;
+    const char* who = F::DMA8;
+    if (a.Hout != 8 || a.Wout != 8 || a.Hin != 8 || a.Win != 8) WDM_FAIL(WDM_EINVAL, "%s: 8x8 maps only", who);
+    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.w_img_stride || a.m_valid || F::dma8_rejects(a)) WDM_FAIL(WDM_EINVAL, "%s: unsupported operand combination", who);
+    WDM_TRY(set_extents(a, (double)a.B * 64, F::ES, who));
+    WDM_TRY(set_shortcut_extents(a, F::ES, F::SC_KSTEP, who));
+    bool done;      // in-tile GroupNorm of the output: a workgroup holds two whole images x BN columns
+    WDM_TRY(check_stats(a, 64 / conv_stat_rows(8, 8, 16 * C::WM), out_norm_shape_ok(a, C::BN), who, &done));
+    if (done) return WDM_OK;
+    F::copy_weights(a);
+    a.mtiles = (a.B + C::NI - 1) / C::NI;
+    a.ntiles = (a.Cout + C::BN - 1) / C::BN;
+    int grid;
+    // every XCD walks 1/4 of the N tiles: its share of the 10-21 MB weight tensor (2.6-5 MB) stays in its 4 MB L2 instead of being re-streamed from the
+    // Infinity Cache by all eight -- time-neutral, half the HBM-side traffic (profiles/r02_traffic.json)
+    grouped_grid(a, 4, &grid);
+    WDM_NAME(name, "convdma8%s_3x3s1_t8x8x2_bn%dw4_%s|8x8 %d->%d%s", F::TAG, C::BN, F::DT, a.Cin, a.Cout, a.sx0 ? " +1x1" : "");
+    static std::atomic<unsigned> devs{0};
+    return launch_named(KERN, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, F::ES, (double)a.B * 64, (double)a.B * 64));
+}
+// Upsample in sub-pixel form (conv_up4_kernel.h, conv_up4x3_kernel.h): a.Hin x a.Win = a.Hout x a.Wout is the LOW-resolution map, y is (2 Hout) x (2 Wout), a.w holds
+// the 16 pre-summed taps [phase][dy'][dx'][rows][cin] (k_pack_up4)
+template <class F, class C, auto KERN>
+static int launch_up4_as(const ConvArgs& a0, hipStream_t s) {
+    constexpr int TILE = C::TH, NI = C::NI;
+    ConvArgs a = a0;
+    const char* who = F::UP4;
+    if (a.Hout % TILE || a.Wout % TILE || a.Hin != a.Hout || a.Win != a.Wout || (NI > 1 && (a.Hout != TILE || a.Wout != TILE)))
+        WDM_FAIL(WDM_EINVAL, "%s: %dx%d map does not fit the %dx%d tile", who, a.Hout, a.Wout, TILE, TILE);
+    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.res || a.sx0 || a.temb || a.w_img_stride || a.y_mode != Y_NHWC || a.Cout % 8 || a.m_valid || F::up4_rejects(a))
+        WDM_FAIL(WDM_EINVAL, "%s: unsupported operand combination (Cin=%d Cout=%d)", who, a.Cin, a.Cout);
+    if (F::up4_weight_bytes(a) >= 4294901760.0) WDM_FAIL(WDM_EINVAL, "%s: weights exceed the 4 GB buffer-offset range", who);
+    F::up4_weights(a);
+    WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, F::ES, who));
+    bool done;      // slabs of the (2H) x (2W) output: four phases
+    WDM_TRY(check_stats(a, 4 * (a.Hout / TILE) * (a.Wout / TILE) * ((TILE * TILE) / conv_stat_rows(TILE, TILE, 16 * C::WM)), false, who, &done));
+    if (done) return WDM_OK;
+    a.up4 = 1;
+    a.up4_ntp = (a.Cout + C::BN - 1) / C::BN;
+    a.mtiles = NI == 1 ? a.B * (a.Hout / TILE) * (a.Wout / TILE) : (a.B + NI - 1) / NI;
+    a.ntiles = 4 * a.up4_ntp;
+    int grid;
+    plain_grid(a, &grid);                            // N fastest: the four phases of an M tile run back to back behind one halo tile
+    WDM_NAME(name, "convup4%s_2x2x4_t%dx%dx%d_bn%dw8_%s|%dx%d %d->%d", F::TAG, TILE, TILE, NI, C::BN, F::DT, 2 * a.Hout, 2 * a.Wout, a.Cin, a.Cout);
+    const double Mhi = 4.0 * a.B * a.Hout * a.Wout;
+    const Work w = {2.0 * Mhi * a.Cout * 4.0 * a.Cin,             // executed: 4 taps per output pixel (the 9-tap form has 2.25x more)
+                    (double)a.B * a.Hin * a.Win * a.Cin * F::ES + 16.0 * a.Cout * (double)a.Cin * F::ES + Mhi * a.Cout * F::ES};
+    static std::atomic<unsigned> devs{0};
+    return launch_named(KERN, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, w);
+}
+// Downsample conv (3x3 stride 2, zero pad right / bottom) over the input's four phases (conv_s2_kernel.h, conv_s2x3_kernel.h)
+template <class F, class C, auto KERN>
+static int launch_s2_as(const ConvArgs& a0, hipStream_t s) {
+    ConvArgs a = a0;
+    const char* who = F::S2;
+    if (a.Hout % 16 || a.Wout % 16 || a.Hin != 2 * a.Hout || a.Win != 2 * a.Wout) WDM_FAIL(WDM_EINVAL, "%s: %dx%d -> %dx%d does not fit the 16x16 tile", who, a.Hin, a.Win, a.Hout, a.Wout);
+    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.sx0 || a.w_img_stride || a.m_valid || a.yn) WDM_FAIL(WDM_EINVAL, "%s: unsupported operand combination (Cin=%d Cout=%d)", who, a.Cin, a.Cout);
+    WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, F::ES, who));
+    bool done;
+    static_assert(256 / conv_stat_rows(16, 16, 16 * C::WM) == 4, "64-row statistics slabs in both families");
+    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, who, &done));
+    if (done) return WDM_OK;
+    F::s2_weights(a);
+    a.mtiles = a.B * (a.Hout / 16) * (a.Wout / 16);
+    a.ntiles = (a.Cout + C::BN - 1) / C::BN;
+    int grid;
+    plain_grid(a, &grid);
+    WDM_NAME(name, "convs2%s_3x3s2_t16x16x1_bn%dw8_%s|%dx%d %d->%d", F::TAG, C::BN, F::DT, a.Hout, a.Wout, a.Cin, a.Cout);
+    static std::atomic<unsigned> devs{0};
+    return launch_named(KERN, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, F::ES, (double)a.B * a.Hin * a.Win, (double)a.B * a.Hout * a.Wout));
+}
+// 256-column tiles (3x3 stride-1, sub-pixel upsample, 1x1 GEMM; the same bits as the 128-column ones): WDM_BN256 = 0 never, 1 (default) where the grid still
+// fills the chip -- launches the caller keeps in flight side by side (wdm_set_concurrent_streams) count together --, 2 wherever the shape allows
+static bool wide_tiles(const ConvArgs& a, long long wg256) {
+    const int v = env_cfg().bn256;
+    return v && a.Cout % 256 == 0 && (v == 2 || wg256 * concurrent_streams() >= 200);
+}
+// 512 x 128 tiles (32 x 16 pixels): layers with one or a few 128-column N tiles and enough pixel tiles that the chip stays full at half their number
+// (TallCfg: the configuration of the family's 512 x 128 kernel, for its MAX_CIN)
+template <class TallCfg>
+static bool tall_tiles(const ConvArgs& a) {
+    const int v = env_cfg().bn256;
+    if (!v || a.Hout % 32 || a.Wout % 16 || a.Cout % 128 || a.Cin > TallCfg::MAX_CIN) return false;
+    return v == 2 || (long long)a.B * (a.Hout / 32) * (a.Wout / 16) * (a.Cout / 128) * concurrent_streams() >= 200;
+}
 #ifdef WDM_HAS_GEMM
 // ---- bf16 LDS-DMA kernels -----------------------------------------------------------------------------------------------------------------------
 // 3x3 stride-1 on 16-pixel-multiple maps: 256 x 128 tile (conv_dma_kernel.h)
@@ -190,79 +286,26 @@ static int launch_dma_big(const ConvArgs& a0, hipStream_t s) {
 }
 static int launch_dma256(const ConvArgs& a, hipStream_t s) { return launch_dma_big<4, 2, 16>(a, s); }
 static int launch_dma512(const ConvArgs& a, hipStream_t s) { return launch_dma_big<8, 1, 32>(a, s); }
-// 3x3 stride-1 on 8 x 8 maps, two images per tile (conv_dma8_kernel.h), no prologue
+// the 16-bit family of the shared launchers (launch_dma8_as, launch_up4_as, launch_s2_as), and their instantiations on this unit's kernels
+struct H16Family {
+    static constexpr double ES = 2.0;
+    static constexpr int SC_KSTEP = 64;
+    static constexpr const char *TAG = "", *DT = WDM_H16_NAME, *DMA8 = "conv(dma8)", *UP4 = "conv(up4)", *S2 = "conv(s2)";
+    static bool dma8_rejects(const ConvArgs&) { return false; }          // (takes a fused shortcut, and the weights in either layout)
+    static bool up4_rejects(const ConvArgs&) { return false; }
+    static void copy_weights(ConvArgs& a) { use_slab_major(a); }
+    static void s2_weights(ConvArgs& a) { use_slab_major(a); }           // (round 5: the Downsample convs carry the slab-major copy too: whole cache lines per DMA piece)
+    static void up4_weights(ConvArgs& a) {                               // k_pack_up4's slab-major layout [cin / 32][16 taps][rows][32]
+        a.w_tap_stride = (long long)a.w_rows * 32; a.w_row_stride = 32; a.w_slab_stride = 16 * a.w_rows * 32;
+    }
+    static double up4_weight_bytes(const ConvArgs& a) { return (double)a.w_bytes; }
+};
 template <int BN_>
-static int launch_dma8(const ConvArgs& a0, hipStream_t s) {
-    using C = ConvDma8Cfg<BN_>;
-    ConvArgs a = a0;
-    if (a.Hout != 8 || a.Wout != 8 || a.Hin != 8 || a.Win != 8) WDM_FAIL(WDM_EINVAL, "conv(dma8): 8x8 maps only");
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.w_img_stride || a.m_valid) WDM_FAIL(WDM_EINVAL, "conv(dma8): unsupported operand combination");
-    WDM_TRY(set_extents(a, (double)a.B * 64, 2.0, "conv(dma8)"));
-    WDM_TRY(set_shortcut_extents(a, 2.0, 64, "conv(dma8)"));
-    bool done;      // in-tile GroupNorm of the output: a workgroup holds two whole images x BN columns
-    WDM_TRY(check_stats(a, 64 / conv_stat_rows(8, 8, 16 * C::WM), out_norm_shape_ok(a, C::BN), "conv(dma8)", &done));
-    if (done) return WDM_OK;
-    use_slab_major(a);
-    a.mtiles = (a.B + C::NI - 1) / C::NI;
-    a.ntiles = (a.Cout + C::BN - 1) / C::BN;
-    int grid;
-    // every XCD walks 1/4 of the N tiles: its share of the 10-21 MB weight tensor (2.6-5 MB) stays in its 4 MB L2 instead of being re-streamed from the
-    // Infinity Cache by all eight -- time-neutral, half the HBM-side traffic (profiles/r02_traffic.json)
-    grouped_grid(a, 4, &grid);
-    WDM_NAME(name, "convdma8_3x3s1_t8x8x2_bn%dw4_" WDM_H16_NAME "|8x8 %d->%d%s", BN_, a.Cin, a.Cout, a.sx0 ? " +1x1" : "");
-    static std::atomic<unsigned> devs{0};
-    return launch_named(conv_dma8_kernel<BN_, 2, WDM_T>, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, 2.0, (double)a.B * 64, (double)a.B * 64));
-}
-// Upsample in sub-pixel form (conv_up4_kernel.h): a.Hin x a.Win = a.Hout x a.Wout is the LOW-resolution map, y is (2 Hout) x (2 Wout), a.w holds the 16
-// pre-summed taps [phase][dy'][dx'][rows][cin] (k_pack_up4)
+static int launch_dma8(const ConvArgs& a, hipStream_t s) { return launch_dma8_as<H16Family, ConvDma8Cfg<BN_>, conv_dma8_kernel<BN_, 2, WDM_T>>(a, s); }
 template <int TILE, int NI, int WN = 4>
-static int launch_up4(const ConvArgs& a0, hipStream_t s) {
-    using C = ConvUp4Cfg<TILE, NI, WN>;
-    ConvArgs a = a0;
-    if (a.Hout % TILE || a.Wout % TILE || a.Hin != a.Hout || a.Win != a.Wout || (NI > 1 && (a.Hout != TILE || a.Wout != TILE)))
-        WDM_FAIL(WDM_EINVAL, "conv(up4): %dx%d map does not fit the %dx%d tile", a.Hout, a.Wout, TILE, TILE);
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.res || a.sx0 || a.temb || a.w_img_stride || a.y_mode != Y_NHWC || a.Cout % 8 || a.m_valid)
-        WDM_FAIL(WDM_EINVAL, "conv(up4): unsupported operand combination (Cin=%d Cout=%d)", a.Cin, a.Cout);
-    if ((double)a.w_bytes >= 4294901760.0) WDM_FAIL(WDM_EINVAL, "conv(up4): weights exceed the 4 GB buffer-offset range");
-    // k_pack_up4's slab-major layout [cin / 32][16 taps][rows][32]
-    a.w_tap_stride = (long long)a.w_rows * 32; a.w_row_stride = 32; a.w_slab_stride = 16 * a.w_rows * 32;
-    WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 2.0, "conv(up4)"));
-    bool done;      // slabs of the (2H) x (2W) output: four phases
-    WDM_TRY(check_stats(a, 4 * (a.Hout / TILE) * (a.Wout / TILE) * ((TILE * TILE) / conv_stat_rows(TILE, TILE, 16 * C::WM)), false, "conv(up4)", &done));
-    if (done) return WDM_OK;
-    a.up4 = 1;
-    a.up4_ntp = (a.Cout + C::BN - 1) / C::BN;
-    a.mtiles = NI == 1 ? a.B * (a.Hout / TILE) * (a.Wout / TILE) : (a.B + NI - 1) / NI;
-    a.ntiles = 4 * a.up4_ntp;
-    int grid;
-    plain_grid(a, &grid);                            // N fastest: the four phases of an M tile run back to back behind one halo tile
-    WDM_NAME(name, "convup4_2x2x4_t%dx%dx%d_bn%dw8_" WDM_H16_NAME "|%dx%d %d->%d", TILE, TILE, NI, C::BN, 2 * a.Hout, 2 * a.Wout, a.Cin, a.Cout);
-    const double Mhi = 4.0 * a.B * a.Hout * a.Wout;
-    const Work w = {2.0 * Mhi * a.Cout * 4.0 * a.Cin,             // executed: 4 taps per output pixel (the 9-tap form has 2.25x more)
-                    (double)a.B * a.Hin * a.Win * a.Cin * 2.0 + 16.0 * a.Cout * (double)a.Cin * 2.0 + Mhi * a.Cout * 2.0};
-    static std::atomic<unsigned> devs{0};
-    return launch_named(conv_up4_kernel<TILE, NI, WN, WDM_T>, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, w);
-}
-// Downsample conv (3x3 stride 2, zero pad right / bottom) over the input's four phases (conv_s2_kernel.h)
+static int launch_up4(const ConvArgs& a, hipStream_t s) { return launch_up4_as<H16Family, ConvUp4Cfg<TILE, NI, WN>, conv_up4_kernel<TILE, NI, WN, WDM_T>>(a, s); }
 template <int WN>
-static int launch_s2(const ConvArgs& a0, hipStream_t s) {
-    using C = ConvS2Cfg<16, 1, WN>;
-    ConvArgs a = a0;
-    if (a.Hout % 16 || a.Wout % 16 || a.Hin != 2 * a.Hout || a.Win != 2 * a.Wout) WDM_FAIL(WDM_EINVAL, "conv(s2): %dx%d -> %dx%d does not fit the 16x16 tile", a.Hin, a.Win, a.Hout, a.Wout);
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.sx0 || a.w_img_stride || a.m_valid || a.yn) WDM_FAIL(WDM_EINVAL, "conv(s2): unsupported operand combination (Cin=%d Cout=%d)", a.Cin, a.Cout);
-    WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 2.0, "conv(s2)"));
-    bool done;
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * (256 / conv_stat_rows(16, 16, 16 * C::WM)), false, "conv(s2)", &done));
-    if (done) return WDM_OK;
-    use_slab_major(a);                               // (round 5: the Downsample convs carry the slab-major copy too: whole cache lines per DMA piece)
-    a.mtiles = a.B * (a.Hout / 16) * (a.Wout / 16);
-    a.ntiles = (a.Cout + C::BN - 1) / C::BN;
-    int grid;
-    plain_grid(a, &grid);
-    WDM_NAME(name, "convs2_3x3s2_t16x16x1_bn%dw8_" WDM_H16_NAME "|%dx%d %d->%d", C::BN, a.Hout, a.Wout, a.Cin, a.Cout);
-    static std::atomic<unsigned> devs{0};
-    return launch_named(conv_s2_kernel<16, 1, WN, WDM_T>, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, 2.0, (double)a.B * a.Hin * a.Win, (double)a.B * a.Hout * a.Wout));
-}
+static int launch_s2(const ConvArgs& a, hipStream_t s) { return launch_s2_as<H16Family, ConvS2Cfg<16, 1, WN>, conv_s2_kernel<16, 1, WN, WDM_T>>(a, s); }
 // 1x1 convolution / batched GEMM on the LDS-DMA GEMM kernel (conv_gemm_kernel.h)
 // TH = 16: 256-pixel tiles, 8 waves 4 (M) x 2 (N) of 64 x 16 WN; TH = 8: 128-pixel tiles (8 x 16 "maps": the weight-gradient GEMMs of layers with 128 / 384 output
 // channels, whose M is the channel count), 8 waves 2 (M) x 4 (N) of 64 x 32
@@ -284,18 +327,6 @@ static int launch_gemm(const ConvArgs& a0, hipStream_t s) {
     WDM_NAME(name, "gemm_1x1_t%dx16x1_bn%d_" WDM_H16_NAME "|%dx%d %d->%d", TH, C::BN, a.Hout, a.Wout, a.Cin, a.Cout);
     static std::atomic<unsigned> devs{0};
     return launch_named(conv_gemm_kernel<TH, 16, 1, WAVES_M, WAVES_N, 4, WN, WDM_T>, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 1.0, 2.0, (double)a.B * a.Hin * a.Win, (double)a.B * a.Hout * a.Wout));
-}
-// 256-column tiles (3x3 stride-1, sub-pixel upsample, 1x1 GEMM; the same bits as the 128-column ones): WDM_BN256 = 0 never, 1 (default) where the grid still
-// fills the chip -- launches the caller keeps in flight side by side (wdm_set_concurrent_streams) count together --, 2 wherever the shape allows
-static bool wide_tiles(const ConvArgs& a, long long wg256) {
-    const int v = env_cfg().bn256;
-    return v && a.Cout % 256 == 0 && (v == 2 || wg256 * concurrent_streams() >= 200);
-}
-// 512 x 128 tiles (32 x 16 pixels): layers with one or a few 128-column N tiles and enough pixel tiles that the chip stays full at half their number
-static bool tall_tiles(const ConvArgs& a) {
-    const int v = env_cfg().bn256;
-    if (!v || a.Hout % 32 || a.Wout % 16 || a.Cout % 128 || a.Cin > ConvDma256Cfg<8, 1, 4, 8, 32>::MAX_CIN) return false;
-    return v == 2 || (long long)a.B * (a.Hout / 32) * (a.Wout / 16) * (a.Cout / 128) * concurrent_streams() >= 200;
 }
 #endif
 
@@ -322,17 +353,6 @@ static int launch_dmax3(const ConvArgs& a0, hipStream_t s) {
     static std::atomic<unsigned> devs{0};
     return launch_named(conv_dmax3_kernel, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, 4.0, (double)a.B * a.Hin * a.Win, (double)a.B * a.Hout * a.Wout));
 }
-// the workgroup-count rules of the bf16 path's big tiles (tall_tiles / wide_tiles), same switch
-static bool tall_tiles_x3(const ConvArgs& a) {
-    const int v = env_cfg().bn256;
-    if (!v || a.Hout % 32 || a.Wout % 16 || a.Cout % 128 || a.Cin > ConvDmaX3TCfg<true>::MAX_CIN) return false;
-    return v == 2 || (long long)a.B * (a.Hout / 32) * (a.Wout / 16) * (a.Cout / 128) * concurrent_streams() >= 200;
-}
-static bool wide_tiles_x3(const ConvArgs& a) {
-    const int v = env_cfg().bn256;
-    if (!v || a.Cout % 256) return false;
-    return v == 2 || (long long)a.B * (a.Hout / 16) * (a.Wout / 16) * (a.Cout / 256) * concurrent_streams() >= 200;
-}
 // ... on 512 x 128 / 256 x 256 tiles (conv_dmax3t_kernel.h): bit-identical to launch_dmax3's tiling; pre-split weights, no shortcut phase, no in-tile GroupNorm of the output
 template <bool TALL>
 static int launch_dmax3t(const ConvArgs& a0, hipStream_t s) {
@@ -354,52 +374,24 @@ static int launch_dmax3t(const ConvArgs& a0, hipStream_t s) {
     static std::atomic<unsigned> devs{0};
     return launch_named(conv_dmax3t_kernel<TALL>, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, 4.0, (double)a.B * a.Hin * a.Win, (double)a.B * a.Hout * a.Wout));
 }
-// 8 x 8 maps (conv_dma8x3_kernel.h): needs the model's pre-split weight copy
+// the f32x3 family of the shared launchers, and their instantiations on this unit's kernels
+struct X3Family {
+    static constexpr double ES = 4.0;
+    static constexpr int SC_KSTEP = 32;
+    static constexpr const char *TAG = "x3", *DT = "f32x3", *DMA8 = "conv(dma8x3)", *UP4 = "conv(up4x3)", *S2 = "conv(s2x3)";
+    static bool dma8_rejects(const ConvArgs& a) { return a.sx0 || !a.w_sm; }      // no shortcut phase; needs the model's pre-split weight copy
+    static bool up4_rejects(const ConvArgs& a) { return a.yn != nullptr; }
+    static void copy_weights(ConvArgs& a) { a.w = a.w_sm; a.w_split = 1; }
+    static void s2_weights(ConvArgs&) {}                                           // (Downsample convs have no pre-split copy: the kernel splits in LDS)
+    static void up4_weights(ConvArgs&) {}                                          // a.w holds the pre-summed, pre-split taps (k_pack_up4, WDM_F32X3) at the caller's strides
+    static double up4_weight_bytes(const ConvArgs& a) { return 4.0 * a.w_tap_stride * 4.0; }      // the four taps of a phase: what the kernel's descriptor spans
+};
 template <int BN_>
-static int launch_dma8x3(const ConvArgs& a0, hipStream_t s) {
-    using C = ConvDma8X3Cfg<BN_>;
-    ConvArgs a = a0;
-    if (a.Hout != 8 || a.Wout != 8 || a.Hin != 8 || a.Win != 8) WDM_FAIL(WDM_EINVAL, "conv(dma8x3): 8x8 maps only");
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.w_img_stride || a.m_valid || a.sx0 || !a.w_sm) WDM_FAIL(WDM_EINVAL, "conv(dma8x3): unsupported operand combination");
-    WDM_TRY(set_extents(a, (double)a.B * 64, 4.0, "conv(dma8x3)"));
-    bool done;
-    WDM_TRY(check_stats(a, 64 / conv_stat_rows(8, 8, 16 * C::WM), out_norm_shape_ok(a, C::BN), "conv(dma8x3)", &done));
-    if (done) return WDM_OK;
-    a.w = a.w_sm; a.w_split = 1;
-    a.mtiles = (a.B + C::NI - 1) / C::NI;
-    a.ntiles = (a.Cout + C::BN - 1) / C::BN;
-    int grid;
-    grouped_grid(a, 4, &grid);                       // N-tile groups per XCD as launch_dma8
-    WDM_NAME(name, "convdma8x3_3x3s1_t8x8x2_bn%dw4_f32x3|8x8 %d->%d", BN_, a.Cin, a.Cout);
-    static std::atomic<unsigned> devs{0};
-    return launch_named(conv_dma8x3_kernel<BN_>, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, 4.0, (double)a.B * 64, (double)a.B * 64));
-}
-// Upsample in sub-pixel form (conv_up4x3_kernel.h): a.w holds the 16 pre-summed, pre-split taps (k_pack_up4, WDM_F32X3)
+static int launch_dma8x3(const ConvArgs& a, hipStream_t s) { return launch_dma8_as<X3Family, ConvDma8X3Cfg<BN_>, conv_dma8x3_kernel<BN_>>(a, s); }
 template <int TILE, int NI>
-static int launch_up4x3(const ConvArgs& a0, hipStream_t s) {
-    using C = ConvUp4X3Cfg<TILE, NI>;
-    ConvArgs a = a0;
-    if (a.Hout % TILE || a.Wout % TILE || a.Hin != a.Hout || a.Win != a.Wout || (NI > 1 && (a.Hout != TILE || a.Wout != TILE)))
-        WDM_FAIL(WDM_EINVAL, "conv(up4x3): %dx%d map does not fit the %dx%d tile", a.Hout, a.Wout, TILE, TILE);
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.res || a.sx0 || a.temb || a.w_img_stride || a.y_mode != Y_NHWC || a.Cout % 8 || a.m_valid || a.yn)
-        WDM_FAIL(WDM_EINVAL, "conv(up4x3): unsupported operand combination (Cin=%d Cout=%d)", a.Cin, a.Cout);
-    if (4.0 * a.w_tap_stride * 4.0 >= 4294901760.0) WDM_FAIL(WDM_EINVAL, "conv(up4x3): weights exceed the 4 GB buffer-offset range");
-    WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 4.0, "conv(up4x3)"));
-    bool done;
-    WDM_TRY(check_stats(a, 4 * (a.Hout / TILE) * (a.Wout / TILE) * ((TILE * TILE) / conv_stat_rows(TILE, TILE, 16 * C::WM)), false, "conv(up4x3)", &done));
-    if (done) return WDM_OK;
-    a.up4 = 1;
-    a.up4_ntp = (a.Cout + C::BN - 1) / C::BN;
-    a.mtiles = NI == 1 ? a.B * (a.Hout / TILE) * (a.Wout / TILE) : (a.B + NI - 1) / NI;
-    a.ntiles = 4 * a.up4_ntp;
-    int grid;
-    plain_grid(a, &grid);
-    WDM_NAME(name, "convup4x3_2x2x4_t%dx%dx%d_bn%dw8_f32x3|%dx%d %d->%d", TILE, TILE, NI, C::BN, 2 * a.Hout, 2 * a.Wout, a.Cin, a.Cout);
-    const double Mhi = 4.0 * a.B * a.Hout * a.Wout;
-    const Work w = {2.0 * Mhi * a.Cout * 4.0 * a.Cin, (double)a.B * a.Hin * a.Win * a.Cin * 4.0 + 16.0 * a.Cout * (double)a.Cin * 4.0 + Mhi * a.Cout * 4.0};
-    static std::atomic<unsigned> devs{0};
-    return launch_named(conv_up4x3_kernel<TILE, NI>, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, w);
-}
+static int launch_up4x3(const ConvArgs& a, hipStream_t s) { return launch_up4_as<X3Family, ConvUp4X3Cfg<TILE, NI>, conv_up4x3_kernel<TILE, NI>>(a, s); }
+template <int WN>
+static int launch_s2x3(const ConvArgs& a, hipStream_t s) { return launch_s2_as<X3Family, ConvS2X3Cfg<WN>, conv_s2x3_kernel<WN>>(a, s); }
 // 1x1 convolutions / batched GEMMs (conv_gemmx3_kernel.h: both operands split in LDS)
 static int launch_gemmx3(const ConvArgs& a0, hipStream_t s) {
     using C = GemmX3Cfg;
@@ -417,25 +409,6 @@ static int launch_gemmx3(const ConvArgs& a0, hipStream_t s) {
     WDM_NAME(name, "gemmx3_1x1_t16x16x1_bn128_f32x3|%dx%d %d->%d", a.Hout, a.Wout, a.Cin, a.Cout);
     static std::atomic<unsigned> devs{0};
     return launch_named(conv_gemmx3_kernel, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 1.0, 4.0, (double)a.B * a.Hin * a.Win, (double)a.B * a.Hout * a.Wout));
-}
-// Downsample conv (conv_s2x3_kernel.h)
-template <int WN>
-static int launch_s2x3(const ConvArgs& a0, hipStream_t s) {
-    using C = ConvS2X3Cfg<WN>;
-    ConvArgs a = a0;
-    if (a.Hout % 16 || a.Wout % 16 || a.Hin != 2 * a.Hout || a.Win != 2 * a.Wout) WDM_FAIL(WDM_EINVAL, "conv(s2x3): %dx%d -> %dx%d does not fit the 16x16 tile", a.Hin, a.Win, a.Hout, a.Wout);
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.sx0 || a.w_img_stride || a.m_valid || a.yn) WDM_FAIL(WDM_EINVAL, "conv(s2x3): unsupported operand combination (Cin=%d Cout=%d)", a.Cin, a.Cout);
-    WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, 4.0, "conv(s2x3)"));
-    bool done;
-    WDM_TRY(check_stats(a, (a.Hout / 16) * (a.Wout / 16) * 4, false, "conv(s2x3)", &done));
-    if (done) return WDM_OK;
-    a.mtiles = a.B * (a.Hout / 16) * (a.Wout / 16);
-    a.ntiles = (a.Cout + C::BN - 1) / C::BN;
-    int grid;
-    plain_grid(a, &grid);
-    WDM_NAME(name, "convs2x3_3x3s2_t16x16x1_bn%dw8_f32x3|%dx%d %d->%d", C::BN, a.Hout, a.Wout, a.Cin, a.Cout);
-    static std::atomic<unsigned> devs{0};
-    return launch_named(conv_s2x3_kernel<WN>, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, 4.0, (double)a.B * a.Hin * a.Win, (double)a.B * a.Hout * a.Wout));
 }
 #endif
 
@@ -492,7 +465,7 @@ int WDM_LAUNCH_NAME(const ConvArgs& a, int mode, hipStream_t s) {
                 // whether it can must not depend on the batch, which the workgroup-count rule does)
                 const bool wants_yn = (a.yn != nullptr || a.query_yn != nullptr) && a.Hout == 16 && a.Wout == 16;
                 if (!wants_yn && wide_tiles(a, (long long)a.B * (a.Hout / 16) * (a.Wout / 16) * (a.Cout / 256))) return launch_dma256(a, s);
-                if (!wants_yn && tall_tiles(a)) return launch_dma512(a, s);
+                if (!wants_yn && tall_tiles<ConvDma256Cfg<8, 1, 4, 8, 32>>(a)) return launch_dma512(a, s);
                 return launch_dma(a, s);
             }
             // any batch size (a lone image fills half a tile); the N tile by Cout alone (the two tilings sum a slab's GroupNorm partials in different associations)
@@ -503,8 +476,8 @@ int WDM_LAUNCH_NAME(const ConvArgs& a, int mode, hipStream_t s) {
                 // 512 x 128 tiles by the workgroup-count rule of the bf16 path (tall_tiles), where this kernel's restrictions allow (a conv asked to also
                 // normalise its output never comes here: 16 x 16 maps only)
                 const bool wants_yn = a.yn != nullptr || a.query_yn != nullptr;
-                if (a.w_sm && !a.sx0 && !wants_yn && wide_tiles_x3(a)) return launch_dmax3t<false>(a, s);
-                if (a.w_sm && !a.sx0 && !wants_yn && tall_tiles_x3(a)) return launch_dmax3t<true>(a, s);
+                if (a.w_sm && !a.sx0 && !wants_yn && wide_tiles(a, (long long)a.B * (a.Hout / 16) * (a.Wout / 16) * (a.Cout / 256))) return launch_dmax3t<false>(a, s);
+                if (a.w_sm && !a.sx0 && !wants_yn && tall_tiles<ConvDmaX3TCfg<true>>(a)) return launch_dmax3t<true>(a, s);
                 return launch_dmax3(a, s);
             }
             if (dma && img8 && a.w_sm && !a.pro && !a.x1 && !a.sx0 && a.Cin % 16 == 0 && shared_w && !a.m_valid && a.Cout % 8 == 0) return a.Cout % 48 == 0 ? launch_dma8x3<48>(a, s) : launch_dma8x3<64>(a, s);

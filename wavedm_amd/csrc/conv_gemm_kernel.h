@@ -19,6 +19,7 @@
 // past the packed matrix) are outside the buffer descriptor: the DMA writes zeros.
 #pragma once
 #include "conv_kernel.h"
+#include "lds_dma.h"
 #ifndef WDM_GABL
 #define WDM_GABL 0      // ablation mask for tools/gemm_ablate.hip: 1 no epilogue, 2 no MFMA, 4 DMA for the first two stages only
 #endif
@@ -66,7 +67,6 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const int bid,
     if (NI == 1) conv_decode_image<TH, TW>(a, mt, img0, tile_in_img, oy0, ox0);
     else { img0 = mt * NI; oy0 = 0; ox0 = 0; }
 
-    constexpr unsigned OOB = 0xFFFF0000u;
     // ---- per-lane source offsets of this wave's chunks (loop-invariant; the K step is a scalar offset)
     unsigned a_v0[A_CPW], a_v1[A_CPW], b_v[B_CPW];
 #pragma unroll
@@ -78,36 +78,21 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const int bid,
         const int iy = oy0 + r / TW, ix = ox0 + r % TW;
         const bool ok = img_g < a.B && iy < a.Hin && ix < a.Win;
         const unsigned gp = (unsigned)((conv_x_img(a, img_g) * a.Hin + iy) * a.Win + ix);
-        a_v0[j] = ok ? gp * (unsigned)(a.xs0 * 2) + (unsigned)(u * 16) : OOB;
-        a_v1[j] = ok ? gp * (unsigned)(a.xs1 * 2) + (unsigned)(u * 16) : OOB;
+        a_v0[j] = ok ? gp * (unsigned)(a.xs0 * 2) + (unsigned)(u * 16) : DMA_OOB;
+        a_v1[j] = ok ? gp * (unsigned)(a.xs1 * 2) + (unsigned)(u * 16) : DMA_OOB;
     }
 #pragma unroll
     for (int j = 0; j < B_CPW; ++j) {
         const int row = (wave * B_CPW + j) * 8 + (lane >> 3);
         const int u = (lane & 7) ^ ((row >> 1) & 7);
         const int n = n0 + row;
-        b_v[j] = n < a.w_rows ? (unsigned)(n * a.w_row_stride * 2 + u * 16) : OOB;
+        b_v[j] = n < a.w_rows ? (unsigned)(n * a.w_row_stride * 2 + u * 16) : DMA_OOB;
     }
 
-    // The LDS-DMA is issued from inline asm: hipcc waits vmcnt(0) before the first ds_read after a DMA it knows about (it cannot
-    // prove the read does not alias the destination), which would drain the ring every K step.  It does not count asm loads, so
-    // every wait on them below is explicit.  M0 carries the wave-uniform LDS byte address; it is saved / restored inside the
-    // statement because the compiler does not expect it to change.
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    auto make_q = [](const void* p, unsigned bytes) __attribute__((always_inline)) {      // raw buffer descriptor: base, stride 0, num_records, flags
-        const unsigned long long v = (unsigned long long)p;
-        return i32x4{(int)(unsigned)v, (int)((unsigned)(v >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-    };
+    // (lds_dma.h: the DMA is inline asm the compiler does not count, so every wait on it below is explicit)
     const i32x4 q_x0 = make_q(a.x0, a.x0_bytes), q_x1 = make_q(a.x1 ? a.x1 : a.x0, a.x1_bytes);
     const i32x4 q_w = make_q((const T*)a.w + conv_w_img_offset(a, img0), a.w_bytes);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-    auto dma16 = [&](const i32x4& rsrc, unsigned lds_addr, unsigned voff, int soff) __attribute__((always_inline)) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff), "s"(lds_addr), "s"(rsrc), "s"(soff)
-                     : "memory");
-    };
     auto issue = [&](int k, int buf) __attribute__((always_inline)) {
         const int c = k * C::BK;
         const unsigned base = lds0 + buf * STAGE;

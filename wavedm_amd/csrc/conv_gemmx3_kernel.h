@@ -8,37 +8,28 @@
 // the weight-side fragment is the group as stored ([w_hi | w_lo] x 16 channels), the pixel-side fragment its hi half in all four k-groups, then its lo half.
 #pragma once
 #include "conv_kernel.h"
+#include "conv_gemm_kernel.h"
+#include "lds_dma.h"
 
 namespace wdm {
 
-struct GemmX3Cfg {
+// conv_gemm_kernel.h's 256 x 128 tiling (128-byte rows, ring of three 48 KB stages) with 32 fp32 channels per stage instead of 64 16-bit ones
+struct GemmX3Cfg : GemmCfg<16, 16, 1, 4, 2, 4, 4> {
     static constexpr int TH = 16, TW = 16, WAVES_M = 4, WAVES_N = 2, WM = 4, WN = 4;
-    static constexpr int NWAVES = 8, NTHREADS = 512, M = 256, BN = 128, BK = 32;
-    static constexpr int A_BYTES = M * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;      // 48 KB
-    static constexpr int NBUF = 3;
-    static constexpr int EPI_BYTES = NWAVES * 64 * (16 * WN + 4) * 4;
-    static constexpr int LDS_BYTES = NBUF * STAGE > EPI_BYTES ? NBUF * STAGE : EPI_BYTES;      // 144 KB
-    static constexpr int A_CPW = (M / 8) / NWAVES, B_CPW = (BN / 8) / NWAVES;                  // 1 KB chunks (8 rows) per wave per stage: 4 + 2
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+    static constexpr int BK = 32;
 };
+static_assert(GemmX3Cfg::BN == 128 && GemmX3Cfg::NTHREADS == 512 && GemmX3Cfg::A_CPW == 4 && GemmX3Cfg::B_CPW == 2 && GemmX3Cfg::NBUF == 3 && GemmX3Cfg::STAGE == 49152 &&
+              GemmX3Cfg::LDS_BYTES == 147456, "GemmX3Cfg");
 
 // The K loop of the GEMM as a phase other kernels can run too (conv_dmax3_kernel.h: the ResnetBlock's 1x1 shortcut accumulated into conv2's tile): rows of the A
 // operand = the tile's 256 pixels at a_v0 / a_v1 (per-lane byte offsets into q_a0 / q_a1 of this wave's chunks; the second tensor takes over at channel C0),
 // rows of the B operand at b_v into q_w, nk stages of 32 channels; every LDS byte from `smem` up to 3 stages is overwritten.  The caller has drained its DMA
 // queue and passed a barrier.
-typedef int gx3_i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void gemmx3_phase(f32x4 (&acc)[4][4], char* smem, const gx3_i32x4& q_a0, const gx3_i32x4& q_a1, const gx3_i32x4& q_w, const unsigned (&a_v0)[4],
+__device__ __forceinline__ void gemmx3_phase(f32x4 (&acc)[4][4], char* smem, const i32x4& q_a0, const i32x4& q_a1, const i32x4& q_w, const unsigned (&a_v0)[4],
                                              const unsigned (&a_v1)[4], const unsigned (&b_v)[2], int C0, int nk, int lane, int wave, int wave_m, int wave_n) {
     using C = GemmX3Cfg;
     constexpr int WM = C::WM, WN = C::WN, A_BYTES = C::A_BYTES, STAGE = C::STAGE, A_CPW = C::A_CPW, B_CPW = C::B_CPW;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-    auto dma16 = [&](const gx3_i32x4& rsrc, unsigned lds_addr, unsigned voff, int soff) __attribute__((always_inline)) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff), "s"(lds_addr), "s"(rsrc), "s"(soff)
-                     : "memory");
-    };
     auto issue = [&](int k, int buf) __attribute__((always_inline)) {
         const int c = k * C::BK;
         const unsigned base = lds0 + buf * STAGE;
@@ -61,12 +52,10 @@ __device__ __forceinline__ void gemmx3_phase(f32x4 (&acc)[4][4], char* smem, con
         const int dhi = ((u & 4) | ((u & 3) >> 1)) ^ sw;
         char* rowp = pc + (lane >> 3) * 128;
         const uint4 v = *(const uint4*)(pc + lane * 16);
-        const float x0 = __uint_as_float(v.x), x1 = __uint_as_float(v.y), x2 = __uint_as_float(v.z), x3 = __uint_as_float(v.w);
-        const unsigned h01 = TI<__bf16>::pack2(x0, x1), h23 = TI<__bf16>::pack2(x2, x3);
-        const unsigned l01 = TI<__bf16>::pack2(x0 - __uint_as_float(h01 << 16), x1 - __uint_as_float(h01 & 0xffff0000u));
-        const unsigned l23 = TI<__bf16>::pack2(x2 - __uint_as_float(h23 << 16), x3 - __uint_as_float(h23 & 0xffff0000u));
-        *(uint2*)(rowp + dhi * 16 + (u & 1) * 8) = make_uint2(h01, h23);
-        *(uint2*)(rowp + (dhi ^ 2) * 16 + (u & 1) * 8) = make_uint2(l01, l23);
+        uint2 hi, lo;
+        x3_split_unit(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w), hi, lo);
+        *(uint2*)(rowp + dhi * 16 + (u & 1) * 8) = hi;
+        *(uint2*)(rowp + (dhi ^ 2) * 16 + (u & 1) * 8) = lo;
     };
     auto split = [&](int buf) __attribute__((always_inline)) {
         char* base = smem + buf * STAGE;
@@ -113,11 +102,7 @@ __device__ __forceinline__ void gemmx3_phase(f32x4 (&acc)[4][4], char* smem, con
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
-                for (int j = 0; j < WN; ++j) {
-                    const bf16x8 w = __builtin_bit_cast(bf16x8, bfr[j]);          // [w_hi | w_lo]: the MFMA's row operand (mma16t); small terms first
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, __builtin_bit_cast(bf16x8, al[i]), acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, __builtin_bit_cast(bf16x8, ah[i]), acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < WN; ++j) x3_mma(acc[i][j], bfr[j], ah[i], al[i]);
         }
         if (k + 1 < nk) {
             if (k + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CPW) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -144,7 +129,6 @@ __global__ __launch_bounds__(512, 2) void conv_gemmx3_kernel(const ConvArgs a) {
     int img0, oy0, ox0, tile_in_img = 0;
     conv_decode_image<TH, TW>(a, mt, img0, tile_in_img, oy0, ox0);
 
-    constexpr unsigned OOB = 0xFFFF0000u;
     unsigned a_v0[A_CPW], a_v1[A_CPW], b_v[B_CPW];
 #pragma unroll
     for (int j = 0; j < A_CPW; ++j) {
@@ -153,23 +137,19 @@ __global__ __launch_bounds__(512, 2) void conv_gemmx3_kernel(const ConvArgs a) {
         const int iy = oy0 + row / TW, ix = ox0 + row % TW;
         const bool ok = img0 < a.B && iy < a.Hin && ix < a.Win;
         const unsigned gp = (unsigned)((conv_x_img(a, img0) * a.Hin + iy) * a.Win + ix);
-        a_v0[j] = ok ? gp * (unsigned)(a.xs0 * 4) + (unsigned)(u * 16) : OOB;
-        a_v1[j] = ok ? gp * (unsigned)(a.xs1 * 4) + (unsigned)(u * 16) : OOB;
+        a_v0[j] = ok ? gp * (unsigned)(a.xs0 * 4) + (unsigned)(u * 16) : DMA_OOB;
+        a_v1[j] = ok ? gp * (unsigned)(a.xs1 * 4) + (unsigned)(u * 16) : DMA_OOB;
     }
 #pragma unroll
     for (int j = 0; j < B_CPW; ++j) {
         const int row = (wave * B_CPW + j) * 8 + (lane >> 3);
         const int u = (lane & 7) ^ ((row >> 1) & 7);
         const int n = n0 + row;
-        b_v[j] = n < a.w_rows ? (unsigned)(n * a.w_row_stride * 4 + u * 16) : OOB;
+        b_v[j] = n < a.w_rows ? (unsigned)(n * a.w_row_stride * 4 + u * 16) : DMA_OOB;
     }
 
-    auto make_q = [](const void* p, unsigned bytes) __attribute__((always_inline)) {
-        const unsigned long long v = (unsigned long long)p;
-        return gx3_i32x4{(int)(unsigned)v, (int)((unsigned)(v >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-    };
-    const gx3_i32x4 q_x0 = make_q(a.x0, a.x0_bytes), q_x1 = make_q(a.x1 ? a.x1 : a.x0, a.x1_bytes);
-    const gx3_i32x4 q_w = make_q((const float*)a.w + conv_w_img_offset(a, img0), a.w_bytes);
+    const i32x4 q_x0 = make_q(a.x0, a.x0_bytes), q_x1 = make_q(a.x1 ? a.x1 : a.x0, a.x1_bytes);
+    const i32x4 q_w = make_q((const float*)a.w + conv_w_img_offset(a, img0), a.w_bytes);
     f32x4 acc[WM][WN];
 #pragma unroll
     for (int i = 0; i < WM; ++i)

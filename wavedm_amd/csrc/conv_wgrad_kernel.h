@@ -21,6 +21,7 @@
 // The DMA is lane-linear (lane L writes bytes [16 L, 16 L + 16) of its 1 KB piece), so the rotation is applied to the SOURCE address of each lane.
 #pragma once
 #include "conv_kernel.h"
+#include "lds_dma.h"
 
 namespace wdm {
 
@@ -126,22 +127,10 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const WgradArgs a) {
     const int xs = from0 ? a.xs0 : a.xs1;
     const int cx = from0 ? a.C0 : a.C1;                         // channels of that tensor
 
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    auto make_q = [](const void* p, unsigned bytes) __attribute__((always_inline)) {
-        const unsigned long long v = (unsigned long long)p;
-        return i32x4{(int)(unsigned)v, (int)((unsigned)(v >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-    };
     const i32x4 q_dy = make_q(a.dy, a.dy_bytes);
     const i32x4 q_x = from0 ? make_q(a.x0, a.x0_bytes) : make_q(a.x1, a.x1_bytes);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-    auto dma16 = [&](const i32x4& rsrc, unsigned lds_addr, unsigned voff) __attribute__((always_inline)) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff), "s"(lds_addr), "s"(rsrc)
-                     : "memory");
-    };
-    constexpr unsigned OOB = 0xFFFFFFF0u;
+    constexpr unsigned OOB = 0xFFFFFFF0u;        // this kernel's own marker, not DMA_OOB: nothing is added to it (dma16_soff0)
     constexpr int NONE = -2147483647 - 1;
 
     // ---- DMA sources of this wave's pieces, relative to the chunk's first pixel (chunk-invariant part)
@@ -189,10 +178,10 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const WgradArgs a) {
             const int q = wave * NP + j;
             const int im = hyx[j] >> 16, hy = (hyx[j] >> 8) & 255, hx = hyx[j] & 255;
             if (q < 32) {
-                dma16(q_dy, base + q * 1024, rel[j] != NONE && img + im < a.B ? o_dy + (unsigned)rel[j] : OOB);
+                dma16_soff0(q_dy, base + q * 1024, rel[j] != NONE && img + im < a.B ? o_dy + (unsigned)rel[j] : OOB);
             } else if (q < C::PIECES) {
                 const bool ok = rel[j] != NONE && img + im < a.B && (unsigned)(y0 - 1 + hy) < (unsigned)a.H && (unsigned)(x0 - 1 + hx) < (unsigned)a.W;
-                dma16(q_x, base + C::DY_BYTES + (q - 32) * 1024, ok ? o_x + (unsigned)rel[j] : OOB);
+                dma16_soff0(q_x, base + C::DY_BYTES + (q - 32) * 1024, ok ? o_x + (unsigned)rel[j] : OOB);
             }
         }
     };
