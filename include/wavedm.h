@@ -95,7 +95,10 @@ int wdm_pack_channels(wdm_handle* h, const float* src, int nch, int H, int W, co
  *   coefficients (host floats, computed by the caller in fp32 like utils/sampling.py:10-13):
  *     sqrt_1m_at = sqrt(1-abar_t), sqrt_at = sqrt(abar_t), sqrt_at_next, c2 = sqrt(1-abar_next)
  *   x0 = (x_t - eps*sqrt_1m_at)/sqrt_at ;  x_next = sqrt_at_next*x0 + c2*eps
- * Pixels covered by no patch get eps = 0/0 = NaN exactly like the reference's division. */
+ * Pixels covered by no patch get eps = 0/0 = NaN exactly like the reference's division.
+ * This and the three 3-channel names below are the `_c` entry points further down at channels = 3: the same kernels, the same bits.  With a patch list
+ * they therefore refuse nimg > 65535 (the image is a launch-grid dimension there) with WDM_EINVAL; patches == NULL, the element-wise identity form,
+ * has no such limit. */
 int wdm_ddim_update(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, const float* x_t,
                     int nimg, int H, int W, float sqrt_1m_at, float sqrt_at, float sqrt_at_next, float c2,
                     float* x0_out, float* x_next_out, void* stream);
@@ -119,8 +122,9 @@ int wdm_ddim_from_sums(wdm_handle* h, const float* acc_cnt, const float* x_t, in
 
 /* The four entry points above for ANY number of prediction channels (`channels` = model.pred_channels: 12 = the whole coarse level, 48 = every band
  * diffused): eps (n, channels, p, p), x_t / x0_out / x_next_out / noise (NIMG, channels, H, W), acc_cnt 2 * NIMG*channels*H*W floats (sums | counts).
- * A pixel's covering patches are searched within its image's span of the patch list only, once for up to four channels; each channel's sum still runs in
- * patch-list order in fp32, so channels = 3 returns the bits of the entry points above.  patches == NULL is the element-wise identity form. */
+ * A pixel's covering patches are searched within its image's span of the patch list only, once for up to four channels; each channel's sum runs in
+ * patch-list order in fp32 like the reference's sequential "+=".  With a patch list, nimg and channels are launch-grid dimensions: more than 65535 of either,
+ * or H * W beyond 2^31 - 257, is WDM_EINVAL.  patches == NULL is the element-wise identity form (n == nimg, p == H == W) and has no such limit. */
 int wdm_ddim_update_c(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t,
                       int nimg, int H, int W, float sqrt_1m_at, float sqrt_at, float sqrt_at_next, float c2,
                       float* x0_out, float* x_next_out, void* stream);

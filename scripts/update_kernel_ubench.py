@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time the scatter-mean + DDIM update entry points alone at restore()'s default group (7 images of 120x180 in the wavelet domain, 45 patches of 64x64 each):
-`wdm_ddim_update` (3 channels) against `wdm_ddim_update_c` at 3, 12 and 48 channels.  HIP events around 50 back-to-back launches after 5 warm-up launches, three
+`wdm_ddim_update` (3 channels) and `wdm_ddim_update_c` at 3, 12 and 48 channels.  Both names reach one kernel, `scatter_update_c_kernel` -- the first line is the
+forward's cost at C = 3 and should equal the second; against a library from before the 3-channel kernel was retired (WAVEDM_LIB) it times that kernel.  HIP events around 50 back-to-back launches after 5 warm-up launches, three
 repetitions, sorted.  The inputs are larger than the L2 at 48 channels (248 MB of eps) but not at 3 (15.5 MB): the 3-channel figures are cache-warm, as they are not
 inside the sampler, where a UNet call runs between two updates.
 

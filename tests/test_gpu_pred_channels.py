@@ -1,6 +1,7 @@
 """GPU: any `model.pred_channels` -- the channel-count scatter-mean / DDIM-update entry points, the sampler on every path it has, and
 DiffusiveRestoration.restore for (pred_channels, use_other_channels, other_channels_begin) = (48, False, 0), (48, True, 48), (12, True, 12), (12, False, 0),
-against float64 restatements written here, the CPU oracle and the reference's own results (tests/golden/pred_channels.npz)."""
+against float64 restatements written here, the CPU oracle, the reference's own results (tests/golden/pred_channels.npz) and, at 3 channels, the recorded bits of
+the retired 3-channel kernel (tests/golden/scatter_update_c3.npz)."""
 import os
 import subprocess
 import sys
@@ -113,28 +114,70 @@ GEOMS = [(1, 30, 45, 16, 4), (7, 120, 180, 64, 16)]                # test_gpu_ke
 
 
 @pytest.mark.parametrize("geom", GEOMS)
-def test_three_channels_give_the_bits_of_the_original_entry_points(geom):
+def test_three_channels_give_the_bits_of_the_original_entry_points(golden, geom):
+    """The 3-channel names forward to the channel-count kernels at C = 3: both spellings agree (the forwards pass their arguments in the right order) and both give
+    the bits that `ddim_update_kernel`, the 3-channel kernel these names ran before it was retired, gave on the same inputs
+    (tests/golden/scatter_update_c3.npz, recorded on an MI355X by tests/golden/make_golden_scatter_update.py; the 7-image geometry as every 97th element)."""
     from oracle import wavedm_oracle as O
+    g = golden("scatter_update_c3.npz")
     nimg, H, W, p, r = geom
+    gi = GEOMS.index(geom)
+    keep = (lambda t: t.cpu()) if gi == 0 else (lambda t: sub(t, 97))
     tri = _grid(O, nimg, H, W, p, r)
     n = len(tri)
     assert n == nimg * (45 if p == 64 else len(O.grid_corners(30, 45, 16, 4)))
     eps, xt, noise = seeded((n, 3, p, p), 1).cuda(), seeded((nimg, 3, H, W), 2).cuda(), seeded((nimg, 3, H, W), 3).cuda()
     perm = torch.randperm(n, generator=torch.Generator().manual_seed(4)).tolist()
-    for name, order in (("image-major", list(range(n))), ("shuffled", perm)):
+    for name, key, order in (("image-major", "major", list(range(n))), ("shuffled", "shuffled", perm)):
         pt = torch.tensor([tri[i] for i in order], dtype=torch.int32).cuda()
         e = eps[order].contiguous()
         for nz in (None, noise):
             a, b = _call_old(e, pt, n, p, xt, nimg, H, W, nz), _call_new(3, e, pt, n, p, xt, nimg, H, W, nz)
             assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (name, nz is not None)
+            want_x0, want_xn = torch.from_numpy(g[f"g{gi}_{key}_x0"]), torch.from_numpy(g[f"g{gi}_{key}_xn" if nz is None else f"g{gi}_{key}_xn_eta"])
+            assert want_x0.shape == keep(b[0]).shape and want_x0.dtype == torch.float32
+            assert torch.equal(keep(b[0]), want_x0) and torch.equal(keep(b[1]), want_xn), (name, nz is not None)
     # the identity list
     e, x = seeded((5, 3, 16, 16), 5).cuda(), seeded((5, 3, 16, 16), 6).cuda()
     a, b = _call_old(e, None, 5, 16, x, 5, 16, 16), _call_new(3, e, None, 5, 16, x, 5, 16, 16)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    assert torch.equal(b[0].cpu(), torch.from_numpy(g["id_x0"])) and torch.equal(b[1].cpu(), torch.from_numpy(g["id_xn"]))
     # an uncovered pixel is 0 / 0 = NaN, like the reference's division
     pt2 = torch.tensor([(0, 0, 0)], dtype=torch.int32).cuda()
     x0, _ = _call_new(3, eps, pt2, 1, p, xt, nimg, H, W)
     assert torch.isnan(x0[0, 0, H - 1, W - 1]) and not torch.isnan(x0[0, 0, 0, 0])
+
+
+@pytest.mark.parametrize("C", [3, 5])
+def test_partial_sums_are_the_cpu_sums_bit_for_bit(C):
+    """`wdm_patch_accumulate_c` only adds fp32 numbers in patch-list order -- nothing to contract, no division --, so a CPU loop that adds in the same order gives
+    the same bits: sums and counts, image-major and shuffled list.  C = 5 has a padded last chunk (c0 + j >= C) whatever the channels per thread."""
+    from oracle import wavedm_oracle as O
+    from wavedm_amd import _lib
+    L, h = _lib.lib(), _lib.handle(0)
+    nimg, H, W, p, r = GEOMS[0]
+    tri = _grid(O, nimg, H, W, p, r)
+    n = len(tri)
+    eps = seeded((n, C, p, p), 70 + C)
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(4)).tolist()
+    for name, order in (("image-major", list(range(n))), ("shuffled", perm)):
+        e = eps[order].contiguous()
+        acc, cnt = torch.zeros(nimg, C, H, W, dtype=torch.float32), torch.zeros(nimg, C, H, W, dtype=torch.float32)
+        for j, i in enumerate(order):
+            im, hi, wi = tri[i]
+            acc[im, :, hi:hi + p, wi:wi + p] += e[j]
+            cnt[im, :, hi:hi + p, wi:wi + p] += 1
+        pt = torch.tensor([tri[i] for i in order], dtype=torch.int32).cuda()
+        got = torch.full((2 * acc.numel(),), 7.0, device="cuda")
+        _lib.check(L.wdm_patch_accumulate_c(h, _lib.ptr(e.cuda()), _lib.ptr(pt), n, p, C, nimg, H, W, _lib.ptr(got), _lib.stream_ptr()))
+        torch.cuda.synchronize()
+        got = got.cpu()
+        assert torch.equal(got[:acc.numel()], acc.flatten()) and torch.equal(got[acc.numel():], cnt.flatten()), name
+        if C == 3:                                                                          # the 3-channel name: the same launch
+            got3 = torch.full_like(got, 7.0).cuda()
+            _lib.check(L.wdm_patch_accumulate(h, _lib.ptr(e.cuda()), _lib.ptr(pt), n, p, nimg, H, W, _lib.ptr(got3), _lib.stream_ptr()))
+            torch.cuda.synchronize()
+            assert torch.equal(got3.cpu(), got), name
 
 
 @pytest.mark.parametrize("C", [1, 12, 48])

@@ -72,15 +72,16 @@ int wdm_pack_channels(wdm_handle* h, const float* src, int nch, int H, int W, co
     if (!h || !src || !x96) WDM_FAIL(WDM_EINVAL, "wdm_pack_channels: null argument");
     return k_pack_channels(src, nch, H, W, patches, n, p, x96, c_total, c_off, dtype, (hipStream_t)stream);
 }
+// the 3-channel names: the channel-count kernels at C = 3
 int wdm_ddim_update(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, const float* x_t, int nimg, int H, int W, float sqrt_1m_at,
                     float sqrt_at, float sqrt_at_next, float c2, float* x0_out, float* x_next_out, void* stream) {
     if (!h || !eps || !x_t || !x0_out || !x_next_out) WDM_FAIL(WDM_EINVAL, "wdm_ddim_update: null argument");
-    return k_ddim_update(eps, patches, n, p, x_t, nimg, H, W, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out, (hipStream_t)stream);
+    return k_ddim_update_c(eps, patches, n, p, 3, x_t, nimg, H, W, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out, (hipStream_t)stream, nullptr, 0.f, "ddim_update");
 }
 int wdm_ddim_update_eta(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, const float* x_t, int nimg, int H, int W, float sqrt_1m_at,
                         float sqrt_at, float sqrt_at_next, float c1, float c2, const float* noise, float* x0_out, float* x_next_out, void* stream) {
     if (!h || !eps || !x_t || !x0_out || !x_next_out || !noise) WDM_FAIL(WDM_EINVAL, "wdm_ddim_update_eta: null argument");
-    return k_ddim_update(eps, patches, n, p, x_t, nimg, H, W, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out, (hipStream_t)stream, noise, c1);
+    return k_ddim_update_c(eps, patches, n, p, 3, x_t, nimg, H, W, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out, (hipStream_t)stream, noise, c1, "ddim_update");
 }
 int wdm_patch_accumulate(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int nimg, int H, int W, float* acc_cnt, void* stream) {
     if (!h || !acc_cnt || (n > 0 && (!eps || !patches))) WDM_FAIL(WDM_EINVAL, "wdm_patch_accumulate: null argument");
@@ -88,12 +89,12 @@ int wdm_patch_accumulate(wdm_handle* h, const float* eps, const int32_t* patches
         WDM_HIP(hipMemsetAsync(acc_cnt, 0, (size_t)nimg * 3 * H * W * 2 * sizeof(float), (hipStream_t)stream));
         return WDM_OK;
     }
-    return k_patch_accumulate(eps, patches, n, p, nimg, H, W, acc_cnt, (hipStream_t)stream);
+    return k_patch_accumulate_c(eps, patches, n, p, 3, nimg, H, W, acc_cnt, (hipStream_t)stream, "patch_accumulate");
 }
 int wdm_ddim_from_sums(wdm_handle* h, const float* acc_cnt, const float* x_t, int nimg, int H, int W, float sqrt_1m_at, float sqrt_at, float sqrt_at_next,
                        float c2, float* x0_out, float* x_next_out, void* stream) {
     if (!h || !acc_cnt || !x_t || !x0_out || !x_next_out) WDM_FAIL(WDM_EINVAL, "wdm_ddim_from_sums: null argument");
-    return k_ddim_from_sums(acc_cnt, x_t, nimg, H, W, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out, (hipStream_t)stream);
+    return k_ddim_from_sums(acc_cnt, x_t, nimg, H, W, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out, (hipStream_t)stream, 3);
 }
 int wdm_ddim_update_c(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t, int nimg, int H, int W,
                       float sqrt_1m_at, float sqrt_at, float sqrt_at_next, float c2, float* x0_out, float* x_next_out, void* stream) {

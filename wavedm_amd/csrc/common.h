@@ -137,15 +137,13 @@ int k_dwt_fwd(const float* x, float* y, int B, int H, int W, hipStream_t s, floa
 int k_dwt_inv(const float* y, float* x, int B, int h, int w, hipStream_t s, const float* y_lo = nullptr, int lo_total = 0, int n_lo = 0, int post = 0);
 int k_pack_channels(const float* src, int nch, int H, int W, const int32_t* patches, int n, int p, void* x96,
                     int c_total, int c_off, int dtype, hipStream_t s);
-int k_ddim_update(const float* eps, const int32_t* patches, int n, int p, const float* x_t, int nimg, int H, int W,
-                  float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s, const float* noise = nullptr, float c1 = 0.f);
-int k_patch_accumulate(const float* eps, const int32_t* patches, int n, int p, int nimg, int H, int W, float* acc_cnt, hipStream_t s);
+// scatter-mean + DDIM update for any number of prediction channels C (model.pred_channels); who: the entry point's name in error messages
+int k_ddim_update_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san,
+                    float c2, float* x0, float* xn, hipStream_t s, const float* noise = nullptr, float c1 = 0.f, const char* who = "ddim_update_c");
+int k_patch_accumulate_c(const float* eps, const int32_t* patches, int n, int p, int C, int nimg, int H, int W, float* acc_cnt, hipStream_t s,
+                         const char* who = "patch_accumulate_c");
 int k_ddim_from_sums(const float* acc_cnt, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san, float c2, float* x0,
-                     float* xn, hipStream_t s, int C = 3);
-// the same three for any number of prediction channels C (model.pred_channels)
-int k_ddim_update_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, int nimg, int H, int W,
-                    float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s, const float* noise = nullptr, float c1 = 0.f);
-int k_patch_accumulate_c(const float* eps, const int32_t* patches, int n, int p, int C, int nimg, int H, int W, float* acc_cnt, hipStream_t s);
+                     float* xn, hipStream_t s, int C);
 // images of different sizes in one call (the ragged layout, include/wavedm.h): the gather and the eta = 0 scatter-mean + DDIM update
 int k_pack_channels_ragged(const float* src, int nch, const int32_t* img_tab, const int64_t* pix_off, int nimg, const int32_t* patches, int n, int p, void* x96,
                            int c_total, int c_off, int dtype, hipStream_t s);

@@ -1,6 +1,8 @@
 // HBM-bound kernels of the sampling path: Haar wavelet-packet DWT/IDWT, patch gather into the UNet input,
 // scatter-mean + DDIM update, layout conversion, GroupNorm statistics, attention softmax, the timestep-embedding
 // MLP, and weight packing.  All deterministic (no atomics): every reduction has a fixed order.
+#include <type_traits>
+
 #include "common.h"
 #include "gn_group.h"
 
@@ -128,27 +130,30 @@ __global__ __launch_bounds__(256) void pack_channels_kernel(const float* __restr
 // The same gather with coalesced accesses on BOTH sides (the kernel above reads NCHW with the channel as the fastest thread index: lanes H W floats apart).
 // One workgroup per (patch, patch row): the row's nch x p values are read channel by channel -- consecutive lanes = consecutive pixels of one channel
 // plane --, turned in LDS (row stride p + 1 floats: odd, conflict-free both ways) and written pixel by pixel, channels fastest, as the NHWC row wants them.
+// row0: the row's first pixel in channel 0 of its (nch, H, W) image; out: the same pixel in the NHWC patch, at the first destination channel.
 constexpr int PACK_MAX_P = 128, PACK_MAX_CH = 48;
 template <typename T>
-__global__ __launch_bounds__(256) void pack_channels_rows_kernel(const float* __restrict__ src, int nch, int H, int W, const int32_t* __restrict__ patches,
-                                                                 int p, T* __restrict__ x96, int c_total, int c_off) {
-    h16_mode_init<T>();
+__device__ __forceinline__ void gather_row(const float* row0, int nch, int H, int W, int p, T* out, int c_total) {
     __shared__ float tile[PACK_MAX_CH * (PACK_MAX_P + 1)];
-    const int k = (int)(blockIdx.x / (unsigned)p), yy = (int)(blockIdx.x - (unsigned)k * (unsigned)p);
-    int img = k, hi = 0, wi = 0;
-    if (patches != nullptr) { img = patches[3 * k]; hi = patches[3 * k + 1]; wi = patches[3 * k + 2]; }
     const int ld = p + 1, tot = nch * p;
-    const float* row0 = src + ((long long)img * nch * H + hi + yy) * W + wi;
     for (int id = threadIdx.x; id < tot; id += 256) {
         const int c = id / p, xx = id - c * p;
         tile[c * ld + xx] = row0[(long long)c * H * W + xx];
     }
     __syncthreads();
-    T* out = x96 + ((long long)k * p + yy) * p * c_total + c_off;
     for (int id = threadIdx.x; id < tot; id += 256) {
         const int xx = id / nch, c = id - xx * nch;
         TI<T>::st(out, (long long)xx * c_total + c, tile[c * ld + xx]);
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void pack_channels_rows_kernel(const float* __restrict__ src, int nch, int H, int W, const int32_t* __restrict__ patches,
+                                                                 int p, T* __restrict__ x96, int c_total, int c_off) {
+    h16_mode_init<T>();
+    const int k = (int)(blockIdx.x / (unsigned)p), yy = (int)(blockIdx.x - (unsigned)k * (unsigned)p);
+    int img = k, hi = 0, wi = 0;
+    if (patches != nullptr) { img = patches[3 * k]; hi = patches[3 * k + 1]; wi = patches[3 * k + 2]; }
+    gather_row<T>(src + ((long long)img * nch * H + hi + yy) * W + wi, nch, H, W, p, x96 + ((long long)k * p + yy) * p * c_total + c_off, c_total);
 }
 
 int k_pack_channels(const float* src, int nch, int H, int W, const int32_t* patches, int n, int p, void* x96, int c_total, int c_off, int dtype,
@@ -170,107 +175,46 @@ int k_pack_channels(const float* src, int nch, int H, int W, const int32_t* patc
 }
 
 // =================================================================================================
-// scatter-mean + DDIM update (ddm_wavelet.py:485-502).  Gather form: every full-image element sums the patches that
-// cover it in patch-list order -- the same order as the reference's sequential "+=", so the fp32 sum is identical.
+// scatter-mean + DDIM update (ddm_wavelet.py:485-502), any number of prediction channels C (model.pred_channels: 3, 12, 48, ...).  Gather form: every full-image
+// element sums the patches that cover it in patch-list order -- the same order as the reference's sequential "+=", so the fp32 sum is identical.
 // =================================================================================================
-__global__ __launch_bounds__(256) void ddim_update_kernel(const float* __restrict__ eps, const int32_t* __restrict__ patches, int n, int p,
-                                                          const float* __restrict__ x_t, int nimg, int H, int W, float s1m, float sa, float san, float c2,
-                                                          float* __restrict__ x0o, float* __restrict__ xno, const float* __restrict__ noise, float c1) {
-    const long long total = (long long)nimg * 3 * H * W;
-    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
-        const int xx = (int)(id % W);
-        const int yy = (int)((id / W) % H);
-        const int c = (int)((id / ((long long)W * H)) % 3);
-        const int img = (int)(id / ((long long)W * H * 3));
-        float acc = 0.f, cnt = 0.f;
-        if (patches == nullptr) {
-            acc = eps[id];
-            cnt = 1.f;
-        } else {
-            for (int k = 0; k < n; ++k) {
-                const int pi = patches[3 * k], hi = patches[3 * k + 1], wi = patches[3 * k + 2];
-                if (pi == img && (unsigned)(yy - hi) < (unsigned)p && (unsigned)(xx - wi) < (unsigned)p) {
-                    acc += eps[(((long long)k * 3 + c) * p + (yy - hi)) * p + (xx - wi)];
-                    cnt += 1.f;
-                }
-            }
+// The DDIM update of element `id` from its mean eps `et` -- the one place the expression is written.  eta != 0 (ddm_wavelet.py:500-502):
+// at_next.sqrt() * x0_t + c1 * randn_like(x) + c2 * et, summed left to right like the reference's expression.  No __restrict__ here or in the two device
+// functions below: the kernels' parameters carry it, and repeating it changes the instruction order of the kernels they are inlined into.
+__device__ __forceinline__ void ddim_store(long long id, float et, const float* x_t, float s1m, float sa, float san, float c2,
+                                           const float* noise, float c1, float* x0o, float* xno) {
+    const float xt = x_t[id];
+    const float x0 = (xt - et * s1m) / sa;
+    x0o[id] = x0;
+    xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;
+}
+
+// Pixel (yy, xx) of image img walks the entries [lo, hi) of the patch list ONCE for its CH channels c0 .. c0 + CH - 1: one coverage test per (pixel, patch), CH
+// accumulators in registers, each summed in patch-list order in fp32.  Entries of other images inside the span are skipped, so any span that holds the image's
+// entries gives the same sums.  Adds to acc[] and to cnt, the number of covering patches; the caller zeroes them (zeroed in here, the compiler splits the empty
+// span off into a path of its own: the same bits from another instruction stream, profiles/scatter_update_unify.md).
+template <int CH>
+__device__ __forceinline__ void span_walk(const float* eps, const int32_t* patches, int lo, int hi, int img, int yy, int xx, int p,
+                                          int C, int c0, float (&acc)[CH], float& cnt) {
+    const long long pp = (long long)p * p;
+    for (int k = lo; k < hi; ++k) {
+        const int pi = patches[3 * k], hi_ = patches[3 * k + 1], wi = patches[3 * k + 2];
+        if (pi == img && (unsigned)(yy - hi_) < (unsigned)p && (unsigned)(xx - wi) < (unsigned)p) {
+            const float* e = eps + ((long long)k * C + c0) * pp + (long long)(yy - hi_) * p + (xx - wi);
+#pragma unroll
+            for (int j = 0; j < CH; ++j)
+                if (c0 + j < C) acc[j] += e[j * pp];
+            cnt += 1.f;
         }
-        const float et = acc / cnt;
-        const float xt = x_t[id];
-        const float x0 = (xt - et * s1m) / sa;
-        x0o[id] = x0;
-        // eta != 0 (ddm_wavelet.py:500-502): at_next.sqrt() * x0_t + c1 * randn_like(x) + c2 * et, summed left to right like the reference's expression
-        xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;
     }
 }
 
-int k_ddim_update(const float* eps, const int32_t* patches, int n, int p, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san,
-                  float c2, float* x0, float* xn, hipStream_t s, const float* noise, float c1) {
-    if (n <= 0 || nimg <= 0) WDM_FAIL(WDM_EINVAL, "ddim_update: bad arguments");
-    if (patches == nullptr && (p != H || p != W || n != nimg)) WDM_FAIL(WDM_EINVAL, "ddim_update: identity patch list needs n == nimg, p == H == W");
-    const long long total = (long long)nimg * 3 * H * W;
-    const int g = nblocks(total, 256) > 16384 ? 16384 : nblocks(total, 256);
-    hipLaunchKernelGGL(ddim_update_kernel, dim3(g), dim3(256), 0, s, eps, patches, n, p, x_t, nimg, H, W, s1m, sa, san, c2, x0, xn, noise, c1);
-    WDM_HIP(hipGetLastError());
-    return WDM_OK;
-}
-
-// ---- patch-sharded single image: each rank owns a subset of the patches.  patch_accumulate writes the rank's
-// partial sums [0 .. nimg*3*H*W) and partial counts [nimg*3*H*W ..) into ONE buffer (one all-reduce per step); ddim_from_sums
-// divides the reduced sums by the reduced counts and applies the same DDIM update as ddim_update_kernel.
-__global__ __launch_bounds__(256) void patch_accumulate_kernel(const float* __restrict__ eps, const int32_t* __restrict__ patches, int n, int p, int nimg, int H,
-                                                               int W, float* __restrict__ acc_cnt) {
-    const long long total = (long long)nimg * 3 * H * W;
-    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
-        const int xx = (int)(id % W);
-        const int yy = (int)((id / W) % H);
-        const int c = (int)((id / ((long long)W * H)) % 3);
-        const int img = (int)(id / ((long long)W * H * 3));
-        float acc = 0.f, cnt = 0.f;
-        for (int k = 0; k < n; ++k) {
-            const int pi = patches[3 * k], hi = patches[3 * k + 1], wi = patches[3 * k + 2];
-            if (pi == img && (unsigned)(yy - hi) < (unsigned)p && (unsigned)(xx - wi) < (unsigned)p) {
-                acc += eps[(((long long)k * 3 + c) * p + (yy - hi)) * p + (xx - wi)];
-                cnt += 1.f;
-            }
-        }
-        acc_cnt[id] = acc;
-        acc_cnt[total + id] = cnt;
-    }
-}
-__global__ __launch_bounds__(256) void ddim_from_sums_kernel(const float* __restrict__ acc_cnt, const float* __restrict__ x_t, long long total, float s1m, float sa,
-                                                             float san, float c2, float* __restrict__ x0o, float* __restrict__ xno) {
-    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
-        const float et = acc_cnt[id] / acc_cnt[total + id];
-        const float x0 = (x_t[id] - et * s1m) / sa;
-        x0o[id] = x0;
-        xno[id] = san * x0 + c2 * et;
-    }
-}
-int k_patch_accumulate(const float* eps, const int32_t* patches, int n, int p, int nimg, int H, int W, float* acc_cnt, hipStream_t s) {
-    if (n < 0 || nimg <= 0 || !patches) WDM_FAIL(WDM_EINVAL, "patch_accumulate: bad arguments");
-    const long long total = (long long)nimg * 3 * H * W;
-    const int g = nblocks(total, 256) > 16384 ? 16384 : nblocks(total, 256);
-    hipLaunchKernelGGL(patch_accumulate_kernel, dim3(g), dim3(256), 0, s, eps, patches, n, p, nimg, H, W, acc_cnt);
-    WDM_HIP(hipGetLastError());
-    return WDM_OK;
-}
-int k_ddim_from_sums(const float* acc_cnt, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s, int C) {
-    const long long total = (long long)nimg * C * H * W;
-    if (total <= 0) WDM_FAIL(WDM_EINVAL, "ddim_from_sums: empty image");
-    const int g = nblocks(total, 256) > 16384 ? 16384 : nblocks(total, 256);
-    hipLaunchKernelGGL(ddim_from_sums_kernel, dim3(g), dim3(256), 0, s, acc_cnt, x_t, total, s1m, sa, san, c2, x0, xn);
-    WDM_HIP(hipGetLastError());
-    return WDM_OK;
-}
-
-// ---- any number of prediction channels (model.pred_channels: 3, 12, 48, ...).  Which patches cover a pixel does not depend on the channel, and a pixel is
-// covered only by patches of its own image.  Thread = (pixel, chunk of CH <= 4 channels), workgroup = 256 consecutive pixels of ONE image: the workgroup first finds
-// [k_lo, k_hi), the span of the patch list that holds its image's entries (a strided scan + min / max reduction; image-major lists -- what ddim_sample builds from
-// a corner list -- give exactly the image's slice, any other order a wider span that is still filtered by image below, so every list stays correct), then every
-// thread walks that span ONCE for its CH channels: one coverage test per (pixel, patch), CH accumulators in registers, each summed in patch-list order in fp32
-// exactly like ddim_update_kernel (at C = 3 the same bits).  Lanes are consecutive pixels: the eps reads of one (patch, channel) and all stores are coalesced.
-// ACCUM: the patch-sharded form, partial sums | partial counts instead of the update.  No atomics: a result element has one writer.
+// Which patches cover a pixel does not depend on the channel, and a pixel is covered only by patches of its own image.  Thread = (pixel, chunk of CH <= 4
+// channels), workgroup = 256 consecutive pixels of ONE image: the workgroup first finds [k_lo, k_hi), the span of the patch list that holds its image's entries
+// (a strided scan + min / max reduction; image-major lists -- what ddim_sample builds from a corner list -- give exactly the image's slice, any other order a wider
+// span that span_walk still filters by image, so every list stays correct), then every thread walks that span.  Lanes are consecutive pixels: the eps reads of
+// one (patch, channel) and all stores are coalesced.  ACCUM: the patch-sharded form (each rank owns a subset of the patches), the rank's partial
+// sums [0 .. total) | partial counts [total ..) in ONE buffer (one all-reduce per step) instead of the update.  No atomics: a result element has one writer.
 template <int CH, bool ACCUM>
 __global__ __launch_bounds__(256) void scatter_update_c_kernel(const float* __restrict__ eps, const int32_t* __restrict__ patches, int n, int p, int C,
                                                                const float* __restrict__ x_t, int H, int W, float s1m, float sa, float san, float c2,
@@ -294,17 +238,7 @@ __global__ __launch_bounds__(256) void scatter_update_c_kernel(const float* __re
     float acc[CH], cnt = 0.f;
 #pragma unroll
     for (int j = 0; j < CH; ++j) acc[j] = 0.f;
-    const long long pp = (long long)p * p;
-    for (int k = lo; k < hi; ++k) {
-        const int pi = patches[3 * k], hi_ = patches[3 * k + 1], wi = patches[3 * k + 2];
-        if (pi == img && (unsigned)(yy - hi_) < (unsigned)p && (unsigned)(xx - wi) < (unsigned)p) {
-            const float* e = eps + ((long long)k * C + c0) * pp + (long long)(yy - hi_) * p + (xx - wi);
-#pragma unroll
-            for (int j = 0; j < CH; ++j)
-                if (c0 + j < C) acc[j] += e[j * pp];
-            cnt += 1.f;
-        }
-    }
+    span_walk<CH>(eps, patches, lo, hi, img, yy, xx, p, C, c0, acc, cnt);
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
         if (c0 + j >= C) continue;
@@ -313,95 +247,97 @@ __global__ __launch_bounds__(256) void scatter_update_c_kernel(const float* __re
             acc_cnt[id] = acc[j];
             acc_cnt[total + id] = cnt;
         } else {
-            const float et = acc[j] / cnt;
-            const float xt = x_t[id];
-            const float x0 = (xt - et * s1m) / sa;
-            x0o[id] = x0;
-            xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;
+            ddim_store(id, acc[j] / cnt, x_t, s1m, sa, san, c2, noise, c1, x0o, xno);
         }
     }
 }
-// the identity patch list (every image is its own patch): the element-wise form, any channel count
+// The two element-wise forms.  The identity patch list (every image is its own patch): et = eps.  The second half of the patch-sharded pair: et = the all-reduced
+// sums / counts of ACCUM.  Two kernels, not one with a null `den`: the compiler contracts ddim_store's x_next differently once `noise` is known to be null at
+// compile time (profiles/scatter_update_unify.md), so ddim_from_sums_kernel with a run-time `noise` would not give the bits it has always given.
 __global__ __launch_bounds__(256) void ddim_update_identity_kernel(const float* __restrict__ eps, const float* __restrict__ x_t, long long total, float s1m, float sa,
                                                                    float san, float c2, float* __restrict__ x0o, float* __restrict__ xno,
                                                                    const float* __restrict__ noise, float c1) {
-    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
-        const float et = eps[id] / 1.f;
-        const float xt = x_t[id];
-        const float x0 = (xt - et * s1m) / sa;
-        x0o[id] = x0;
-        xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;
-    }
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x)
+        ddim_store(id, eps[id], x_t, s1m, sa, san, c2, noise, c1, x0o, xno);
+}
+__global__ __launch_bounds__(256) void ddim_from_sums_kernel(const float* __restrict__ acc_cnt, const float* __restrict__ x_t, long long total, float s1m, float sa,
+                                                             float san, float c2, float* __restrict__ x0o, float* __restrict__ xno) {
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x)
+        ddim_store(id, acc_cnt[id] / acc_cnt[total + id], x_t, s1m, sa, san, c2, nullptr, 0.f, x0o, xno);
+}
+static int elementwise_grid(long long total) { return nblocks(total, 256) > 16384 ? 16384 : nblocks(total, 256); }
+
+// Channels per thread: 4, 2 or 1 -- the largest that still gives the chip 4 workgroups per CU (1024 in all), pixblocks = the 256-pixel blocks of all images -- and
+// launch(integral_constant<int, CH>) with it.  Measured (scripts/update_kernel_ubench.py, EXPERIMENTS.md): with the search confined to the image's span, sharing
+// it between channels buys little on short spans and too few workgroups cost a lot (12 channels of 7 x 120 x 180 in one 16-channel chunk, 595 workgroups: 161 us;
+// in chunks of 4, 1785 workgroups: 63 us); on a long span (625 entries) one channel per thread loses again (262 vs 183 us)
+template <typename F>
+static void with_channels_per_thread(long long pixblocks, int C, F&& launch) {
+    int ch = 4;
+    while (ch > 1 && pixblocks * ((C + ch - 1) / ch) < 1024) ch >>= 1;
+    if (ch == 1) launch(std::integral_constant<int, 1>{});
+    else if (ch == 2) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 4>{});
 }
 template <bool ACCUM>
 static int launch_scatter_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san,
                             float c2, float* x0, float* xn, const float* noise, float c1, float* acc_cnt, hipStream_t s) {
     const long long total = (long long)nimg * C * H * W;
-    // channels per thread: 4, 2 or 1 -- the largest that still gives the chip 4 workgroups per CU.  Measured (scripts/update_kernel_ubench.py, EXPERIMENTS.md): with the search
-    // confined to the image's span, sharing it between channels buys little on short spans and too few workgroups cost a lot (12 channels of 7 x 120 x 180 in one
-    // 16-channel chunk, 595 workgroups: 161 us; in chunks of 4, 1785 workgroups: 63 us); on a long span (625 entries) one channel per thread loses again (262 vs 183 us)
-    const long long pixblocks = (long long)nblocks((long long)H * W, 256) * nimg;
-    int ch = 4;
-    while (ch > 1 && pixblocks * ((C + ch - 1) / ch) < 1024) ch >>= 1;
-    const dim3 grid(nblocks((long long)H * W, 256), nimg, (C + ch - 1) / ch);
-#define WDM_SCATTER_C(CH_) hipLaunchKernelGGL((scatter_update_c_kernel<CH_, ACCUM>), grid, dim3(256), 0, s, eps, patches, n, p, C, x_t, H, W, s1m, sa, san, c2, x0, xn, noise, c1, acc_cnt, total)
-    if (ch == 1) WDM_SCATTER_C(1);
-    else if (ch == 2) WDM_SCATTER_C(2);
-    else WDM_SCATTER_C(4);
-#undef WDM_SCATTER_C
+    const int pixblocks = nblocks((long long)H * W, 256);
+    with_channels_per_thread((long long)pixblocks * nimg, C, [&](auto ch) {
+        constexpr int CH = decltype(ch)::value;
+        hipLaunchKernelGGL((scatter_update_c_kernel<CH, ACCUM>), dim3(pixblocks, nimg, (C + CH - 1) / CH), dim3(256), 0, s, eps, patches, n, p, C, x_t, H, W, s1m, sa,
+                           san, c2, x0, xn, noise, c1, acc_cnt, total);
+    });
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }
-static int check_scatter_c(const char* who, int n, int p, int C, int nimg, int H, int W) {
+// list: the call launches scatter_update_c_kernel, whose grid carries the image in y and the channel chunk in z (the element-wise form has no such limit)
+static int check_scatter_c(const char* who, int n, int p, int C, int nimg, int H, int W, bool list) {
     if (n <= 0 || nimg <= 0 || C <= 0 || p <= 0 || H <= 0 || W <= 0) WDM_FAIL(WDM_EINVAL, "%s: bad arguments", who);
-    if (nimg > 65535 || C > 65535 || (long long)H * W > 2147483647LL - 256) WDM_FAIL(WDM_EINVAL, "%s: %d images x %d channels x %dx%d exceeds the launch grid", who, nimg, C, H, W);
+    if (list && (nimg > 65535 || C > 65535 || (long long)H * W > 2147483647LL - 256))
+        WDM_FAIL(WDM_EINVAL, "%s: %d images x %d channels x %dx%d exceeds the launch grid", who, nimg, C, H, W);
     return WDM_OK;
 }
 int k_ddim_update_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san,
-                    float c2, float* x0, float* xn, hipStream_t s, const float* noise, float c1) {
-    if (int e = check_scatter_c("ddim_update_c", n, p, C, nimg, H, W)) return e;
+                    float c2, float* x0, float* xn, hipStream_t s, const float* noise, float c1, const char* who) {
+    if (int e = check_scatter_c(who, n, p, C, nimg, H, W, patches != nullptr)) return e;
     if (patches == nullptr) {
-        if (p != H || p != W || n != nimg) WDM_FAIL(WDM_EINVAL, "ddim_update_c: identity patch list needs n == nimg, p == H == W");
+        if (p != H || p != W || n != nimg) WDM_FAIL(WDM_EINVAL, "%s: identity patch list needs n == nimg, p == H == W", who);
         const long long total = (long long)nimg * C * H * W;
-        const int g = nblocks(total, 256) > 16384 ? 16384 : nblocks(total, 256);
-        hipLaunchKernelGGL(ddim_update_identity_kernel, dim3(g), dim3(256), 0, s, eps, x_t, total, s1m, sa, san, c2, x0, xn, noise, c1);
+        hipLaunchKernelGGL(ddim_update_identity_kernel, dim3(elementwise_grid(total)), dim3(256), 0, s, eps, x_t, total, s1m, sa, san, c2, x0, xn, noise, c1);
         WDM_HIP(hipGetLastError());
         return WDM_OK;
     }
     return launch_scatter_c<false>(eps, patches, n, p, C, x_t, nimg, H, W, s1m, sa, san, c2, x0, xn, noise, c1, nullptr, s);
 }
-int k_patch_accumulate_c(const float* eps, const int32_t* patches, int n, int p, int C, int nimg, int H, int W, float* acc_cnt, hipStream_t s) {
-    if (!patches) WDM_FAIL(WDM_EINVAL, "patch_accumulate_c: bad arguments");
-    if (int e = check_scatter_c("patch_accumulate_c", n, p, C, nimg, H, W)) return e;
+int k_patch_accumulate_c(const float* eps, const int32_t* patches, int n, int p, int C, int nimg, int H, int W, float* acc_cnt, hipStream_t s, const char* who) {
+    if (!patches) WDM_FAIL(WDM_EINVAL, "%s: bad arguments", who);
+    if (int e = check_scatter_c(who, n, p, C, nimg, H, W, true)) return e;
     return launch_scatter_c<true>(eps, patches, n, p, C, nullptr, nimg, H, W, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, 0.f, acc_cnt, s);
+}
+int k_ddim_from_sums(const float* acc_cnt, const float* x_t, int nimg, int H, int W, float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s, int C) {
+    const long long total = (long long)nimg * C * H * W;
+    if (total <= 0) WDM_FAIL(WDM_EINVAL, "ddim_from_sums: empty image");
+    hipLaunchKernelGGL(ddim_from_sums_kernel, dim3(elementwise_grid(total)), dim3(256), 0, s, acc_cnt, x_t, total, s1m, sa, san, c2, x0, xn);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
 }
 
 // ---- images of DIFFERENT sizes in one call: the ragged layout (include/wavedm.h).  A ragged C-channel tensor is one flat f32 buffer, image i
 // the plain (C, H_i, W_i) block at element C * pix_off[i]; img_tab holds (H, W, patch_lo, patch_hi) per image -- [patch_lo, patch_hi) is the image's slice of the
 // image-major patch list --, blk_tab the first 256-pixel block of each image (blk_tab[nimg] = all blocks), pix_off the 64-bit prefix sum of H_i W_i.  The two
-// kernels that cross image boundaries are the plain ones with H, W and the base pointer looked up instead of passed: the same reads, the same sums in the same
-// order, the same expression -- per image the bits of the plain kernels on that image alone.
+// kernels that cross image boundaries are the plain ones with H, W and the base pointer looked up instead of passed, around the same device functions
+// (gather_row; span_walk and ddim_store) -- per image the bits of the plain kernels on that image alone.
 template <typename T>
 __global__ __launch_bounds__(256) void pack_channels_rows_ragged_kernel(const float* __restrict__ src, int nch, const int32_t* __restrict__ img_tab,
                                                                         const int64_t* __restrict__ pix_off, const int32_t* __restrict__ patches, int p,
                                                                         T* __restrict__ x96, int c_total, int c_off) {
     h16_mode_init<T>();
-    __shared__ float tile[PACK_MAX_CH * (PACK_MAX_P + 1)];
     const int k = (int)(blockIdx.x / (unsigned)p), yy = (int)(blockIdx.x - (unsigned)k * (unsigned)p);
     const int img = patches[3 * k], hi = patches[3 * k + 1], wi = patches[3 * k + 2];
     const int H = img_tab[4 * img], W = img_tab[4 * img + 1];
-    const int ld = p + 1, tot = nch * p;
-    const float* row0 = src + (long long)nch * pix_off[img] + (long long)(hi + yy) * W + wi;
-    for (int id = threadIdx.x; id < tot; id += 256) {
-        const int c = id / p, xx = id - c * p;
-        tile[c * ld + xx] = row0[(long long)c * H * W + xx];
-    }
-    __syncthreads();
-    T* out = x96 + ((long long)k * p + yy) * p * c_total + c_off;
-    for (int id = threadIdx.x; id < tot; id += 256) {
-        const int xx = id / nch, c = id - xx * nch;
-        TI<T>::st(out, (long long)xx * c_total + c, tile[c * ld + xx]);
-    }
+    gather_row<T>(src + (long long)nch * pix_off[img] + (long long)(hi + yy) * W + wi, nch, H, W, p, x96 + ((long long)k * p + yy) * p * c_total + c_off, c_total);
 }
 
 int k_pack_channels_ragged(const float* src, int nch, const int32_t* img_tab, const int64_t* pix_off, int nimg, const int32_t* patches, int n, int p, void* x96,
@@ -417,6 +353,8 @@ int k_pack_channels_ragged(const float* src, int nch, const int32_t* img_tab, co
 
 // scatter_update_c_kernel over the ragged layout, eta = 0.  Workgroup = 256 consecutive pixels of ONE image, found by a binary search of blk_tab on the block
 // index -- uniform per workgroup, a few scalar loads --; the image's span of the patch list comes from img_tab (no scan).  One writer per element, no atomics.
+// noise / c1 are always null / 0 here and stay run-time parameters all the same: known to be null at compile time, the compiler contracts ddim_store's x_next
+// another way (mul, mul, add for mul, fma) and the last bit would no longer be the plain kernel's (profiles/scatter_update_unify.md).
 template <int CH>
 __global__ __launch_bounds__(256) void scatter_update_ragged_kernel(const float* __restrict__ eps, const int32_t* __restrict__ patches, int n, int p, int C,
                                                                     const float* __restrict__ x_t, const int32_t* __restrict__ img_tab,
@@ -439,27 +377,12 @@ __global__ __launch_bounds__(256) void scatter_update_ragged_kernel(const float*
     float acc[CH], cnt = 0.f;
 #pragma unroll
     for (int j = 0; j < CH; ++j) acc[j] = 0.f;
-    const long long pp = (long long)p * p;
-    for (int k = lo; k < hi; ++k) {
-        const int pi = patches[3 * k], hi_ = patches[3 * k + 1], wi = patches[3 * k + 2];
-        if (pi == img && (unsigned)(yy - hi_) < (unsigned)p && (unsigned)(xx - wi) < (unsigned)p) {
-            const float* e = eps + ((long long)k * C + c0) * pp + (long long)(yy - hi_) * p + (xx - wi);
-#pragma unroll
-            for (int j = 0; j < CH; ++j)
-                if (c0 + j < C) acc[j] += e[j * pp];
-            cnt += 1.f;
-        }
-    }
+    span_walk<CH>(eps, patches, lo, hi, img, yy, xx, p, C, c0, acc, cnt);
     const long long base = (long long)C * pix_off[img];
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
         if (c0 + j >= C) continue;
-        const long long id = base + (long long)(c0 + j) * HW + pix;
-        const float et = acc[j] / cnt;
-        const float xt = x_t[id];
-        const float x0 = (xt - et * s1m) / sa;
-        x0o[id] = x0;
-        xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;      // scatter_update_c_kernel's line, character for character; noise is always null here (eta = 0)
+        ddim_store(base + (long long)(c0 + j) * HW + pix, acc[j] / cnt, x_t, s1m, sa, san, c2, noise, c1, x0o, xno);
     }
 }
 
@@ -467,15 +390,11 @@ int k_ddim_update_ragged(const float* eps, const int32_t* patches, int n, int p,
                          const int64_t* pix_off, int nimg, int nblk, float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s) {
     if (nimg < 1 || n < 1 || p < 1 || C < 1 || nblk < 1) WDM_FAIL(WDM_EINVAL, "ddim_update_ragged: bad arguments");
     if (C > 65535) WDM_FAIL(WDM_EINVAL, "ddim_update_ragged: %d channels exceed the launch grid", C);
-    // channels per thread: launch_scatter_c's rule, counted over all images' pixel blocks
-    int ch = 4;
-    while (ch > 1 && (long long)nblk * ((C + ch - 1) / ch) < 1024) ch >>= 1;
-    const dim3 grid(nblk, (C + ch - 1) / ch);
-#define WDM_SCATTER_R(CH_) hipLaunchKernelGGL((scatter_update_ragged_kernel<CH_>), grid, dim3(256), 0, s, eps, patches, n, p, C, x_t, img_tab, blk_tab, pix_off, nimg, s1m, sa, san, c2, x0, xn, (const float*)nullptr, 0.f)
-    if (ch == 1) WDM_SCATTER_R(1);
-    else if (ch == 2) WDM_SCATTER_R(2);
-    else WDM_SCATTER_R(4);
-#undef WDM_SCATTER_R
+    with_channels_per_thread(nblk, C, [&](auto ch) {
+        constexpr int CH = decltype(ch)::value;
+        hipLaunchKernelGGL((scatter_update_ragged_kernel<CH>), dim3(nblk, (C + CH - 1) / CH), dim3(256), 0, s, eps, patches, n, p, C, x_t, img_tab, blk_tab, pix_off,
+                           nimg, s1m, sa, san, c2, x0, xn, (const float*)nullptr, 0.f);
+    });
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }

@@ -342,7 +342,7 @@ class DenoisingDiffusion_Wavelet(object):
     def _ddim_overlapping_global(self, x, x_cond, seq, model, b, corners, p_size, total, eta=0.):
         """The `use_global` branch of generalized_steps_overlapping (ddm_wavelet.py:479-483): every patch is [x_cond crop | x_t crop] and the
         model also sees the whole image `total`, repeated for each patch.  Crops and concatenation are tensor plumbing; the UNet and the
-        scatter-mean + DDIM update are library kernels (`wdm_ddim_update`, the one the main sampler uses)."""
+        scatter-mean + DDIM update are library kernels (`wdm_ddim_update_c`, the one the main sampler uses)."""
         if total is None:
             raise ValueError("use_global=True needs `total`, the whole image the patches attend to")
         if not self.config.data.begin_from_noise:
@@ -355,7 +355,7 @@ class DenoisingDiffusion_Wavelet(object):
         p = int(p_size)
         tri = [(im, int(hi), int(wi)) for im in range(nimg) for (hi, wi) in corners]
         patches = torch.tensor(tri, dtype=torch.int32).to(self.device)
-        upd = sampling.scatter_update_fns(_lib.lib(), _lib.handle(self.device.index or 0), pc)
+        L, h = _lib.lib(), _lib.handle(self.device.index or 0)
         abar = sampling.alpha_bar_table(b)
         seq_next = [-1] + seq[:-1]
         xs, x0_preds, xt = [x], [], x
@@ -372,13 +372,13 @@ class DenoisingDiffusion_Wavelet(object):
                 if eta != 0.:                                                       # ddm_wavelet.py:500-502
                     c1 = eta * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
                     noise = torch.randn_like(xt)
-                    upd.update_eta(_lib.ptr(eps), _lib.ptr(patches), len(tri), p, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
-                                   float(at.sqrt()), float(at_next.sqrt()), float(c1), float(((1 - at_next) - c1 ** 2).sqrt()),
-                                   _lib.ptr(noise), _lib.ptr(x0), _lib.ptr(xn), _lib.stream_ptr())
+                    _lib.check(L.wdm_ddim_update_eta_c(h, _lib.ptr(eps), _lib.ptr(patches), len(tri), p, pc, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
+                                                       float(at.sqrt()), float(at_next.sqrt()), float(c1), float(((1 - at_next) - c1 ** 2).sqrt()),
+                                                       _lib.ptr(noise), _lib.ptr(x0), _lib.ptr(xn), _lib.stream_ptr()))
                 else:
-                    upd.update(_lib.ptr(eps), _lib.ptr(patches), len(tri), p, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
-                               float(at.sqrt()), float(at_next.sqrt()), float((1 - at_next).sqrt()), _lib.ptr(x0), _lib.ptr(xn),
-                               _lib.stream_ptr())
+                    _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps), _lib.ptr(patches), len(tri), p, pc, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
+                                                   float(at.sqrt()), float(at_next.sqrt()), float((1 - at_next).sqrt()), _lib.ptr(x0), _lib.ptr(xn),
+                                                   _lib.stream_ptr()))
                 x0_preds.append(x0)
                 xs.append(xn)
                 xt = xn

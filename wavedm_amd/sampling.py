@@ -166,40 +166,6 @@ def graph_cache_clear():
     _GRAPHS = None
 
 
-class scatter_update_fns:
-    """The scatter-mean + DDIM update launches for `pc` prediction channels, with the argument lists of the 3-channel entry points.  pc == 3 (raindrop_wavelet.yml)
-    keeps the original kernels -- the shipped configuration runs what it always ran --, every other count goes to the channel-count entry points
-    (`wdm_ddim_update_c` ...: the coverage search confined to the image's span of the patch list and shared by up to four channels; the same bits at 3,
-    tests/test_gpu_pred_channels.py)."""
-
-    def __init__(self, L, h, pc):
-        self.L, self.h, self.pc = L, h, int(pc)
-
-    def update(self, eps, patches, n, p, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st):
-        if self.pc == 3:
-            _lib.check(self.L.wdm_ddim_update(self.h, eps, patches, n, p, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
-        else:
-            _lib.check(self.L.wdm_ddim_update_c(self.h, eps, patches, n, p, self.pc, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
-
-    def update_eta(self, eps, patches, n, p, xt, nimg, H, W, s1m, sa, san, c1, c2, noise, x0, xn, st):
-        if self.pc == 3:
-            _lib.check(self.L.wdm_ddim_update_eta(self.h, eps, patches, n, p, xt, nimg, H, W, s1m, sa, san, c1, c2, noise, x0, xn, st))
-        else:
-            _lib.check(self.L.wdm_ddim_update_eta_c(self.h, eps, patches, n, p, self.pc, xt, nimg, H, W, s1m, sa, san, c1, c2, noise, x0, xn, st))
-
-    def accumulate(self, eps, patches, n, p, nimg, H, W, acc_cnt, st):
-        if self.pc == 3:
-            _lib.check(self.L.wdm_patch_accumulate(self.h, eps, patches, n, p, nimg, H, W, acc_cnt, st))
-        else:
-            _lib.check(self.L.wdm_patch_accumulate_c(self.h, eps, patches, n, p, self.pc, nimg, H, W, acc_cnt, st))
-
-    def from_sums(self, acc_cnt, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st):
-        if self.pc == 3:
-            _lib.check(self.L.wdm_ddim_from_sums(self.h, acc_cnt, xt, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
-        else:
-            _lib.check(self.L.wdm_ddim_from_sums_c(self.h, acc_cnt, xt, self.pc, nimg, H, W, s1m, sa, san, c2, x0, xn, st))
-
-
 class RaggedLayout:
     """Images of DIFFERENT sizes in one sampler call (include/wavedm.h): a ragged C-channel tensor is one flat f32 buffer in which image i
     is the plain (C, h_i, w_i) block at element C * pix_off[i], pix_off the prefix sum of h_i * w_i -- one layout for x_cond, x_t / x0 / x_next and x_other.
@@ -401,7 +367,6 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
     assert ncond + pc + nother == cin, f"channel split {ncond}+{pc}+{nother} != UNet in_channels {cin}"
     if pc < 1:
         raise ValueError("ddim_sample: x has no prediction channels")
-    upd = scatter_update_fns(L, h, pc)
     with torch.cuda.device(dev):
         if corners is None:
             p = H
@@ -504,22 +469,22 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
                                 for i in range(lo, hi, max_batch):
                                     j = min(i + max_batch, hi)
                                     unet.forward_nhwc(x96[i:j], t_dev[k:k + 1], eps[i:j], temb_row=None if temb is None else temb[k], ws_slot=ci)
-                                upd.update(_lib.ptr(eps[lo:hi]), None, hi - lo, p, _lib.ptr(xt[lo:hi]), hi - lo, H, W, s1m, sa, san, c2,
-                                           _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc)
+                                _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps[lo:hi]), None, hi - lo, p, pc, _lib.ptr(xt[lo:hi]), hi - lo, H, W, s1m, sa, san, c2,
+                                                               _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc))
                     else:
                         if n:
                             _lib.check(L.wdm_pack_channels(h, _lib.ptr(xt), pc, H, W, pptr, n, p, _lib.ptr(x96), cin, ncond, unet._dtype_code, st))
                         for i in range(0, n, call_b):
                             unet.forward_nhwc(x96[i:i + call_b], t_dev[k:k + 1], eps[i:i + call_b], temb_row=None if temb is None else temb[k])
                         if sharded:
-                            upd.accumulate(_lib.ptr(eps), pptr, n, p, nimg, H, W, _lib.ptr(acc_cnt), st)      # sums | counts: 2 * NIMG * pc * H * W floats
+                            _lib.check(L.wdm_patch_accumulate_c(h, _lib.ptr(eps), pptr, n, p, pc, nimg, H, W, _lib.ptr(acc_cnt), st))      # sums | counts: 2 * NIMG * pc * H * W floats
                             dist.all_reduce(acc_cnt, op=dist.ReduceOp.SUM, group=grp)
-                            upd.from_sums(_lib.ptr(acc_cnt), _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st)
+                            _lib.check(L.wdm_ddim_from_sums_c(h, _lib.ptr(acc_cnt), _lib.ptr(xt), pc, nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st))
                         elif noise is not None:
-                            upd.update_eta(_lib.ptr(eps), pptr, n, p, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c1, c2, _lib.ptr(noise),
-                                           _lib.ptr(x0), _lib.ptr(xn), st)
+                            _lib.check(L.wdm_ddim_update_eta_c(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c1, c2, _lib.ptr(noise),
+                                                               _lib.ptr(x0), _lib.ptr(xn), st))
                         else:
-                            upd.update(_lib.ptr(eps), pptr, n, p, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st)
+                            _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st))
                     # lists as the reference returns them; with `keep` given, what nobody asked for is dropped at once (inside a captured graph its memory is reused)
                     x0_preds.append(x0 if keep_set is None or (k - S) in keep_set else None)
                     xs.append(xn)
