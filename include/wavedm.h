@@ -300,6 +300,22 @@ int wdm_hfrm_forward(wdm_hfrm* m, const float* x, int B, int H, int W, float* y,
 int wdm_hfrm_set_local(wdm_hfrm* m, int base_h, int base_w, int train_h, int train_w);
 int wdm_hfrm_local_kernel(const wdm_hfrm* m, int level, int* kh, int* kw);
 int wdm_hfrm_local_pool(wdm_handle* h, const void* x, int B, int H, int W, int d, int kh, int kw, int dtype, void* compact_out, void* stream);
+/* Pictures beyond the conv kernel's launch range.  Every 1x1 / 2x2 convolution of the HFRM is a GEMM on a kernel that addresses its operands through
+ * buffer descriptors with 32-bit offsets: an input below 4 294 901 760 bytes, an output or residual below 4 026 531 840.  A GEMM with an operand beyond that
+ * runs as several launches over consecutive row ranges -- each the largest multiple of 256 rows whose operands all stay below the limit, the last one the
+ * remainder -- with the bits of a single launch; the closing 3x3 conv_out then runs on a direct kernel without extents (fp32 accumulation in another order
+ * than the MFMA form).  A picture within the range takes the launches it always took.  wdm_hfrm_forward refuses more than 2^27 pixels per image (the bound up to
+ * which every index of the path is checked) with WDM_EINVAL before its first launch; below that the workspace decides.
+ *   wdm_hfrm_set_max_launch_bytes: lowers both limits to `bytes` (never raises them), for tests and diagnosis; 0 restores the kernels' own.  WDM_EINVAL
+ *   for a negative value or one that does not hold a 256-row tile of the model's widest GEMM operand.  Takes effect at the next forward.
+ *   wdm_hfrm_chunk_rows: host only -- the rows per launch of a GEMM of M rows, cin -> cout channels, under the current limit (M itself: one launch).
+ *   wdm_hfrm_conv_out: the direct conv_out alone, for tests: x (B, H, W, cin) NHWC and res (B, H, W, cout) NHWC in dtype (WDM_F32 or WDM_BF16), w (cout, cin,
+ *   3, 3) and bias fp32 (w is rounded to dtype as the packed copy is) -> y (B, cout, H, W) f32 = conv3x3(x, pad 1) + bias + res.  cin = 32, cout = 3.  Waits
+ *   for the stream. */
+int wdm_hfrm_set_max_launch_bytes(wdm_hfrm* m, int64_t bytes);
+int wdm_hfrm_chunk_rows(const wdm_hfrm* m, int64_t M, int cin, int cout, int has_res, int64_t* rows);
+int wdm_hfrm_conv_out(wdm_handle* h, const void* x, const void* res, const float* w, const float* bias, int B, int H, int W, int cin, int cout, int dtype,
+                      float* y, void* stream);
 
 /* ---- output side of DiffusiveRestoration.restore ---------------------------------
  * wdm_image_sqdiff: a, b (B,3,H,W) f32 on the device -> sums[B][2] (device, fp64):

@@ -23,8 +23,10 @@ from .unet import _Node, resolve_dtype
 
 
 class HFRM(nn.Module):
-    # batch chunk: keeps every activation below the kernels' 4 GB buffer-descriptor range
+    # batch chunk: a call of several images stays within the conv kernel's 4 GB launch range; a single image beyond it runs its GEMMs in row chunks
     MAX_PIXELS = 1 << 22
+    # per image: the bound up to which every index of the path is checked; below it memory decides
+    MAX_IMAGE_PIXELS = 1 << 27
 
     def __init__(self, in_channel=3, dim=32, mid_blk_num=1, enc_blk_nums=[], dec_blk_nums=[], win_size=8, dtype=None):
         super().__init__()
@@ -59,6 +61,7 @@ class HFRM(nn.Module):
         self._packed_sig = None
         self._ws = {}
         self._local = None          # ((base_h, base_w), (train_h, train_w)) after convert(), None: global pooling
+        self._max_launch = 0        # wdm_hfrm_set_max_launch_bytes; 0: the kernels' own limits
 
     # ---- test-time local converter (arch.py:46-130) ---------------------------------------------
     @staticmethod
@@ -90,6 +93,26 @@ class HFRM(nn.Module):
             self._local = ((bh, bw), (th, tw))
         self._ws = {}
         return self
+
+    @property
+    def max_launch_bytes(self):
+        """The limit on the bytes one conv-kernel launch may address, 0 (default): the kernels' own (4 GB of 32-bit buffer offsets).  A GEMM with an
+        operand beyond it runs in row chunks, bit-identical to one launch; `conv_out` beyond it runs on its direct kernel.  Setting it only ever
+        lowers the limit (tests, diagnosis); a value below one 256-row tile of the widest layer is refused.  Resets the cached workspace."""
+        return self._max_launch
+
+    @max_launch_bytes.setter
+    def max_launch_bytes(self, nbytes):
+        nbytes = int(nbytes)
+        _lib.check(_lib.lib().wdm_hfrm_set_max_launch_bytes(self._m, nbytes))
+        self._max_launch = nbytes
+        self._ws = {}
+
+    def chunk_rows(self, M, cin, cout, has_res=False):
+        """Rows per launch of a GEMM of M rows, cin -> cout channels, under the current limit (M: one launch).  Host only."""
+        rows = C.c_int64()
+        _lib.check(_lib.lib().wdm_hfrm_chunk_rows(self._m, int(M), int(cin), int(cout), int(bool(has_res)), C.byref(rows)))
+        return int(rows.value)
 
     @property
     def local_kernels(self):
@@ -167,6 +190,8 @@ class HFRM(nn.Module):
         B, Cc, H, W = x.shape
         if Cc != self.in_channel:
             raise ValueError(f"HFRM: {Cc} input channels, expected {self.in_channel}")
+        if H * W > self.MAX_IMAGE_PIXELS:           # before anything is launched (the library refuses the same, wdm_hfrm_forward)
+            raise ValueError(f"HFRM: {H} x {W} = {H * W} pixels per image exceed the bound of 2^27 = {self.MAX_IMAGE_PIXELS}")
         self.pack_weights()
         y = torch.empty_like(x)
         chunk = max(1, self.MAX_PIXELS // (H * W))

@@ -19,6 +19,8 @@ using namespace wdm;
 
 namespace wdm {
 
+constexpr long long WDM_HFRM_MAX_PIXELS = 1LL << 27;      // per image: wdm_hfrm::forward
+
 // ---- LayerNorm2d (arch.py:7-43): per pixel over channels, biased variance --------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void ln2d_kernel(const T* __restrict__ x, T* __restrict__ y, long long M, int C, const float* __restrict__ w,
@@ -409,6 +411,116 @@ __global__ __launch_bounds__(256) void conv3x3_cin3_kernel(const float* __restri
     for (int o = 0; o < DIM; o += VEC) *(uint4*)(y + pix * DIM + o) = TI<T>::pack(acc + o);
 }
 
+// conv_out beyond the conv kernel's launch range: 3x3 pad 1, DIM -> COUT, + bias + the NHWC residual, NCHW f32 out (arch.py:214, 252).  Plain pointers and
+// 64-bit offsets: no extent limits the map.  Eight lanes share a pixel column, each owns four of its 32 channels with their COUT x 9 x 4 weights in registers
+// (rounded to the model dtype as k_pack_conv rounds the packed copy: the two forms differ in accumulation order only).  A block takes a unit of 32 columns x
+// CONV_OUT_ROWS output rows and walks DOWN it: an activation row is loaded once -- three 16- / 8-byte vectors per lane, the columns x - 1, x, x + 1, a wave's eight
+// columns one contiguous run -- and feeds the three output rows it belongs to (as their bottom, middle and top tap row), so a pixel costs 3 (ROWS + 2) / ROWS loads
+// instead of 9; the rows i + 1 and i + 2 are in flight while row i is multiplied.  Taps outside the map are loaded from a clamped address and replaced by
+// zero (no branch), rows past the map's end are walked and not stored.  The eight partial sums of an output meet in three xor-shuffles; lane co stores output co.
+template <typename T> __device__ __forceinline__ float round_to(float v) { return v; }
+template <> __device__ __forceinline__ float round_to<__bf16>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+template <typename T> __device__ __forceinline__ void ld4(const T* p, float* f);
+template <> __device__ __forceinline__ void ld4<float>(const float* p, float* f) { TI<float>::unpack(*(const uint4*)p, f); }
+template <> __device__ __forceinline__ void ld4<__bf16>(const __bf16* p, float* f) {
+    const uint2 u = *(const uint2*)p;
+    TI<__bf16>::unpack2(u.x, f[0], f[1]);
+    TI<__bf16>::unpack2(u.y, f[2], f[3]);
+}
+constexpr int CONV_OUT_ROWS = 16, CONV_OUT_COLS = 32;      // output rows / columns of a unit; ROWS + 2 input rows, a multiple of 3 (the walk's buffers and sums rotate by three)
+template <typename T, int DIM, int COUT>
+__global__ __launch_bounds__(256) void conv_out_direct_kernel(const T* __restrict__ x, const T* __restrict__ res, float* __restrict__ y, int B, int H, int W, int bands,
+                                                              int segs, const float* __restrict__ w, const float* __restrict__ bias) {
+    static_assert(DIM == 32 && COUT <= 8, "eight lanes of four channels per pixel; lane co stores output co");
+    static_assert((CONV_OUT_ROWS + 2) % 3 == 0, "three input rows per round of the walk");
+    const int l = threadIdx.x & 7, c = l * 4, grp = threadIdx.x >> 3;
+    float wr[COUT][9][4];
+#pragma unroll
+    for (int co = 0; co < COUT; ++co)
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) wr[co][t][e] = round_to<T>(w[((long long)co * DIM + c + e) * 9 + t]);       // w is [co][ci][3][3]
+    const float bl = l < COUT ? bias[l] : 0.f;
+    const long long units = (long long)B * bands * segs;
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const int seg = (int)(u % segs);
+        const long long t = u / segs;
+        const int band = (int)(t % bands);
+        const long long b = t / bands;
+        const int y0 = band * CONV_OUT_ROWS, px = seg * CONV_OUT_COLS + grp;
+        const bool live = px < W;
+        const int pxc = min(px, W - 1);                                // a lane group past the row's end walks the last column again and stores nothing
+        const int xl = max(pxc - 1, 0), xr = min(pxc + 1, W - 1);
+        const bool inl = pxc - 1 >= 0, inr = pxc + 1 < W;
+        const T* xb = x + b * H * W * DIM + c;
+        float f[3][3][4];                                              // [input row i % 3][dx][channel]
+        auto load = [&](int i, float (*d)[4]) {                        // input row i of the walk: image row y0 - 1 + i
+            const int r = y0 - 1 + i;
+            const bool in = (unsigned)r < (unsigned)H;
+            const T* row = xb + (long long)min(max(r, 0), H - 1) * W * DIM;
+            ld4<T>(row + (long long)xl * DIM, d[0]);
+            ld4<T>(row + (long long)pxc * DIM, d[1]);
+            ld4<T>(row + (long long)xr * DIM, d[2]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { d[0][e] = in && inl ? d[0][e] : 0.f; d[1][e] = in ? d[1][e] : 0.f; d[2][e] = in && inr ? d[2][e] : 0.f; }
+        };
+        float acc[3][COUT];                                            // [output row o % 3], o = image row - (y0 - 1)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int co = 0; co < COUT; ++co) acc[k][co] = 0.f;
+        load(0, f[0]);
+        load(1, f[1]);
+#pragma unroll 1
+        for (int i0 = 0; i0 < CONV_OUT_ROWS + 2; i0 += 3) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int i = i0 + j;
+                if (i + 2 < CONV_OUT_ROWS + 2) load(i + 2, f[(j + 2) % 3]);
+                // input row i is the top tap row (dy = 0) of output o = i + 1, which starts here, the middle one of o = i and the bottom one of o = i - 1, which ends here
+                float (*d)[4] = f[j];
+#pragma unroll
+                for (int co = 0; co < COUT; ++co) {
+                    float s0 = 0.f, s1 = acc[j][co], s2 = acc[(j + 2) % 3][co];
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            s0 += d[dx][e] * wr[co][dx][e];
+                            s1 += d[dx][e] * wr[co][3 + dx][e];
+                            s2 += d[dx][e] * wr[co][6 + dx][e];
+                        }
+                    acc[(j + 1) % 3][co] = s0; acc[j][co] = s1; acc[(j + 2) % 3][co] = s2;
+                }
+                float mine = 0.f;
+#pragma unroll
+                for (int co = 0; co < COUT; ++co) {
+                    float sm = acc[(j + 2) % 3][co];
+                    sm += __shfl_xor(sm, 1); sm += __shfl_xor(sm, 2); sm += __shfl_xor(sm, 4);
+                    if (l == co) mine = sm;
+                }
+                const int py = y0 + i - 2;                             // output o = i - 1
+                if (i >= 2 && py < H && live && l < COUT) {
+                    const long long pix = (b * H + py) * W + px;
+                    y[((b * COUT + l) * H + py) * W + px] = mine + bl + TI<T>::ld(res, pix * COUT + l);
+                }
+            }
+        }
+    }
+}
+// x (B, H, W, 32) NHWC and res (B, H, W, cout) NHWC in the model dtype, w (cout, 32, 3, 3) and bias fp32 -> y (B, cout, H, W) f32
+int k_conv_out_direct(const void* x, const void* res, const float* w, const float* bias, int B, int H, int W, int cin, int cout, int dtype, float* y, hipStream_t s) {
+    if (cin != 32 || cout != 3) WDM_FAIL(WDM_EINVAL, "conv_out (direct form): %d -> %d channels; the kernel is built for 32 -> 3", cin, cout);
+    const int bands = (H + CONV_OUT_ROWS - 1) / CONV_OUT_ROWS, segs = (W + CONV_OUT_COLS - 1) / CONV_OUT_COLS;
+    const long long units = (long long)B * bands * segs;
+    const unsigned grid = (unsigned)std::min<long long>(units, 256 * 12);      // 2 blocks of 4 waves fit a CU at this kernel's registers (242 / 212 VGPRs: 2 waves per SIMD); six rounds of them, the loop covers the rest
+    if (dtype == WDM_BF16) hipLaunchKernelGGL((conv_out_direct_kernel<__bf16, 32, 3>), dim3(grid), dim3(256), 0, s, (const __bf16*)x, (const __bf16*)res, y, B, H, W, bands, segs, w, bias);
+    else hipLaunchKernelGGL((conv_out_direct_kernel<float, 32, 3>), dim3(grid), dim3(256), 0, s, (const float*)x, (const float*)res, y, B, H, W, bands, segs, w, bias);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
 // parameter packing helpers -----------------------------------------------------------------------------------
 // 1x1 / 2x2 conv weight [cout][cin][k][k] f32 -> GEMM matrix [rows_pad][k*k*cin] (row-major, k index (i*k+j)*cin + c), each row
 // optionally scaled by rowscale[cout] (beta / gamma folding); bias likewise
@@ -460,6 +572,31 @@ struct wdm_hfrm {
     bool local = false;
     int base_hw[2] = {0, 0}, train_hw[2] = {0, 0};
     int lk_h[9] = {0}, lk_w[9] = {0};
+    // The conv kernel addresses its operands through buffer descriptors with 32-bit offsets (conv_dispatch.inc: inputs below X_RANGE bytes, outputs and residuals
+    // below Y_RANGE); max_launch (wdm_hfrm_set_max_launch_bytes, 0: unset) only ever lowers the two.  A GEMM beyond them runs as several launches over consecutive
+    // row ranges (gemm_rows), conv_out beyond them on the direct kernel (conv_out_direct_kernel).
+    static constexpr long long X_RANGE = 4294901760LL, Y_RANGE = 4026531840LL;
+    static constexpr int CHUNK_UNIT = 256;                            // rows: the largest M tile of the MODE_P1 kernels
+    long long max_launch = 0;
+    long long x_range() const { return max_launch ? std::min(X_RANGE, max_launch) : X_RANGE; }
+    long long y_range() const { return max_launch ? std::min(Y_RANGE, max_launch) : Y_RANGE; }
+    // rows per launch of a GEMM over M rows: M when every operand fits the range, else the largest multiple of CHUNK_UNIT for which x (cin wide) and y / res
+    // (cout wide) all stay below it (0: not even one unit does -- wdm_hfrm_set_max_launch_bytes refuses such a value for this model's GEMMs)
+    long long chunk_rows(long long M, int cin, int cout) const {
+        const long long es = (long long)dsize(cfg.dtype), xb = cin * es, yb = cout * es;
+        if (M * xb < x_range() && M * yb < y_range()) return M;
+        return std::min((x_range() - 1) / xb, (y_range() - 1) / yb) / CHUNK_UNIT * CHUNK_UNIT;
+    }
+    int widest_gemm() const {                                         // channels of the widest GEMM operand of this model
+        int wd = 0;
+        for (auto& b : bg) wd = std::max(wd, std::max(b.g1.cin, b.g1.cout));
+        for (auto& g : g_up) wd = std::max(wd, std::max(g.cin, g.cout));
+        for (auto& g : g_down) wd = std::max(wd, std::max(g.cin, g.cout));
+        return wd;
+    }
+    // conv_out's activation outside the conv kernel's range: the one condition conv_dispatch.inc holds that launch to (its output / residual check covers NHWC
+    // outputs of 8n channels; the residual and the NCHW f32 output, in_channel wide, are smaller than the activation in any case)
+    bool conv_out_direct(long long M) const { return M * cfg.dim * (long long)dsize(cfg.dtype) >= x_range(); }
 
     size_t take(size_t bytes) { size_t o = packed_bytes; packed_bytes = align_up(packed_bytes + bytes, 256); return o; }
     GemmD gemm(int cin, int cout) {
@@ -527,16 +664,27 @@ int wdm_hfrm::finalize(hipStream_t s) {
     return WDM_OK;
 }
 
-// y[M][cout] = x[M][cin] . W^T + bias (+ res): plain GEMM on the conv kernel, pixels flattened onto a 16-wide grid
+// y[M][cout] = x[M][cin] . W^T + bias (+ res): plain GEMM on the conv kernel, pixels flattened onto a 16-wide grid.  Operands beyond the kernel's launch
+// range: one launch per chunk_rows() consecutive rows, base pointers advanced in 64-bit arithmetic.  A chunk may start in the middle of an image or an image
+// row -- the rows of a GEMM are independent and an output row's K order does not depend on the tile it sits in, so the chunked result has the bits of one launch.
 int wdm_hfrm::gemm_rows(Ctx& c, const GemmD& g, const void* x, long long M, const void* res, void* y) {
     if (c.dry) return WDM_OK;
-    const int Hp = (int)align_up((size_t)((M + 15) / 16), 16);
     const ConvW w = cw(g);
-    ConvArgs a = gemm_args(1, Hp, 16, x, g.cin, g.cin, w.w, g.cin, 0, g.rows_pad, g.cout, y, Y_NHWC, dsize(c.dtype));
-    a.bias = w.b;
-    a.res = res; a.res_s = g.cout;
-    a.m_valid = M;      // the descriptor extents must describe the real tensor (M rows), not the padded grid
-    return launch_conv(a, MODE_P1, c.dtype, c.s);
+    const long long es = (long long)dsize(c.dtype);
+    auto launch = [&](const void* xr, const void* rr, void* yr, long long rows) {
+        const int Hp = (int)align_up((size_t)((rows + 15) / 16), 16);
+        ConvArgs a = gemm_args(1, Hp, 16, xr, g.cin, g.cin, w.w, g.cin, 0, g.rows_pad, g.cout, yr, Y_NHWC, dsize(c.dtype));
+        a.bias = w.b;
+        a.res = rr; a.res_s = g.cout;
+        a.m_valid = rows;      // the descriptor extents must describe the real tensor (its rows), not the padded grid
+        return launch_conv(a, MODE_P1, c.dtype, c.s);
+    };
+    const long long step = chunk_rows(M, g.cin, g.cout);
+    if (step >= M) return launch(x, res, y, M);
+    if (step <= 0) WDM_FAIL(WDM_EINVAL, "HFRM: max_launch_bytes = %lld leaves no room for %d rows of a %d -> %d GEMM", max_launch, CHUNK_UNIT, g.cin, g.cout);
+    for (long long r0 = 0; r0 < M; r0 += step)
+        WDM_TRY(launch((const char*)x + r0 * g.cin * es, res ? (const char*)res + r0 * g.cout * es : nullptr, (char*)y + r0 * g.cout * es, std::min(step, M - r0)));
+    return WDM_OK;
 }
 
 int wdm_hfrm::run_block(Ctx& c, const Block& b, Tens& t, int B, int H, int W, int level) {
@@ -609,6 +757,8 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
     const int nlev = cfg.n_enc;
     if (H % (1 << nlev) || W % (1 << nlev)) WDM_FAIL(WDM_EINVAL, "HFRM: H=%d W=%d must be multiples of %d", H, W, 1 << nlev);
     if (H % 8 || W % 8) WDM_FAIL(WDM_EINVAL, "HFRM: H and W must be multiples of 8");
+    // the kernels' indices are audited up to this map; below it memory decides
+    if ((long long)H * W > WDM_HFRM_MAX_PIXELS) WDM_FAIL(WDM_EINVAL, "HFRM: %d x %d = %lld pixels per image exceed the bound of 2^27 = %lld", H, W, (long long)H * W, WDM_HFRM_MAX_PIXELS);
     int d = cfg.dim, h = H, w = W;
     Tens t; t.C = d; t.H = h; t.W = w; t.xs = d;
     t.p = c.ar->alloc((size_t)B * h * w * d * es);
@@ -658,8 +808,10 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         t = nt; d /= 2; h *= 2; w *= 2;
         for (auto& b : L.dec[i]) WDM_TRY(run_block(c, b, t, B, h, w, nlev - 1 - i));
     }
-    // conv_out 3x3 (dim -> 3) + input, NCHW f32 out
-    {
+    // conv_out 3x3 (dim -> 3) + input, NCHW f32 out: on the conv kernel (MFMA) within its launch range, on the direct kernel beyond it
+    if (conv_out_direct((long long)B * h * w)) {
+        if (!c.dry) WDM_TRY(k_conv_out_direct(t.p, xin, raw(L.conv_out.w), raw(L.conv_out.b), B, h, w, cfg.dim, cfg.in_channel, c.dtype, yout, c.s));
+    } else {
         ConvW cwo; cwo.w = packed + raw_bytes + cout_w_off; cwo.b = raw(L.conv_out.b); cwo.cin = cfg.dim; cwo.cout = cfg.in_channel; cwo.k = 3; cwo.rows_pad = conv_rows_pad(cfg.in_channel);
         Tens xi; xi.p = xin; xi.C = cfg.in_channel; xi.H = h; xi.W = w; xi.xs = cfg.in_channel;
         Tens dummy;
@@ -763,6 +915,37 @@ int wdm_hfrm_local_pool(wdm_handle* h, const void* x, int B, int H, int W, int d
     (void)hipFree(colsum);
     if (rc == WDM_OK && e != hipSuccess) WDM_FAIL(WDM_EHIP, "wdm_hfrm_local_pool: %s", hipGetErrorString(e));
     return rc;
+}
+int wdm_hfrm_set_max_launch_bytes(wdm_hfrm* m, int64_t bytes) {
+    if (!m) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_max_launch_bytes: null argument");
+    if (bytes < 0) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_max_launch_bytes: %lld is negative (0: the kernels' own limits)", (long long)bytes);
+    const long long tile = (long long)wdm_hfrm::CHUNK_UNIT * m->widest_gemm() * (long long)dsize(m->cfg.dtype);
+    if (bytes && bytes <= tile)
+        WDM_FAIL(WDM_EINVAL, "wdm_hfrm_set_max_launch_bytes: %lld bytes do not hold one %d-row tile of the widest layer (%lld bytes; operands stay below the limit)",
+                 (long long)bytes, wdm_hfrm::CHUNK_UNIT, tile);
+    m->max_launch = bytes;
+    return WDM_OK;
+}
+int wdm_hfrm_chunk_rows(const wdm_hfrm* m, int64_t M, int cin, int cout, int has_res, int64_t* rows) {
+    (void)has_res;                                                     // the residual is as wide as the output and under the same limit
+    if (!m || !rows) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_chunk_rows: null argument");
+    if (M <= 0 || cin <= 0 || cout <= 0) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_chunk_rows: bad shape");
+    const long long r = m->chunk_rows(M, cin, cout);
+    if (r <= 0) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_chunk_rows: the limit holds no %d rows of a %d -> %d GEMM", wdm_hfrm::CHUNK_UNIT, cin, cout);
+    *rows = r;
+    return WDM_OK;
+}
+/* conv_out's direct form on its own (unit tests): waits for the stream */
+int wdm_hfrm_conv_out(wdm_handle* h, const void* x, const void* res, const float* w, const float* bias, int B, int H, int W, int cin, int cout, int dtype, float* y,
+                      void* stream) {
+    (void)h;
+    if (!x || !res || !w || !bias || !y) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_conv_out: null argument");
+    if (dtype != WDM_BF16 && dtype != WDM_F32) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_conv_out: dtype must be f32 or bf16");
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)H * W > WDM_HFRM_MAX_PIXELS) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_conv_out: bad shape");
+    if (((uintptr_t)x) & 15) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_conv_out: x must be 16-byte aligned");
+    WDM_TRY(k_conv_out_direct(x, res, w, bias, B, H, W, cin, cout, dtype, y, (hipStream_t)stream));
+    WDM_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return WDM_OK;
 }
 size_t wdm_hfrm_workspace_bytes(const wdm_hfrm* m, int B, int H, int W) {
     if (!m || B <= 0) return 0;
