@@ -74,6 +74,23 @@ int wdm_dwt_fwd_affine(wdm_handle* h, const float* x, float scale, float shift, 
 int wdm_dwt_inv_compose(wdm_handle* h, const float* y_lo, int lo_channels, int n_lo, const float* y_hi, float* x, int B, int hh, int ww,
                         int to_unit_range, void* stream);
 
+/* wdm_ensemble_compose: N diffusion samples per image reduced to their mean image and per-pixel spread, fused with the compose + IDWT above (no
+ * counterpart in the reference, which draws one sample).  All in fp32, in a fixed order, without atomics; everything is queued on `stream`.
+ *   preds     (B * n_samples, lo_channels, hh, ww) : sample k of image i is row i * n_samples + k
+ *   y_hi      (B, 48, hh, ww)                      : the bands that are not predicted; may be NULL when n_lo == 48
+ *   mean_img  (B, 3, 4hh, 4ww)
+ *   std_img   same shape, or NULL
+ *   mean_coef (B, n_lo, hh, ww), or NULL
+ * mean coefficient = (((p_0 + p_1) + p_2) + ...) / (float)n_samples, samples added in ascending order, the last step a division.
+ * mean_img = what wdm_dwt_inv_compose makes of [mean_coef[:, :n_lo] | y_hi[:, n_lo:]] (n_samples == 1: its bits).
+ * std_img  = the unbiased (n_samples - 1) standard deviation over the samples of the UNCLAMPED pixel (IDWT(compose(p_k, y_hi)) + 1) / 2, in two passes
+ *            (the mean first, then the squared deviations, added in ascending order); only the n_lo predicted bands enter the deviations.  Without
+ *            to_unit_range the factor 1/2 is dropped.  n_samples == 1 with std_img is WDM_EINVAL.
+ * An image's result does not depend on the batch around it.  Limits, else WDM_EINVAL and nothing is launched: 1 <= n_samples <= 256; n_lo a multiple of 3
+ * in [3, 48], n_lo <= lo_channels; B * n_samples <= 65535.  Element offsets are 64-bit. */
+int wdm_ensemble_compose(wdm_handle* h, const float* preds, int lo_channels, int n_lo, int n_samples, const float* y_hi, float* mean_img,
+                         float* std_img, float* mean_coef, int B, int hh, int ww, int to_unit_range, void* stream);
+
 /* ---- layout helpers at the UNet boundary ---------------------------------------------------
  * A "patch list" is n triples (img, hi, wi) of int32 on the DEVICE: patch k is the p x p window
  * at (hi, wi) of image `img` of a (NIMG, C, H, W) NCHW f32 tensor.  It restates the reference's

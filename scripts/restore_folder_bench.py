@@ -5,6 +5,7 @@
                                                                                         # the same N as [degraded | gt] pairs through restore()
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/restore_folder_bench.py --kernels
     python scripts/restore_folder_bench.py --summarize DIR                              # the trace -> a table: time and bytes/s per kernel and size
+    python scripts/restore_folder_bench.py --samples 4 [--n 8] [--size 480 720]         # args.samples = 4 against four args.samples = 1 passes (profiles/ensemble.md)
     python scripts/restore_folder_bench.py --mixed [--n 32] [--steps 25] [--dtype f16]  # args.mix_sizes off / on / on / off: a folder of mixed sizes, the
                                                                                         # uniform folder (profiles/restore_folder_mixed.md)
 
@@ -137,6 +138,76 @@ def mixed(a):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def ensemble(a):
+    """args.samples = N against N passes with args.samples = 1 (profiles/ensemble.md): a folder of --n pictures of --size, PNGs written, the legs N, 1, 1, N in
+    ONE process after a warm-up pass of each.  A `1` leg is N whole passes over the folder with N seeds -- what a user has to do without the option.  One line
+    per leg: seconds for the N samples of every picture; then the ratio of the means."""
+    import torch
+    from PIL import Image
+    import wavedm_amd
+    from wavedm_amd import procedural as P
+    torch.set_grad_enabled(False)
+    dev = torch.device("cuda", 0)
+    cfg = P.raindrop_wavelet_config()
+    cfg.device = dev
+    base = SimpleNamespace(resume="", sampling_timesteps=a.steps, local_rank=0, image_folder="", test_set="raindrop", grid_r=16, seed=61)
+    d = wavedm_amd.DenoisingDiffusion_Wavelet(base, cfg, generator="procedural", dtype=a.dtype or "f16")
+    d.model.load_state_dict(P.procedural_state_dict(cfg, seed=61), strict=True)
+    N, (h, w) = a.samples, a.size
+    tmp = tempfile.mkdtemp(prefix="wdm_rfe_")
+    try:
+        src = os.path.join(tmp, "in")
+        os.makedirs(src)
+        for k in range(a.n):
+            Image.fromarray(picture(h, w, seed=4 + k)).save(os.path.join(src, f"img{k:03d}.png"))
+
+        def leg(samples, tag):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            for q in range(1 if samples > 1 else N):
+                args = SimpleNamespace(**vars(base))
+                args.samples, args.seed = samples, 61 + q
+                rest = wavedm_amd.DiffusiveRestoration(d, args, cfg, save_images=True)
+                with contextlib.redirect_stdout(io.StringIO()):
+                    rest.restore_folder(src, os.path.join(tmp, f"out_{tag}_{q}"), r=16)
+                rest.writer.close()
+                calls += len(rest.last_calls)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, calls
+
+        print(f"{a.n} x {h}x{w}, {a.steps} steps, mode {d.model.dtype_name}, {N} samples per picture, PNGs written")
+        leg(N, "warm_n"), leg(1, "warm_1")
+        ts = {N: [], 1: []}
+        for k, samples in enumerate((N, 1, 1, N)):
+            dt, calls = leg(samples, f"leg{k}")
+            ts[samples].append(dt)
+            what = f"--samples {N}, one pass" if samples > 1 else f"--samples 1, {N} passes"
+            print(f"{what:24s}: {dt:.3f} s for {a.n * N} samples ({a.n * N / dt:.2f} samples/s), {calls} sampler calls", flush=True)
+        m_n, m_1 = sum(ts[N]) / 2, sum(ts[1]) / 2
+        print(f"ratio: --samples {N} takes {m_n / m_1:.3f} of the time of {N} --samples 1 passes ({m_1 / m_n:.2f}x)")
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def ensemble_kernel(a):
+    """wdm_ensemble_compose REPS times per shape (mean + std, 3 of 48 bands predicted), for a kernel trace: 480x720 with N = 4 and 16, 3000x4000 with N = 4."""
+    import torch
+    from wavedm_amd.wavelet import WaveletTransform
+    dev = torch.device("cuda", 0)
+    rec = WaveletTransform(scale=2, dec=False)
+    for (h, w), n in (((480, 720), 4), ((480, 720), 16), ((3000, 4000), 4)):
+        g = torch.Generator(device=dev).manual_seed(3)
+        preds = torch.randn(n, 3, h // 4, w // 4, device=dev, generator=g)
+        hi = torch.randn(1, 48, h // 4, w // 4, device=dev, generator=g)
+        for _ in range(a.reps):
+            mean, std, _ = rec.compose_ensemble(preds, hi, 3, n, want_std=True)
+        torch.cuda.synchronize()
+        # bytes: preds read twice (mean pass, deviation pass), 45 bands of hi once, two images written
+        moved = 4 * (2 * preds.numel() + 45 * (h // 4) * (w // 4) + 2 * mean.numel())
+        print(f"{h}x{w} N={n}: {a.reps} launches, {moved} bytes each", flush=True)
+
+
 def kernels(a):
     """Each kernel REPS times per size, the sizes one after the other (the summary tells them apart by their grids)."""
     import torch
@@ -189,9 +260,13 @@ if __name__ == "__main__":
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--summarize", default=None, metavar="DIR")
+    ap.add_argument("--samples", type=int, default=1, help="args.samples = N against N passes with args.samples = 1 over --n pictures of --size; with --kernels: the reduction kernel alone")
+    ap.add_argument("--size", type=int, nargs=2, metavar=("H", "W"), default=(480, 720), help="with --samples: the pictures' size")
     a = ap.parse_args()
     if a.summarize:
         summarize(a.summarize)
+    elif a.samples > 1:
+        (ensemble_kernel if a.kernels else ensemble)(a)
     elif a.mixed:
         mixed(a)
     elif a.kernels:

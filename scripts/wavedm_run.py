@@ -62,7 +62,23 @@ def parse(argv=None):
     ap.add_argument("--max_steps", type=int, default=None)
     ap.add_argument("--no_save", action="store_true", help="eval: metrics only, no PNGs")
     ap.add_argument("--ssim", action="store_true", help="eval: also SSIM (Y channel) of every output against its gt, on the device; prints an `ssim all` line")
+    ap.add_argument("--samples", type=int, default=1,
+                    help="eval, restore: diffusion samples per image, run as rows of ONE sampler call that share the image's decode, HFRM call and DWT; the output is the "
+                         "image of their mean coefficients (fp32, fixed order).  Every single sample is the restoration its seed gives alone, bit for bit, and sample 0 is the "
+                         "--samples 1 restoration.  The effect on restoration quality has not been measured.")
+    ap.add_argument("--save-std", dest="save_std", action="store_true",
+                    help="eval, restore: with --samples >= 2 also write <stem>_std.png (eval: <name>_std.png), clamp(std_gain * std, 0, 1) of the per-pixel unbiased "
+                         "standard deviation of the samples' unclamped pixels")
+    ap.add_argument("--std_gain", type=float, default=8.0, help="with --save-std: the factor the standard deviation is multiplied by before the 8-bit conversion")
     a = ap.parse_args(argv)
+    if a.samples < 1:
+        ap.error("--samples needs at least 1")
+    if a.samples > 1 and a.mode == "train":
+        ap.error("--samples is a test-time option (eval, restore)")
+    if a.samples > 1 and a.mix_sizes:
+        ap.error("--samples > 1 is not built for --mix-sizes (the ragged layout draws one sample per image)")
+    if a.save_std and a.samples == 1:
+        ap.error("--save-std needs --samples >= 2 (the spread of one sample is undefined)")
     a.early_stop = not a.full_length
     a.images_per_call = a.images_per_call or None          # None: DiffusiveRestoration's automatic grouping
     a.rank = int(os.environ.get("RANK", 0))

@@ -67,6 +67,11 @@ int wdm_dwt_inv_compose(wdm_handle* h, const float* y_lo, int lo_channels, int n
     if (!h || !x || !y_hi) WDM_FAIL(WDM_EINVAL, "wdm_dwt_inv_compose: null argument");
     return k_dwt_inv(y_hi, x, B, hh, ww, (hipStream_t)stream, y_lo, lo_channels, n_lo, to_unit_range);
 }
+int wdm_ensemble_compose(wdm_handle* h, const float* preds, int lo_channels, int n_lo, int n_samples, const float* y_hi, float* mean_img, float* std_img,
+                         float* mean_coef, int B, int hh, int ww, int to_unit_range, void* stream) {
+    if (!h) WDM_FAIL(WDM_EINVAL, "wdm_ensemble_compose: null argument");
+    return k_ensemble_compose(preds, lo_channels, n_lo, n_samples, y_hi, mean_img, std_img, mean_coef, B, hh, ww, to_unit_range, (hipStream_t)stream);
+}
 int wdm_pack_channels(wdm_handle* h, const float* src, int nch, int H, int W, const int32_t* patches, int n, int p, void* x96, int c_total, int c_off,
                       int dtype, void* stream) {
     if (!h || !src || !x96) WDM_FAIL(WDM_EINVAL, "wdm_pack_channels: null argument");

@@ -57,6 +57,24 @@ __global__ __launch_bounds__(256) void dwt_fwd_kernel(const float* __restrict__ 
     }
 }
 
+// The inverse of one 4x4 block in place (t[j] = sub-band j in, t[idx] = pixel out) and its store -- shared by dwt_inv_kernel and ensemble_compose_kernel.
+__device__ __forceinline__ void idwt_block(float* t, int post) {
+    wht16(t);   // the basis is orthonormal and symmetric in (j, idx): the inverse is the same butterfly
+    if (post) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) t[i] = fminf(fmaxf((t[i] + 1.0f) * 0.5f, 0.0f), 1.0f);
+    }
+}
+__device__ __forceinline__ void store_block(const float* t, float* dst, int W) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        float rq[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rq[q] = t[((p & 1) << 3) | ((q & 1) << 2) | ((p >> 1) << 1) | (q >> 1)];
+        *(float4*)(dst + (long long)p * W) = make_float4(rq[0], rq[1], rq[2], rq[3]);
+    }
+}
+
 // Coefficient channel ch = j*3 + c comes from y_lo (B, lo_total, h, w) when ch < n_lo, else from y (B, 48, h, w): the
 // torch.cat([x0[:, :pc], hf_wav[:, pc:]]) of restoration.py:114 without materialising it (n_lo = 0: plain inverse).
 // post != 0: clamp((x + 1) / 2, 0, 1) = inverse_data_transform (restoration.py:12-13) on the way out.
@@ -75,19 +93,69 @@ __global__ __launch_bounds__(256) void dwt_inv_kernel(const float* __restrict__ 
             const int chn = j * 3 + c;
             t[j] = chn < n_lo ? y_lo[(((long long)b * lo_total + chn) * h + u) * w + v] : y[(((long long)b * 48 + chn) * h + u) * w + v];
         }
-        wht16(t);   // the basis is orthonormal and symmetric in (j, idx): the inverse is the same butterfly
-        if (post) {
+        idwt_block(t, post);
+        store_block(t, x + (((long long)b * 3 + c) * H + 4 * u) * W + 4 * v, W);
+    }
+}
+
+// The ensemble reduction fused with compose + IDWT (include/wavedm.h: wdm_ensemble_compose).  One thread per 4x4 pixel block of one colour plane, like
+// dwt_inv_kernel: its 16 coefficients are channels j*3 + c.  Pass 1: the predicted ones (chn < n_lo) are the mean over the N sample rows b*N + k of
+// preds, added in ascending k and divided by (float)N; the others come from y_hi; idwt_block gives the mean image (n_samples == 1: dwt_inv_kernel's bits).
+// Pass 2 (std_img only): per sample the deviation of its pixels from the mean image is the IDWT of its coefficients' deviations (the transform is linear,
+// the y_hi bands cancel), squared and added in ascending k; sqrt(sum / (N - 1)), halved with `post` (the pixel is (x + 1) / 2, unclamped).
+// Coefficient loads are 4 bytes per lane, consecutive across the wave; pixel stores 16 bytes.  No atomics, no cross-thread reduction.
+__global__ __launch_bounds__(256) void ensemble_compose_kernel(const float* __restrict__ preds, int lo_total, int n_lo, int N, const float* __restrict__ y_hi,
+                                                               float* __restrict__ mean_img, float* __restrict__ std_img, float* __restrict__ mean_coef,
+                                                               int B, int h, int w, int post) {
+    const int H = h << 2, W = w << 2;
+    const long long plane = (long long)h * w;
+    const long long total = (long long)B * 3 * plane;
+    const float fN = (float)N;
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
+        const long long uv = id % plane;
+        const int c = (int)((id / plane) % 3);
+        const int b = (int)(id / (plane * 3));
+        const float* row0 = preds + (long long)b * N * lo_total * plane + uv;       // sample 0 of image b, channel 0, this block
+        float m[16];
 #pragma unroll
-            for (int i = 0; i < 16; ++i) t[i] = fminf(fmaxf((t[i] + 1.0f) * 0.5f, 0.0f), 1.0f);
+        for (int j = 0; j < 16; ++j) {
+            const int chn = j * 3 + c;
+            if (chn < n_lo) {
+                const float* src = row0 + chn * plane;
+                float s = src[0];
+                for (int k = 1; k < N; ++k) s += src[(long long)k * lo_total * plane];
+                m[j] = s / fN;
+                if (mean_coef != nullptr) mean_coef[((long long)b * n_lo + chn) * plane + uv] = m[j];
+            } else {
+                m[j] = y_hi[((long long)b * 48 + chn) * plane + uv];
+            }
         }
-        float* dst = x + (((long long)b * 3 + c) * H + 4 * u) * W + 4 * v;
+        const long long pix = (((long long)b * 3 + c) * H + 4 * (uv / w)) * W + 4 * (uv % w);
+        float t[16];
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            float rq[4];
+        for (int j = 0; j < 16; ++j) t[j] = m[j];
+        idwt_block(t, post);
+        store_block(t, mean_img + pix, W);
+        if (std_img == nullptr) continue;
+        float acc[16];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) rq[q] = t[((p & 1) << 3) | ((q & 1) << 2) | ((p >> 1) << 1) | (q >> 1)];
-            *(float4*)(dst + (long long)p * W) = make_float4(rq[0], rq[1], rq[2], rq[3]);
+        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+        for (int k = 0; k < N; ++k) {
+            const float* src = row0 + (long long)k * lo_total * plane;
+            float d[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int chn = j * 3 + c;
+                d[j] = chn < n_lo ? src[chn * plane] - m[j] : 0.0f;
+            }
+            wht16(d);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] += d[i] * d[i];
         }
+        const float inv = 1.0f / (float)(N - 1), half = post ? 0.5f : 1.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = sqrtf(acc[i] * inv) * half;
+        store_block(acc, std_img + pix, W);
     }
 }
 
@@ -103,6 +171,20 @@ int k_dwt_inv(const float* y, float* x, int B, int h, int w, hipStream_t s, cons
     if (n_lo < 0 || n_lo > 48 || (n_lo > 0 && (!y_lo || lo_total < n_lo))) WDM_FAIL(WDM_EINVAL, "dwt_inv: bad low-band source (%d of %d channels)", n_lo, lo_total);
     const long long total = (long long)B * 3 * h * w;
     hipLaunchKernelGGL(dwt_inv_kernel, dim3(nblocks(total, 256) > 8192 ? 8192 : nblocks(total, 256)), dim3(256), 0, s, y, x, B, h, w, y_lo, lo_total, n_lo, post);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+int k_ensemble_compose(const float* preds, int lo_total, int n_lo, int N, const float* y_hi, float* mean_img, float* std_img, float* mean_coef, int B, int h,
+                       int w, int post, hipStream_t s) {
+    if (!preds || !mean_img) WDM_FAIL(WDM_EINVAL, "ensemble_compose: null argument");
+    if (B <= 0 || h <= 0 || w <= 0) WDM_FAIL(WDM_EINVAL, "ensemble_compose: bad shape");
+    if (N < 1 || N > 256 || (long long)B * N > 65535) WDM_FAIL(WDM_EINVAL, "ensemble_compose: %d samples of %d images (1 <= samples <= 256, rows <= 65535)", N, B);
+    if (n_lo < 3 || n_lo > 48 || n_lo % 3 || n_lo > lo_total) WDM_FAIL(WDM_EINVAL, "ensemble_compose: bad predicted bands (%d of %d channels)", n_lo, lo_total);
+    if (!y_hi && n_lo != 48) WDM_FAIL(WDM_EINVAL, "ensemble_compose: y_hi is NULL with %d of 48 bands predicted", n_lo);
+    if (std_img && N == 1) WDM_FAIL(WDM_EINVAL, "ensemble_compose: the spread of one sample is undefined");
+    const long long total = (long long)B * 3 * h * w;
+    hipLaunchKernelGGL(ensemble_compose_kernel, dim3(nblocks(total, 256) > 8192 ? 8192 : nblocks(total, 256)), dim3(256), 0, s, preds, lo_total, n_lo, N, y_hi,
+                       mean_img, std_img, mean_coef, B, h, w, post);
     WDM_HIP(hipGetLastError());
     return WDM_OK;
 }

@@ -269,12 +269,22 @@ class DenoisingDiffusion_Wavelet(object):
                                "sample_image(..., total=<whole image>, use_global=True)")
 
     def sample_image(self, x_cond, x, x_other=None, last=True, patch_locs=None, patch_size=None, total=None,
-                     use_global=False, use_other=False, stop_at=None):
-        """ddm_wavelet.py:295-309.  `stop_at` (not in the reference; default None = every step, like the reference): a negative index k -- the caller reads
+                     use_global=False, use_other=False, stop_at=None, samples=1):
+        """ddm_wavelet.py:295-309.  `samples` (not in the reference; default 1): N trajectories per image in one sampler call -- x holds B * N start noises, sample k
+        of image i in row i * N + k, x_cond / x_other B rows (sampling.ddim_sample).  `stop_at` (not in the reference; default None = every step, like the reference): a negative index k -- the caller reads
         nothing after x0_preds[k], so the steps behind it are skipped and the lists padded with None (sampling.ddim_sample).  DiffusiveRestoration.restore,
         which consumes x0_preds[-5] only (restoration.py:108), passes -5."""
         if last and stop_at is not None:
             raise ValueError("sample_image: last=True returns xs[-1], which an early stop does not compute")
+        samples = int(samples)
+        if samples < 1:
+            raise ValueError(f"sample_image: samples = {samples} (at least 1)")
+        if samples > 1 and use_global:
+            raise NotImplementedError("sample_image: samples > 1 is not built for the use_global branch")
+        if samples > 1 and getattr(self, "patch_group", None) is not None:
+            raise ValueError("sample_image: samples > 1 is not built for the patch-sharded mode (patch_group)")
+        if samples > 1 and x.shape[0] != samples * x_cond.shape[0]:
+            raise ValueError(f"sample_image: x has {x.shape[0]} rows, x_cond {x_cond.shape[0]}: x.shape[0] must be samples * x_cond.shape[0] (samples = {samples})")
         skip = self.config.diffusion.num_diffusion_timesteps // self.args.sampling_timesteps
         seq = range(0, self.config.diffusion.num_diffusion_timesteps, skip)
         if patch_locs is None:
@@ -283,11 +293,11 @@ class DenoisingDiffusion_Wavelet(object):
             # (generalized_steps starts from x as given whatever data.begin_from_noise says: there is no q-sample of x_cond on this path)
             self._require_plain_unet("sample_image(patch_locs=None)")
             xs = sampling.ddim_sample(self.model, x, x_cond, None, list(seq), self.betas, corners=None, max_batch=getattr(self.args, "max_batch", 64),
-                                      stop_at=stop_at)
+                                      stop_at=stop_at, samples=samples)
             return xs[0][-1] if last else xs
         xs = self.generalized_steps_overlapping(x, x_cond, seq, self.model, self.betas, eta=0., corners=patch_locs,
                                                 p_size=patch_size, total=total, use_global=use_global,
-                                                x_other=x_other, use_other=use_other, stop_at=stop_at)
+                                                x_other=x_other, use_other=use_other, stop_at=stop_at, samples=samples)
         if last:
             xs = xs[0][-1]
         return xs
@@ -314,9 +324,11 @@ class DenoisingDiffusion_Wavelet(object):
                                            max_batch=getattr(self.args, "max_batch", None) or sampling.DEFAULT_MAX_BATCH, stop_at=stop_at)
 
     def generalized_steps_overlapping(self, x, x_cond, seq, model, b, eta=0., corners=None, p_size=None,
-                                      manual_batching=True, total=None, x_other=None, use_global=False, use_other=False, stop_at=None):
+                                      manual_batching=True, total=None, x_other=None, use_global=False, use_other=False, stop_at=None, samples=1):
         """ddm_wavelet.py:437-506 on the device (eta != 0 included: :500-502, one randn_like(x) per step from the device generator)."""
         if use_global:
+            if samples != 1:
+                raise NotImplementedError("generalized_steps_overlapping: samples > 1 is not built for the use_global branch")
             if stop_at is not None:
                 raise NotImplementedError("stop_at is not built for the use_global branch")
             return self._ddim_overlapping_global(x, x_cond, list(seq), model, b, corners, p_size, total, eta=eta)
@@ -325,13 +337,14 @@ class DenoisingDiffusion_Wavelet(object):
             x_other = None                                                      # ddm_wavelet.py:471-473: the UNet sees [x_cond | x_t] only
         if not self.config.data.begin_from_noise:                              # ddm_wavelet.py:445-447
             a = (1 - b).cumprod(dim=0)[self.num_timesteps - 1]
-            x = x_cond[:, :x.shape[1]] * a.sqrt() + x * (1.0 - a).sqrt()
+            xc = x_cond[:, :x.shape[1]]
+            x = (xc if samples == 1 else xc.repeat_interleave(samples, dim=0)) * a.sqrt() + x * (1.0 - a).sqrt()
         grp = getattr(self, "patch_group", None)
         if grp is not None:                                                    # patch-sharded latency mode: identical start noise on every rank
             import torch.distributed as dist
             dist.broadcast(x, src=0, group=None if grp is True else grp)
         xs, x0_preds = sampling.ddim_sample(model, x, x_cond, x_other, list(seq), b, corners=corners, p_size=p_size,
-                                            max_batch=getattr(self.args, "max_batch", None) or sampling.DEFAULT_MAX_BATCH, patch_group=grp, eta=eta, stop_at=stop_at)
+                                            max_batch=getattr(self.args, "max_batch", None) or sampling.DEFAULT_MAX_BATCH, patch_group=grp, eta=eta, stop_at=stop_at, samples=samples)
         if self.verbose:
             for i_t, x0, xn in zip(reversed(list(seq)), x0_preds, xs[1:]):
                 if x0 is None:

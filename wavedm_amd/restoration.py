@@ -70,6 +70,33 @@ def file_seed(seed, name):
     return ((int(seed) & 0x7FFFFFFF) << 32) | zlib.crc32(name.encode("utf-8"))
 
 
+def sample_seed(seed, name, k):
+    """The seed of sample k of one file's `args.samples` start noises in restore_folder.  k = 0 is file_seed(seed, name): sample 0 is the single-sample
+    restoration.  k >= 1 takes the CRC-32 of name + NUL + str(k) instead of the name's (NUL cannot occur in a file name, so no other file's name collides
+    with it).  63 bits, like file_seed."""
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"sample_seed: sample {k}")
+    if k == 0:
+        return file_seed(seed, name)
+    return ((int(seed) & 0x7FFFFFFF) << 32) | zlib.crc32((name + "\0" + str(k)).encode("utf-8"))
+
+
+def std_output_name(name):
+    """Input name -> the name of its spread map (args.save_std): <stem>_std.png beside <stem>.png."""
+    return os.path.splitext(name)[0] + "_std.png"
+
+
+def check_std_names(names):
+    """args.save_std writes <stem>_std.png beside every <stem>.png: an input whose own output has that name (a_std.jpg beside a.png) is a ValueError that names
+    both, before anything runs -- like two inputs with one output (datasets.output_names)."""
+    outs = {os.path.splitext(n)[0] + ".png": n for n in names}
+    for n in names:
+        o = std_output_name(n)
+        if o in outs:
+            raise ValueError(f"restore_folder: the spread map of {n!r} and the output of {outs[o]!r} would both be written to {o!r} (--save-std)")
+
+
 _WS_BYTES = {}      # (kind, config bytes, B[, H, W]) -> workspace bytes the library asks for (host computations, a few hundred distinct keys at most)
 
 
@@ -96,9 +123,13 @@ def _workspace_bytes(kind, cfg, *dims, local=None):
     return _WS_BYTES[key]
 
 
-def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None):
+def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None, samples=1):
     """The terms of estimate_restore_bytes, by name.  `hfrm_local`: what DenoisingDiffusion_Wavelet.hfrm_local holds -- None, or (base_size, train_size)
-    of the HFRM's local pooling, whose workspace is larger."""
+    of the HFRM's local pooling, whose workspace is larger.  `samples`: trajectories per image (args.samples) -- the sampler's state (start noise, the kept
+    x_t and x0, eps, the gathered UNet input's rows) is held per sample, the conditioning and the HFRM per image."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError(f"restore_terms: samples = {samples} (at least 1)")
     from .arch import HFRM
     from .ddm_wavelet import DenoisingDiffusion_Wavelet
     from .procedural import unet_in_channels
@@ -110,13 +141,13 @@ def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps
     elsize = 2 if code in (_lib.WDM_BF16, _lib.WDM_F16) else 4
     hp, wp = imageio.padded_size(h, w, 16, 4 * p)
     hl, wl = sampling.overlapping_grid_indices(hp // 4, wp // 4, p, r)
-    n = n_img * len(hl) * len(wl)
+    n = n_img * samples * len(hl) * len(wl)
     split = pc < int(m.in_channels)
     n_other = int(m.in_channels) - int(m.other_channels_begin) if (split and m.use_other_channels) else 0
     px, px16 = hp * wp, (hp // 4) * (wp // 4)
     # f32 tensors of the group's size: x, x_cond (48 bands at 1/16 = 3 planes), the output; with an HFRM its image and bands; x_other; the sampler's lists
     # (start noise, x_t and x0 of every step: sample_image keeps them); the 8-bit input and output
-    full = n_img * (4 * (px * (3 + 3 + 3 + (6 if split else 0)) + px16 * (n_other + pc * (2 * int(steps) + 1))) + 2 * 3 * int(h) * int(w))
+    full = n_img * (4 * (px * (3 + 3 + 3 + (6 if split else 0)) + px16 * (n_other + samples * pc * (2 * int(steps) + 1))) + 2 * 3 * int(h) * int(w))
     hfrm = 0
     if split:
         # the HFRM runs min(n_img, MAX_PIXELS / (hp wp)) images per call (arch.HFRM.forward); its workspace grows with the pixels of a call, so one image's
@@ -136,12 +167,12 @@ def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps
     return dict(x96=n * p * p * cin * elsize, eps=n * pc * p * p * 4, full=full, hfrm=hfrm, unet=unet)
 
 
-def estimate_restore_bytes(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None):
+def estimate_restore_bytes(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None, samples=1):
     """Device bytes one sampler call of restore_folder needs for `n_img` images of h x w pixels -- host arithmetic, nothing is allocated: the gathered UNet
     input (n patches x p x p x cin in the compute type), eps (n x pc x p x p f32), the f32 tensors of the group's padded size, the HFRM's workspace and the
     UNet's for the largest call.  `r`: the patch grid's stride (default 16), `steps`: the DDIM steps, `hfrm_local`: the HFRM's local-pooling mode (restore_terms).
-    Non-decreasing in h, w and n_img."""
-    return sum(restore_terms(h, w, n_img, config, max_batch, dtype, r, steps, hfrm_local).values())
+    `samples`: trajectories per image (restore_terms).  Non-decreasing in h, w, n_img and samples."""
+    return sum(restore_terms(h, w, n_img, config, max_batch, dtype, r, steps, hfrm_local, samples).values())
 
 
 def folder_patch_count(h, w, p, r=None):
@@ -174,13 +205,14 @@ def estimate_restore_bytes_mixed(sizes, config, max_batch=None, dtype=None, r=No
 MIX_MAX_IMAGES = 64      # images per sampler call of the automatic mixed-size grouping, at most
 
 
-def mix_group_step(counts, nxt, max_batch, images_per_call=None):
+def mix_group_step(counts, nxt, max_batch, images_per_call=None, samples=1):
     """The grouping rule of args.mix_sizes, host arithmetic: the open group holds images of `counts` patches each (input order), the next image has `nxt`.
     -> (before, after): close the open group BEFORE the image joins (it then opens a new one), close the group AFTER it joined.
     images_per_call = N: N images per call whatever their sizes.  Automatic (None, 0, "auto"): a group is closed when the next image would push its patches
     over max_batch -- one UNet call per step carries the whole group --, and at MIX_MAX_IMAGES images; an image of more than max_batch patches is a group of
-    its own.  (The feeder adds today's rule on top: with automatic grouping, what is there goes at once while the sampler waits for input.)"""
-    counts, nxt, mb = list(counts), int(nxt), int(max_batch)
+    its own.  (The feeder adds today's rule on top: with automatic grouping, what is there goes at once while the sampler waits for input.)
+    samples: every image counts as that many rows of its patches."""
+    counts, nxt, mb = [int(c) * int(samples) for c in counts], int(nxt) * int(samples), int(max_batch)
     if images_per_call not in (None, 0, "auto", "Auto", "AUTO"):
         return False, len(counts) + 1 >= max(1, int(images_per_call))
     if nxt > mb:
@@ -232,29 +264,48 @@ class DiffusiveRestoration:
         self.diffusion = diffusion
         self.save_images = save_images
         self.writer = None
+        self._samples, self._save_std = 1, False
         if os.path.isfile(getattr(args, "resume", "") or ""):
             self.diffusion.model.eval()                                        # restoration.py:23-25
         else:
             print("Pre-trained diffusion model path is missing!")
+
+    def _ensemble_args(self, what, mix=False):
+        """args.samples (default 1), args.save_std, args.std_gain (default 8.0), checked before anything runs."""
+        n = getattr(self.args, "samples", None)
+        n = 1 if n is None else int(n)
+        save_std = bool(getattr(self.args, "save_std", False))
+        if n < 1:
+            raise ValueError(f"{what}: --samples {n} (args.samples: at least 1)")
+        if n > 256:
+            raise ValueError(f"{what}: --samples {n} (args.samples: at most 256, the reduction kernel's limit)")
+        if n > 1 and mix:
+            raise ValueError(f"{what}: --samples {n} with --mix-sizes (args.samples > 1 with args.mix_sizes): the ragged layout draws one sample per image")
+        if n > 1 and getattr(self.diffusion, "patch_group", None) is not None:
+            raise ValueError(f"{what}: --samples {n} (args.samples > 1) is not built for the patch-sharded mode (patch_group)")
+        if save_std and n == 1:
+            raise ValueError(f"{what}: --save-std (args.save_std) needs --samples >= 2 (args.samples): the spread of one sample is undefined")
+        gain = getattr(self.args, "std_gain", None)
+        self._samples, self._save_std, self._std_gain = n, save_std, 8.0 if gain is None else float(gain)
 
     # ---- grouping ---------------------------------------------------------------------------------------------------
     def _max_batch(self):
         mb = getattr(self.diffusion.args, "max_batch", None) or getattr(self.args, "max_batch", None)
         return int(mb) if mb else sampling.DEFAULT_MAX_BATCH
 
-    def images_per_call_for(self, h, w, r=None):
+    def images_per_call_for(self, h, w, r=None, samples=1):
         """How many loader items of wavelet-domain size h x w go into one sampler call: `args.images_per_call` when it is a number; otherwise ("auto", None, 0)
         the smallest count (up to 16) whose patches fill the UNet calls to >= 97 %, else the best-filling one.  A UNet call works in units of 64 patches -- every
         level's launch then holds whole rounds of workgroups on the 256 CUs (64 patches = 256 tiles of a 16x16 or 32x32 map, 512 of a 64x64 map or an 8x8 map's
         two-image tiles) --, and the sampler splits n patches into ceil(n / max_batch) equal calls (sampling.ddim_sample).  45 patches per 480x720 image under the
         default cap of 384: 7 images = 315 patches = one call, 98 % of five units (profiles/r06_restore_sweep.log: 8 x 45 = 360 in calls of 120 6.32 img/s,
-        in one call 6.47; a call of 144 = 2.25 units 5.70)."""
+        in one call 6.47; a call of 144 = 2.25 units 5.70).  `samples`: an image counts as that many rows of its patches; a group holds at least one image."""
         v = getattr(self.args, "images_per_call", None)
         if v not in (None, 0, "auto", "Auto", "AUTO"):
             return max(1, int(v))
         p_size = self.config.data.patch_size if self.config.data.wavelet_in_unet else self.config.data.image_size
         hl, wl = sampling.overlapping_grid_indices(h, w, p_size, r)
-        P, mb = len(hl) * len(wl), self._max_batch()
+        P, mb = len(hl) * len(wl) * max(1, int(samples)), self._max_batch()
 
         def fill(n_img):
             n = n_img * P
@@ -309,7 +360,7 @@ class DiffusiveRestoration:
                         emit(group)
                         group = []
                     if not group:
-                        limit = self.images_per_call_for(item[0].shape[-2] // 4, item[0].shape[-1] // 4, r)
+                        limit = self.images_per_call_for(item[0].shape[-2] // 4, item[0].shape[-1] // 4, r, samples=self._samples)
                     group.append(item)
                     # full -- or, with automatic grouping, the sampler is WAITING for input (the start of a run, a loader slower than the GPU): what is there goes
                     # at once, the GPU starts on image 1 while the loader still decodes image 2 (per-image results do not depend on the grouping)
@@ -365,9 +416,14 @@ class DiffusiveRestoration:
                 w.save(inp[sl], os.path.join(image_folder, f"{name}_cond.png"))
                 w.save(gt[sl], os.path.join(image_folder, f"{name}_gt.png"))
         xs, x0_preds = self.diffusive_restoration(x_cond, x_other=x_other, r=r, last=False, total=None,
-                                                  use_global=False, use_other=use_other, stop_at=-5 if early else None)
+                                                  use_global=False, use_other=use_other, stop_at=-5 if early else None, **({"samples": self._samples} if self._samples != 1 else {}))
         pred = x0_preds[-5]                                                    # :108
-        x_output = rec(pred, hf_wav if split else pred)                        # :114-115, :124, :134 (all bands diffused: the second source contributes nothing)
+        x_std = None
+        if self._samples == 1:
+            x_output = rec(pred, hf_wav if split else pred)                    # :114-115, :124, :134 (all bands diffused: the second source contributes nothing)
+        else:
+            # args.samples: the mean of the samples' coefficients stands where the one sample's stood -- for the output and for the diagnostic images below
+            x_output, x_std, pred = d.wavelet_rec.compose_ensemble(pred, hf_wav if split else None, pc, self._samples, want_std=self._save_std, want_coef=True)
         H, W = x_output.shape[-2:]
         # the three pairs the reference prints: output, "cond" (IDWT(DWT(x)) == x: the input), HFRM image (restoration.py:146 clamps x_output_wdnet first)
         self._mark("main: sampler queued")
@@ -386,9 +442,11 @@ class DiffusiveRestoration:
             for k, name in enumerate(names):
                 sl = slice(k, k + 1)
                 w.save(x_output[sl], os.path.join(image_folder, f"{name}_output.png"))
+                if x_std is not None:
+                    w.save((x_std[sl] * self._std_gain).clamp_(0.0, 1.0), os.path.join(image_folder, f"{name}_std.png"))
                 if use_other:
                     w.save(rec(pred[sl], x_gt[sl]), os.path.join(image_folder, f"{name}_lrdiff_hrgt.png"))     # :112-113
-        return dict(names=names, out=x_output, sums=sums_host, done=done, HW=(H, W), keep=(pinned, sums))
+        return dict(names=names, out=x_output, std=x_std, sums=sums_host, done=done, HW=(H, W), keep=(pinned, sums))
 
     def _finish_group(self, g, acc):
         """Wait for a queued group's metric sums and print what the reference prints per image."""
@@ -407,6 +465,8 @@ class DiffusiveRestoration:
                 acc["wdnet"].append(m_hf[k][1])
             print("psnr this", m_out[k][0])
             print("psnr cond", m_cond[k][0])
+        if g.get("std") is not None:
+            acc["std"] += [g["std"][k:k + 1] for k in range(len(g["names"]))]
         return [g["out"][k:k + 1] for k in range(len(g["names"]))]
 
     def restore(self, val_loader, validation="snow", r=None):
@@ -417,6 +477,7 @@ class DiffusiveRestoration:
             raise NotImplementedError("DiffusiveRestoration.restore: only the data.wavelet / not data.wavelet_in_unet branch (raindrop_wavelet.yml) is accelerated")
         if cfg.model.pred_channels > cfg.model.in_channels:
             raise ValueError(f"model.pred_channels {cfg.model.pred_channels} exceeds the {cfg.model.in_channels} wavelet bands (model.in_channels)")
+        self._ensemble_args("restore")
         image_folder = os.path.join(self.args.image_folder, cfg.data.dataset, validation)
         if os.environ.get("WAVEDM_RESTORE_TRACE", "0") == "1":
             import time
@@ -424,7 +485,7 @@ class DiffusiveRestoration:
         if self.save_images and self.writer is None:
             self.writer = imageio.AsyncImageWriter()
         self._ssim = bool(getattr(self.args, "ssim", False))
-        acc = {"torch": [], "y": [], "wdnet": [], "ssim": []}
+        acc = {"torch": [], "y": [], "wdnet": [], "ssim": [], "std": []}
         outputs, pending = [], None
         # groups staged ahead of the sampler: bounded by BYTES (args.prefetch_bytes, default 2 GB of device + pinned memory each), not by count -- a short
         # validation set is read to its end at once, which also lets a fork-based DataLoader's worker processes exit early (see _StageBudget)
@@ -474,6 +535,7 @@ class DiffusiveRestoration:
                 print("ssim all", float(np.mean(acc["ssim"])))
         self.last_outputs, self.last_psnrs, self.last_psnrs_y = outputs, acc["torch"], acc["y"]
         self.last_ssims_y = acc["ssim"] if self._ssim else None
+        self.last_stds = acc["std"]                                             # args.save_std: the f32 (1,3,H,W) spread maps, in loader order
         return outputs, acc["torch"]
 
     # ---- photographs at their own size, without ground truth -----------------------------------------
@@ -553,7 +615,7 @@ class DiffusiveRestoration:
                     group = []
                 if not group:
                     hp, wp = imageio.padded_size(img.shape[0], img.shape[1], 16, p4)
-                    limit = self.images_per_call_for(hp // 4, wp // 4, r)
+                    limit = self.images_per_call_for(hp // 4, wp // 4, r, samples=self._samples)
                 group.append((img, name))
                 if len(group) >= limit or (auto and hungry.is_set()):
                     emit(group)
@@ -570,7 +632,7 @@ class DiffusiveRestoration:
         (what torch's allocator holds without using counts as free: it is handed out again)."""
         dev = self.diffusion.device
         est = estimate_restore_bytes(H, W, n, self.config, self._max_batch(), self.diffusion.model.dtype_name, r, int(self.diffusion.args.sampling_timesteps),
-                                     hfrm_local=getattr(self.diffusion, "hfrm_local", None))
+                                     hfrm_local=getattr(self.diffusion, "hfrm_local", None), samples=self._samples)
         limit = getattr(self.args, "max_restore_bytes", None)
         if not limit:
             limit = 0.8 * (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
@@ -594,24 +656,34 @@ class DiffusiveRestoration:
                 x_other = hf_wav[:, ob:].contiguous()
         seed = getattr(self.args, "seed", None)
         seed = 61 if seed is None else seed
-        noise = torch.cat([torch.randn((1, pc, Hp // 4, Wp // 4), device=dev, generator=torch.Generator(device=dev).manual_seed(file_seed(seed, name)))
-                           for name in names], dim=0)
+        N = self._samples
+        noise = torch.cat([torch.randn((1, pc, Hp // 4, Wp // 4), device=dev, generator=torch.Generator(device=dev).manual_seed(sample_seed(seed, name, k)))
+                           for name in names for k in range(N)], dim=0)
         h_list, w_list = sampling.overlapping_grid_indices(Hp // 4, Wp // 4, p, r)
         corners = [(i, j) for i in h_list for j in w_list]
         early = bool(getattr(self.args, "early_stop", True))
         xs, x0_preds = d.sample_image(x_cond, noise, x_other=x_other, last=False, patch_locs=corners, patch_size=p, total=None,
-                                      use_global=False, use_other=use_other, stop_at=-5 if early else None)
+                                      use_global=False, use_other=use_other, stop_at=-5 if early else None, **({"samples": N} if N != 1 else {}))
         pred = x0_preds[-5]
-        out = d.wavelet_rec.compose(pred, hf_wav if split else pred, pc)
+        std = s8 = None
+        if N == 1:
+            out = d.wavelet_rec.compose(pred, hf_wav if split else pred, pc)
+        else:                                                                  # the mean of the N samples' coefficients -> one image; their per-pixel spread
+            out, std, _ = d.wavelet_rec.compose_ensemble(pred, hf_wav if split else None, pc, N, want_std=self._save_std)
         self._mark("main: sampler queued")
         q8 = imageio.to_u8_hwc(out, crop=(H, W))
+        if std is not None:
+            s8 = imageio.to_u8_hwc((std * self._std_gain).clamp_(0.0, 1.0), crop=(H, W))
         for k, name in enumerate(names):
             if out_paths[name] is not None:
                 self.writer.save_u8(q8[k], out_paths[name])
+                if s8 is not None:
+                    self.writer.save_u8(s8[k], os.path.join(os.path.dirname(out_paths[name]), os.path.basename(std_output_name(name))))
         kept = [out[k:k + 1, :, :H, :W].clone() for k in range(n)] if keep_outputs else []
+        kept_std = [std[k:k + 1, :, :H, :W].clone() for k in range(n)] if (keep_outputs and std is not None) else []
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
-        return dict(names=names, done=done, HW=(H, W), patches=len(corners), kept=kept, keep=(u8, q8))
+        return dict(names=names, done=done, HW=(H, W), patches=len(corners), kept=kept, kept_std=kept_std, keep=(u8, q8, s8))
 
     def _fits_mixed(self, shapes, r):
         """_fits for one sampler call over photographs of different sizes (estimate_restore_bytes_mixed)."""
@@ -709,10 +781,13 @@ class DiffusiveRestoration:
             raise ValueError(f"model.pred_channels {cfg.model.pred_channels} exceeds the {cfg.model.in_channels} wavelet bands (model.in_channels)")
         if int(d.args.sampling_timesteps) < 5:
             raise IndexError("x0_preds[-5] needs at least 5 sampling steps (restoration.py:108)")
+        self._ensemble_args("restore_folder", mix=bool(getattr(self.args, "mix_sizes", False)))
         items = datasets.ImageFolder(src, recursive=recursive) if isinstance(src, (str, os.PathLike)) else src
         listed = getattr(getattr(items, "dataset", items), "names", None)
         if listed is not None:
             datasets.output_names(listed)                                       # two inputs, one output: refused before anything runs
+            if self._save_std:
+                check_std_names(listed)                                         # ... and an input whose output is another's spread map
         write = dst is not None and self.save_images
         if os.environ.get("WAVEDM_RESTORE_TRACE", "0") == "1":
             import time
@@ -722,6 +797,7 @@ class DiffusiveRestoration:
         results, outputs, taken, pending = [], [], {}, []
         self.last_info = []
         self.last_calls = []                                                    # one tuple of names per sampler call, in order
+        stds = []
 
         def finish(g):
             g["done"].synchronize()
@@ -731,6 +807,7 @@ class DiffusiveRestoration:
                 print(f"{name}: {HW[1]}x{HW[0]}, {patches} patches")
                 self.last_info.append((name, HW, patches))
             outputs.extend(g["kept"])
+            stds.extend(g.get("kept_std", ()))
 
         q, stop = queue.Queue(), threading.Event()
         budget = _StageBudget(int(getattr(self.args, "prefetch_bytes", 2 << 30)), stop)
@@ -759,6 +836,11 @@ class DiffusiveRestoration:
                         if o in taken:
                             raise ValueError(f"restore_folder: {taken[o]!r} and {name!r} would both be written to {o!r}")
                         taken[o] = name
+                        if self._save_std:                                     # (an iterable without a list of names: the same rule, as the files come)
+                            so = std_output_name(name)
+                            if so in taken:
+                                raise ValueError(f"restore_folder: the spread map of {name!r} and the output of {taken[so]!r} would both be written to {so!r} (--save-std)")
+                            taken[so] = name
                         out_paths[name] = os.path.join(dst, *o.split("/")) if write else None
                         results.append((name, out_paths[name]))
                     cur = torch.cuda.current_stream(d.device)
@@ -782,7 +864,8 @@ class DiffusiveRestoration:
                             H, W = shape(lo)
                             ok, est, limit = self._fits(H, W, 1, r)
                             if not ok:
-                                raise RuntimeError(f"restore_folder: {names[lo]!r} ({W}x{H}) needs an estimated {est} bytes of device memory, "
+                                raise RuntimeError(f"restore_folder: {names[lo]!r} ({W}x{H})" + (f" with its {self._samples} samples" if self._samples > 1 else "") +
+                                                   f" needs an estimated {est} bytes of device memory, "
                                                    f"{int(limit)} are available (args.max_restore_bytes, else 0.8 of the free memory)")
                         self.last_calls.append(tuple(names[lo:hi]))
                         if shapes is None:
@@ -804,18 +887,20 @@ class DiffusiveRestoration:
         if self.writer is not None:
             self.writer.flush()
         self.last_outputs = outputs
+        self.last_stds = stds                                                   # keep_outputs with args.save_std: the cropped f32 (1,3,H,W) spread maps
         return results
 
-    def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None):
+    def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None, samples=1):
         """restoration.py:170-185.  The start noise is drawn image by image (the reference sees one image per call), so a
-        batched call consumes the generator exactly like the same images restored one after the other.  `stop_at`: see sample_image."""
+        batched call consumes the generator exactly like the same images restored one after the other.  `stop_at`: see sample_image.
+        `samples`: one draw per (image, sample), image-major -- image 0's samples, then image 1's --, from the same generator."""
         p_size = self.config.data.patch_size if self.config.data.wavelet_in_unet else self.config.data.image_size
         h_list, w_list = self.overlapping_grid_indices(x_cond, output_size=p_size, r=r)
         corners = [(i, j) for i in h_list for j in w_list]
         shp = (1, self.config.model.pred_channels, x_cond.shape[2], x_cond.shape[3])
-        x = torch.cat([torch.randn(shp, device=self.diffusion.device) for _ in range(x_cond.shape[0])], dim=0)
+        x = torch.cat([torch.randn(shp, device=self.diffusion.device) for _ in range(x_cond.shape[0] * int(samples))], dim=0)
         return self.diffusion.sample_image(x_cond, x, x_other=x_other, last=last, patch_locs=corners, patch_size=p_size,
-                                           total=total, use_global=use_global, use_other=use_other, stop_at=stop_at)
+                                           total=total, use_global=use_global, use_other=use_other, stop_at=stop_at, **({"samples": int(samples)} if int(samples) != 1 else {}))
 
     def overlapping_grid_indices(self, x_cond, output_size, r=None):
         """restoration.py:187-196."""

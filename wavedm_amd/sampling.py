@@ -324,7 +324,7 @@ def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=6
 
 
 def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None, max_batch=64, keep="all", stop_at=None,
-                patch_group=None, streams=None, eta=0.0):
+                patch_group=None, streams=None, eta=0.0, samples=1):
     """DDIM over `seq` (ascending list of timesteps) for NIMG images; eta = 0 (what every caller in the reference passes) is the deterministic sampler.
 
     x (NIMG,pc,H,W) start noise, x_cond (NIMG,48,H,W), x_other (NIMG,48 - other_channels_begin,H,W) or None: fp32 on the GPU.  pc = model.pred_channels is
@@ -352,7 +352,19 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
           and ONE all-reduce(sum) per step (RCCL) combines partial sums and overlap counts before the DDIM update, which every
           rank then applies identically.  All ranks must pass the same x / x_cond / x_other.  The fp32 sum order differs from
           the sequential scatter by at most the association of the per-rank partial sums.
+    samples: N trajectories per image in ONE call: x has NIMG = B * N rows, x_cond and x_other B; sample k of image i is row i * N + k and is
+          conditioned on image i.  The step-invariant channels of the UNet input are gathered once, through a second patch list whose image index is
+          row // N (the same wdm_pack_channels, nothing replicated); everything else runs on the B * N rows as for any batch, so row i * N + k holds the bits
+          of a plain call on `repeat_interleave`d conditioning.  Not with patch_group.  samples = 1 is the plain call, launch for launch.
     """
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError(f"ddim_sample: samples = {samples} (at least 1)")
+    if samples > 1 and patch_group is not None:
+        raise ValueError("ddim_sample: samples > 1 is not built for the patch-sharded mode (patch_group)")
+    if x.shape[0] != samples * x_cond.shape[0] or (samples > 1 and x_other is not None and x_other.shape[0] != x_cond.shape[0]):
+        raise ValueError(f"ddim_sample: x has {x.shape[0]} rows, x_cond {x_cond.shape[0]}" + (f", x_other {x_other.shape[0]}" if x_other is not None else "") +
+                         f": x.shape[0] must be samples * x_cond.shape[0] (samples = {samples})")
     x = _lib.require_cuda_f32(x, "x")
     x_cond = _lib.require_cuda_f32(x_cond, "x_cond")
     if x_other is not None:
@@ -372,6 +384,7 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
             p = H
             assert H == W == unet.resolution
             n, patches, pptr = nimg, None, None
+            tri = None
         else:
             p = int(p_size)
             if all(len(c) == 2 for c in corners):
@@ -391,6 +404,12 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
             n = len(tri)
             patches = _device_const(dev, "patches", tuple(tri) if tri else ((0, 0, 0),), torch.int32)
             pptr = _lib.ptr(patches)
+        # the conditioning's patch list: the same windows, of image row // samples (samples = 1: the list above itself)
+        cpatches, cptr = patches, pptr
+        if samples > 1:
+            ctri = tuple((im // samples, hi, wi) for (im, hi, wi) in tri) if tri is not None else tuple((im // samples, 0, 0) for im in range(nimg))
+            cpatches = _device_const(dev, "patches", ctri, torch.int32)
+            cptr = _lib.ptr(cpatches)
         assert p == unet.resolution, "patch size must equal config.data.image_size (unet.py:351)"
         sharded = corners is not None and patch_group is not None
         if patch_group is not None and corners is None:
@@ -417,9 +436,9 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
             st = _lib.stream_ptr()
             x96 = torch.empty(max(n, 1), p, p, cin, device=dev, dtype=unet._torch_dtype)
             if n:
-                _lib.check(L.wdm_pack_channels(h, _lib.ptr(x_cond), ncond, H, W, pptr, n, p, _lib.ptr(x96), cin, 0, unet._dtype_code, st))
+                _lib.check(L.wdm_pack_channels(h, _lib.ptr(x_cond), ncond, H, W, cptr, n, p, _lib.ptr(x96), cin, 0, unet._dtype_code, st))
                 if nother:
-                    _lib.check(L.wdm_pack_channels(h, _lib.ptr(x_other), nother, H, W, pptr, n, p, _lib.ptr(x96), cin, ncond + pc, unet._dtype_code, st))
+                    _lib.check(L.wdm_pack_channels(h, _lib.ptr(x_other), nother, H, W, cptr, n, p, _lib.ptr(x96), cin, ncond + pc, unet._dtype_code, st))
             eps = torch.empty(max(n, 1), pc, p, p, device=dev, dtype=torch.float32)
             acc_cnt = torch.empty(2 * x.numel(), device=dev, dtype=torch.float32) if sharded else None
             # the timestep-dependent part of the UNet (embedding MLP, every temb_proj) for the WHOLE sequence at once: four launches per run instead of per step
@@ -511,8 +530,8 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
             # sequence, the patch list, the call size, what is kept, the schedule's bytes (cached per betas tensor: no read-back per call), the temb-table switch
             xs, x0_preds = _replay_graph(unet, run_loop, x, x_cond, x_other, n_run,
                                          (tuple(seq), None if corners is None else tuple(map(tuple, tri)), p, max_batch, call_b, keep_set, n_run, _betas_entry(betas)[1],
-                                          os.environ.get("WAVEDM_TEMB_TABLE", "1"), str(x_cond.dtype), None if x_other is None else str(x_other.dtype)),
-                                         keepalive=(patches, t_dev))
+                                          os.environ.get("WAVEDM_TEMB_TABLE", "1"), str(x_cond.dtype), None if x_other is None else str(x_other.dtype), samples),
+                                         keepalive=(patches, cpatches, t_dev))
         else:
             xs, x0_preds = run_loop(x, x_cond, x_other, n_run, multi)
         if keep != "all":

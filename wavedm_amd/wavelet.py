@@ -73,6 +73,34 @@ class WaveletTransform(nn.Module):
                                                           B, hh, ww, 1 if to_unit_range else 0, _lib.stream_ptr()))
         return y
 
+    def compose_ensemble(self, preds, hi, n_lo, samples, want_std=False, want_coef=False, to_unit_range=True):
+        """rec only: `samples` diffusion samples per image -> (mean image, std map or None, mean coefficients or None) in one kernel (include/wavedm.h:
+        wdm_ensemble_compose).  preds (B * samples, C >= n_lo, h, w), sample k of image i in row i * samples + k; hi (B, 48, h, w), or None when n_lo == 48.
+        The mean coefficient is (((p_0 + p_1) + ...) / samples in fp32; the mean image is compose(mean, hi, n_lo) -- with samples == 1 its bits --; the std map
+        is the unbiased standard deviation of the UNCLAMPED pixel over the samples (want_std needs samples >= 2)."""
+        assert not self.dec
+        preds = _lib.require_cuda_f32(preds, "WaveletTransform preds")
+        if hi is not None:
+            hi = _lib.require_cuda_f32(hi, "WaveletTransform hi")
+        samples, n_lo = int(samples), int(n_lo)
+        if preds.dim() != 4 or samples < 1 or preds.shape[0] % samples:
+            raise ValueError(f"WaveletTransform.compose_ensemble: preds {tuple(preds.shape)} do not hold whole groups of samples = {samples}")
+        B, (hh, ww) = preds.shape[0] // samples, preds.shape[2:]
+        if hi is not None and tuple(hi.shape) != (B, 48, hh, ww):
+            raise ValueError(f"WaveletTransform.compose_ensemble: preds {tuple(preds.shape)} / hi {tuple(hi.shape)} / samples {samples}")
+        if want_std and samples < 2:
+            raise ValueError("WaveletTransform.compose_ensemble: want_std needs samples >= 2 (the spread of one sample is undefined)")
+        dev = preds.device
+        mean = torch.empty(B, 3, hh * 4, ww * 4, device=dev, dtype=torch.float32)
+        std = torch.empty_like(mean) if want_std else None
+        coef = torch.empty(B, n_lo, hh, ww, device=dev, dtype=torch.float32) if want_coef else None
+        if B:
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().wdm_ensemble_compose(_lib.handle(dev.index or 0), _lib.ptr(preds), preds.shape[1], n_lo, samples,
+                                                           None if hi is None else _lib.ptr(hi), _lib.ptr(mean), None if std is None else _lib.ptr(std),
+                                                           None if coef is None else _lib.ptr(coef), B, hh, ww, 1 if to_unit_range else 0, _lib.stream_ptr()))
+        return mean, std, coef
+
     def forward(self, x):
         x = _lib.require_cuda_f32(x, "WaveletTransform input")
         L, h = _lib.lib(), _lib.handle(x.device.index or 0)
