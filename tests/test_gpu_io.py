@@ -2,6 +2,7 @@
 asynchronous PNG writes, several images per sampler call, and the loader -> restore pipeline end to end."""
 import os
 import random
+import threading
 from types import SimpleNamespace
 
 import numpy as np
@@ -128,6 +129,7 @@ def test_restore_surfaces_loader_errors_and_short_schedules(tmp_path):
     rest = wavedm_amd.DiffusiveRestoration(d, args, d.config, save_images=False)
     with pytest.raises(OSError, match="truncated PNG"):
         rest.restore(bad_loader(), validation="raindrop", r=4)
+    assert not any(t.name == "wavedm-restore-feeder" for t in threading.enumerate())      # stopped and joined before the error left restore()
     assert rest.restore([], validation="raindrop", r=4) == ([], [])                      # an empty loader: nothing queued, nothing printed
     # a loader batch of several images, 5-D as a parse_patches loader yields them (restoration.py:72 flattens): split into images, the items keep their order
     g = torch.Generator().manual_seed(8)

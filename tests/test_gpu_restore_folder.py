@@ -3,6 +3,7 @@ DiffusiveRestoration.restore_folder against the public pieces it is made of.  Ev
 import os
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -239,6 +240,7 @@ def test_memory_budget_falls_back_to_one_image_per_call_then_refuses(model, tmp_
     with pytest.raises(RuntimeError, match=rf"a\.png.*93x70.*{est(1)} bytes"):
         _run(rest, src, tmp_path / "none")
     assert batches == [] and not (tmp_path / "none").exists()
+    assert not any(t.name == "wavedm-restore-feeder" for t in threading.enumerate())      # an error of the main thread's: the feeder is stopped and joined all the same
 
 
 def test_restore_folder_refusals(model, tmp_path, monkeypatch):
@@ -268,6 +270,7 @@ def test_restore_folder_refusals(model, tmp_path, monkeypatch):
     (src / "b.png").write_bytes(whole[:len(whole) // 2])
     with pytest.raises(OSError, match=r"b\.png"):
         _run(_restorer(model), src, tmp_path / "o5")
+    assert not any(t.name == "wavedm-restore-feeder" for t in threading.enumerate())
 
 
 def test_cli_restore_and_eval(tmp_path):

@@ -111,6 +111,51 @@ def test_grouping_rule():
     assert counts == [8, 45]
 
 
+def _same_size_groups(shapes, limit):
+    """The feeder's loop over _same_size_group_step, without its threads; an empty group would show up as such."""
+    groups, cur = [], []
+    for s in shapes:
+        before, after = restoration._same_size_group_step(cur, s, limit(s) if callable(limit) else limit)
+        if before:
+            groups.append(cur)
+            cur = []
+        cur = cur + [s]
+        if after:
+            groups.append(cur)
+            cur = []
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def test_same_size_grouping_rule():
+    big, odd = (1, 6, 96, 112), (1, 6, 64, 80)
+    step = restoration._same_size_group_step
+    # a different shape closes the open group before the image joins; nothing is open: nothing to close
+    assert step([big, big], odd, 8) == (True, False) and step([big, big], big, 8) == (False, False) and step([], odd, 8) == (False, False)
+    # the limit-th image closes its group after it joined -- also when it has just opened the group
+    assert step([big] * 6, big, 8) == (False, False) and step([big] * 7, big, 8) == (False, True)
+    assert step([], big, 1) == (False, True) and step([big], odd, 1) == (True, True) and step([big], odd, 2) == (True, False)
+    assert step([], big, 0) == (False, True)                                     # a group holds at least one image
+    # the sequence of tests/test_gpu_io.py: seven 96x112 images, one 64x80 inserted at index 4, limit 8 -> 4, 1, 3
+    seq = [big] * 7
+    seq.insert(4, odd)
+    assert _same_size_groups(seq, 8) == [[big] * 4, [odd], [big] * 3]
+    assert [len(g) for g in _same_size_groups(seq, 2)] == [2, 2, 1, 2, 1] and [len(g) for g in _same_size_groups(seq, 1)] == [1] * 8
+    # a limit per size (images_per_call_for of the item's own size): the item's limit is its group's
+    assert [len(g) for g in _same_size_groups(seq, lambda s: 3 if s == big else 1)] == [3, 1, 1, 3]
+    # never an empty group, every image exactly once and in order, whatever the shapes and the limit
+    for limit in (1, 2, 3, 8):
+        for shapes in ([], [big], [odd, big], seq, [big, odd] * 4, [odd] * 9):
+            groups = _same_size_groups(shapes, limit)
+            assert all(groups) and [s for g in groups for s in g] == shapes
+            assert all(len(set(g)) == 1 and len(g) <= limit for g in groups)
+    # a pure function: the inputs are not changed; lists compare like tuples (torch.Size is a tuple)
+    open_ = [big, big]
+    step(open_, odd, 8)
+    assert open_ == [big, big] and step([list(big)], big, 8) == (False, False)
+
+
 def test_folder_patch_count_is_the_padded_grid():
     assert restoration.folder_patch_count(70, 93, 16, 4) == 2 * 3              # padded to 80 x 96: 20 x 24 in the wavelet domain
     assert restoration.folder_patch_count(33, 40, 16, 4) == 1                  # smaller than one patch: padded to 64 x 64

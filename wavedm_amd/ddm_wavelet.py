@@ -431,7 +431,7 @@ class DenoisingDiffusion_Wavelet(object):
                 inp, gt = x[:, :3].contiguous(), x[:, 3:].contiguous()
                 x_cond = self.wavelet_dec(x_all[:, :3].contiguous())
                 x_gt = self.wavelet_dec(x_all[:, 3:].contiguous())
-                # every band diffused (pred_channels == in_channels): no HFRM, no other channels (DiffusiveRestoration._launch_group has the rules)
+                # every band diffused (pred_channels == in_channels): no HFRM, no other channels (DiffusiveRestoration._bands has the rules)
                 split = pc < cfg.model.in_channels
                 use_other = bool(cfg.model.use_other_channels) and split
                 hf_wav = self.wavelet_dec(data_transform(self.generator(inp)).contiguous()) if split else None
@@ -467,7 +467,7 @@ class DenoisingDiffusion_Wavelet(object):
         x_cond = self.wavelet_dec.forward_affine(rainy01)                        # DWT(2x - 1): data_transform folded into the kernel
         m = self.config.model
         pc, ob = m.pred_channels, m.other_channels_begin
-        split = pc < m.in_channels                                                # every band diffused: no HFRM, no other channels (DiffusiveRestoration._launch_group)
+        split = pc < m.in_channels                                                # every band diffused: no HFRM, no other channels (DiffusiveRestoration._bands)
         hf_wav = x_other = None
         if split:
             hf = self.generator(rainy01) if hfrm_out01 is None else hfrm_out01

@@ -26,7 +26,8 @@ What makes this call surface as fast as the sampler underneath it -- all of it b
 * a pipeline of depth two over the groups: a feeder thread pulls the loader, pins the group and copies it to the device on a copy stream while the
   previous group samples; the main thread queues a group's whole device work (HFRM, DWTs, sampler, IDWT, metric sums, 8-bit conversion) WITHOUT waiting
   for it, and only then reads the metrics of the group before -- the GPU's queue never runs dry between groups, PNG encoding runs behind in the writer's
-  threads.  Console lines come out in loader order, as before.
+  threads.  Console lines come out in loader order, as before.  `_Pipeline` is that pipeline -- staging, feeder loop, queue, budget, hand-over, stop and
+  join --, once, for every mode below; the grouping rules are pure functions beside it (`_same_size_group_step`, `mix_group_step`).
 
 `restore_folder(src, dst)` is the same machinery for what the reference cannot do: a folder of photographs at their own size, without ground truth
 (DESIGN.md §3.5).  Every image is padded on the device to what the models accept (imageio.ingest: multiples of 16, at least one 4p-pixel patch per
@@ -35,7 +36,11 @@ ONE PNG under the input's name.  No 720x480 resize: this path deliberately depar
 per FILE (file_seed), so a file's result depends on nothing but its pixels, its name and the seed."""
 from __future__ import annotations
 
+import collections
 import os
+import queue
+import threading
+import time
 import zlib
 
 import numpy as np
@@ -95,6 +100,21 @@ def check_std_names(names):
         o = std_output_name(n)
         if o in outs:
             raise ValueError(f"restore_folder: the spread map of {n!r} and the output of {outs[o]!r} would both be written to {o!r} (--save-std)")
+
+
+def _claim_output_names(taken, name, save_std=False):
+    """The rules of datasets.output_names and check_std_names as the files come (an iterable without a list of names): `taken` maps the output names
+    claimed so far to their inputs and gains `name`'s.  -> the output name, <stem>.png."""
+    o = os.path.splitext(name)[0] + ".png"
+    if o in taken:
+        raise ValueError(f"restore_folder: {taken[o]!r} and {name!r} would both be written to {o!r}")
+    taken[o] = name
+    if save_std:
+        so = std_output_name(name)
+        if so in taken:
+            raise ValueError(f"restore_folder: the spread map of {name!r} and the output of {taken[so]!r} would both be written to {so!r} (--save-std)")
+        taken[so] = name
+    return o
 
 
 _WS_BYTES = {}      # (kind, config bytes, B[, H, W]) -> workspace bytes the library asks for (host computations, a few hundred distinct keys at most)
@@ -213,7 +233,7 @@ def mix_group_step(counts, nxt, max_batch, images_per_call=None, samples=1):
     its own.  (The feeder adds today's rule on top: with automatic grouping, what is there goes at once while the sampler waits for input.)
     samples: every image counts as that many rows of its patches."""
     counts, nxt, mb = [int(c) * int(samples) for c in counts], int(nxt) * int(samples), int(max_batch)
-    if images_per_call not in (None, 0, "auto", "Auto", "AUTO"):
+    if not _is_auto(images_per_call):
         return False, len(counts) + 1 >= max(1, int(images_per_call))
     if nxt > mb:
         return bool(counts), True
@@ -222,11 +242,22 @@ def mix_group_step(counts, nxt, max_batch, images_per_call=None, samples=1):
     return False, len(counts) + 1 >= MIX_MAX_IMAGES
 
 
+def _same_size_group_step(shapes, nxt, limit):
+    """The grouping rule of restore() and of restore_folder without args.mix_sizes, in mix_group_step's form: the open group holds images of `shapes`
+    (all equal), the next one has shape `nxt`, and `limit` is images_per_call_for of ITS size -- the limit of the group it ends up in, whichever that is.
+    -> (before, after): a different shape closes the open group before the image joins, the limit-th image closes its group after it joined."""
+    before = bool(shapes) and tuple(shapes[0]) != tuple(nxt)
+    return before, (0 if before else len(shapes)) + 1 >= max(1, int(limit))
+
+
+def _is_auto(images_per_call):
+    return images_per_call in (None, 0, "auto", "Auto", "AUTO")
+
+
 class _StageBudget:
     """Bytes of staged input (pinned host + device copies) the feeder may hold ahead of the sampler."""
 
     def __init__(self, limit, stop):
-        import threading
         self.limit, self.used, self.stop, self.cv = max(1, limit), 0, stop, threading.Condition()
 
     def acquire(self, n):
@@ -245,12 +276,131 @@ class _StageBudget:
             self.cv.notify_all()
 
 
+# one group as the feeder hands it over: the device tensor, the names, the event of its copy, the pinned buffer behind it (None: the items were on the
+# device already), the bytes the budget was charged for it, and the per-image (H, W) of a flat mixed-size buffer (None: one array of equal-sized images)
+_Staged = collections.namedtuple("_Staged", "dev names copied pinned nbytes shapes")
+
+
+class _Pipeline:
+    """The pipeline of depth two under restore() and restore_folder(): a feeder thread walks (tensor, name) items, forms groups, pins each and copies it to the
+    device on a copy stream; the main thread iterates over the staged groups, queues each one's device work and hands it to queued(), which waits for the group
+    BEFORE it only then.  `with` stops and joins the feeder before anything, an exception included, leaves the caller.
+
+    layout: how a group lies in its one buffer -- "f32": restore()'s (1,6,H,W) items -> (n,6,H,W) f32; "u8": (H,W,3) u8 photographs of one size -> (n,H,W,3);
+    "flat": photographs of any sizes back to back in one flat u8 buffer (args.mix_sizes).  key(tensor) is what the grouping rule sees of an item, step(keys of
+    the open group, key) -> (close before, close after) is the rule (_same_size_group_step, mix_group_step); `auto`: partial groups go out while the sampler waits."""
+
+    def __init__(self, rest, items, layout, key, step, auto, finish):
+        self.rest, self.dev, self.layout, self.finish, self.pending = rest, rest.diffusion.device, layout, finish, None
+        # groups staged ahead of the sampler: bounded by BYTES (args.prefetch_bytes, default 2 GB of device + pinned memory each), not by count -- a short
+        # validation set is read to its end at once, which also lets a fork-based DataLoader's worker processes exit early (see _StageBudget)
+        self.q, self.stop = queue.Queue(), threading.Event()
+        self.budget = _StageBudget(int(getattr(rest.args, "prefetch_bytes", 2 << 30)), self.stop)
+        self.hungry = threading.Event()                                         # set while the main thread waits for a group
+        self.feeder = threading.Thread(target=self._feed, args=(items, key, step, auto), name="wavedm-restore-feeder", daemon=True)
+
+    def __enter__(self):
+        self.feeder.start()
+        return self
+
+    def __exit__(self, *exc):
+        self.stop.set()
+        self.budget.wake()                                                      # (an error in the caller: the feeder runs into its stop flag instead of waiting for room)
+        self.feeder.join()
+
+    def _stage(self, group):
+        """One group -> one pinned buffer -> one H2D copy on the copy stream -> a _Staged on the queue, charged to the budget by its bytes."""
+        rest, dev, f32, flat = self.rest, self.dev, self.layout == "f32", self.layout == "flat"
+        ts, names = [t for t, _ in group], [n for _, n in group]
+        rest._mark(f"feeder: {'mixed ' if flat else ''}group of {len(group)} read")
+        shapes = [tuple(t.shape[:2]) for t in ts] if flat else None
+        rows = ts if f32 else [t.reshape(-1) for t in ts] if flat else [t[None] for t in ts]
+        dtype = torch.float32 if f32 else torch.uint8
+        if ts[0].is_cuda:                                                       # nothing pinned, nothing charged
+            x = torch.cat(rows, dim=0).to(dtype).contiguous()
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            self.q.put(_Staged(x, names, ev, None, 0, shapes))
+            return
+        # gathered straight into pinned memory (the host allocator recycles these blocks once their copies are done)
+        xp = _lib.pinned_dontfork(torch.empty((sum(row.shape[0] for row in rows),) + tuple(rows[0].shape[1:]), dtype=dtype, pin_memory=True))
+        o = 0
+        for row in rows:
+            # (restore(): a pin_memory=True loader's own pinned batch is kept out of the NEXT fork as well)
+            xp[o:o + row.shape[0]].copy_(_lib.pinned_dontfork(row) if f32 else row)
+            o += row.shape[0]
+        with torch.cuda.stream(self.copy_stream):
+            xd = xp.to(dev, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        rest._mark("feeder: group pinned, copy queued")
+        nbytes = xp.numel() * xp.element_size()                                 # f32 bytes in restore(), one byte per sample in the folder modes
+        self.budget.acquire(nbytes)
+        self.q.put(_Staged(xd, names, ev, xp, nbytes, shapes))
+
+    def _feed(self, items, key, step, auto):
+        """The feeder thread.  Puts _Staged groups on the queue, an exception if one happened (surfaced by __iter__), then None."""
+        try:
+            torch.cuda.set_device(self.dev)
+            self.copy_stream = torch.cuda.Stream(device=self.dev)
+            group, keys = [], []
+            for t, name in items:
+                if self.stop.is_set():
+                    return
+                k = key(t)
+                before, after = step(keys, k)
+                if before and group:
+                    self._stage(group)
+                    group, keys = [], []
+                group.append((t, name))
+                keys.append(k)
+                # full -- or, with automatic grouping, the sampler is WAITING for input (the start of a run, a loader slower than the GPU): what is there goes
+                # at once, the GPU starts on image 1 while the loader still decodes image 2 (per-image results do not depend on the grouping)
+                if after or (auto and self.hungry.is_set()):
+                    self._stage(group)
+                    group, keys = [], []
+            if group:
+                self._stage(group)
+        except BaseException as e:
+            self.q.put(e)
+        finally:
+            self.q.put(None)
+
+    def __iter__(self):
+        """Staged groups, each released from the budget and ordered behind its copy on the current stream; at the end the last queued group is finished."""
+        cur = torch.cuda.current_stream(self.dev)
+        while True:
+            try:
+                staged = self.q.get_nowait()
+            except queue.Empty:
+                self.hungry.set()
+                staged = self.q.get()
+                self.hungry.clear()
+            if staged is None:
+                break
+            if isinstance(staged, BaseException):
+                raise staged
+            self.rest._mark("main: group taken")
+            self.budget.release(staged.nbytes)
+            cur.wait_event(staged.copied)
+            staged.dev.record_stream(cur)                                       # (allocated on the feeder's copy stream)
+            yield staged
+        if self.pending is not None:
+            self.finish(self.pending)
+
+    def queued(self, g):
+        """Everything of sampler call k is queued (g: what `finish` needs of it): now, and not before, the host waits for call k - 1."""
+        self.rest._mark("main: group queued")
+        if self.pending is not None:
+            self.finish(self.pending)
+            self.rest._mark("main: previous group's numbers in")
+        self.pending = g
+
+
 class DiffusiveRestoration:
     def _mark(self, what):
         """WAVEDM_RESTORE_TRACE=1: host-side timeline of restore() in self.trace [(seconds since the call, thread, label)] (scripts/restore_trace.py)."""
         if self.trace is not None:
-            import threading
-            import time
             ev = None
             if threading.current_thread() is threading.main_thread() and os.environ.get("WAVEDM_RESTORE_TRACE_GPU", "0") == "1":
                 ev = torch.cuda.Event(enable_timing=True)                       # when the GPU gets to this point of the main stream
@@ -301,7 +451,7 @@ class DiffusiveRestoration:
         default cap of 384: 7 images = 315 patches = one call, 98 % of five units (profiles/r06_restore_sweep.log: 8 x 45 = 360 in calls of 120 6.32 img/s,
         in one call 6.47; a call of 144 = 2.25 units 5.70).  `samples`: an image counts as that many rows of its patches; a group holds at least one image."""
         v = getattr(self.args, "images_per_call", None)
-        if v not in (None, 0, "auto", "Auto", "AUTO"):
+        if not _is_auto(v):
             return max(1, int(v))
         p_size = self.config.data.patch_size if self.config.data.wavelet_in_unet else self.config.data.image_size
         hl, wl = sampling.overlapping_grid_indices(h, w, p_size, r)
@@ -315,94 +465,72 @@ class DiffusiveRestoration:
         cap = max(16, mb // max(P, 1))
         return max(range(1, cap + 1), key=lambda n: (min(fill(n), 0.97), -n))        # the smallest count that reaches 97 %, else the best fill (then the smallest)
 
-    def _feed(self, val_loader, r, q, stop, budget, hungry):
-        """Feeder thread: loader items -> groups of same-sized images -> pinned -> device (copy stream).  Puts (x_dev, names, copy_done_event, pinned) on q,
-        an exception if one happened, then None."""
-        dev = self.diffusion.device
-        try:
-            torch.cuda.set_device(dev)
-            copy_stream = torch.cuda.Stream(device=dev)
-            group, limit, n_emitted = [], 1, 0
-            # partial groups are a timing decision of THIS process: never in the patch-sharded mode, where every rank must form the same groups (one all-reduce per step)
-            auto = (getattr(self.args, "images_per_call", None) in (None, 0, "auto", "Auto", "AUTO")) and getattr(self.diffusion, "patch_group", None) is None
+    # ---- what a call reads of its options, once, after its refusals (_ensemble_args, _check_steps) ------------------
+    def _check_steps(self):
+        """restore_folder refuses before anything runs; restore() when its first group arrives, so that an empty loader still returns ([], [])."""
+        if int(self.diffusion.args.sampling_timesteps) < 5:
+            raise IndexError("x0_preds[-5] needs at least 5 sampling steps (restoration.py:108)")
 
-            def emit(group):
-                nonlocal n_emitted
-                n_emitted += 1
-                self._mark(f"feeder: group of {len(group)} read")
-                names = [it[1] for it in group]
-                if group[0][0].is_cuda:
-                    x = torch.cat([it[0] for it in group], dim=0).float().contiguous()
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(dev))
-                    q.put((x, names, ev, None))
-                    return
-                # gathered straight into pinned memory (the host allocator recycles these blocks once their copies are done)
-                xp = _lib.pinned_dontfork(torch.empty((len(group),) + tuple(group[0][0].shape[1:]), dtype=torch.float32, pin_memory=True))
-                for k, it in enumerate(group):
-                    xp[k].copy_(_lib.pinned_dontfork(it[0])[0])                # (a pin_memory=True loader's own pinned batch: kept out of the NEXT fork as well)
-                with torch.cuda.stream(copy_stream):
-                    xd = xp.to(dev, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_stream)
-                self._mark("feeder: group pinned, copy queued")
-                budget.acquire(xp.numel() * 4)
-                q.put((xd, names, ev, xp))
+    def _call_options(self, write):
+        """args.early_stop -> the sampler's stop_at, args.seed (default 61), the sampler's `samples` keyword, args.ssim; the trace and the writer start here."""
+        seed = getattr(self.args, "seed", None)
+        self._seed = 61 if seed is None else seed
+        self._stop_at = -5 if bool(getattr(self.args, "early_stop", True)) else None
+        self._samples_kw = {"samples": self._samples} if self._samples != 1 else {}
+        self._ssim = bool(getattr(self.args, "ssim", False))
+        if os.environ.get("WAVEDM_RESTORE_TRACE", "0") == "1":
+            self.trace, self._t0 = [], time.perf_counter()
+        if write and self.writer is None:
+            self.writer = imageio.AsyncImageWriter()
 
-            for i, (x, y, total) in enumerate(val_loader):
-                if stop.is_set():
-                    return
-                x = x.flatten(start_dim=0, end_dim=1) if x.ndim == 5 else x    # restoration.py:72
-                for k in range(x.shape[0]):                                    # loader batches are split into images
-                    name = y[k] if isinstance(y, (list, tuple)) and len(y) == x.shape[0] else y
-                    item = (x[k:k + 1], name)
-                    if group and group[0][0].shape != item[0].shape:           # a different size closes the group
-                        emit(group)
-                        group = []
-                    if not group:
-                        limit = self.images_per_call_for(item[0].shape[-2] // 4, item[0].shape[-1] // 4, r, samples=self._samples)
-                    group.append(item)
-                    # full -- or, with automatic grouping, the sampler is WAITING for input (the start of a run, a loader slower than the GPU): what is there goes
-                    # at once, the GPU starts on image 1 while the loader still decodes image 2 (per-image results do not depend on the grouping)
-                    if len(group) >= limit or (auto and hungry.is_set()):
-                        emit(group)
-                        group = []
-            if group:
-                emit(group)
-        except BaseException as e:                                             # surfaced by restore()
-            q.put(e)
-        finally:
-            q.put(None)
+    def _end_call(self):
+        self._mark("main: last group done")
+        if self.writer is not None:
+            self.writer.flush()
+        self._mark("main: PNGs flushed")
+
+    def _bands(self):
+        """(split, use_other).  model.pred_channels == model.in_channels: every band is diffused -- no HFRM call, no HFRM DWT, no "wdnet" numbers
+        (restoration.py:90-96, :111, :145).  x_other exists only with use_other_channels (:98-104) AND at least one channel: `other_channels_begin == in_channels`
+        means none, so the trainable spelling of the all-bands model (use_other_channels True, begin 48) restores like use_other_channels False."""
+        m = self.config.model
+        split = m.pred_channels < m.in_channels
+        return split, bool(m.use_other_channels) and split
+
+    def _condition(self, x, out=(None, None)):
+        """What a sampler call is conditioned on, from the degraded images x (n,3,H,W) -> (x_cond, hf, hf_wav, x_other, split, use_other); the rules: _bands.
+        out: views of ragged buffers to write x_cond and x_other into (_launch_mixed_group)."""
+        m, d = self.config.model, self.diffusion
+        x_cond = d.wavelet_dec.forward_affine(x, out=out[0])                   # restoration.py:79, :88: DWT(2x - 1) in one kernel
+        self._mark("main: DWTs queued")
+        split, use_other = self._bands()
+        hf = hf_wav = x_other = None
+        if split:
+            hf = d.generator(x)                                                # :94 (HFRM)
+            self._mark("main: HFRM queued")
+            hf_wav = d.wavelet_dec.forward_affine(hf.contiguous())             # :95-96
+            if use_other:                                                      # :102
+                x_other = hf_wav[:, m.other_channels_begin:].contiguous() if out[1] is None else out[1].copy_(hf_wav[:, m.other_channels_begin:])
+        return x_cond, hf, hf_wav, x_other, split, use_other
+
+    def _compose(self, x0_preds, hf_wav, split, want_coef=False):
+        """x0_preds[-5] (restoration.py:108) -> (image, spread map or None, the coefficients behind the image).  One sample: IDWT(cat([pred[:, :pc], hf_wav[:, pc:]]))
+        -> clamp((x + 1) / 2) in one kernel (:114-115, :124, :134; all bands diffused: the second source contributes nothing).  args.samples: the mean of the
+        samples' coefficients stands where the one sample's stood, and with want_coef it is handed back for the diagnostic images."""
+        pred, pc, rec = x0_preds[-5], self.config.model.pred_channels, self.diffusion.wavelet_rec
+        if self._samples == 1:
+            return rec.compose(pred, hf_wav if split else pred, pc), None, pred
+        return rec.compose_ensemble(pred, hf_wav if split else None, pc, self._samples, want_std=self._save_std, want_coef=want_coef)
 
     # ---- one sampler call over a group of same-sized loader items: everything QUEUED here, nothing waited for ---------
     def _launch_group(self, staged, r, image_folder):
-        cfg, d = self.config, self.diffusion
-        pc, ob = cfg.model.pred_channels, cfg.model.other_channels_begin
-        x, names, copied, pinned = staged
-        cur = torch.cuda.current_stream(d.device)
-        cur.wait_event(copied)
-        x.record_stream(cur)                                                   # (allocated on the feeder's copy stream)
+        d, pc = self.diffusion, self.config.model.pred_channels
+        self._check_steps()
+        x, names = staged.dev, staged.names
         inp, gt = x[:, :3].contiguous(), x[:, 3:].contiguous()
-        x_cond = d.wavelet_dec.forward_affine(inp)                             # restoration.py:79, :88: DWT(2x - 1) in one kernel
-        x_gt = d.wavelet_dec.forward_affine(gt)                                # :89
-        self._mark("main: DWTs queued")
-        # model.pred_channels == model.in_channels: every band is diffused -- no HFRM call, no HFRM DWT, no "wdnet" numbers (restoration.py:90-96, :111, :145).
-        # x_other exists only with use_other_channels (:98-104) AND at least one channel: `other_channels_begin == in_channels` means none, so the trainable
-        # spelling of the all-bands model (use_other_channels True, begin 48) restores like use_other_channels False (DESIGN.md §7)
-        split = pc < cfg.model.in_channels
-        use_other = bool(cfg.model.use_other_channels) and split
-        hf = hf_wav = x_other = None
-        if split:
-            hf = d.generator(inp)                                              # :94 (HFRM)
-            self._mark("main: HFRM queued")
-            hf_wav = d.wavelet_dec.forward_affine(hf.contiguous())             # :95-96
-            if use_other:
-                x_other = hf_wav[:, ob:].contiguous()                          # :102
-        early = bool(getattr(self.args, "early_stop", True))
-        if int(self.diffusion.args.sampling_timesteps) < 5:
-            raise IndexError("x0_preds[-5] needs at least 5 sampling steps (restoration.py:108)")
+        x_gt = d.wavelet_dec.forward_affine(gt)                                # restoration.py:89
+        x_cond, hf, hf_wav, x_other, split, use_other = self._condition(inp)
         rec = lambda lo, hi: d.wavelet_rec.compose(lo, hi, pc)                    # IDWT(cat([lo[:, :pc], hi[:, pc:]])) -> clamp((x + 1) / 2), one kernel
-        names = [n[0] if isinstance(n, (list, tuple)) else n for n in names]
         w = self.writer if self.save_images else None
         if w is not None:
             # five of the reference's seven PNGs per image do not depend on the sampler: converted and handed to the writer BEFORE the sampler is queued, so that
@@ -416,14 +544,8 @@ class DiffusiveRestoration:
                 w.save(inp[sl], os.path.join(image_folder, f"{name}_cond.png"))
                 w.save(gt[sl], os.path.join(image_folder, f"{name}_gt.png"))
         xs, x0_preds = self.diffusive_restoration(x_cond, x_other=x_other, r=r, last=False, total=None,
-                                                  use_global=False, use_other=use_other, stop_at=-5 if early else None, **({"samples": self._samples} if self._samples != 1 else {}))
-        pred = x0_preds[-5]                                                    # :108
-        x_std = None
-        if self._samples == 1:
-            x_output = rec(pred, hf_wav if split else pred)                    # :114-115, :124, :134 (all bands diffused: the second source contributes nothing)
-        else:
-            # args.samples: the mean of the samples' coefficients stands where the one sample's stood -- for the output and for the diagnostic images below
-            x_output, x_std, pred = d.wavelet_rec.compose_ensemble(pred, hf_wav if split else None, pc, self._samples, want_std=self._save_std, want_coef=True)
+                                                  use_global=False, use_other=use_other, stop_at=self._stop_at, **self._samples_kw)
+        x_output, x_std, pred = self._compose(x0_preds, hf_wav, split, want_coef=True)
         H, W = x_output.shape[-2:]
         # the three pairs the reference prints: output, "cond" (IDWT(DWT(x)) == x: the input), HFRM image (restoration.py:146 clamps x_output_wdnet first)
         self._mark("main: sampler queued")
@@ -437,7 +559,7 @@ class DiffusiveRestoration:
         sums_host = _lib.pinned_dontfork(torch.empty(sums.shape, dtype=sums.dtype, pin_memory=True))
         sums_host.copy_(sums, non_blocking=True)
         done = torch.cuda.Event()
-        done.record(cur)
+        done.record(torch.cuda.current_stream(d.device))
         if w is not None:
             for k, name in enumerate(names):
                 sl = slice(k, k + 1)
@@ -446,14 +568,14 @@ class DiffusiveRestoration:
                     w.save((x_std[sl] * self._std_gain).clamp_(0.0, 1.0), os.path.join(image_folder, f"{name}_std.png"))
                 if use_other:
                     w.save(rec(pred[sl], x_gt[sl]), os.path.join(image_folder, f"{name}_lrdiff_hrgt.png"))     # :112-113
-        return dict(names=names, out=x_output, std=x_std, sums=sums_host, done=done, HW=(H, W), keep=(pinned, sums))
+        return dict(names=names, out=x_output, std=x_std, sums=sums_host, done=done, HW=(H, W), keep=(staged.pinned, sums))
 
     def _finish_group(self, g, acc):
         """Wait for a queued group's metric sums and print what the reference prints per image."""
         g["done"].synchronize()
         H, W = g["HW"]
         n = len(g["names"])
-        npair = 3 if self.config.model.pred_channels < self.config.model.in_channels else 2      # (no HFRM image when every band is diffused)
+        npair = 3 if self._bands()[0] else 2                                   # (no HFRM image when every band is diffused)
         sums = g["sums"][:npair * n * 2].view(npair, n, 2) if self._ssim else g["sums"]
         m = [imageio.psnr_from_sums(sums[j], H, W) for j in range(npair)]
         m_out, m_cond, m_hf = m[0], m[1], (m[2] if npair == 3 else None)
@@ -470,61 +592,32 @@ class DiffusiveRestoration:
         return [g["out"][k:k + 1] for k in range(len(g["names"]))]
 
     def restore(self, val_loader, validation="snow", r=None):
-        import queue
-        import threading
         cfg, d = self.config, self.diffusion
         if not (cfg.data.wavelet and not cfg.data.wavelet_in_unet):
             raise NotImplementedError("DiffusiveRestoration.restore: only the data.wavelet / not data.wavelet_in_unet branch (raindrop_wavelet.yml) is accelerated")
         if cfg.model.pred_channels > cfg.model.in_channels:
             raise ValueError(f"model.pred_channels {cfg.model.pred_channels} exceeds the {cfg.model.in_channels} wavelet bands (model.in_channels)")
         self._ensemble_args("restore")
+        self._call_options(self.save_images)
         image_folder = os.path.join(self.args.image_folder, cfg.data.dataset, validation)
-        if os.environ.get("WAVEDM_RESTORE_TRACE", "0") == "1":
-            import time
-            self.trace, self._t0 = [], time.perf_counter()
-        if self.save_images and self.writer is None:
-            self.writer = imageio.AsyncImageWriter()
-        self._ssim = bool(getattr(self.args, "ssim", False))
         acc = {"torch": [], "y": [], "wdnet": [], "ssim": [], "std": []}
-        outputs, pending = [], None
-        # groups staged ahead of the sampler: bounded by BYTES (args.prefetch_bytes, default 2 GB of device + pinned memory each), not by count -- a short
-        # validation set is read to its end at once, which also lets a fork-based DataLoader's worker processes exit early (see _StageBudget)
-        q, stop = queue.Queue(), threading.Event()
-        budget = _StageBudget(int(getattr(self.args, "prefetch_bytes", 2 << 30)), stop)
-        hungry = threading.Event()                                              # set while the main thread waits for a group
-        feeder = threading.Thread(target=self._feed, args=(val_loader, r, q, stop, budget, hungry), name="wavedm-restore-feeder", daemon=True)
-        feeder.start()
-        try:
-            with torch.no_grad(), torch.cuda.device(d.device):
-                while True:
-                    try:
-                        staged = q.get_nowait()
-                    except queue.Empty:
-                        hungry.set()
-                        staged = q.get()
-                        hungry.clear()
-                    if staged is None:
-                        break
-                    if isinstance(staged, BaseException):
-                        raise staged
-                    self._mark("main: group taken")
-                    budget.release(staged[0].numel() * 4 if staged[3] is not None else 0)
-                    cur = self._launch_group(staged, r, image_folder)          # group k queued behind group k - 1 ...
-                    self._mark("main: group queued")
-                    if pending is not None:
-                        outputs += self._finish_group(pending, acc)            # ... before the host waits for k - 1's numbers
-                        self._mark("main: previous group's numbers in")
-                    pending = cur
-                if pending is not None:
-                    outputs += self._finish_group(pending, acc)
-        finally:
-            stop.set()
-            budget.wake()                                                      # (an error above: the feeder runs into its stop flag instead of waiting for room)
-            feeder.join()
-        self._mark("main: last group done")
-        if self.writer is not None:
-            self.writer.flush()
-        self._mark("main: PNGs flushed")
+        outputs = []
+
+        def items():
+            for x, y, total in val_loader:
+                x = x.flatten(start_dim=0, end_dim=1) if x.ndim == 5 else x    # restoration.py:72
+                for k in range(x.shape[0]):                                    # loader batches are split into images
+                    name = y[k] if isinstance(y, (list, tuple)) and len(y) == x.shape[0] else y
+                    yield x[k:k + 1], (name[0] if isinstance(name, (list, tuple)) else name)
+
+        # partial groups are a timing decision of THIS process: never in the patch-sharded mode, where every rank must form the same groups (one all-reduce per step)
+        auto = _is_auto(getattr(self.args, "images_per_call", None)) and getattr(d, "patch_group", None) is None
+        step = lambda shapes, s: _same_size_group_step(shapes, s, self.images_per_call_for(s[-2] // 4, s[-1] // 4, r, samples=self._samples))
+        finish = lambda g: outputs.extend(self._finish_group(g, acc))
+        with torch.no_grad(), torch.cuda.device(d.device), _Pipeline(self, items(), "f32", lambda t: tuple(t.shape), step, auto, finish) as pipe:
+            for staged in pipe:
+                pipe.queued(self._launch_group(staged, r, image_folder))
+        self._end_call()
         if acc["torch"]:
             print("psnr all torch", float(np.mean(acc["torch"])))
             print("psnr all np", float(np.mean(acc["y"])))
@@ -539,138 +632,37 @@ class DiffusiveRestoration:
         return outputs, acc["torch"]
 
     # ---- photographs at their own size, without ground truth -----------------------------------------
-    def _feed_folder(self, items, r, q, stop, budget, hungry):
-        """restore_folder's feeder thread: (u8 (H,W,3), name) items -> groups of same-sized images -> pinned -> device (copy stream), one byte per sample.
-        Puts (u8_dev (n,H,W,3), names, copy_done_event, pinned) on q, an exception if one happened, then None."""
-        dev = self.diffusion.device
-        p4 = 4 * self.config.data.image_size
-        try:
-            torch.cuda.set_device(dev)
-            copy_stream = torch.cuda.Stream(device=dev)
-            group, limit = [], 1
-            auto = getattr(self.args, "images_per_call", None) in (None, 0, "auto", "Auto", "AUTO")
-
-            def emit(group):
-                self._mark(f"feeder: group of {len(group)} read")
-                names = [it[1] for it in group]
-                if group[0][0].is_cuda:
-                    x = torch.stack([it[0] for it in group]).contiguous()
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(dev))
-                    q.put((x, names, ev, None))
-                    return
-                xp = _lib.pinned_dontfork(torch.empty((len(group),) + tuple(group[0][0].shape), dtype=torch.uint8, pin_memory=True))
-                for k, it in enumerate(group):
-                    xp[k].copy_(it[0])
-                with torch.cuda.stream(copy_stream):
-                    xd = xp.to(dev, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_stream)
-                budget.acquire(xp.numel())
-                q.put((xd, names, ev, xp))
-
-            def emit_mixed(group):
-                """args.mix_sizes: the group's images, of any sizes, in ONE flat pinned u8 buffer (image k at offs[k], H_k * W_k * 3 bytes) and one H2D copy."""
-                self._mark(f"feeder: mixed group of {len(group)} read")
-                names, shapes = [it[1] for it in group], [tuple(it[0].shape[:2]) for it in group]
-                if group[0][0].is_cuda:
-                    x = torch.cat([it[0].reshape(-1) for it in group])
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(dev))
-                    q.put((x, names, ev, None, shapes))
-                    return
-                xp = _lib.pinned_dontfork(torch.empty(sum(3 * h * w for (h, w) in shapes), dtype=torch.uint8, pin_memory=True))
-                o = 0
-                for it in group:
-                    xp[o:o + it[0].numel()].copy_(it[0].reshape(-1))
-                    o += it[0].numel()
-                with torch.cuda.stream(copy_stream):
-                    xd = xp.to(dev, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_stream)
-                budget.acquire(xp.numel())
-                q.put((xd, names, ev, xp, shapes))
-
-            mix, counts = bool(getattr(self.args, "mix_sizes", False)), []
-            for img, name in items:
-                if stop.is_set():
-                    return
-                name = name[0] if isinstance(name, (list, tuple)) else name
-                if not (isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[-1] == 3):
-                    raise TypeError(f"restore_folder: {name!r}: expected a uint8 (H,W,3) tensor, got {getattr(img, 'dtype', type(img))} {tuple(getattr(img, 'shape', ()))}")
-                if mix:                                                     # images of any sizes share a call, in input order: mix_group_step
-                    cnt = folder_patch_count(img.shape[0], img.shape[1], p4 // 4, r)
-                    before, after = mix_group_step(counts, cnt, self._max_batch(), getattr(self.args, "images_per_call", None))
-                    if before and group:
-                        emit_mixed(group)
-                        group, counts = [], []
-                    group.append((img, name))
-                    counts.append(cnt)
-                    if after or (auto and hungry.is_set()):
-                        emit_mixed(group)
-                        group, counts = [], []
-                    continue
-                if group and group[0][0].shape != img.shape:               # only images of equal ORIGINAL size share a call
-                    emit(group)
-                    group = []
-                if not group:
-                    hp, wp = imageio.padded_size(img.shape[0], img.shape[1], 16, p4)
-                    limit = self.images_per_call_for(hp // 4, wp // 4, r, samples=self._samples)
-                group.append((img, name))
-                if len(group) >= limit or (auto and hungry.is_set()):
-                    emit(group)
-                    group = []
-            if group:
-                (emit_mixed if mix else emit)(group)
-        except BaseException as e:                                             # surfaced by restore_folder()
-            q.put(e)
-        finally:
-            q.put(None)
-
-    def _fits(self, H, W, n, r):
-        """(fits, estimate, limit) of one sampler call over n images of H x W: args.max_restore_bytes if set, else 0.8 of the device memory that is free now
-        (what torch's allocator holds without using counts as free: it is handed out again)."""
-        dev = self.diffusion.device
-        est = estimate_restore_bytes(H, W, n, self.config, self._max_batch(), self.diffusion.model.dtype_name, r, int(self.diffusion.args.sampling_timesteps),
-                                     hfrm_local=getattr(self.diffusion, "hfrm_local", None), samples=self._samples)
+    def _within_limit(self, r, estimate, *sizes, **kw):
+        """(fits, estimate, limit) of estimate(*sizes, config, max_batch, dtype, r, steps, hfrm_local=, ...) against args.max_restore_bytes if set, else 0.8 of
+        the device memory that is free now (what torch's allocator holds without using counts as free: it is handed out again)."""
+        d, dev = self.diffusion, self.diffusion.device
+        est = estimate(*sizes, self.config, self._max_batch(), d.model.dtype_name, r, int(d.args.sampling_timesteps), hfrm_local=getattr(d, "hfrm_local", None), **kw)
         limit = getattr(self.args, "max_restore_bytes", None)
         if not limit:
             limit = 0.8 * (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
         return est <= limit, est, limit
 
+    def _fits(self, H, W, n, r):
+        """_within_limit for one sampler call over n images of H x W (estimate_restore_bytes)."""
+        return self._within_limit(r, estimate_restore_bytes, H, W, n, samples=self._samples)
+
     def _launch_folder_group(self, u8, names, r, out_paths, keep_outputs):
         """One sampler call over same-sized photographs: everything QUEUED, nothing waited for."""
-        cfg, d = self.config, self.diffusion
-        pc, ob, p = cfg.model.pred_channels, cfg.model.other_channels_begin, cfg.data.image_size
-        dev = d.device
+        d, dev = self.diffusion, self.diffusion.device
+        pc, p = self.config.model.pred_channels, self.config.data.image_size
         n, H, W, _ = u8.shape
         x = imageio.ingest(u8, 16, 4 * p)
         Hp, Wp = x.shape[-2:]
-        x_cond = d.wavelet_dec.forward_affine(x)
-        split = pc < cfg.model.in_channels
-        use_other = bool(cfg.model.use_other_channels) and split
-        hf_wav = x_other = None
-        if split:                                                              # (as _launch_group: no HFRM call at all when every band is diffused)
-            hf_wav = d.wavelet_dec.forward_affine(d.generator(x).contiguous())
-            if use_other:
-                x_other = hf_wav[:, ob:].contiguous()
-        seed = getattr(self.args, "seed", None)
-        seed = 61 if seed is None else seed
-        N = self._samples
-        noise = torch.cat([torch.randn((1, pc, Hp // 4, Wp // 4), device=dev, generator=torch.Generator(device=dev).manual_seed(sample_seed(seed, name, k)))
-                           for name in names for k in range(N)], dim=0)
+        x_cond, _, hf_wav, x_other, split, use_other = self._condition(x)
+        noise = torch.cat([torch.randn((1, pc, Hp // 4, Wp // 4), device=dev, generator=torch.Generator(device=dev).manual_seed(sample_seed(self._seed, name, k)))
+                           for name in names for k in range(self._samples)], dim=0)
         h_list, w_list = sampling.overlapping_grid_indices(Hp // 4, Wp // 4, p, r)
         corners = [(i, j) for i in h_list for j in w_list]
-        early = bool(getattr(self.args, "early_stop", True))
         xs, x0_preds = d.sample_image(x_cond, noise, x_other=x_other, last=False, patch_locs=corners, patch_size=p, total=None,
-                                      use_global=False, use_other=use_other, stop_at=-5 if early else None, **({"samples": N} if N != 1 else {}))
-        pred = x0_preds[-5]
-        std = s8 = None
-        if N == 1:
-            out = d.wavelet_rec.compose(pred, hf_wav if split else pred, pc)
-        else:                                                                  # the mean of the N samples' coefficients -> one image; their per-pixel spread
-            out, std, _ = d.wavelet_rec.compose_ensemble(pred, hf_wav if split else None, pc, N, want_std=self._save_std)
+                                      use_global=False, use_other=use_other, stop_at=self._stop_at, **self._samples_kw)
+        out, std, _ = self._compose(x0_preds, hf_wav, split)                    # args.samples: the mean of the samples' coefficients -> one image; their per-pixel spread
         self._mark("main: sampler queued")
+        s8 = None
         q8 = imageio.to_u8_hwc(out, crop=(H, W))
         if std is not None:
             s8 = imageio.to_u8_hwc((std * self._std_gain).clamp_(0.0, 1.0), crop=(H, W))
@@ -683,32 +675,24 @@ class DiffusiveRestoration:
         kept_std = [std[k:k + 1, :, :H, :W].clone() for k in range(n)] if (keep_outputs and std is not None) else []
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
-        return dict(names=names, done=done, HW=(H, W), patches=len(corners), kept=kept, kept_std=kept_std, keep=(u8, q8, s8))
+        return dict(names=names, done=done, HW=[(H, W)] * n, patches=[len(corners)] * n, kept=kept, kept_std=kept_std, keep=(u8, q8, s8))
 
     def _fits_mixed(self, shapes, r):
         """_fits for one sampler call over photographs of different sizes (estimate_restore_bytes_mixed)."""
-        dev = self.diffusion.device
-        est = estimate_restore_bytes_mixed(shapes, self.config, self._max_batch(), self.diffusion.model.dtype_name, r, int(self.diffusion.args.sampling_timesteps),
-                                           hfrm_local=getattr(self.diffusion, "hfrm_local", None))
-        limit = getattr(self.args, "max_restore_bytes", None)
-        if not limit:
-            limit = 0.8 * (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
-        return est <= limit, est, limit
+        return self._within_limit(r, estimate_restore_bytes_mixed, shapes)
 
     def _launch_mixed_group(self, imgs, names, r, out_paths, keep_outputs):
         """args.mix_sizes: one sampler call over photographs of DIFFERENT sizes (imgs: (1,H,W,3) u8 on the device): everything QUEUED, nothing waited for.
         x_cond, the start noise and x_other are ragged tensors (sampling.RaggedLayout); ingest, DWT, HFRM and its DWT run per run of consecutive images of equal
         padded size and write views of them, compose / crop / 8-bit conversion run per image -- all with the kernels of _launch_folder_group, so every file's
         bits are the ones it gets there."""
-        cfg, d = self.config, self.diffusion
-        pc, ob, p = cfg.model.pred_channels, cfg.model.other_channels_begin, cfg.data.image_size
-        dev = d.device
+        d, dev = self.diffusion, self.diffusion.device
+        pc, p = self.config.model.pred_channels, self.config.data.image_size
         n = len(imgs)
         x_in = [imageio.ingest(u, 16, 4 * p) for u in imgs]
         layout = sampling.RaggedLayout([(x.shape[-2] // 4, x.shape[-1] // 4) for x in x_in], p, r)
-        split = pc < cfg.model.in_channels
-        use_other = bool(cfg.model.use_other_channels) and split
-        n_other = cfg.model.in_channels - ob
+        split, use_other = self._bands()
+        n_other = self.config.model.in_channels - self.config.model.other_channels_begin
         x_cond = torch.empty(layout.numel(48), device=dev, dtype=torch.float32)
         x_other = torch.empty(layout.numel(n_other), device=dev, dtype=torch.float32) if use_other else None
         noise = torch.empty(layout.numel(pc), device=dev, dtype=torch.float32)
@@ -720,20 +704,13 @@ class DiffusiveRestoration:
             while i1 < n and layout.sizes[i1] == layout.sizes[i0]:
                 i1 += 1
             x = x_in[i0] if i1 - i0 == 1 else torch.cat(x_in[i0:i1], dim=0)
-            d.wavelet_dec.forward_affine(x, out=run_view(x_cond, 48, i0, i1))
-            if split:                                                          # (as _launch_folder_group: no HFRM call at all when every band is diffused)
-                hw = d.wavelet_dec.forward_affine(d.generator(x).contiguous())
-                for k in range(i0, i1):
-                    hf_wav[k] = hw[k - i0:k - i0 + 1]
-                if use_other:
-                    run_view(x_other, n_other, i0, i1).copy_(hw[:, ob:])
+            hw = self._condition(x, out=(run_view(x_cond, 48, i0, i1), run_view(x_other, n_other, i0, i1) if use_other else None))[2]
+            for k in range(i0, i1):
+                hf_wav[k] = hw[k - i0:k - i0 + 1] if split else None
             i0 = i1
-        seed = getattr(self.args, "seed", None)
-        seed = 61 if seed is None else seed
         for k, name in enumerate(names):
-            layout.view(noise, pc, k).copy_(torch.randn((1, pc) + layout.sizes[k], device=dev, generator=torch.Generator(device=dev).manual_seed(file_seed(seed, name))))
-        early = bool(getattr(self.args, "early_stop", True))
-        xs, x0_preds = d.sample_image_ragged(x_cond, noise, layout, x_other=x_other, use_other=use_other, stop_at=-5 if early else None)
+            layout.view(noise, pc, k).copy_(torch.randn((1, pc) + layout.sizes[k], device=dev, generator=torch.Generator(device=dev).manual_seed(file_seed(self._seed, name))))
+        xs, x0_preds = d.sample_image_ragged(x_cond, noise, layout, x_other=x_other, use_other=use_other, stop_at=self._stop_at)
         pred = x0_preds[-5]
         self._mark("main: sampler queued")
         q8s, kept = [], []
@@ -749,7 +726,7 @@ class DiffusiveRestoration:
                 kept.append(out[:, :, :H, :W].clone())
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
-        return dict(names=names, done=done, HW=[tuple(u.shape[1:3]) for u in imgs], patches=list(layout.patch_counts), kept=kept, keep=(imgs, q8s))
+        return dict(names=names, done=done, HW=[tuple(u.shape[1:3]) for u in imgs], patches=list(layout.patch_counts), kept=kept, kept_std=[], keep=(imgs, q8s))
 
     def restore_folder(self, src, dst=None, r=None, recursive=False, keep_outputs=False):
         """Restore photographs at their own size, without ground truth -> [(name, output path or None), ...] in input order.
@@ -767,8 +744,6 @@ class DiffusiveRestoration:
         automatically as many as fill one UNet call (mix_group_step) --, on the ragged layout of sampling.RaggedLayout; files are never reordered, and every
         file's result, the printed lines, last_info, last_outputs and the returned list are what the mode gives switched off, bit for bit.  self.last_calls
         holds one tuple of names per sampler call of the last run, in either mode."""
-        import queue
-        import threading
         from . import datasets
         cfg, d = self.config, self.diffusion
         if not (cfg.data.wavelet and not cfg.data.wavelet_in_unet):
@@ -779,115 +754,81 @@ class DiffusiveRestoration:
             raise NotImplementedError("DiffusiveRestoration.restore_folder: the patch-sharded mode (patch_group) is not built for folders; shard the FILES over the ranks (ImageFolder(shard=))")
         if cfg.model.pred_channels > cfg.model.in_channels:
             raise ValueError(f"model.pred_channels {cfg.model.pred_channels} exceeds the {cfg.model.in_channels} wavelet bands (model.in_channels)")
-        if int(d.args.sampling_timesteps) < 5:
-            raise IndexError("x0_preds[-5] needs at least 5 sampling steps (restoration.py:108)")
-        self._ensemble_args("restore_folder", mix=bool(getattr(self.args, "mix_sizes", False)))
-        items = datasets.ImageFolder(src, recursive=recursive) if isinstance(src, (str, os.PathLike)) else src
-        listed = getattr(getattr(items, "dataset", items), "names", None)
+        self._check_steps()
+        mix, per_call = bool(getattr(self.args, "mix_sizes", False)), getattr(self.args, "images_per_call", None)
+        self._ensemble_args("restore_folder", mix=mix)
+        src =datasets.ImageFolder(src, recursive=recursive) if isinstance(src, (str, os.PathLike)) else src
+        listed = getattr(getattr(src, "dataset", src), "names", None)
         if listed is not None:
             datasets.output_names(listed)                                       # two inputs, one output: refused before anything runs
             if self._save_std:
                 check_std_names(listed)                                         # ... and an input whose output is another's spread map
         write = dst is not None and self.save_images
-        if os.environ.get("WAVEDM_RESTORE_TRACE", "0") == "1":
-            import time
-            self.trace, self._t0 = [], time.perf_counter()
-        if write and self.writer is None:
-            self.writer = imageio.AsyncImageWriter()
-        results, outputs, taken, pending = [], [], {}, []
+        self._call_options(write)
+        results, outputs, stds, taken = [], [], [], {}
         self.last_info = []
         self.last_calls = []                                                    # one tuple of names per sampler call, in order
-        stds = []
+        p = cfg.data.image_size
+
+        def items():
+            for img, name in src:
+                name = name[0] if isinstance(name, (list, tuple)) else name
+                if not (isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[-1] == 3):
+                    raise TypeError(f"restore_folder: {name!r}: expected a uint8 (H,W,3) tensor, got {getattr(img, 'dtype', type(img))} {tuple(getattr(img, 'shape', ()))}")
+                yield img, name
+
+        if mix:                                                                 # images of any sizes share a call, in input order: mix_group_step on their patch counts
+            layout, key = "flat", lambda t: folder_patch_count(t.shape[0], t.shape[1], p, r)
+            step = lambda counts, cnt: mix_group_step(counts, cnt, self._max_batch(), per_call)
+        else:                                                                   # only images of equal ORIGINAL size share a call
+            layout, key = "u8", lambda t: tuple(t.shape)
+            step = lambda shapes, s: _same_size_group_step(shapes, s, self.images_per_call_for(*(v // 4 for v in imageio.padded_size(s[0], s[1], 16, 4 * p)), r, samples=self._samples))
 
         def finish(g):
             g["done"].synchronize()
-            for k, name in enumerate(g["names"]):
-                mixed = isinstance(g["patches"], list)                         # a mixed-size call: every image has its own size and patch count
-                HW, patches = (g["HW"][k], g["patches"][k]) if mixed else (g["HW"], g["patches"])
+            for name, HW, patches in zip(g["names"], g["HW"], g["patches"]):
                 print(f"{name}: {HW[1]}x{HW[0]}, {patches} patches")
                 self.last_info.append((name, HW, patches))
             outputs.extend(g["kept"])
-            stds.extend(g.get("kept_std", ()))
+            stds.extend(g["kept_std"])
 
-        q, stop = queue.Queue(), threading.Event()
-        budget = _StageBudget(int(getattr(self.args, "prefetch_bytes", 2 << 30)), stop)
-        hungry = threading.Event()
-        feeder = threading.Thread(target=self._feed_folder, args=(items, r, q, stop, budget, hungry), name="wavedm-restore-feeder", daemon=True)
-        feeder.start()
-        try:
-            with torch.no_grad(), torch.cuda.device(d.device):
-                while True:
-                    try:
-                        staged = q.get_nowait()
-                    except queue.Empty:
-                        hungry.set()
-                        staged = q.get()
-                        hungry.clear()
-                    if staged is None:
-                        break
-                    if isinstance(staged, BaseException):
-                        raise staged
-                    u8, names, copied, pinned = staged[:4]
-                    shapes = staged[4] if len(staged) > 4 else None            # args.mix_sizes: a flat buffer of images of these (H, W)
-                    budget.release(u8.numel() if pinned is not None else 0)
-                    out_paths = {}
-                    for name in names:
-                        o = os.path.splitext(name)[0] + ".png"
-                        if o in taken:
-                            raise ValueError(f"restore_folder: {taken[o]!r} and {name!r} would both be written to {o!r}")
-                        taken[o] = name
-                        if self._save_std:                                     # (an iterable without a list of names: the same rule, as the files come)
-                            so = std_output_name(name)
-                            if so in taken:
-                                raise ValueError(f"restore_folder: the spread map of {name!r} and the output of {taken[so]!r} would both be written to {so!r} (--save-std)")
-                            taken[so] = name
-                        out_paths[name] = os.path.join(dst, *o.split("/")) if write else None
-                        results.append((name, out_paths[name]))
-                    cur = torch.cuda.current_stream(d.device)
-                    cur.wait_event(copied)
-                    u8.record_stream(cur)                                      # (allocated on the feeder's copy stream)
-                    if shapes is None:
-                        n, H, W = u8.shape[:3]
-                        image = lambda k: u8[k:k + 1]
-                        shape = lambda k: (H, W)
-                        together = n == 1 or self._fits(H, W, n, r)[0]
+        with torch.no_grad(), torch.cuda.device(d.device), _Pipeline(self, items(), layout, key, step, _is_auto(per_call), finish) as pipe:
+            for staged in pipe:
+                u8, names, n = staged.dev, staged.names, len(staged.names)
+                out_paths = {}
+                for name in names:
+                    o = _claim_output_names(taken, name, self._save_std)
+                    out_paths[name] = os.path.join(dst, *o.split("/")) if write else None
+                    results.append((name, out_paths[name]))
+                if mix:                                                         # a flat buffer of images of these (H, W)
+                    shapes = staged.shapes
+                    offs = [sum(3 * h * w for (h, w) in shapes[:k]) for k in range(n)]
+                    image = lambda k: u8[offs[k]:offs[k] + 3 * shapes[k][0] * shapes[k][1]].view((1,) + tuple(shapes[k]) + (3,))
+                    together = n == 1 or self._fits_mixed(shapes, r)[0]
+                else:
+                    shapes = [tuple(u8.shape[1:3])] * n
+                    image = lambda k: u8[k:k + 1]
+                    together = n == 1 or self._fits(*shapes[0], n, r)[0]
+                # a group that does not fit runs one image per call; one image that does not fit is refused before any kernel of it is launched
+                for lo, hi in ([(0, n)] if together else [(k, k + 1) for k in range(n)]):
+                    if hi - lo == 1:
+                        H, W = shapes[lo]
+                        ok, est, limit = self._fits(H, W, 1, r)
+                        if not ok:
+                            raise RuntimeError(f"restore_folder: {names[lo]!r} ({W}x{H})" + (f" with its {self._samples} samples" if self._samples > 1 else "") +
+                                               f" needs an estimated {est} bytes of device memory, "
+                                               f"{int(limit)} are available (args.max_restore_bytes, else 0.8 of the free memory)")
+                    self.last_calls.append(tuple(names[lo:hi]))
+                    if hi - lo == 1:                                            # one image, in either mode: the plain path (the same bits either way)
+                        g = self._launch_folder_group(image(lo), names[lo:hi], r, out_paths, keep_outputs)
+                    elif mix:
+                        g = self._launch_mixed_group([image(k) for k in range(lo, hi)], names[lo:hi], r, out_paths, keep_outputs)
                     else:
-                        n = len(names)
-                        offs = [sum(3 * h * w for (h, w) in shapes[:k]) for k in range(n)]
-                        image = lambda k: u8[offs[k]:offs[k] + 3 * shapes[k][0] * shapes[k][1]].view((1,) + tuple(shapes[k]) + (3,))
-                        shape = lambda k: shapes[k]
-                        together = n == 1 or self._fits_mixed(shapes, r)[0]
-                    # a group that does not fit runs one image per call; one image that does not fit is refused before any kernel of it is launched
-                    calls = [(0, n)] if together else [(k, k + 1) for k in range(n)]
-                    for lo, hi in calls:
-                        if hi - lo == 1:
-                            H, W = shape(lo)
-                            ok, est, limit = self._fits(H, W, 1, r)
-                            if not ok:
-                                raise RuntimeError(f"restore_folder: {names[lo]!r} ({W}x{H})" + (f" with its {self._samples} samples" if self._samples > 1 else "") +
-                                                   f" needs an estimated {est} bytes of device memory, "
-                                                   f"{int(limit)} are available (args.max_restore_bytes, else 0.8 of the free memory)")
-                        self.last_calls.append(tuple(names[lo:hi]))
-                        if shapes is None:
-                            g = self._launch_folder_group(u8[lo:hi], names[lo:hi], r, out_paths, keep_outputs)      # group k queued behind group k - 1 ...
-                        elif hi - lo == 1:                                     # one image: the plain path (the same bits either way)
-                            g = self._launch_folder_group(image(lo), names[lo:hi], r, out_paths, keep_outputs)
-                        else:
-                            g = self._launch_mixed_group([image(k) for k in range(lo, hi)], names[lo:hi], r, out_paths, keep_outputs)
-                        self._mark("main: group queued")
-                        pending.append(g)
-                        while len(pending) > 1:
-                            finish(pending.pop(0))                             # ... before the host waits for k - 1
-                while pending:
-                    finish(pending.pop(0))
-        finally:
-            stop.set()
-            budget.wake()
-            feeder.join()
-        if self.writer is not None:
-            self.writer.flush()
+                        g = self._launch_folder_group(u8, names, r, out_paths, keep_outputs)
+                    pipe.queued(g)                                              # call k queued behind call k - 1 before the host waits for k - 1
+        self._end_call()
         self.last_outputs = outputs
-        self.last_stds = stds                                                   # keep_outputs with args.save_std: the cropped f32 (1,3,H,W) spread maps
+        self.last_stds = stds                                                 # keep_outputs with args.save_std: the cropped f32 (1,3,H,W) spread maps
         return results
 
     def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None, samples=1):
