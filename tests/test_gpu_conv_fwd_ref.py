@@ -94,6 +94,10 @@ CONV = [
     (0, 96, 160, 1, 16, 48, H, {}, "convdma_3x3s1_t16x16x1_bn128"),                        # ragged N tile, 16 x 48 map
     (0, 64, 256, 1, 16, 32, H, {"WDM_BN256": "2"}, "convdma_3x3s1_t16x16x1_bn256"),       # 256 x 256 tile, 16 x 32 map
     (0, 64, 128, 2, 32, 16, H, {"WDM_BN256": "2"}, "convdma_3x3s1_t32x16x1_bn128"),       # 512 x 128 tile, 32 x 16 map
+    # ONE K slab: every prefetch "one slab ahead" is the clamped copy and no halo slab is transformed inside the loop -- each ring schedule of conv_dma3x3.h
+    (0, 32, 128, 1, 16, 16, H, {}, "convdma_3x3s1_t16x16x1_bn128"),                        # ... ring of four
+    (0, 32, 256, 1, 16, 16, H, {"WDM_BN256": "2"}, "convdma_3x3s1_t16x16x1_bn256"),       # ... ring of two
+    (0, 32, 128, 1, 32, 16, H, {"WDM_BN256": "2"}, "convdma_3x3s1_t32x16x1_bn128"),       # ... ring of three
     (0, 256, 192, 3, 8, 8, H, {}, "convdma8_3x3s1_t8x8x2_bn48"),                           # 8 x 8 LDS-DMA, Cout % 48 == 0, odd B
     (0, 1280, 256, 3, 8, 8, H, {}, "convdma8_3x3s1_t8x8x2_bn64"),                          # ... bn64, Cin 1280
     (2, 128, 128, 3, 8, 8, H, {}, "convup4_2x2x4_t8x8x4"),                                  # sub-pixel Upsample of 8 x 8 maps
@@ -112,6 +116,9 @@ CONV = [
     (0, 48, 136, 1, 16, 32, ("f32x3",), {}, "convdmax3_3x3s1_t16x16x1_bn128"),             # ragged N tile, Cin % 32 != 0
     (0, 64, 256, 1, 16, 32, ("f32x3",), {"WDM_BN256": "2"}, "convdmax3_3x3s1_t16x16x1_bn256"),
     (0, 64, 128, 2, 32, 16, ("f32x3",), {"WDM_BN256": "2"}, "convdmax3_3x3s1_t32x16x1_bn128"),
+    (0, 16, 128, 1, 16, 16, ("f32x3",), {}, "convdmax3_3x3s1_t16x16x1_bn128"),             # one K slab (16 channels): ring of four,
+    (0, 16, 256, 1, 16, 16, ("f32x3",), {"WDM_BN256": "2"}, "convdmax3_3x3s1_t16x16x1_bn256"),      # ... of two,
+    (0, 16, 128, 1, 32, 16, ("f32x3",), {"WDM_BN256": "2"}, "convdmax3_3x3s1_t32x16x1_bn128"),      # ... of three
     (0, 96, 144, 3, 8, 8, ("f32x3",), {}, "convdma8x3_3x3s1_t8x8x2_bn48"),
     (0, 256, 128, 3, 8, 8, ("f32x3",), {}, "convdma8x3_3x3s1_t8x8x2_bn64"),
     (2, 128, 128, 3, 8, 8, ("f32x3",), {}, "convup4x3_2x2x4_t8x8x4"),
@@ -218,6 +225,7 @@ BLOCKS = [
     (64, 0, 128, 1, 64, 1, A, {}, {"h16": ["+1x1"], "f32x3": ["+1x1"]}),                                        # 64 x 64, fused shortcut
     (768, 512, 256, 1, 16, 1, H, {}, {"h16": ["convdma_3x3s1"]}),                                                # concat: group 19 of 40 channels straddles the seam
     (384, 256, 256, 2, 16, 2, ("f32x3", "f32"), {}, {"f32x3": ["convdmax3"]}),                                 # concat, 20-channel groups: group 19 straddles
+    (32, 0, 128, 1, 16, 1, H, {}, {"h16": ["convdma_3x3s1_t16x16x1"]}),                                          # conv1 is ONE K slab under the GroupNorm prologue (one channel per group)
     (256, 0, 256, 3, 8, 3, A, {}, {"h16": ["convdma8_3x3s1"]}),                                                  # 8 x 8: GroupNorm pass, odd B
     (384, 0, 256, 2, 8, 1, H, {}, {"h16": ["convdma8_3x3s1", "+1x1"]}),                                         # 8 x 8, fused shortcut
     (128, 0, 256, 2, 32, 2, H, {"WDM_CONV_DMA": "0"}, {"h16": ["conv_3x3s1", "conv_1x1"]}),                    # register-staged, 1x1 shortcut as its own GEMM

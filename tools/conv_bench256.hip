@@ -48,7 +48,6 @@ int main(int argc, char** argv) {
     const int rounds = getenv("ROUNDS") ? atoi(getenv("ROUNDS")) : 3, iters = getenv("IT") ? atoi(getenv("IT")) : 10;
     using C128 = ConvDmaCfg;
     using C256 = ConvDma256Cfg<4, 2, 4, 8, 16>;
-    using C256h = ConvDma256Cfg<2, 4, 4, 4, 8>;
     std::vector<Variant> vars = {
         {"t256x128", conv_dma_kernel<false>, C128::LDS_BYTES, 16, 128, 0},
         {"t256x128P", conv_dma_kernel<true>, C128::LDS_BYTES, 16, 128, 0},
