@@ -172,6 +172,26 @@ int wdm_ddim_update_ragged(wdm_handle* h, const float* eps, const int32_t* patch
                            const int32_t* img_tab, const int32_t* blk_tab, const int64_t* pix_off, int nimg, int nblk, float sqrt_1m_at,
                            float sqrt_at, float sqrt_at_next, float c2, float* x0_out, float* x_next_out, void* stream);
 
+/* ---- DPM-Solver++(2M) multistep update (no reference counterpart, whose only integrator is the DDIM step) ----------------
+ * The scatter-mean of wdm_ddim_update_c, wdm_ddim_from_sums_c and wdm_ddim_update_ragged followed by the second-order multistep rule for the
+ * probability-flow ODE instead of the DDIM step:
+ *   x0     = (x_t - eps*sqrt_1m_at)/sqrt_at                    -- the expression, and for the same inputs the bits, of the DDIM entry points
+ *   x_next = fma(cp, x0_prev, fma(c0, x0, cx * x_t))           -- three roundings, the same in all three entry points
+ *   x0_prev : the previous step's x0_out, the shape of x_t; may not alias x0_out or x_next_out
+ *   cx, c0, cp : host floats (wavedm_amd.sampling.solver_coefficients): cx = sigma_next/sigma_t, c0 = g (1 + 1/(2r)), cp = -g/(2r),
+ *                g = alpha_next (1 - exp(-h)), h the step's log-SNR gap and r the ratio of the previous gap to it.
+ * Argument order, patch-list rules, 0/0 = NaN on uncovered pixels, refusals (WDM_EINVAL, nothing launched) and grid limits are those of the DDIM
+ * sibling; a null x0_prev is WDM_EINVAL.  The sharded pair is wdm_patch_accumulate_c, unchanged, then wdm_multistep_from_sums_c.
+ * Additions to the ABI: WDM_ABI_VERSION stays 1. */
+int wdm_multistep_update_c(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t,
+                           const float* x0_prev, int nimg, int H, int W, float sqrt_1m_at, float sqrt_at, float cx, float c0, float cp,
+                           float* x0_out, float* x_next_out, void* stream);
+int wdm_multistep_from_sums_c(wdm_handle* h, const float* acc_cnt, const float* x_t, const float* x0_prev, int channels, int nimg, int H, int W,
+                              float sqrt_1m_at, float sqrt_at, float cx, float c0, float cp, float* x0_out, float* x_next_out, void* stream);
+int wdm_multistep_update_ragged(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t,
+                                const float* x0_prev, const int32_t* img_tab, const int32_t* blk_tab, const int64_t* pix_off, int nimg, int nblk,
+                                float sqrt_1m_at, float sqrt_at, float cx, float c0, float cp, float* x0_out, float* x_next_out, void* stream);
+
 /* NCHW f32 (B,C,H,W) -> NHWC dtype (B,H,W,C) and back (used by the drop-in model(x, t) call). */
 int wdm_nchw_to_nhwc(wdm_handle* h, const float* src, void* dst, int B, int C, int H, int W, int dtype,
                      void* stream);

@@ -12,7 +12,7 @@ OWN SIZE, without ground truth and without the evaluation protocol's 720x480 res
 --output/<same relative name>.png; one line per image, then `restored N images in T s (X img/s)`.  Under torchrun the files are split over the ranks.
 --config is a file name under ./configs or a path.  Under torchrun every rank restores its share of the validation images (the
 loaders use a DistributedSampler) and rank 0 prints the PSNR over all of them; training all-reduces gradients over RCCL.
-Extras: --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train),
+Extras: --solver {ddim,dpmpp2m} and --x0_index K (eval, restore: the sampler's integrator and which x0 prediction becomes the image), --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train),
 --hfrm-local [--hfrm-base-size H W] [--hfrm-train-size H W] (eval, restore: the HFRM's channel attention pools over a window instead of the whole image)."""
 import argparse
 import os
@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import wavedm_amd                                       # noqa: E402
 from wavedm_amd import datasets                         # noqa: E402
 from wavedm_amd.config import load_config               # noqa: E402
+from wavedm_amd.sampling import SOLVERS, resolve_x0_index      # noqa: E402
 
 
 def parse(argv=None):
@@ -38,7 +39,14 @@ def parse(argv=None):
     ap.add_argument("--config", required=True, help="YAML file (name under ./configs, or a path)")
     ap.add_argument("--resume", default="", help="diffusion checkpoint (*.pth.tar) to evaluate / to resume from")
     ap.add_argument("--grid_r", type=int, default=16, help="stride of the overlapping patch grid (wavelet-domain pixels)")
-    ap.add_argument("--sampling_timesteps", type=int, default=25, help="DDIM steps")
+    ap.add_argument("--sampling_timesteps", type=int, default=25, help="sampling steps (UNet sweeps over the patch list)")
+    ap.add_argument("--solver", default="ddim", choices=list(SOLVERS),
+                    help="eval, restore: the sampler's integrator.  ddim (default): the reference's first-order step.  dpmpp2m: DPM-Solver++(2M), second order from the "
+                         "previous step's x0 prediction at no further UNet call; the first and the last two steps stay first-order (DESIGN.md 3.5.3), so up to 3 steps it "
+                         "is ddim.  Meant for fewer --sampling_timesteps; its effect on a trained model's restoration quality has not been measured.")
+    ap.add_argument("--x0_index", type=int, default=None, metavar="K",
+                    help="eval, restore: which x0 prediction becomes the image, a negative index -sampling_timesteps <= K <= -1; with early stop the steps behind it are "
+                         "not run.  Default: -5 with --solver ddim (the reference's x0_preds[-5]), -1 with --solver dpmpp2m (the solver's solution)")
     ap.add_argument("--test_set", default="raindrop")
     ap.add_argument("--image_folder", default="results/images", help="where restored images / validation sheets are written")
     ap.add_argument("--seed", type=int, default=61)
@@ -71,6 +79,13 @@ def parse(argv=None):
                          "standard deviation of the samples' unclamped pixels")
     ap.add_argument("--std_gain", type=float, default=8.0, help="with --save-std: the factor the standard deviation is multiplied by before the 8-bit conversion")
     a = ap.parse_args(argv)
+    if a.mode == "train" and (a.solver != "ddim" or a.x0_index is not None):
+        ap.error("--solver and --x0_index are test-time options (eval, restore)")
+    if a.x0_index is not None:
+        try:
+            resolve_x0_index(a.x0_index, a.solver, a.sampling_timesteps, "--x0_index")
+        except ValueError as e:
+            ap.error(str(e))
     if a.samples < 1:
         ap.error("--samples needs at least 1")
     if a.samples > 1 and a.mode == "train":

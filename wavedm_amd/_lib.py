@@ -76,6 +76,9 @@ def lib():
         "wdm_ddim_from_sums_c": (i, [vp, vp, vp, i, i, i, i, f, f, f, f, vp, vp, vp]),
         "wdm_pack_channels_ragged": (i, [vp, vp, i, vp, vp, i, vp, i, i, vp, i, i, i, vp]),
         "wdm_ddim_update_ragged": (i, [vp, vp, vp, i, i, i, vp, vp, vp, vp, i, i, f, f, f, f, vp, vp, vp]),
+        "wdm_multistep_update_c": (i, [vp, vp, vp, i, i, i, vp, vp, i, i, i, f, f, f, f, f, vp, vp, vp]),
+        "wdm_multistep_from_sums_c": (i, [vp, vp, vp, vp, i, i, i, i, f, f, f, f, f, vp, vp, vp]),
+        "wdm_multistep_update_ragged": (i, [vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, i, i, f, f, f, f, f, vp, vp, vp]),
         "wdm_nchw_to_nhwc": (i, [vp, vp, vp, i, i, i, i, i, vp]),
         "wdm_nhwc_to_nchw": (i, [vp, vp, vp, i, i, i, i, i, vp]),
         "wdm_unet_create": (i, [vp, C.POINTER(UNetConfig), C.POINTER(vp)]),
@@ -169,7 +172,8 @@ def lib():
 
 EXPORTED = ["wdm_abi_version", "wdm_last_error", "wdm_create", "wdm_destroy", "wdm_dwt_fwd", "wdm_dwt_inv",
             "wdm_pack_channels", "wdm_ddim_update", "wdm_ddim_update_eta", "wdm_patch_accumulate", "wdm_ddim_from_sums",
-            "wdm_ddim_update_c", "wdm_ddim_update_eta_c", "wdm_patch_accumulate_c", "wdm_ddim_from_sums_c", "wdm_pack_channels_ragged", "wdm_ddim_update_ragged", "wdm_nchw_to_nhwc", "wdm_nhwc_to_nchw", "wdm_unet_create",
+            "wdm_ddim_update_c", "wdm_ddim_update_eta_c", "wdm_patch_accumulate_c", "wdm_ddim_from_sums_c", "wdm_pack_channels_ragged", "wdm_ddim_update_ragged",
+            "wdm_multistep_update_c", "wdm_multistep_from_sums_c", "wdm_multistep_update_ragged", "wdm_nchw_to_nhwc", "wdm_nhwc_to_nchw", "wdm_unet_create",
             "wdm_unet_destroy", "wdm_unet_num_params", "wdm_unet_param_info", "wdm_unet_packed_bytes",
             "wdm_unet_set_packed", "wdm_unet_load_param", "wdm_unet_mark_loaded", "wdm_unet_workspace_bytes",
             "wdm_unet_forward", "wdm_unet_temb_rows", "wdm_unet_temb_table", "wdm_unet_forward_temb", "wdm_resblock_forward", "wdm_attn_forward", "wdm_conv_forward", "wdm_temb_forward",

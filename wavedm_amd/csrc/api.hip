@@ -139,6 +139,25 @@ int wdm_ddim_update_ragged(wdm_handle* h, const float* eps, const int32_t* patch
     return k_ddim_update_ragged(eps, patches, n, p, channels, x_t, img_tab, blk_tab, pix_off, nimg, nblk, sqrt_1m_at, sqrt_at, sqrt_at_next, c2, x0_out, x_next_out,
                                 (hipStream_t)stream);
 }
+// the DPM-Solver++(2M) multistep update: the argument order, refusals and grid limits of the DDIM entry points above, x0_prev behind x_t
+int wdm_multistep_update_c(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t, const float* x0_prev, int nimg,
+                           int H, int W, float sqrt_1m_at, float sqrt_at, float cx, float c0, float cp, float* x0_out, float* x_next_out, void* stream) {
+    if (!h || !eps || !x_t || !x0_prev || !x0_out || !x_next_out) WDM_FAIL(WDM_EINVAL, "wdm_multistep_update_c: null argument");
+    return k_multistep_update_c(eps, patches, n, p, channels, x_t, x0_prev, nimg, H, W, sqrt_1m_at, sqrt_at, cx, c0, cp, x0_out, x_next_out, (hipStream_t)stream);
+}
+int wdm_multistep_from_sums_c(wdm_handle* h, const float* acc_cnt, const float* x_t, const float* x0_prev, int channels, int nimg, int H, int W, float sqrt_1m_at,
+                              float sqrt_at, float cx, float c0, float cp, float* x0_out, float* x_next_out, void* stream) {
+    if (!h || !acc_cnt || !x_t || !x0_prev || !x0_out || !x_next_out || channels <= 0) WDM_FAIL(WDM_EINVAL, "wdm_multistep_from_sums_c: null argument");
+    return k_multistep_from_sums(acc_cnt, x_t, x0_prev, nimg, H, W, sqrt_1m_at, sqrt_at, cx, c0, cp, x0_out, x_next_out, (hipStream_t)stream, channels);
+}
+int wdm_multistep_update_ragged(wdm_handle* h, const float* eps, const int32_t* patches, int n, int p, int channels, const float* x_t, const float* x0_prev,
+                                const int32_t* img_tab, const int32_t* blk_tab, const int64_t* pix_off, int nimg, int nblk, float sqrt_1m_at, float sqrt_at,
+                                float cx, float c0, float cp, float* x0_out, float* x_next_out, void* stream) {
+    if (!h || !eps || !patches || !x_t || !x0_prev || !img_tab || !blk_tab || !pix_off || !x0_out || !x_next_out)
+        WDM_FAIL(WDM_EINVAL, "wdm_multistep_update_ragged: null argument");
+    return k_multistep_update_ragged(eps, patches, n, p, channels, x_t, x0_prev, img_tab, blk_tab, pix_off, nimg, nblk, sqrt_1m_at, sqrt_at, cx, c0, cp, x0_out,
+                                     x_next_out, (hipStream_t)stream);
+}
 int wdm_nchw_to_nhwc(wdm_handle* h, const float* src, void* dst, int B, int C, int H, int W, int dtype, void* stream) {
     if (!h || !src || !dst) WDM_FAIL(WDM_EINVAL, "wdm_nchw_to_nhwc: null argument");
     return k_nchw_to_nhwc(src, dst, B, C, H, W, dtype, (hipStream_t)stream);

@@ -151,6 +151,14 @@ int k_pack_channels_ragged(const float* src, int nch, const int32_t* img_tab, co
                            int c_total, int c_off, int dtype, hipStream_t s);
 int k_ddim_update_ragged(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, const int32_t* img_tab, const int32_t* blk_tab,
                          const int64_t* pix_off, int nimg, int nblk, float s1m, float sa, float san, float c2, float* x0, float* xn, hipStream_t s);
+// the same four forms with the DPM-Solver++(2M) multistep update (multistep_store): x_next = cx * x_t + c0 * x0 + cp * x0_prev
+int k_multistep_update_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, const float* x0_prev, int nimg, int H, int W, float s1m,
+                         float sa, float cx, float c0, float cp, float* x0, float* xn, hipStream_t s);
+int k_multistep_from_sums(const float* acc_cnt, const float* x_t, const float* x0_prev, int nimg, int H, int W, float s1m, float sa, float cx, float c0, float cp,
+                          float* x0, float* xn, hipStream_t s, int C);
+int k_multistep_update_ragged(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, const float* x0_prev, const int32_t* img_tab,
+                              const int32_t* blk_tab, const int64_t* pix_off, int nimg, int nblk, float s1m, float sa, float cx, float c0, float cp, float* x0,
+                              float* xn, hipStream_t s);
 int k_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, int dtype, hipStream_t s);
 int k_nhwc_to_nchw(const void* src, float* dst, int B, int C, int H, int W, int dtype, hipStream_t s);
 // GroupNorm(32, eps): partial statistics float4[B][nslab][C] = (pivot, sum(x-K), sum((x-K)^2), n) and their finalisation

@@ -270,6 +270,17 @@ __device__ __forceinline__ void ddim_store(long long id, float et, const float* 
     x0o[id] = x0;
     xno[id] = noise ? san * x0 + c1 * noise[id] + c2 * et : san * x0 + c2 * et;
 }
+// The DPM-Solver++(2M) update of element `id`: x0 is ddim_store's expression, written the same way -- the same bits for the same inputs --,
+// x_next = cx * x_t + c0 * x0 + cp * x0_prev with the previous step's x0 prediction.  The contraction is spelled out (one product, two fmas) instead of left to
+// the compiler, which settles it kernel by kernel (the comments below): the four forms that call this must agree to the bit.  A function of its own beside
+// ddim_store, not a second mode of it: the kernels around ddim_store keep their instruction streams.
+__device__ __forceinline__ void multistep_store(long long id, float et, const float* x_t, const float* x0_prev, float s1m, float sa, float cx, float c0, float cp,
+                                                float* x0o, float* xno) {
+    const float xt = x_t[id];
+    const float x0 = (xt - et * s1m) / sa;
+    x0o[id] = x0;
+    xno[id] = __builtin_fmaf(cp, x0_prev[id], __builtin_fmaf(c0, x0, cx * xt));
+}
 
 // Pixel (yy, xx) of image img walks the entries [lo, hi) of the patch list ONCE for its CH channels c0 .. c0 + CH - 1: one coverage test per (pixel, patch), CH
 // accumulators in registers, each summed in patch-list order in fp32.  Entries of other images inside the span are skipped, so any span that holds the image's
@@ -476,6 +487,125 @@ int k_ddim_update_ragged(const float* eps, const int32_t* patches, int n, int p,
         constexpr int CH = decltype(ch)::value;
         hipLaunchKernelGGL((scatter_update_ragged_kernel<CH>), dim3(nblk, (C + CH - 1) / CH), dim3(256), 0, s, eps, patches, n, p, C, x_t, img_tab, blk_tab, pix_off,
                            nimg, s1m, sa, san, c2, x0, xn, (const float*)nullptr, 0.f);
+    });
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
+// ---- scatter-mean + DPM-Solver++(2M) multistep update: the four forms of the DDIM update above around multistep_store -- list, element-wise
+// identity, from all-reduced sums (wdm_patch_accumulate_c feeds it unchanged), ragged.  The same walk (span_walk: sums in patch-list order, 0 / 0 = NaN where no
+// patch covers a pixel), the same thread layout and channel-chunk rule, one stream more to read (x0_prev), cx / c0 / cp in place of san / c2.  Kernels of their
+// own, not template modes of the DDIM ones, so that those compile to what they always did.  (ch0: the thread's first channel; c0 is a coefficient here.)
+template <int CH>
+__global__ __launch_bounds__(256) void scatter_multistep_c_kernel(const float* __restrict__ eps, const int32_t* __restrict__ patches, int n, int p, int C,
+                                                                  const float* __restrict__ x_t, const float* __restrict__ x0_prev, int H, int W, float s1m,
+                                                                  float sa, float cx, float c0, float cp, float* __restrict__ x0o, float* __restrict__ xno) {
+    __shared__ int s_lo[4], s_hi[4];
+    const int img = blockIdx.y, ch0 = blockIdx.z * CH;
+    const int HW = H * W;
+    int lo = n, hi = 0;
+    for (int k = threadIdx.x; k < n; k += 256)
+        if (patches[3 * k] == img) { lo = min(lo, k); hi = max(hi, k + 1); }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    lo = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
+    hi = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= HW) return;
+    const int yy = pix / W, xx = pix - yy * W;
+    float acc[CH], cnt = 0.f;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) acc[j] = 0.f;
+    span_walk<CH>(eps, patches, lo, hi, img, yy, xx, p, C, ch0, acc, cnt);
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        if (ch0 + j >= C) continue;
+        multistep_store(((long long)img * C + ch0 + j) * HW + pix, acc[j] / cnt, x_t, x0_prev, s1m, sa, cx, c0, cp, x0o, xno);
+    }
+}
+__global__ __launch_bounds__(256) void multistep_update_identity_kernel(const float* __restrict__ eps, const float* __restrict__ x_t,
+                                                                        const float* __restrict__ x0_prev, long long total, float s1m, float sa, float cx, float c0,
+                                                                        float cp, float* __restrict__ x0o, float* __restrict__ xno) {
+#pragma clang loop vectorize(disable) interleave(disable)      // (else the grid-stride loop is interleaved by two behind a 64-bit trip-count division)
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x)
+        multistep_store(id, eps[id], x_t, x0_prev, s1m, sa, cx, c0, cp, x0o, xno);
+}
+__global__ __launch_bounds__(256) void multistep_from_sums_kernel(const float* __restrict__ acc_cnt, const float* __restrict__ x_t,
+                                                                  const float* __restrict__ x0_prev, long long total, float s1m, float sa, float cx, float c0,
+                                                                  float cp, float* __restrict__ x0o, float* __restrict__ xno) {
+#pragma clang loop vectorize(disable) interleave(disable)      // (else the grid-stride loop is interleaved by two behind a 64-bit trip-count division)
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x)
+        multistep_store(id, acc_cnt[id] / acc_cnt[total + id], x_t, x0_prev, s1m, sa, cx, c0, cp, x0o, xno);
+}
+template <int CH>
+__global__ __launch_bounds__(256) void scatter_multistep_ragged_kernel(const float* __restrict__ eps, const int32_t* __restrict__ patches, int n, int p, int C,
+                                                                       const float* __restrict__ x_t, const float* __restrict__ x0_prev,
+                                                                       const int32_t* __restrict__ img_tab, const int32_t* __restrict__ blk_tab,
+                                                                       const int64_t* __restrict__ pix_off, int nimg, float s1m, float sa, float cx, float c0,
+                                                                       float cp, float* __restrict__ x0o, float* __restrict__ xno) {
+    const int blk = blockIdx.x, ch0 = blockIdx.y * CH;
+    int a = 0, b = nimg;                       // blk_tab[a] <= blk < blk_tab[b]
+    while (b - a > 1) {
+        const int m = (a + b) >> 1;
+        if (blk_tab[m] <= blk) a = m; else b = m;
+    }
+    const int img = a;
+    const int H = img_tab[4 * img], W = img_tab[4 * img + 1];
+    const int lo = max(img_tab[4 * img + 2], 0), hi = min(img_tab[4 * img + 3], n);
+    const int HW = H * W;
+    const int pix = (blk - blk_tab[img]) * 256 + threadIdx.x;
+    if (pix >= HW) return;
+    const int yy = pix / W, xx = pix - yy * W;
+    float acc[CH], cnt = 0.f;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) acc[j] = 0.f;
+    span_walk<CH>(eps, patches, lo, hi, img, yy, xx, p, C, ch0, acc, cnt);
+    const long long base = (long long)C * pix_off[img];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        if (ch0 + j >= C) continue;
+        multistep_store(base + (long long)(ch0 + j) * HW + pix, acc[j] / cnt, x_t, x0_prev, s1m, sa, cx, c0, cp, x0o, xno);
+    }
+}
+
+int k_multistep_update_c(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, const float* x0_prev, int nimg, int H, int W, float s1m,
+                         float sa, float cx, float c0, float cp, float* x0, float* xn, hipStream_t s) {
+    if (int e = check_scatter_c("multistep_update_c", n, p, C, nimg, H, W, patches != nullptr)) return e;
+    if (patches == nullptr) {
+        if (p != H || p != W || n != nimg) WDM_FAIL(WDM_EINVAL, "multistep_update_c: identity patch list needs n == nimg, p == H == W");
+        const long long total = (long long)nimg * C * H * W;
+        hipLaunchKernelGGL(multistep_update_identity_kernel, dim3(elementwise_grid(total)), dim3(256), 0, s, eps, x_t, x0_prev, total, s1m, sa, cx, c0, cp, x0, xn);
+        WDM_HIP(hipGetLastError());
+        return WDM_OK;
+    }
+    const int pixblocks = nblocks((long long)H * W, 256);
+    with_channels_per_thread((long long)pixblocks * nimg, C, [&](auto ch) {
+        constexpr int CH = decltype(ch)::value;
+        hipLaunchKernelGGL((scatter_multistep_c_kernel<CH>), dim3(pixblocks, nimg, (C + CH - 1) / CH), dim3(256), 0, s, eps, patches, n, p, C, x_t, x0_prev, H, W,
+                           s1m, sa, cx, c0, cp, x0, xn);
+    });
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+int k_multistep_from_sums(const float* acc_cnt, const float* x_t, const float* x0_prev, int nimg, int H, int W, float s1m, float sa, float cx, float c0, float cp,
+                          float* x0, float* xn, hipStream_t s, int C) {
+    const long long total = (long long)nimg * C * H * W;
+    if (total <= 0) WDM_FAIL(WDM_EINVAL, "multistep_from_sums: empty image");
+    hipLaunchKernelGGL(multistep_from_sums_kernel, dim3(elementwise_grid(total)), dim3(256), 0, s, acc_cnt, x_t, x0_prev, total, s1m, sa, cx, c0, cp, x0, xn);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+int k_multistep_update_ragged(const float* eps, const int32_t* patches, int n, int p, int C, const float* x_t, const float* x0_prev, const int32_t* img_tab,
+                              const int32_t* blk_tab, const int64_t* pix_off, int nimg, int nblk, float s1m, float sa, float cx, float c0, float cp, float* x0,
+                              float* xn, hipStream_t s) {
+    if (nimg < 1 || n < 1 || p < 1 || C < 1 || nblk < 1) WDM_FAIL(WDM_EINVAL, "multistep_update_ragged: bad arguments");
+    if (C > 65535) WDM_FAIL(WDM_EINVAL, "multistep_update_ragged: %d channels exceed the launch grid", C);
+    with_channels_per_thread(nblk, C, [&](auto ch) {
+        constexpr int CH = decltype(ch)::value;
+        hipLaunchKernelGGL((scatter_multistep_ragged_kernel<CH>), dim3(nblk, (C + CH - 1) / CH), dim3(256), 0, s, eps, patches, n, p, C, x_t, x0_prev, img_tab,
+                           blk_tab, pix_off, nimg, s1m, sa, cx, c0, cp, x0, xn);
     });
     WDM_HIP(hipGetLastError());
     return WDM_OK;

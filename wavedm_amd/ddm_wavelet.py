@@ -56,6 +56,13 @@ def _identity_generator(x):        # the stand-in for a missing HFRM checkpoint 
     return x
 
 
+def _resolve_solver(diffusion, solver, who, use_global=False):
+    """The `solver` keyword of the sampling calls: None -> args.solver, else "ddim"; what cannot run is refused here, before anything is launched."""
+    if solver is None:
+        solver = getattr(getattr(diffusion, "args", None), "solver", None) or "ddim"
+    return sampling.check_solver(solver, who, use_global=use_global)
+
+
 class DenoisingDiffusion_Wavelet(object):
     def __init__(self, args, config, generator=None, dtype=None, verbose=False):
         super().__init__()
@@ -269,8 +276,9 @@ class DenoisingDiffusion_Wavelet(object):
                                "sample_image(..., total=<whole image>, use_global=True)")
 
     def sample_image(self, x_cond, x, x_other=None, last=True, patch_locs=None, patch_size=None, total=None,
-                     use_global=False, use_other=False, stop_at=None, samples=1):
-        """ddm_wavelet.py:295-309.  `samples` (not in the reference; default 1): N trajectories per image in one sampler call -- x holds B * N start noises, sample k
+                     use_global=False, use_other=False, stop_at=None, samples=1, solver=None):
+        """ddm_wavelet.py:295-309.  `solver` (not in the reference; default args.solver, else "ddim", the reference's step): "ddim" or "dpmpp2m", the second-order
+        multistep rule of sampling.ddim_sample -- not with use_global.  `samples` (not in the reference; default 1): N trajectories per image in one sampler call -- x holds B * N start noises, sample k
         of image i in row i * N + k, x_cond / x_other B rows (sampling.ddim_sample).  `stop_at` (not in the reference; default None = every step, like the reference): a negative index k -- the caller reads
         nothing after x0_preds[k], so the steps behind it are skipped and the lists padded with None (sampling.ddim_sample).  DiffusiveRestoration.restore,
         which consumes x0_preds[-5] only (restoration.py:108), passes -5."""
@@ -285,6 +293,7 @@ class DenoisingDiffusion_Wavelet(object):
             raise ValueError("sample_image: samples > 1 is not built for the patch-sharded mode (patch_group)")
         if samples > 1 and x.shape[0] != samples * x_cond.shape[0]:
             raise ValueError(f"sample_image: x has {x.shape[0]} rows, x_cond {x_cond.shape[0]}: x.shape[0] must be samples * x_cond.shape[0] (samples = {samples})")
+        solver = _resolve_solver(self, solver, "sample_image", use_global=use_global)
         skip = self.config.diffusion.num_diffusion_timesteps // self.args.sampling_timesteps
         seq = range(0, self.config.diffusion.num_diffusion_timesteps, skip)
         if patch_locs is None:
@@ -293,19 +302,20 @@ class DenoisingDiffusion_Wavelet(object):
             # (generalized_steps starts from x as given whatever data.begin_from_noise says: there is no q-sample of x_cond on this path)
             self._require_plain_unet("sample_image(patch_locs=None)")
             xs = sampling.ddim_sample(self.model, x, x_cond, None, list(seq), self.betas, corners=None, max_batch=getattr(self.args, "max_batch", 64),
-                                      stop_at=stop_at, samples=samples)
+                                      stop_at=stop_at, samples=samples, solver=solver)
             return xs[0][-1] if last else xs
         xs = self.generalized_steps_overlapping(x, x_cond, seq, self.model, self.betas, eta=0., corners=patch_locs,
                                                 p_size=patch_size, total=total, use_global=use_global,
-                                                x_other=x_other, use_other=use_other, stop_at=stop_at, samples=samples)
+                                                x_other=x_other, use_other=use_other, stop_at=stop_at, samples=samples, solver=solver)
         if last:
             xs = xs[0][-1]
         return xs
 
-    def sample_image_ragged(self, x_cond, x, layout, x_other=None, use_other=False, stop_at=None):
+    def sample_image_ragged(self, x_cond, x, layout, x_other=None, use_other=False, stop_at=None, solver=None):
         """sample_image(last=False, patch_locs=<each image's grid>) for images of DIFFERENT sizes in one sampler call: x_cond, x (the start noise) and x_other are
         ragged tensors of `layout` (sampling.RaggedLayout).  eta = 0, one device, not captured into a hipGraph; every image's lists hold the bits it gets alone
-        (sampling.ddim_sample_ragged).  -> (xs, x0_preds), lists of flat tensors."""
+        (sampling.ddim_sample_ragged).  `solver`: as in sample_image.  -> (xs, x0_preds), lists of flat tensors."""
+        solver = _resolve_solver(self, solver, "sample_image_ragged")
         self._require_plain_unet("sample_image_ragged")
         if getattr(self, "patch_group", None) is not None:
             raise NotImplementedError("sample_image_ragged: the patch-sharded mode (patch_group) is not built for ragged calls")
@@ -321,11 +331,13 @@ class DenoisingDiffusion_Wavelet(object):
                 layout.view(x0, pc, i).copy_(layout.view(x_cond, nc, i)[:, :pc] * a.sqrt() + layout.view(x, pc, i) * (1.0 - a).sqrt())
             x = x0
         return sampling.ddim_sample_ragged(self.model, x, x_cond, x_other, layout, list(seq), self.betas,
-                                           max_batch=getattr(self.args, "max_batch", None) or sampling.DEFAULT_MAX_BATCH, stop_at=stop_at)
+                                           max_batch=getattr(self.args, "max_batch", None) or sampling.DEFAULT_MAX_BATCH, stop_at=stop_at, solver=solver)
 
     def generalized_steps_overlapping(self, x, x_cond, seq, model, b, eta=0., corners=None, p_size=None,
-                                      manual_batching=True, total=None, x_other=None, use_global=False, use_other=False, stop_at=None, samples=1):
-        """ddm_wavelet.py:437-506 on the device (eta != 0 included: :500-502, one randn_like(x) per step from the device generator)."""
+                                      manual_batching=True, total=None, x_other=None, use_global=False, use_other=False, stop_at=None, samples=1, solver="ddim"):
+        """ddm_wavelet.py:437-506 on the device (eta != 0 included: :500-502, one randn_like(x) per step from the device generator).  `solver`: "ddim", the
+        reference's step, or "dpmpp2m" (sampling.ddim_sample; eta = 0 only, not with use_global)."""
+        sampling.check_solver(solver, "generalized_steps_overlapping", eta=eta, use_global=use_global)
         if use_global:
             if samples != 1:
                 raise NotImplementedError("generalized_steps_overlapping: samples > 1 is not built for the use_global branch")
@@ -344,7 +356,7 @@ class DenoisingDiffusion_Wavelet(object):
             import torch.distributed as dist
             dist.broadcast(x, src=0, group=None if grp is True else grp)
         xs, x0_preds = sampling.ddim_sample(model, x, x_cond, x_other, list(seq), b, corners=corners, p_size=p_size,
-                                            max_batch=getattr(self.args, "max_batch", None) or sampling.DEFAULT_MAX_BATCH, patch_group=grp, eta=eta, stop_at=stop_at, samples=samples)
+                                            max_batch=getattr(self.args, "max_batch", None) or sampling.DEFAULT_MAX_BATCH, patch_group=grp, eta=eta, stop_at=stop_at, samples=samples, solver=solver)
         if self.verbose:
             for i_t, x0, xn in zip(reversed(list(seq)), x0_preds, xs[1:]):
                 if x0 is None:
@@ -402,14 +414,14 @@ class DenoisingDiffusion_Wavelet(object):
         _, c, h, w = x_cond.shape
         return sampling.overlapping_grid_indices(h, w, output_size, r)
 
-    def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None):
-        """ddm_wavelet.py:413-424.  `stop_at`: see sample_image."""
+    def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None, solver=None):
+        """ddm_wavelet.py:413-424.  `stop_at`, `solver`: see sample_image."""
         p_size = self.config.data.patch_size if self.config.data.wavelet_in_unet else self.config.data.image_size
         h_list, w_list = self.overlapping_grid_indices(x_cond, output_size=p_size, r=r)
         corners = [(i, j) for i in h_list for j in w_list]
         x = torch.randn((x_cond.shape[0], self.config.model.pred_channels, x_cond.shape[2], x_cond.shape[3]), device=self.device)
         return self.sample_image(x_cond, x, x_other=x_other, patch_locs=corners, last=last, patch_size=p_size,
-                                 total=total, use_global=use_global, use_other=use_other, stop_at=stop_at)
+                                 total=total, use_global=use_global, use_other=use_other, stop_at=stop_at, solver=solver)
 
     def restore(self, val_loader, validation="snow", r=None, epoch=0):
         """ddm_wavelet.py:340-411, the training loop's validation sheet: the first two items of `val_loader` are restored and
@@ -436,7 +448,7 @@ class DenoisingDiffusion_Wavelet(object):
                 use_other = bool(cfg.model.use_other_channels) and split
                 hf_wav = self.wavelet_dec(data_transform(self.generator(inp)).contiguous()) if split else None
                 _, x0_preds = self.diffusive_restoration(x_cond, x_other=hf_wav[:, ob:].contiguous() if use_other else None, r=r, last=False,
-                                                         use_global=False, use_other=use_other,
+                                                         use_global=False, use_other=use_other, solver="ddim",      # the sheet stays the reference's whatever args.solver says
                                                          stop_at=-5 if getattr(self.args, "early_stop", True) else None)      # only x_output_list[1][-5] is read (ddm_wavelet.py:378)
                 pred = x0_preds[-5]
                 rec = lambda lo, hi: inverse_data_transform(self.wavelet_rec(torch.cat([lo[:, :pc], hi[:, pc:]], dim=1).contiguous()))

@@ -415,6 +415,7 @@ class DiffusiveRestoration:
         self.save_images = save_images
         self.writer = None
         self._samples, self._save_std = 1, False
+        self._x0_index, self._solver_kw = -5, {}
         if os.path.isfile(getattr(args, "resume", "") or ""):
             self.diffusion.model.eval()                                        # restoration.py:23-25
         else:
@@ -437,6 +438,19 @@ class DiffusiveRestoration:
             raise ValueError(f"{what}: --save-std (args.save_std) needs --samples >= 2 (args.samples): the spread of one sample is undefined")
         gain = getattr(self.args, "std_gain", None)
         self._samples, self._save_std, self._std_gain = n, save_std, 8.0 if gain is None else float(gain)
+
+    def _solver_args(self, what):
+        """args.solver (default "ddim") and args.x0_index -- which entry of x0_preds becomes the image --, checked before anything runs.  x0_index None is -5
+        with ddim, the reference's x0_preds[-5] (restoration.py:108: the same launches, the same PNG bytes), and -1 with dpmpp2m, the solver's solution; whether
+        the run has that many steps is _check_steps' question."""
+        theirs = getattr(self.diffusion.args, "solver", None)                   # (sample_image's own default; usually the same args object)
+        solver = sampling.check_solver(getattr(self.args, "solver", None) or theirs or "ddim", what)
+        k = getattr(self.args, "x0_index", None)
+        if k is None:
+            self._x0_index = -5 if solver == "ddim" else -1
+        else:
+            self._x0_index = sampling.resolve_x0_index(k, solver, int(self.diffusion.args.sampling_timesteps), f"{what}: --x0_index (args.x0_index)")
+        self._solver_kw = {"solver": solver} if (solver != "ddim" or theirs) else {}
 
     # ---- grouping ---------------------------------------------------------------------------------------------------
     def _max_batch(self):
@@ -468,14 +482,15 @@ class DiffusiveRestoration:
     # ---- what a call reads of its options, once, after its refusals (_ensemble_args, _check_steps) ------------------
     def _check_steps(self):
         """restore_folder refuses before anything runs; restore() when its first group arrives, so that an empty loader still returns ([], [])."""
-        if int(self.diffusion.args.sampling_timesteps) < 5:
-            raise IndexError("x0_preds[-5] needs at least 5 sampling steps (restoration.py:108)")
+        k = self._x0_index
+        if int(self.diffusion.args.sampling_timesteps) < -k:
+            raise IndexError(f"x0_preds[{k}] needs at least {-k} sampling steps (restoration.py:108)")
 
     def _call_options(self, write):
         """args.early_stop -> the sampler's stop_at, args.seed (default 61), the sampler's `samples` keyword, args.ssim; the trace and the writer start here."""
         seed = getattr(self.args, "seed", None)
         self._seed = 61 if seed is None else seed
-        self._stop_at = -5 if bool(getattr(self.args, "early_stop", True)) else None
+        self._stop_at = self._x0_index if bool(getattr(self.args, "early_stop", True)) else None
         self._samples_kw = {"samples": self._samples} if self._samples != 1 else {}
         self._ssim = bool(getattr(self.args, "ssim", False))
         if os.environ.get("WAVEDM_RESTORE_TRACE", "0") == "1":
@@ -514,10 +529,10 @@ class DiffusiveRestoration:
         return x_cond, hf, hf_wav, x_other, split, use_other
 
     def _compose(self, x0_preds, hf_wav, split, want_coef=False):
-        """x0_preds[-5] (restoration.py:108) -> (image, spread map or None, the coefficients behind the image).  One sample: IDWT(cat([pred[:, :pc], hf_wav[:, pc:]]))
+        """x0_preds[args.x0_index] (-5: restoration.py:108) -> (image, spread map or None, the coefficients behind the image).  One sample: IDWT(cat([pred[:, :pc], hf_wav[:, pc:]]))
         -> clamp((x + 1) / 2) in one kernel (:114-115, :124, :134; all bands diffused: the second source contributes nothing).  args.samples: the mean of the
         samples' coefficients stands where the one sample's stood, and with want_coef it is handed back for the diagnostic images."""
-        pred, pc, rec = x0_preds[-5], self.config.model.pred_channels, self.diffusion.wavelet_rec
+        pred, pc, rec = x0_preds[self._x0_index], self.config.model.pred_channels, self.diffusion.wavelet_rec
         if self._samples == 1:
             return rec.compose(pred, hf_wav if split else pred, pc), None, pred
         return rec.compose_ensemble(pred, hf_wav if split else None, pc, self._samples, want_std=self._save_std, want_coef=want_coef)
@@ -544,7 +559,7 @@ class DiffusiveRestoration:
                 w.save(inp[sl], os.path.join(image_folder, f"{name}_cond.png"))
                 w.save(gt[sl], os.path.join(image_folder, f"{name}_gt.png"))
         xs, x0_preds = self.diffusive_restoration(x_cond, x_other=x_other, r=r, last=False, total=None,
-                                                  use_global=False, use_other=use_other, stop_at=self._stop_at, **self._samples_kw)
+                                                  use_global=False, use_other=use_other, stop_at=self._stop_at, **self._samples_kw, **self._solver_kw)
         x_output, x_std, pred = self._compose(x0_preds, hf_wav, split, want_coef=True)
         H, W = x_output.shape[-2:]
         # the three pairs the reference prints: output, "cond" (IDWT(DWT(x)) == x: the input), HFRM image (restoration.py:146 clamps x_output_wdnet first)
@@ -598,6 +613,7 @@ class DiffusiveRestoration:
         if cfg.model.pred_channels > cfg.model.in_channels:
             raise ValueError(f"model.pred_channels {cfg.model.pred_channels} exceeds the {cfg.model.in_channels} wavelet bands (model.in_channels)")
         self._ensemble_args("restore")
+        self._solver_args("restore")
         self._call_options(self.save_images)
         image_folder = os.path.join(self.args.image_folder, cfg.data.dataset, validation)
         acc = {"torch": [], "y": [], "wdnet": [], "ssim": [], "std": []}
@@ -659,7 +675,7 @@ class DiffusiveRestoration:
         h_list, w_list = sampling.overlapping_grid_indices(Hp // 4, Wp // 4, p, r)
         corners = [(i, j) for i in h_list for j in w_list]
         xs, x0_preds = d.sample_image(x_cond, noise, x_other=x_other, last=False, patch_locs=corners, patch_size=p, total=None,
-                                      use_global=False, use_other=use_other, stop_at=self._stop_at, **self._samples_kw)
+                                      use_global=False, use_other=use_other, stop_at=self._stop_at, **self._samples_kw, **self._solver_kw)
         out, std, _ = self._compose(x0_preds, hf_wav, split)                    # args.samples: the mean of the samples' coefficients -> one image; their per-pixel spread
         self._mark("main: sampler queued")
         s8 = None
@@ -710,8 +726,8 @@ class DiffusiveRestoration:
             i0 = i1
         for k, name in enumerate(names):
             layout.view(noise, pc, k).copy_(torch.randn((1, pc) + layout.sizes[k], device=dev, generator=torch.Generator(device=dev).manual_seed(file_seed(self._seed, name))))
-        xs, x0_preds = d.sample_image_ragged(x_cond, noise, layout, x_other=x_other, use_other=use_other, stop_at=self._stop_at)
-        pred = x0_preds[-5]
+        xs, x0_preds = d.sample_image_ragged(x_cond, noise, layout, x_other=x_other, use_other=use_other, stop_at=self._stop_at, **self._solver_kw)
+        pred = x0_preds[self._x0_index]
         self._mark("main: sampler queued")
         q8s, kept = [], []
         for k, name in enumerate(names):
@@ -754,6 +770,7 @@ class DiffusiveRestoration:
             raise NotImplementedError("DiffusiveRestoration.restore_folder: the patch-sharded mode (patch_group) is not built for folders; shard the FILES over the ranks (ImageFolder(shard=))")
         if cfg.model.pred_channels > cfg.model.in_channels:
             raise ValueError(f"model.pred_channels {cfg.model.pred_channels} exceeds the {cfg.model.in_channels} wavelet bands (model.in_channels)")
+        self._solver_args("restore_folder")
         self._check_steps()
         mix, per_call = bool(getattr(self.args, "mix_sizes", False)), getattr(self.args, "images_per_call", None)
         self._ensemble_args("restore_folder", mix=mix)
@@ -831,17 +848,17 @@ class DiffusiveRestoration:
         self.last_stds = stds                                                 # keep_outputs with args.save_std: the cropped f32 (1,3,H,W) spread maps
         return results
 
-    def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None, samples=1):
+    def diffusive_restoration(self, x_cond, x_other=None, r=None, last=True, total=None, use_global=False, use_other=False, stop_at=None, samples=1, solver=None):
         """restoration.py:170-185.  The start noise is drawn image by image (the reference sees one image per call), so a
         batched call consumes the generator exactly like the same images restored one after the other.  `stop_at`: see sample_image.
-        `samples`: one draw per (image, sample), image-major -- image 0's samples, then image 1's --, from the same generator."""
+        `samples`: one draw per (image, sample), image-major -- image 0's samples, then image 1's --, from the same generator.  `solver`: see sample_image."""
         p_size = self.config.data.patch_size if self.config.data.wavelet_in_unet else self.config.data.image_size
         h_list, w_list = self.overlapping_grid_indices(x_cond, output_size=p_size, r=r)
         corners = [(i, j) for i in h_list for j in w_list]
         shp = (1, self.config.model.pred_channels, x_cond.shape[2], x_cond.shape[3])
         x = torch.cat([torch.randn(shp, device=self.diffusion.device) for _ in range(x_cond.shape[0] * int(samples))], dim=0)
         return self.diffusion.sample_image(x_cond, x, x_other=x_other, last=last, patch_locs=corners, patch_size=p_size,
-                                           total=total, use_global=use_global, use_other=use_other, stop_at=stop_at, **({"samples": int(samples)} if int(samples) != 1 else {}))
+                                           total=total, use_global=use_global, use_other=use_other, stop_at=stop_at, **({"samples": int(samples)} if int(samples) != 1 else {}), **({"solver": solver} if solver is not None else {}))
 
     def overlapping_grid_indices(self, x_cond, output_size, r=None):
         """restoration.py:187-196."""

@@ -65,6 +65,75 @@ def alpha_bar_table(betas: torch.Tensor) -> torch.Tensor:
     return _betas_entry(betas)[0]
 
 
+SOLVERS = ("ddim", "dpmpp2m")
+
+
+def check_solver(solver, who, eta=0.0, use_global=False):
+    """The solver's name and what `dpmpp2m` is not built for, refused before any launch."""
+    if solver not in SOLVERS:
+        raise ValueError(f"{who}: unknown solver {solver!r}; the solvers are {', '.join(repr(s) for s in SOLVERS)}")
+    if solver == "dpmpp2m" and float(eta) != 0.0:
+        raise ValueError(f"{who}: solver 'dpmpp2m' with eta = {eta}: the multistep rule integrates the probability-flow ODE (eta = 0); the stochastic term belongs to 'ddim'")
+    if solver == "dpmpp2m" and use_global:
+        raise NotImplementedError(f"{who}: solver 'dpmpp2m' is not built for the use_global branch (the global-attention sampler keeps the DDIM step)")
+    return solver
+
+
+def solver_coefficients(seq, betas, solver):
+    """The host side of a sampler run, in float64: one entry per step k = 0 ... S-1 of `reversed(seq)`, None for a first-order step -- the
+    DDIM entry points, launched as ever -- or a dict for a second-order DPM-Solver++(2M) step:
+        cx, c0, cp : x_next = cx * x_t + c0 * x0 + cp * x0_prev, rounded to fp32 ONCE here (Python floats that hold fp32 values: what the kernel is given)
+        exact      : the three before that rounding
+        h, r       : the step's log-SNR gap and the ratio of the previous gap to it.
+    With i = t_k, j = t_{k+1}, abar from alpha_bar_table (the fp32 values the DDIM path uses, widened), alpha = sqrt(abar), sigma = sqrt(1 - abar),
+    lambda = ln(alpha / sigma):  h = lambda_j - lambda_i, r = (lambda_i - lambda_{t_{k-1}}) / h, g = alpha_j * (-expm1(-h)),
+        cx = sigma_j / sigma_i,  c0 = g * (1 + 1 / (2 r)),  cp = -g / (2 r).
+    A step is second-order iff 1 <= k <= S - 3: step 0 has no history, and the last two -- the one that lands on t = 0 and the one onto abar = 1 -- span
+    log-SNR gaps several times the one before them on this grid (r = 0.24 at S = 25), where the extrapolation does more harm than the DDIM step's first-order
+    error.  So S <= 3 is DDIM throughout, and `solver="ddim"` is None at every step."""
+    check_solver(solver, "solver_coefficients")
+    seq = [int(t) for t in seq]
+    S = len(seq)
+    if solver == "ddim":
+        return [None] * S
+    abar = alpha_bar_table(betas).double().numpy()
+    ts = list(reversed(seq))
+    alpha = lambda t: float(np.sqrt(abar[t + 1]))
+    sigma = lambda t: float(np.sqrt(1.0 - abar[t + 1]))
+    lam = lambda t: float(np.log(alpha(t) / sigma(t)))
+    out = []
+    for k in range(S):
+        if not 1 <= k <= S - 3:
+            out.append(None)
+            continue
+        i, j, prev = ts[k], ts[k + 1], ts[k - 1]
+        h = lam(j) - lam(i)
+        r = (lam(i) - lam(prev)) / h
+        g = alpha(j) * (-np.expm1(-h))
+        exact = (sigma(j) / sigma(i), float(g * (1.0 + 1.0 / (2.0 * r))), float(-g / (2.0 * r)))
+        cx, c0, cp = (float(np.float32(v)) for v in exact)
+        out.append(dict(cx=cx, c0=c0, cp=cp, exact=exact, h=float(h), r=float(r)))
+    return out
+
+
+def resolve_x0_index(x0_index, solver, steps, who="x0_index"):
+    """Which entry of x0_preds a restoration reads (args.x0_index): a negative index K with -steps <= K <= -1.  None: -5 with `ddim` -- the reference's
+    x0_preds[-5] (restoration.py:108) --, -1 with `dpmpp2m`, the solver's solution (at ten steps -5 would read the prediction at t = 400)."""
+    check_solver(solver, who)
+    steps = int(steps)
+    if x0_index is None:
+        k = -5 if solver == "ddim" else -1
+        if -k > steps:
+            raise IndexError(f"x0_preds[{k}] needs at least {-k} sampling steps (restoration.py:108)")
+        return k
+    if isinstance(x0_index, bool) or not isinstance(x0_index, (int, np.integer)):
+        raise ValueError(f"{who}: x0_index = {x0_index!r} is not an integer")
+    k = int(x0_index)
+    if not -steps <= k <= -1:
+        raise ValueError(f"{who}: x0_index = {k} is outside -{steps} ... -1 (a negative index into the {steps} predictions of a run)")
+    return k
+
+
 def _device_const(dev, kind, values, dtype):
     """A small constant on the device, uploaded once per distinct content: a pageable H2D copy waits for the stream (see _betas_entry), and the sampler is called
     with the same patch list / timestep sequence for every group of same-sized images.  The tensors are never written."""
@@ -247,7 +316,7 @@ class RaggedLayout:
                 _device_const(dev, "ragged_blk", self.blk_off, torch.int32), _device_const(dev, "ragged_pix", self.pix_off, torch.int64))
 
 
-def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=64, keep="all", stop_at=None):
+def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=64, keep="all", stop_at=None, solver="ddim"):
     """ddim_sample's plain loop (one stream, unsharded, eta = 0) for images of DIFFERENT sizes in one call.
 
     x (pc channels), x_cond (48) and x_other (or None) are ragged tensors of `layout` (RaggedLayout): flat fp32 buffers on the GPU.  The patches of all
@@ -255,7 +324,9 @@ def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=6
     image and the start of the next, which changes nothing (per-patch results do not depend on the batch, tests/test_gpu_unet.py) --, with the same temb table;
     `wdm_pack_channels_ragged` and `wdm_ddim_update_ragged` are the plain kernels with the image's size looked up.  Every image's result is therefore, bit for
     bit, what ddim_sample returns for that image alone (tests/test_gpu_ragged.py).  `keep` and `stop_at` as in ddim_sample; returns (xs, x0_preds), lists of
-    flat tensors (layout.view gives an image's block).  With WAVEDM_GRAPH=1 a ragged call still launches directly: it is not captured."""
+    flat tensors (layout.view gives an image's block).  With WAVEDM_GRAPH=1 a ragged call still launches directly: it is not captured.
+    `solver`: as in ddim_sample (`wdm_multistep_update_ragged` on the second-order steps)."""
+    check_solver(solver, "ddim_sample_ragged")
     x = _lib.require_cuda_f32(x, "x")
     x_cond = _lib.require_cuda_f32(x_cond, "x_cond")
     if x_other is not None:
@@ -280,6 +351,7 @@ def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=6
         seq = list(seq)
         seq_next = [-1] + seq[:-1]
         abar = alpha_bar_table(betas)
+        coef = solver_coefficients(seq, betas, solver)
         t_dev = _device_const(dev, "timesteps", tuple(float(v) for v in reversed(seq)), torch.float32)
         n_run = len(seq) if stop_at is None else len(seq) + int(stop_at) + 1
         assert 1 <= n_run <= len(seq), f"stop_at={stop_at} out of range for {len(seq)} steps"
@@ -296,6 +368,7 @@ def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=6
         S = len(seq)
         xs, x0_preds = [x], []
         xt = x
+        x0_prev = None                                                          # the previous step's x0 (dpmpp2m), alive here whatever `keep` drops
         for k, (i_t, j_t) in enumerate(zip(reversed(seq), reversed(seq_next))):
             if _TRACE is not None:
                 _TRACE(f"sampler: step {k}")
@@ -311,8 +384,14 @@ def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=6
             _lib.check(L.wdm_pack_channels_ragged(h, _lib.ptr(xt), pc, iptr, optr, nimg, pptr, n, p, _lib.ptr(x96), cin, ncond, unet._dtype_code, st))
             for i in range(0, n, call_b):
                 unet.forward_nhwc(x96[i:i + call_b], t_dev[k:k + 1], eps[i:i + call_b], temb_row=None if temb is None else temb[k])
-            _lib.check(L.wdm_ddim_update_ragged(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), iptr, bptr, optr, nimg, nblk, s1m, sa, san, c2,
-                                                _lib.ptr(x0), _lib.ptr(xn), st))
+            if coef[k] is not None:
+                m = coef[k]
+                _lib.check(L.wdm_multistep_update_ragged(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), _lib.ptr(x0_prev), iptr, bptr, optr, nimg, nblk, s1m, sa,
+                                                         m["cx"], m["c0"], m["cp"], _lib.ptr(x0), _lib.ptr(xn), st))
+            else:
+                _lib.check(L.wdm_ddim_update_ragged(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), iptr, bptr, optr, nimg, nblk, s1m, sa, san, c2,
+                                                    _lib.ptr(x0), _lib.ptr(xn), st))
+            x0_prev = x0
             x0_preds.append(x0 if keep_set is None or (k - S) in keep_set else None)
             xs.append(xn)
             if keep_set is not None and len(xs) >= 3:
@@ -324,7 +403,7 @@ def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=6
 
 
 def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None, max_batch=64, keep="all", stop_at=None,
-                patch_group=None, streams=None, eta=0.0, samples=1):
+                patch_group=None, streams=None, eta=0.0, samples=1, solver="ddim"):
     """DDIM over `seq` (ascending list of timesteps) for NIMG images; eta = 0 (what every caller in the reference passes) is the deterministic sampler.
 
     x (NIMG,pc,H,W) start noise, x_cond (NIMG,48,H,W), x_other (NIMG,48 - other_channels_begin,H,W) or None: fp32 on the GPU.  pc = model.pred_channels is
@@ -356,7 +435,13 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
           conditioned on image i.  The step-invariant channels of the UNet input are gathered once, through a second patch list whose image index is
           row // N (the same wdm_pack_channels, nothing replicated); everything else runs on the B * N rows as for any batch, so row i * N + k holds the bits
           of a plain call on `repeat_interleave`d conditioning.  Not with patch_group.  samples = 1 is the plain call, launch for launch.
+    solver: "ddim" (the default: the reference's first-order step, this function as it always was, launch for launch) or "dpmpp2m", DPM-Solver++(2M)
+          (DESIGN.md §3.5.3): on the steps 1 <= k <= S - 3 the update is x_next = cx * x_t + c0 * x0 + cp * x0_prev with the previous step's x0 prediction
+          (solver_coefficients; `wdm_multistep_update_c`, `wdm_multistep_from_sums_c`), every other step -- the first and the last two -- is the DDIM launch.
+          No further UNet call per step; xs[1] is DDIM's bit for bit, S <= 3 is DDIM throughout.  Runs on every path eta = 0 runs on (chunks on streams keep
+          their own slice of x0_prev; the solver is part of a captured graph's key); eta != 0 is refused: the rule integrates the ODE.
     """
+    check_solver(solver, "ddim_sample", eta=eta)
     samples = int(samples)
     if samples < 1:
         raise ValueError(f"ddim_sample: samples = {samples} (at least 1)")
@@ -417,6 +502,7 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
         seq = list(seq)
         seq_next = [-1] + seq[:-1]
         abar = alpha_bar_table(betas)
+        coef = solver_coefficients(seq, betas, solver)
         t_dev = _device_const(dev, "timesteps", tuple(float(v) for v in reversed(seq)), torch.float32)
         n_run = len(seq) if stop_at is None else len(seq) + int(stop_at) + 1
         assert 1 <= n_run <= len(seq), f"stop_at={stop_at} out of range for {len(seq)} steps"
@@ -446,6 +532,7 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
             S = len(seq)
             xs, x0_preds = [x], []
             xt = x
+            x0_prev, held = None, []          # dpmpp2m: the previous step's x0, alive here whatever `keep` drops (with side streams reading it: until the join)
             # chunks of independent crops, one HIP stream each (see `streams`)
             chunks = None
             if use_chunks:
@@ -479,6 +566,7 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
                         noise = torch.randn_like(x)
                     x0 = torch.empty_like(x)
                     xn = torch.empty_like(x)
+                    m = coef[k]                                                       # None: a first-order step, the DDIM launches below as ever
                     if chunks is not None:
                         # independent crops: every chunk's step on its own stream (same kernels, same per-image bits)
                         for ci, (lo, hi, sc) in enumerate(chunks):
@@ -488,8 +576,14 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
                                 for i in range(lo, hi, max_batch):
                                     j = min(i + max_batch, hi)
                                     unet.forward_nhwc(x96[i:j], t_dev[k:k + 1], eps[i:j], temb_row=None if temb is None else temb[k], ws_slot=ci)
-                                _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps[lo:hi]), None, hi - lo, p, pc, _lib.ptr(xt[lo:hi]), hi - lo, H, W, s1m, sa, san, c2,
-                                                               _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc))
+                                if m is not None:
+                                    _lib.check(L.wdm_multistep_update_c(h, _lib.ptr(eps[lo:hi]), None, hi - lo, p, pc, _lib.ptr(xt[lo:hi]), _lib.ptr(x0_prev[lo:hi]),
+                                                                        hi - lo, H, W, s1m, sa, m["cx"], m["c0"], m["cp"], _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc))
+                                else:
+                                    _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps[lo:hi]), None, hi - lo, p, pc, _lib.ptr(xt[lo:hi]), hi - lo, H, W, s1m, sa, san, c2,
+                                                                   _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc))
+                        if solver != "ddim":
+                            held.append(x0)
                     else:
                         if n:
                             _lib.check(L.wdm_pack_channels(h, _lib.ptr(xt), pc, H, W, pptr, n, p, _lib.ptr(x96), cin, ncond, unet._dtype_code, st))
@@ -498,13 +592,21 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
                         if sharded:
                             _lib.check(L.wdm_patch_accumulate_c(h, _lib.ptr(eps), pptr, n, p, pc, nimg, H, W, _lib.ptr(acc_cnt), st))      # sums | counts: 2 * NIMG * pc * H * W floats
                             dist.all_reduce(acc_cnt, op=dist.ReduceOp.SUM, group=grp)
-                            _lib.check(L.wdm_ddim_from_sums_c(h, _lib.ptr(acc_cnt), _lib.ptr(xt), pc, nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st))
+                            if m is not None:
+                                _lib.check(L.wdm_multistep_from_sums_c(h, _lib.ptr(acc_cnt), _lib.ptr(xt), _lib.ptr(x0_prev), pc, nimg, H, W, s1m, sa,
+                                                                       m["cx"], m["c0"], m["cp"], _lib.ptr(x0), _lib.ptr(xn), st))
+                            else:
+                                _lib.check(L.wdm_ddim_from_sums_c(h, _lib.ptr(acc_cnt), _lib.ptr(xt), pc, nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st))
+                        elif m is not None:
+                            _lib.check(L.wdm_multistep_update_c(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), _lib.ptr(x0_prev), nimg, H, W, s1m, sa,
+                                                                m["cx"], m["c0"], m["cp"], _lib.ptr(x0), _lib.ptr(xn), st))
                         elif noise is not None:
                             _lib.check(L.wdm_ddim_update_eta_c(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c1, c2, _lib.ptr(noise),
                                                                _lib.ptr(x0), _lib.ptr(xn), st))
                         else:
                             _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st))
                     # lists as the reference returns them; with `keep` given, what nobody asked for is dropped at once (inside a captured graph its memory is reused)
+                    x0_prev = x0
                     x0_preds.append(x0 if keep_set is None or (k - S) in keep_set else None)
                     xs.append(xn)
                     if keep_set is not None and len(xs) >= 3 and chunks is None:     # (with side streams still reading them the tensors stay until the loop's join)
@@ -521,6 +623,7 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
                         for q in range(1, len(xs) - 1):
                             if (q - (S + 1)) not in keep_set:
                                 xs[q] = None
+                    del held[:]
             return xs, x0_preds
 
         graphed = (os.environ.get("WAVEDM_GRAPH", "0") == "1" and not sharded and not multi and n > 0 and not _lib.prof_on() and eta == 0.0 and
@@ -530,7 +633,7 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
             # sequence, the patch list, the call size, what is kept, the schedule's bytes (cached per betas tensor: no read-back per call), the temb-table switch
             xs, x0_preds = _replay_graph(unet, run_loop, x, x_cond, x_other, n_run,
                                          (tuple(seq), None if corners is None else tuple(map(tuple, tri)), p, max_batch, call_b, keep_set, n_run, _betas_entry(betas)[1],
-                                          os.environ.get("WAVEDM_TEMB_TABLE", "1"), str(x_cond.dtype), None if x_other is None else str(x_other.dtype), samples),
+                                          os.environ.get("WAVEDM_TEMB_TABLE", "1"), str(x_cond.dtype), None if x_other is None else str(x_other.dtype), solver, samples),
                                          keepalive=(patches, cpatches, t_dev))
         else:
             xs, x0_preds = run_loop(x, x_cond, x_other, n_run, multi)
