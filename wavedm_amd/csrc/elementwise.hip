@@ -939,7 +939,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     if (row >= rows) return;
     const float* src = S + row * n;
     float v[8];
-    const int per = n / 64;    // n in {64, 128, 256, 512}
+    const int per = n / 64;    // every multiple of 64 up to 512: per = 1 ... 8
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
