@@ -44,26 +44,27 @@ def _short(name: str) -> str:
         return f"convdma_3x3s1_t{a[4]}x16x1_bn{16 * a[3] * a[1]}w8{'p' if m.group(2) == '1' else ''}{'s' if a[4] == 32 and m.group(3) == '1' else ''}_bf16"
     if "conv_dmap_kernel" in name:                   # <true>: packed epilogue, <false>: fp32 epilogue (residual convs) -- one name, as the library's profiler reports them
         return "convdmap_3x3s1_t16x16x1_bn128w8_bf16"
-    m = re.search(r"conv_up4_kernelILi(\d+)ELi(\d+)E(?:Li(\d+)E)?", name)
-    if m:
-        return f"convup4_2x2x4_t{m.group(1)}x{m.group(1)}x{m.group(2)}_bn{32 * int(m.group(3) or 4)}w8_bf16"
     m = re.search(r"conv_dmax3t_kernel(?:ILb(\d)E|<(true|false)>)", name)
     if m:                                            # round 4: the f32x3 big tiles, <true> = 512 x 128, <false> = 256 x 256
         tall = m.group(1) == "1" or m.group(2) == "true"
         return "convdmax3_3x3s1_t32x16x1_bn128w8_f32x3" if tall else "convdmax3_3x3s1_t16x16x1_bn256w8_f32x3"
     if "conv_dmax3_kernel" in name:
         return "convdmax3_3x3s1_t16x16x1_bn128w8_f32x3"
-    m = re.search(r"conv_dma8x3_kernelILi(\d+)E", name)
+    m = re.search(r"conv_dma8x3_kernelILi(\d+)E", name) or re.search(r"conv_dma8_kernelILi(\d+)ELi\d+EfE", name)      # (before / since the f32x3 kernels are the <…, float> instantiations)
     if m:
         return f"convdma8x3_3x3s1_t8x8x2_bn{m.group(1)}w4_f32x3"
-    m = re.search(r"conv_up4x3_kernelILi(\d+)ELi(\d+)E", name)
+    m = re.search(r"conv_up4x3_kernelILi(\d+)ELi(\d+)E", name) or re.search(r"conv_up4_kernelILi(\d+)ELi(\d+)ELi\d+EfE", name)
     if m:
         return f"convup4x3_2x2x4_t{m.group(1)}x{m.group(1)}x{m.group(2)}_bn128w8_f32x3"
-    m = re.search(r"conv_s2x3_kernelILi(\d+)E", name)
+    m = re.search(r"conv_s2x3_kernelILi(\d+)E", name) or re.search(r"conv_s2_kernelILi\d+ELi\d+ELi(\d+)EfE", name)
     if m:
         return f"convs2x3_3x3s2_t16x16x1_bn{32 * int(m.group(1))}w8_f32x3"
     if "conv_gemmx3_kernel" in name:
         return "gemmx3_1x1_t16x16x1_bn128_f32x3"
+    # (the <…, float> instantiations of the three tap convs are matched above: the 16-bit patterns come after them)
+    m = re.search(r"conv_up4_kernelILi(\d+)ELi(\d+)E(?:Li(\d+)E)?", name)
+    if m:
+        return f"convup4_2x2x4_t{m.group(1)}x{m.group(1)}x{m.group(2)}_bn{32 * int(m.group(3) or 4)}w8_bf16"
     m = re.search(r"conv_s2_kernelILi(\d+)ELi(\d+)ELi(\d+)E", name)
     if m:
         return f"convs2_3x3s2_t{m.group(1)}x{m.group(1)}x{m.group(2)}_bn{32 * int(m.group(3))}w8_bf16"

@@ -127,6 +127,21 @@ CONV = [
     (1, 64, 128, 2, 32, 32, ("f32x3",), {}, "convs2x3_3x3s2_t16x16x1_bn64"),
     (1, 64, 128, 1, 64, 64, ("f32x3",), {}, "convs2x3_3x3s2_t16x16x1_bn128"),
     (0, 64, 128, 2, 16, 16, ("f32x3",), {"WDM_CONV_DMA": "0"}, "conv_3x3s1_t16x16x1_bn128"),
+    # ONE K slab on the tap convs of conv_taps.h (16-bit Cin 32, f32x3 Cin 16): every request "one slab ahead" is the clamped copy, and the f32x3 schedules must
+    # skip the split of slab 1.  B = 3 on 8 x 8 maps: a last tile with images past the batch (DMA_OOB in the shared halo offsets)
+    (0, 32, 48, 3, 8, 8, H, {}, "convdma8_3x3s1_t8x8x2_bn48"),
+    (0, 32, 64, 3, 8, 8, H, {}, "convdma8_3x3s1_t8x8x2_bn64"),
+    (0, 16, 48, 3, 8, 8, ("f32x3",), {}, "convdma8x3_3x3s1_t8x8x2_bn48"),
+    (0, 16, 64, 3, 8, 8, ("f32x3",), {}, "convdma8x3_3x3s1_t8x8x2_bn64"),
+    (2, 32, 128, 3, 8, 8, H, {}, "convup4_2x2x4_t8x8x4"),                                   # (the sub-pixel form takes Cout >= 128, Cin % 32 == 0: blocks.hip)
+    (2, 32, 128, 1, 16, 16, H, {}, "convup4_2x2x4_t16x16x1_bn128"),
+    (2, 32, 256, 1, 16, 16, H, {"WDM_BN256": "2"}, "convup4_2x2x4_t16x16x1_bn256"),
+    (2, 32, 128, 3, 8, 8, ("f32x3",), {}, "convup4x3_2x2x4_t8x8x4"),                        # ... so f32x3 has TWO slabs at the least: slab 1 split, slab 2 skipped (its one-slab case is not reachable through the library: uncovered)
+    (2, 32, 128, 1, 16, 16, ("f32x3",), {}, "convup4x3_2x2x4_t16x16x1"),
+    (1, 32, 64, 1, 32, 32, H, {}, "convs2_3x3s2_t16x16x1_bn64"),
+    (1, 32, 128, 1, 64, 64, H, {}, "convs2_3x3s2_t16x16x1_bn128"),
+    (1, 16, 64, 1, 32, 32, ("f32x3",), {}, "convs2x3_3x3s2_t16x16x1_bn64"),
+    (1, 16, 128, 1, 64, 64, ("f32x3",), {}, "convs2x3_3x3s2_t16x16x1_bn128"),
     # f32: every mode on conv_kernel.h
     (0, 64, 128, 2, 16, 16, ("f32",), {}, "conv_3x3s1_t16x16x1"),
     (0, 128, 3, 3, 8, 8, ("f32",), {}, "conv_3x3s1_t8x8x1"),

@@ -311,7 +311,7 @@ def test_f32x3_resblock_on_the_lds_dma_kernel(gu, cin, cout, B, H, cat):
         return out, names
     y, k = run()
     y0, k0 = _with({"WDM_CONV_DMA": "0"}, run)
-    tag = "convdma8x3" if H == 8 else "convdmax3"                                    # 8 x 8 maps: conv_dma8x3_kernel.h (48- or 64-column tiles)
+    tag = "convdma8x3" if H == 8 else "convdmax3"                                    # 8 x 8 maps: conv_dma8_kernel.h, E = float (48- or 64-column tiles)
     assert any(n.startswith(tag) for n in k) and not any(n.startswith("convdma") for n in k0), (k, k0)
     ref = gu.resblock(sd, "rb", x0, x1, t, "f32")
     e, e0 = rel_linf(y, ref), rel_linf(y0, ref)
@@ -322,7 +322,7 @@ def test_f32x3_resblock_on_the_lds_dma_kernel(gu, cin, cout, B, H, cat):
 
 @pytest.mark.parametrize("cin,cout,B,H", [(256, 256, 2, 32), (512, 512, 3, 16), (768, 768, 5, 8), (128, 192, 2, 16)])
 def test_f32x3_upsample_in_sub_pixel_form(gu, cin, cout, B, H):
-    """conv_up4x3_kernel.h (f32x3 mode: four 2x2-tap phase convs with pre-summed, pre-split weights) against the 9-tap register-staged form (WDM_UP4=0) and
+    """conv_up4_kernel.h with E = float (f32x3 mode: four 2x2-tap phase convs with pre-summed, pre-split weights) against the 9-tap register-staged form (WDM_UP4=0) and
     torch fp32: the pre-summing reassociates the taps, everything stays inside the f32x3 bound."""
     from wavedm_amd import _lib
     w = gu.seeded((cout, cin, 3, 3), 51) / (cin * 9) ** 0.5
@@ -438,7 +438,7 @@ def test_in_tile_groupnorm_in_the_f32x3_mode(gu):
 
 @pytest.mark.parametrize("cin,cout,B,H", [(128, 128, 3, 64), (256, 256, 2, 32), (96, 192, 2, 32)])
 def test_f32x3_downsample_on_the_lds_dma_kernel(gu, cin, cout, B, H):
-    """conv_s2x3_kernel.h (f32x3 mode: the four-phase Downsample kernel with halo and weights split in LDS) against torch fp32 and the register-staged f32x3 form."""
+    """conv_s2_kernel.h with E = float (f32x3 mode: the four-phase Downsample kernel with halo and weights split in LDS) against torch fp32 and the register-staged f32x3 form."""
     from wavedm_amd import _lib
     w = gu.seeded((cout, cin, 3, 3), 41) / (cin * 9) ** 0.5
     b = gu.seeded((cout,), 42) * 0.1

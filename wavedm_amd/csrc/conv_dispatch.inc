@@ -129,19 +129,19 @@ static bool out_norm_shape_ok(const ConvArgs& a, int bn) {
 }
 // ---- the tilings both LDS-DMA families have (the 16-bit kernels, the f32x3 ones): one launcher each, over the kernel KERN, its configuration C and the family
 // F (H16Family / X3Family below, next to the kernels they serve: a translation unit sees one family's kernels).  F holds what differs:
-//   ES, SC_KSTEP    element bytes; channels per K step of the fused shortcut's phase
+//   ES, BK, SC_KSTEP    element bytes; channels per K slab (64-byte rows); channels per K step of the fused shortcut's phase
 //   TAG, DT         "" / "x3" behind the kernel's name in a profile name, the dtype at its end;  DMA8, UP4, S2: the launcher's name in error messages
 //   dma8_rejects, up4_rejects        the operands this family's kernel does not take on top of the common list
 //   copy_weights, s2_weights, up4_weights, up4_weight_bytes     which weight copy a launch reads and how its extent is bounded
 // `static std::atomic` in a function template: one per instantiation, i.e. per kernel.
 // (launch_dma / launch_dmax3 and launch_gemm / launch_gemmx3 stay apart: different binaries per launch, rejection lists and statistics-slab rules -- more traits than shared lines.)
-// 3x3 stride-1 on 8 x 8 maps, two images per tile (conv_dma8_kernel.h, conv_dma8x3_kernel.h), no prologue
+// 3x3 stride-1 on 8 x 8 maps, two images per tile (conv_dma8_kernel.h: one kernel template, the family is its element type), no prologue
 template <class F, class C, auto KERN>
 static int launch_dma8_as(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     const char* who = F::DMA8;
     if (a.Hout != 8 || a.Wout != 8 || a.Hin != 8 || a.Win != 8) WDM_FAIL(WDM_EINVAL, "%s: 8x8 maps only", who);
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.w_img_stride || a.m_valid || F::dma8_rejects(a)) WDM_FAIL(WDM_EINVAL, "%s: unsupported operand combination", who);
+    if (a.Cin % F::BK || a.C1 != 0 || a.x1 || a.pro || a.w_img_stride || a.m_valid || F::dma8_rejects(a)) WDM_FAIL(WDM_EINVAL, "%s: unsupported operand combination", who);
     WDM_TRY(set_extents(a, (double)a.B * 64, F::ES, who));
     WDM_TRY(set_shortcut_extents(a, F::ES, F::SC_KSTEP, who));
     bool done;      // in-tile GroupNorm of the output: a workgroup holds two whole images x BN columns
@@ -158,7 +158,7 @@ static int launch_dma8_as(const ConvArgs& a0, hipStream_t s) {
     static std::atomic<unsigned> devs{0};
     return launch_named(KERN, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, conv_work(a, 9.0, F::ES, (double)a.B * 64, (double)a.B * 64));
 }
-// Upsample in sub-pixel form (conv_up4_kernel.h, conv_up4x3_kernel.h): a.Hin x a.Win = a.Hout x a.Wout is the LOW-resolution map, y is (2 Hout) x (2 Wout), a.w holds
+// Upsample in sub-pixel form (conv_up4_kernel.h): a.Hin x a.Win = a.Hout x a.Wout is the LOW-resolution map, y is (2 Hout) x (2 Wout), a.w holds
 // the 16 pre-summed taps [phase][dy'][dx'][rows][cin] (k_pack_up4)
 template <class F, class C, auto KERN>
 static int launch_up4_as(const ConvArgs& a0, hipStream_t s) {
@@ -167,7 +167,7 @@ static int launch_up4_as(const ConvArgs& a0, hipStream_t s) {
     const char* who = F::UP4;
     if (a.Hout % TILE || a.Wout % TILE || a.Hin != a.Hout || a.Win != a.Wout || (NI > 1 && (a.Hout != TILE || a.Wout != TILE)))
         WDM_FAIL(WDM_EINVAL, "%s: %dx%d map does not fit the %dx%d tile", who, a.Hout, a.Wout, TILE, TILE);
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.res || a.sx0 || a.temb || a.w_img_stride || a.y_mode != Y_NHWC || a.Cout % 8 || a.m_valid || F::up4_rejects(a))
+    if (a.Cin % F::BK || a.C1 != 0 || a.x1 || a.pro || a.res || a.sx0 || a.temb || a.w_img_stride || a.y_mode != Y_NHWC || a.Cout % 8 || a.m_valid || F::up4_rejects(a))
         WDM_FAIL(WDM_EINVAL, "%s: unsupported operand combination (Cin=%d Cout=%d)", who, a.Cin, a.Cout);
     if (F::up4_weight_bytes(a) >= 4294901760.0) WDM_FAIL(WDM_EINVAL, "%s: weights exceed the 4 GB buffer-offset range", who);
     F::up4_weights(a);
@@ -188,13 +188,13 @@ static int launch_up4_as(const ConvArgs& a0, hipStream_t s) {
     static std::atomic<unsigned> devs{0};
     return launch_named(KERN, grid, C::NTHREADS, C::LDS_BYTES, s, a, devs, name, w);
 }
-// Downsample conv (3x3 stride 2, zero pad right / bottom) over the input's four phases (conv_s2_kernel.h, conv_s2x3_kernel.h)
+// Downsample conv (3x3 stride 2, zero pad right / bottom) over the input's four phases (conv_s2_kernel.h)
 template <class F, class C, auto KERN>
 static int launch_s2_as(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     const char* who = F::S2;
     if (a.Hout % 16 || a.Wout % 16 || a.Hin != 2 * a.Hout || a.Win != 2 * a.Wout) WDM_FAIL(WDM_EINVAL, "%s: %dx%d -> %dx%d does not fit the 16x16 tile", who, a.Hin, a.Win, a.Hout, a.Wout);
-    if (a.Cin % C::BK || a.C1 != 0 || a.x1 || a.pro || a.sx0 || a.w_img_stride || a.m_valid || a.yn) WDM_FAIL(WDM_EINVAL, "%s: unsupported operand combination (Cin=%d Cout=%d)", who, a.Cin, a.Cout);
+    if (a.Cin % F::BK || a.C1 != 0 || a.x1 || a.pro || a.sx0 || a.w_img_stride || a.m_valid || a.yn) WDM_FAIL(WDM_EINVAL, "%s: unsupported operand combination (Cin=%d Cout=%d)", who, a.Cin, a.Cout);
     WDM_TRY(set_extents(a, (double)a.B * a.Hin * a.Win, F::ES, who));
     bool done;
     static_assert(256 / conv_stat_rows(16, 16, 16 * C::WM) == 4, "64-row statistics slabs in both families");
@@ -289,7 +289,7 @@ static int launch_dma512(const ConvArgs& a, hipStream_t s) { return launch_dma_b
 // the 16-bit family of the shared launchers (launch_dma8_as, launch_up4_as, launch_s2_as), and their instantiations on this unit's kernels
 struct H16Family {
     static constexpr double ES = 2.0;
-    static constexpr int SC_KSTEP = 64;
+    static constexpr int BK = 32, SC_KSTEP = 64;
     static constexpr const char *TAG = "", *DT = WDM_H16_NAME, *DMA8 = "conv(dma8)", *UP4 = "conv(up4)", *S2 = "conv(s2)";
     static bool dma8_rejects(const ConvArgs&) { return false; }          // (takes a fused shortcut, and the weights in either layout)
     static bool up4_rejects(const ConvArgs&) { return false; }
@@ -377,7 +377,7 @@ static int launch_dmax3t(const ConvArgs& a0, hipStream_t s) {
 // the f32x3 family of the shared launchers, and their instantiations on this unit's kernels
 struct X3Family {
     static constexpr double ES = 4.0;
-    static constexpr int SC_KSTEP = 32;
+    static constexpr int BK = 16, SC_KSTEP = 32;
     static constexpr const char *TAG = "x3", *DT = "f32x3", *DMA8 = "conv(dma8x3)", *UP4 = "conv(up4x3)", *S2 = "conv(s2x3)";
     static bool dma8_rejects(const ConvArgs& a) { return a.sx0 || !a.w_sm; }      // no shortcut phase; needs the model's pre-split weight copy
     static bool up4_rejects(const ConvArgs& a) { return a.yn != nullptr; }
@@ -387,11 +387,11 @@ struct X3Family {
     static double up4_weight_bytes(const ConvArgs& a) { return 4.0 * a.w_tap_stride * 4.0; }      // the four taps of a phase: what the kernel's descriptor spans
 };
 template <int BN_>
-static int launch_dma8x3(const ConvArgs& a, hipStream_t s) { return launch_dma8_as<X3Family, ConvDma8X3Cfg<BN_>, conv_dma8x3_kernel<BN_>>(a, s); }
+static int launch_dma8x3(const ConvArgs& a, hipStream_t s) { return launch_dma8_as<X3Family, ConvDma8Cfg<BN_>, conv_dma8_kernel<BN_, 2, float>>(a, s); }
 template <int TILE, int NI>
-static int launch_up4x3(const ConvArgs& a, hipStream_t s) { return launch_up4_as<X3Family, ConvUp4X3Cfg<TILE, NI>, conv_up4x3_kernel<TILE, NI>>(a, s); }
+static int launch_up4x3(const ConvArgs& a, hipStream_t s) { return launch_up4_as<X3Family, ConvUp4Cfg<TILE, NI, 4>, conv_up4_kernel<TILE, NI, 4, float>>(a, s); }
 template <int WN>
-static int launch_s2x3(const ConvArgs& a, hipStream_t s) { return launch_s2_as<X3Family, ConvS2X3Cfg<WN>, conv_s2x3_kernel<WN>>(a, s); }
+static int launch_s2x3(const ConvArgs& a, hipStream_t s) { return launch_s2_as<X3Family, ConvS2Cfg<16, 1, WN>, conv_s2_kernel<16, 1, WN, float>>(a, s); }
 // 1x1 convolutions / batched GEMMs (conv_gemmx3_kernel.h: both operands split in LDS)
 static int launch_gemmx3(const ConvArgs& a0, hipStream_t s) {
     using C = GemmX3Cfg;

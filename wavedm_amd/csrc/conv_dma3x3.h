@@ -22,18 +22,6 @@
 
 namespace wdm {
 
-// The K loops have no compiler-visible vector-memory instruction, so every wait on the DMA queue is written here.  dma_wait: this lane's own pieces;
-// dma_sync: ... and the barrier that publishes them (and every lane's LDS writes) to the workgroup.
-template <int N> __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void dma_sync() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 template <class C, typename E>
 struct Dma3x3 {
     static constexpr bool X3 = sizeof(E) == 4;

@@ -4,8 +4,8 @@
 #define WDM_HAS_DMAX3 1
 #include "conv_dmax3_kernel.h"
 #include "conv_dmax3t_kernel.h"
-#include "conv_dma8x3_kernel.h"
-#include "conv_up4x3_kernel.h"
+#include "conv_dma8_kernel.h"
+#include "conv_up4_kernel.h"
 #include "conv_gemmx3_kernel.h"
-#include "conv_s2x3_kernel.h"
+#include "conv_s2_kernel.h"
 #include "conv_dispatch.inc"

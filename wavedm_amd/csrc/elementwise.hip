@@ -1158,7 +1158,7 @@ __global__ __launch_bounds__(256) void pack_up4_kernel(const float* __restrict__
         TI<T>::st(dst, (((long long)(ci >> 5) * 16 + t) * rows_total + o) * 32 + (ci & 31), v);
     }
 }
-// f32x3 mode (conv_up4x3_kernel.h): the same 16 pre-summed taps (fp32 sums), every 16-channel group split and laid out as [hi c0-7 | hi c8-15 | lo c0-7 | lo c8-15]
+// f32x3 mode (conv_up4_kernel.h, E = float): the same 16 pre-summed taps (fp32 sums), every 16-channel group split and laid out as [hi c0-7 | hi c8-15 | lo c0-7 | lo c8-15]
 __global__ __launch_bounds__(256) void pack_up4_x3_kernel(const float* __restrict__ w, int cout, int cin, unsigned* __restrict__ dst, int rows_total) {
     const int upr = cin / 4;
     const long long total = (long long)16 * rows_total * upr;

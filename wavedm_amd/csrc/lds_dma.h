@@ -1,5 +1,5 @@
 // What the LDS-DMA kernels share: the raw buffer descriptor, the `buffer_load_dwordx4 ... lds` wrapper, the offset that lies outside every extent, the
-// channel unit a lane fetches in the 64-byte-row image, and the f32x3 mode's hi / lo handling of a fetched unit (split, re-layout, MFMA pair).
+// channel unit a lane fetches in the 64-byte-row image, the counted waits on the DMA queue, and the f32x3 mode's hi / lo handling of a fetched unit (split, re-layout, MFMA pair).
 #pragma once
 #include "conv_kernel.h"
 
@@ -30,6 +30,18 @@ __device__ __forceinline__ void dma16_soff0(const i32x4& rsrc, unsigned lds_addr
                  : "=&s"(keep)
                  : "v"(voff), "s"(lds_addr), "s"(rsrc)
                  : "memory");
+}
+
+// The K loops have no compiler-visible vector-memory instruction, so every wait on the DMA queue is written here.  dma_wait: this lane's own pieces;
+// dma_sync: ... and the barrier that publishes them (and every lane's LDS writes) to the workgroup.
+template <int N> __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <int N> __device__ __forceinline__ void dma_sync() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 // lane offset of a unit the DMA must fill with zeros (halo outside the image, rows past the weight matrix): outside every descriptor's extent, with any

@@ -167,7 +167,7 @@ int wdm_unet::build() {
         if (l != 0) {
             const Conv& us = L.up_us[l];
             ConvD& d = place_conv(us, 0, false);
-            if ((is_h16(cfg.dtype) || cfg.dtype == WDM_F32X3) && us.cin % 32 == 0 && us.cin >= 128)       // sub-pixel taps for conv_up4_kernel.h / conv_up4x3_kernel.h, next to the 3x3 ones
+            if ((is_h16(cfg.dtype) || cfg.dtype == WDM_F32X3) && us.cin % 32 == 0 && us.cin >= 128)       // sub-pixel taps for conv_up4_kernel.h (either family), next to the 3x3 ones
                 slots[us.w].up4_off = d.up4_off = take((size_t)16 * d.rows_pad * us.cin * dsize(cfg.dtype));
         }
     }
