@@ -353,6 +353,22 @@ int wdm_hfrm_set_max_launch_bytes(wdm_hfrm* m, int64_t bytes);
 int wdm_hfrm_chunk_rows(const wdm_hfrm* m, int64_t M, int cin, int cout, int has_res, int64_t* rows);
 int wdm_hfrm_conv_out(wdm_handle* h, const void* x, const void* res, const float* w, const float* bias, int B, int H, int W, int cin, int cout, int dtype,
                       float* y, void* stream);
+/* One stage of a created, finalized HFRM on its own (unit tests): the very members wdm_hfrm_forward runs (run_block, gemm_rows, the same launches), on the caller's
+ * tensors, so a per-stage reference cannot drift from the model.  Waits for the stream -- not a building block of a forward.
+ *   kind WDM_HFRM_STAGE_BLOCK:    index = the block's position in registration order (encoders, decoders, mid_blks); x, y (B, H, W, d) NHWC in the model dtype
+ *        WDM_HFRM_STAGE_DOWN:     downs[index]: x (B, H, W, d) -> y (B, H/2, W/2, 2d); H and W even
+ *        WDM_HFRM_STAGE_UP:       ups[index] + PixelShuffle + skip: x (B, H, W, d), skip and y (B, 2H, 2W, d/2)
+ *        WDM_HFRM_STAGE_CONV_IN:  x (B, in_channel, H, W) NCHW f32 -> y (B, H, W, dim) NHWC in the model dtype
+ *        WDM_HFRM_STAGE_CONV_OUT: the MFMA form: x (B, H, W, dim) NHWC, the residual (B, H, W, in_channel) NHWC as `skip`, both in the model dtype -> y (B, in_channel,
+ *                                 H, W) NCHW f32; H and W multiples of 8 -- the smallest tile of the conv kernel it runs on is 8 x 8 pixels and its dispatcher
+ *                                 refuses any other map (every map wdm_hfrm_forward gives it is a multiple of 16); for other sizes there is wdm_hfrm_conv_out
+ * Any other H, W >= 1.  Honours wdm_hfrm_set_local (a block pools at its level's window) and wdm_hfrm_set_max_launch_bytes.  All tensors 16-byte aligned, the
+ * workspace 256-byte aligned and at least wdm_hfrm_stage_workspace_bytes (0 on a bad kind, index or shape), else WDM_ENOMEM before the first launch.
+ * Additions to the ABI: WDM_ABI_VERSION stays 1. */
+enum { WDM_HFRM_STAGE_BLOCK = 0, WDM_HFRM_STAGE_DOWN = 1, WDM_HFRM_STAGE_UP = 2, WDM_HFRM_STAGE_CONV_IN = 3, WDM_HFRM_STAGE_CONV_OUT = 4 };
+size_t wdm_hfrm_stage_workspace_bytes(const wdm_hfrm* m, int kind, int index, int B, int H, int W);
+int wdm_hfrm_stage_forward(wdm_hfrm* m, int kind, int index, const void* x, const void* skip, int B, int H, int W, void* y, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ---- output side of DiffusiveRestoration.restore ---------------------------------
  * wdm_image_sqdiff: a, b (B,3,H,W) f32 on the device -> sums[B][2] (device, fp64):

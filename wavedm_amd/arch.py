@@ -185,6 +185,33 @@ class HFRM(nn.Module):
             self._ws = {key: torch.empty(n + 256, dtype=torch.uint8, device=device)}
         return self._ws[key]
 
+    STAGES = {"block": 0, "down": 1, "up": 2, "conv_in": 3, "conv_out": 4}
+
+    def stage_forward(self, kind, index, x, skip=None):
+        """One stage on its own (wdm_hfrm_stage_forward, for unit tests): the code forward() runs, on the caller's tensors.  kind: "block" (index: the block's
+        position in registration order -- encoders, decoders, mid_blks), "down" / "up" (downs[index] / ups[index] with `skip`), "conv_in", "conv_out" (the MFMA
+        form; `skip` is the residual image).  x, skip: fp32 NCHW on the GPU, stored here in the model dtype as NHWC (conv_in's image stays fp32 NCHW) -> fp32
+        NCHW on the GPU, exactly the values the stage stored."""
+        code = self.STAGES[kind]
+        x = _lib.require_cuda_f32(x, "HFRM stage input")
+        self.pack_weights()
+        dt = torch.bfloat16 if self._dtype_code == _lib.WDM_BF16 else torch.float32
+        nhwc = lambda t: t.permute(0, 2, 3, 1).to(dt).contiguous()
+        B, Cc, H, W = x.shape
+        xd = x.contiguous() if kind == "conv_in" else nhwc(x)
+        sk = None if skip is None else nhwc(_lib.require_cuda_f32(skip, "HFRM stage skip"))
+        shape = {"block": (B, H, W, Cc), "down": (B, H // 2, W // 2, 2 * Cc), "up": (B, 2 * H, 2 * W, Cc // 2), "conv_in": (B, H, W, self.dim)}.get(kind)
+        y = torch.empty(shape, dtype=dt, device=x.device) if shape else torch.empty(B, self.in_channel, H, W, dtype=torch.float32, device=x.device)
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            n = int(L.wdm_hfrm_stage_workspace_bytes(self._m, code, int(index), B, H, W))
+            if n == 0:
+                raise RuntimeError("wdm_hfrm_stage_workspace_bytes failed: " + L.wdm_last_error().decode())
+            ws = torch.empty(n + 256, dtype=torch.uint8, device=x.device)
+            _lib.check(L.wdm_hfrm_stage_forward(self._m, code, int(index), _lib.ptr(xd), _lib.ptr(sk) if sk is not None else None, B, H, W, _lib.ptr(y),
+                                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        return y if kind == "conv_out" else y.permute(0, 3, 1, 2).float().contiguous()
+
     def forward(self, x):
         x = _lib.require_cuda_f32(x, "HFRM input")
         B, Cc, H, W = x.shape

@@ -708,7 +708,9 @@ __device__ __forceinline__ void conv_epilogue_packed(const AT& a, f32x4 (&acc)[4
     const bool has_res = a.res != nullptr;
     if (has_res) {
         constexpr unsigned OOBV = 0xFFFF0000u;
-        const long long out_rows = (long long)a.B * a.Hout * a.Wout;                   // (up4 / m_valid launches have no residual: conv_dispatch.inc)
+        // no up4 / m_valid launch comes here with a residual: up4 has none, and conv_epilogue_can_pack refuses m_valid -- the HFRM's GEMMs, which do carry
+        // one, take the fp32-tile epilogue
+        const long long out_rows = (long long)a.B * a.Hout * a.Wout;
         const __amdgpu_buffer_rsrc_t r_res = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, (int)(unsigned)(out_rows * a.res_s * 2), 0x00020000);
         const int c8 = (lane & 7) * 8, lp = lane >> 3;
         const int n = ncol0 + c8;

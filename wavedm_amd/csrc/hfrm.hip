@@ -611,7 +611,12 @@ struct wdm_hfrm {
     int finalize(hipStream_t s);
     int run_block(Ctx& c, const Block& b, Tens& t, int B, int H, int W, int level);
     int gemm_rows(Ctx& c, const GemmD& g, const void* x, long long M, const void* res, void* y);
+    int conv_in_launch(Ctx& c, const float* x, int B, int h, int w, void* y);
+    int down_launch(Ctx& c, int i, const void* x, void* u, int B, int h, int w, int d, void* y);
+    int up_launch(Ctx& c, int i, const void* x, void* p, const void* skip, int B, int h, int w, int d, void* y);
+    int conv_out_mfma(Ctx& c, Tens& t, void* xin, int B, int h, int w, float* yout);
     int forward(Ctx& c, const float* x, int B, int H, int W, float* y);
+    int stage(Ctx& c, int kind, int index, const void* x, const void* skip, int B, int H, int W, void* y);
 };
 
 int wdm_hfrm::build() {
@@ -752,6 +757,39 @@ int wdm_hfrm::run_block(Ctx& c, const Block& b, Tens& t, int B, int H, int W, in
     return WDM_OK;
 }
 
+// ---- the launches of conv_in, a down step, an up step and conv_out's MFMA form: forward() and stage() below both run these --------------------
+int wdm_hfrm::conv_in_launch(Ctx& c, const float* x, int B, int h, int w, void* y) {
+    const int gg = ceil_div((long long)B * h * w, 256);
+    if (c.dtype == WDM_BF16) hipLaunchKernelGGL((conv3x3_cin3_kernel<__bf16, 32>), dim3(gg), dim3(256), 0, c.s, x, (__bf16*)y, B, h, w, cfg.in_channel, raw(L.conv_in.w), raw(L.conv_in.b));
+    else hipLaunchKernelGGL((conv3x3_cin3_kernel<float, 32>), dim3(gg), dim3(256), 0, c.s, x, (float*)y, B, h, w, cfg.in_channel, raw(L.conv_in.w), raw(L.conv_in.b));
+    return WDM_OK;
+}
+// down: space-to-depth (x (B, h, w, d) -> u (B, h/2, w/2, 4d)) + GEMM (4d -> 2d) -> y
+int wdm_hfrm::down_launch(Ctx& c, int i, const void* x, void* u, int B, int h, int w, int d, void* y) {
+    const long long total = (long long)B * (h / 2) * (w / 2) * 4 * (d / (c.dtype == WDM_BF16 ? 8 : 4));
+    const int gg = ceil_div(total, 256) > 16384 ? 16384 : ceil_div(total, 256);
+    if (c.dtype == WDM_BF16) hipLaunchKernelGGL(unshuffle2_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (const __bf16*)x, (__bf16*)u, B, h, w, d);
+    else hipLaunchKernelGGL(unshuffle2_kernel<float>, dim3(gg), dim3(256), 0, c.s, (const float*)x, (float*)u, B, h, w, d);
+    return gemm_rows(c, g_down[i], u, (long long)B * (h / 2) * (w / 2), nullptr, y);
+}
+// up: 1x1 (x (B, h, w, d) -> p (B, h, w, 2d), no bias) + PixelShuffle(2) + skip -> y (B, 2h, 2w, d / 2)
+int wdm_hfrm::up_launch(Ctx& c, int i, const void* x, void* p, const void* skip, int B, int h, int w, int d, void* y) {
+    WDM_TRY(gemm_rows(c, g_up[i], x, (long long)B * h * w, nullptr, p));
+    const long long total = (long long)B * (2 * h) * (2 * w) * (d / 2);
+    const int gg = ceil_div(total, 256) > 16384 ? 16384 : ceil_div(total, 256);
+    if (c.dtype == WDM_BF16) hipLaunchKernelGGL(pixel_shuffle_add_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (const __bf16*)p, (const __bf16*)skip, (__bf16*)y, B, h, w, d / 2);
+    else hipLaunchKernelGGL(pixel_shuffle_add_kernel<float>, dim3(gg), dim3(256), 0, c.s, (const float*)p, (const float*)skip, (float*)y, B, h, w, d / 2);
+    return WDM_OK;
+}
+// conv_out 3x3 (dim -> in_channel) + the NHWC residual, NCHW f32 out, on the conv kernel (MFMA)
+int wdm_hfrm::conv_out_mfma(Ctx& c, Tens& t, void* xin, int B, int h, int w, float* yout) {
+    ConvW cwo; cwo.w = packed + raw_bytes + cout_w_off; cwo.b = raw(L.conv_out.b); cwo.cin = cfg.dim; cwo.cout = cfg.in_channel; cwo.k = 3; cwo.rows_pad = conv_rows_pad(cfg.in_channel);
+    Tens xi; xi.p = xin; xi.C = cfg.in_channel; xi.H = h; xi.W = w; xi.xs = cfg.in_channel;
+    Tens dummy;
+    Ctx cc = c; cc.B = B;
+    return run_conv(cc, cwo, MODE_S1, {.x0 = &t, .res = &xi, .y_mode = Y_NCHW_F32, .y_ext = yout}, &dummy);
+}
+
 int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) {
     const size_t es = dsize(c.dtype);
     const int nlev = cfg.n_enc;
@@ -765,9 +803,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
     void* xin = c.ar->alloc((size_t)B * h * w * cfg.in_channel * es);          // NHWC copy of the input for the final residual
     if (!t.p || !xin) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM)");
     if (!c.dry) {
-        const int gg = ceil_div((long long)B * h * w, 256);
-        if (c.dtype == WDM_BF16) hipLaunchKernelGGL((conv3x3_cin3_kernel<__bf16, 32>), dim3(gg), dim3(256), 0, c.s, x, (__bf16*)t.p, B, h, w, cfg.in_channel, raw(L.conv_in.w), raw(L.conv_in.b));
-        else hipLaunchKernelGGL((conv3x3_cin3_kernel<float, 32>), dim3(gg), dim3(256), 0, c.s, x, (float*)t.p, B, h, w, cfg.in_channel, raw(L.conv_in.w), raw(L.conv_in.b));
+        WDM_TRY(conv_in_launch(c, x, B, h, w, t.p));
         WDM_TRY(k_nchw_to_nhwc(x, xin, B, cfg.in_channel, h, w, c.dtype, c.s));
     }
     std::vector<Tens> encs;
@@ -779,13 +815,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         Tens nt; nt.C = 2 * d; nt.H = h / 2; nt.W = w / 2; nt.xs = 2 * d;
         nt.p = c.ar->alloc((size_t)B * nt.H * nt.W * nt.C * es);
         if (!u || !nt.p) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM down)");
-        if (!c.dry) {
-            const long long total = (long long)B * nt.H * nt.W * 4 * (d / (c.dtype == WDM_BF16 ? 8 : 4));
-            const int gg = ceil_div(total, 256) > 16384 ? 16384 : ceil_div(total, 256);
-            if (c.dtype == WDM_BF16) hipLaunchKernelGGL(unshuffle2_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (const __bf16*)t.p, (__bf16*)u, B, h, w, d);
-            else hipLaunchKernelGGL(unshuffle2_kernel<float>, dim3(gg), dim3(256), 0, c.s, (const float*)t.p, (float*)u, B, h, w, d);
-            WDM_TRY(gemm_rows(c, g_down[i], u, (long long)B * nt.H * nt.W, nullptr, nt.p));
-        }
+        if (!c.dry) WDM_TRY(down_launch(c, i, t.p, u, B, h, w, d, nt.p));
         c.ar->free(u);
         t = nt; d *= 2; h /= 2; w /= 2;
     }
@@ -797,13 +827,7 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
         Tens nt; nt.C = d / 2; nt.H = 2 * h; nt.W = 2 * w; nt.xs = d / 2;
         nt.p = c.ar->alloc((size_t)B * nt.H * nt.W * nt.C * es);
         if (!p || !nt.p) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM up)");
-        if (!c.dry) {
-            WDM_TRY(gemm_rows(c, g_up[i], t.p, (long long)B * h * w, nullptr, p));
-            const long long total = (long long)B * nt.H * nt.W * nt.C;
-            const int gg = ceil_div(total, 256) > 16384 ? 16384 : ceil_div(total, 256);
-            if (c.dtype == WDM_BF16) hipLaunchKernelGGL(pixel_shuffle_add_kernel<__bf16>, dim3(gg), dim3(256), 0, c.s, (const __bf16*)p, (const __bf16*)skip.p, (__bf16*)nt.p, B, h, w, nt.C);
-            else hipLaunchKernelGGL(pixel_shuffle_add_kernel<float>, dim3(gg), dim3(256), 0, c.s, (const float*)p, (const float*)skip.p, (float*)nt.p, B, h, w, nt.C);
-        }
+        if (!c.dry) WDM_TRY(up_launch(c, i, t.p, p, skip.p, B, h, w, d, nt.p));
         c.ar->free(p); c.ar->free(t.p); c.ar->free(skip.p);
         t = nt; d /= 2; h *= 2; w *= 2;
         for (auto& b : L.dec[i]) WDM_TRY(run_block(c, b, t, B, h, w, nlev - 1 - i));
@@ -812,14 +836,60 @@ int wdm_hfrm::forward(Ctx& c, const float* x, int B, int H, int W, float* yout) 
     if (conv_out_direct((long long)B * h * w)) {
         if (!c.dry) WDM_TRY(k_conv_out_direct(t.p, xin, raw(L.conv_out.w), raw(L.conv_out.b), B, h, w, cfg.dim, cfg.in_channel, c.dtype, yout, c.s));
     } else {
-        ConvW cwo; cwo.w = packed + raw_bytes + cout_w_off; cwo.b = raw(L.conv_out.b); cwo.cin = cfg.dim; cwo.cout = cfg.in_channel; cwo.k = 3; cwo.rows_pad = conv_rows_pad(cfg.in_channel);
-        Tens xi; xi.p = xin; xi.C = cfg.in_channel; xi.H = h; xi.W = w; xi.xs = cfg.in_channel;
-        Tens dummy;
-        Ctx cc = c; cc.B = B;
-        WDM_TRY(run_conv(cc, cwo, MODE_S1, {.x0 = &t, .res = &xi, .y_mode = Y_NCHW_F32, .y_ext = yout}, &dummy));
+        WDM_TRY(conv_out_mfma(c, t, xin, B, h, w, yout));
     }
     c.ar->free(t.p); c.ar->free(xin);
     return WDM_OK;
+}
+
+// One stage on its own (wdm_hfrm_stage_forward): the members forward() runs, on the caller's tensors.  A block works in place, so its input is copied into y first.
+int wdm_hfrm::stage(Ctx& c, int kind, int index, const void* x, const void* skip, int B, int H, int W, void* y) {
+    const size_t es = dsize(c.dtype);
+    const int nlev = cfg.n_enc;
+    if ((long long)H * W > WDM_HFRM_MAX_PIXELS) WDM_FAIL(WDM_EINVAL, "HFRM stage: %d x %d pixels per image exceed the bound of 2^27", H, W);
+    switch (kind) {
+    case WDM_HFRM_STAGE_BLOCK: {
+        const Block* blk = nullptr; int level = 0;
+        for (int i = 0; i < nlev; ++i) for (auto& b : L.enc[i]) if (b.idx == index) { blk = &b; level = i; }
+        for (int i = 0; i < cfg.n_dec; ++i) for (auto& b : L.dec[i]) if (b.idx == index) { blk = &b; level = nlev - 1 - i; }
+        for (auto& b : L.mid) if (b.idx == index) { blk = &b; level = nlev; }
+        if (!blk) WDM_FAIL(WDM_EINVAL, "HFRM stage: no block %d (the model has %d)", index, L.n_blocks);
+        Tens t; t.C = blk->d; t.H = H; t.W = W; t.xs = blk->d; t.p = y;
+        if (!c.dry) WDM_HIP(hipMemcpyAsync(y, x, (size_t)B * H * W * blk->d * es, hipMemcpyDeviceToDevice, c.s));
+        return run_block(c, *blk, t, B, H, W, level);
+    }
+    case WDM_HFRM_STAGE_DOWN: {
+        if (index < 0 || index >= nlev) WDM_FAIL(WDM_EINVAL, "HFRM stage: no downs[%d]", index);
+        if (H % 2 || W % 2) WDM_FAIL(WDM_EINVAL, "HFRM stage: downs takes an even map, not %d x %d", H, W);
+        const int d = L.downs[index].cin;
+        void* u = c.ar->alloc((size_t)B * (H / 2) * (W / 2) * 4 * d * es);
+        if (!u) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM down)");
+        if (!c.dry) WDM_TRY(down_launch(c, index, x, u, B, H, W, d, y));
+        c.ar->free(u);
+        return WDM_OK;
+    }
+    case WDM_HFRM_STAGE_UP: {
+        if (index < 0 || index >= cfg.n_dec) WDM_FAIL(WDM_EINVAL, "HFRM stage: no ups[%d]", index);
+        if (!c.dry && !skip) WDM_FAIL(WDM_EINVAL, "HFRM stage: ups needs its skip tensor");
+        const int d = L.ups[index].cin;
+        void* p = c.ar->alloc((size_t)B * H * W * 2 * d * es);
+        if (!p) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM up)");
+        if (!c.dry) WDM_TRY(up_launch(c, index, x, p, skip, B, H, W, d, y));
+        c.ar->free(p);
+        return WDM_OK;
+    }
+    case WDM_HFRM_STAGE_CONV_IN:
+        if (!c.dry) WDM_TRY(conv_in_launch(c, (const float*)x, B, H, W, y));
+        return WDM_OK;
+    case WDM_HFRM_STAGE_CONV_OUT: {
+        if (!c.dry && !skip) WDM_FAIL(WDM_EINVAL, "HFRM stage: conv_out needs its residual (skip)");
+        // the conv kernel's smallest tile is 8 x 8 pixels and conv_dispatch.inc refuses a map that is no multiple of it; refused here, before the workspace is asked for
+        if (H % 8 || W % 8) WDM_FAIL(WDM_EINVAL, "HFRM stage: conv_out's MFMA form runs on the conv kernel, whose tiles are 8 x 8 pixels: %d x %d is no multiple", H, W);
+        Tens t; t.C = cfg.dim; t.H = H; t.W = W; t.xs = cfg.dim; t.p = const_cast<void*>(x);
+        return conv_out_mfma(c, t, const_cast<void*>(skip), B, H, W, (float*)y);
+    }
+    }
+    WDM_FAIL(WDM_EINVAL, "HFRM stage: unknown kind %d", kind);
 }
 
 // =================================================================================================
@@ -969,6 +1039,31 @@ int wdm_hfrm_forward(wdm_hfrm* m, const float* x, int B, int H, int W, float* y,
     Arena ar(workspace, workspace_bytes);
     Ctx c{(hipStream_t)stream, m->cfg.dtype, B, &ar, false};
     return m->forward(c, x, B, H, W, y);
+}
+/* one stage of the network on its own (unit tests): the members wdm_hfrm_forward runs, on the caller's tensors; waits for the stream */
+size_t wdm_hfrm_stage_workspace_bytes(const wdm_hfrm* m, int kind, int index, int B, int H, int W) {
+    if (!m || B <= 0 || H <= 0 || W <= 0) return 0;
+    Arena ar = Arena::dry();
+    Ctx c{nullptr, m->cfg.dtype, B, &ar, true};
+    if (const_cast<wdm_hfrm*>(m)->stage(c, kind, index, nullptr, nullptr, B, H, W, nullptr) != WDM_OK) return 0;
+    return ar.peak() + 4096;
+}
+int wdm_hfrm_stage_forward(wdm_hfrm* m, int kind, int index, const void* x, const void* skip, int B, int H, int W, void* y, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    if (!m || !x || !y || !workspace) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_stage_forward: null argument");
+    if (!m->finalized) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_stage_forward: parameters not loaded / finalized");
+    if (B <= 0 || H <= 0 || W <= 0) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_stage_forward: bad shape");
+    if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)skip)) & 15) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_stage_forward: tensors must be 16-byte aligned");
+    if (((uintptr_t)workspace) & 255) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_stage_forward: workspace must be 256-byte aligned");
+    const size_t need = wdm_hfrm_stage_workspace_bytes(m, kind, index, B, H, W);
+    if (!need) return WDM_EINVAL;                                                   // (the dry run has set the message)
+    if (workspace_bytes < need) WDM_FAIL(WDM_ENOMEM, "wdm_hfrm_stage_forward: workspace too small (%zu bytes given, wdm_hfrm_stage_workspace_bytes asks for %zu)", workspace_bytes, need);
+    Arena ar(workspace, workspace_bytes);
+    Ctx c{(hipStream_t)stream, m->cfg.dtype, B, &ar, false};
+    const int rc = m->stage(c, kind, index, x, skip, B, H, W, y);
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (rc == WDM_OK && e != hipSuccess) WDM_FAIL(WDM_EHIP, "wdm_hfrm_stage_forward: %s", hipGetErrorString(e));
+    return rc;
 }
 
 }  // extern "C"
