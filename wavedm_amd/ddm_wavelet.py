@@ -367,7 +367,7 @@ class DenoisingDiffusion_Wavelet(object):
     def _ddim_overlapping_global(self, x, x_cond, seq, model, b, corners, p_size, total, eta=0.):
         """The `use_global` branch of generalized_steps_overlapping (ddm_wavelet.py:479-483): every patch is [x_cond crop | x_t crop] and the
         model also sees the whole image `total`, repeated for each patch.  Crops and concatenation are tensor plumbing; the UNet and the
-        scatter-mean + DDIM update are library kernels (`wdm_ddim_update_c`, the one the main sampler uses)."""
+        scatter-mean + DDIM update are the sampler's own: sampling._step_scalars and sampling._Stitched.update, a first-order step with or without noise."""
         if total is None:
             raise ValueError("use_global=True needs `total`, the whole image the patches attend to")
         if not self.config.data.begin_from_noise:
@@ -376,34 +376,25 @@ class DenoisingDiffusion_Wavelet(object):
         x = _lib.require_cuda_f32(x, "x")
         x_cond = _lib.require_cuda_f32(x_cond, "x_cond")
         total = _lib.require_cuda_f32(total, "total")
-        nimg, pc, H, W = x.shape
+        nimg, _, H, W = x.shape
         p = int(p_size)
         tri = [(im, int(hi), int(wi)) for im in range(nimg) for (hi, wi) in corners]
         patches = torch.tensor(tri, dtype=torch.int32).to(self.device)
-        L, h = _lib.lib(), _lib.handle(self.device.index or 0)
+        geo = sampling._Stitched(_lib.lib(), _lib.handle(self.device.index or 0), nimg, H, W, p, len(tri), patches)
         abar = sampling.alpha_bar_table(b)
-        seq_next = [-1] + seq[:-1]
         xs, x0_preds, xt = [x], [], x
         cond_p = torch.cat([x_cond[im:im + 1, :, hi:hi + p, wi:wi + p] for (im, hi, wi) in tri], dim=0)
         tot_p = torch.cat([total[im:im + 1] if total.shape[0] == nimg else total[:1] for (im, _, _) in tri], dim=0).contiguous()
         with torch.cuda.device(self.device):
-            for i_t, j_t in zip(reversed(seq), reversed(seq_next)):
-                at, at_next = abar[i_t + 1], abar[j_t + 1]
+            for i_t, j_t in zip(reversed(seq), reversed([-1] + seq[:-1])):
                 xt_p = torch.cat([xt[im:im + 1, :, hi:hi + p, wi:wi + p] for (im, hi, wi) in tri], dim=0)
                 inp = torch.cat([cond_p, xt_p], dim=1).contiguous()
                 t = torch.tensor([float(i_t)], device=self.device)
                 eps = torch.cat([model(inp[i:i + 8], t, tot_p[i:i + 8]) for i in range(0, len(tri), 8)], dim=0).contiguous()      # manual_batching_size 8
                 x0, xn = torch.empty_like(xt), torch.empty_like(xt)
-                if eta != 0.:                                                       # ddm_wavelet.py:500-502
-                    c1 = eta * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
-                    noise = torch.randn_like(xt)
-                    _lib.check(L.wdm_ddim_update_eta_c(h, _lib.ptr(eps), _lib.ptr(patches), len(tri), p, pc, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
-                                                       float(at.sqrt()), float(at_next.sqrt()), float(c1), float(((1 - at_next) - c1 ** 2).sqrt()),
-                                                       _lib.ptr(noise), _lib.ptr(x0), _lib.ptr(xn), _lib.stream_ptr()))
-                else:
-                    _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps), _lib.ptr(patches), len(tri), p, pc, _lib.ptr(xt), nimg, H, W, float((1 - at).sqrt()),
-                                                   float(at.sqrt()), float(at_next.sqrt()), float((1 - at_next).sqrt()), _lib.ptr(x0), _lib.ptr(xn),
-                                                   _lib.stream_ptr()))
+                step = sampling._Step(*sampling._step_scalars(abar, i_t, j_t, eta), None)
+                noise = torch.randn_like(xt) if eta != 0. else None                 # ddm_wavelet.py:500-502
+                geo.update(step, eps, xt, None, noise, x0, xn, _lib.stream_ptr())
                 x0_preds.append(x0)
                 xs.append(xn)
                 xt = xn

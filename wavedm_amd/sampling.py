@@ -9,6 +9,7 @@ syncs per step, ddm_wavelet.py:498-504)."""
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -316,8 +317,207 @@ class RaggedLayout:
                 _device_const(dev, "ragged_blk", self.blk_off, torch.int32), _device_const(dev, "ragged_pix", self.pix_off, torch.int64))
 
 
+def _step_scalars(abar, i_t, j_t, eta=0.0):
+    """(s1m, sa, san, c1, c2) of the step t = i_t -> j_t as Python floats: sqrt(1 - at), sqrt(at), sqrt(at_next) and the two weights of ddm_wavelet.py:500-502
+    (c1 = 0 at eta = 0).  `abar` is alpha_bar_table's: fp32 scalars as compute_alpha returns, fp32 tensor arithmetic like the reference's, float() last."""
+    at, at_next = abar[i_t + 1], abar[j_t + 1]
+    s1m, sa, san = float((1 - at).sqrt()), float(at.sqrt()), float(at_next.sqrt())
+    if eta == 0.0:
+        return s1m, sa, san, 0.0, float((1 - at_next).sqrt())
+    c1t = eta * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
+    return s1m, sa, san, float(c1t), float(((1 - at_next) - c1t ** 2).sqrt())
+
+
+_Step = namedtuple("_Step", "s1m sa san c1 c2 m")       # _step_scalars + the step's solver_coefficients entry (None: first order)
+
+
+def _ptr(t):
+    return None if t is None else _lib.ptr(t)
+
+
+def _rows(rows, *tensors):
+    return tensors if rows is None else tuple(None if t is None else t[rows[0]:rows[1]] for t in tensors)
+
+
+class _Stitched:
+    """The geometry of a call on images of ONE size: `nimg` maps of H x W and `n` windows of p x p, named by `patches`, an (n, 3) int32 device tensor of
+    (img, hi, wi) -- or None, the identity list: row i is image i whole.  `cpatches` names the same windows in the conditioning where its rows differ
+    (samples > 1: image row // samples).  Patch-sharded, `patches` is the rank's slice (n may be 0) while nimg is the whole batch.
+    Every stitched pack / update / accumulate / from_sums launch of the package is issued here, on the library `L` and handle `h` it was given."""
+
+    def __init__(self, L, h, nimg, H, W, p, n, patches=None, cpatches=None):
+        self.L, self.h, self.nimg, self.H, self.W, self.p, self.n = L, h, nimg, H, W, p, n
+        self.patches, self.cpatches = patches, (patches if cpatches is None else cpatches)
+
+    def pack(self, src, nch, c_off, x96, dtype_code, stream, cond=False, rows=None):
+        """The windows of `src` (nch channels) -> channels c_off ... of the NHWC UNet input x96; `cond`: through the conditioning's list; `rows`: as in update."""
+        if not self.n:
+            return
+        src, x96 = _rows(rows, src, x96)
+        _lib.check(self.L.wdm_pack_channels(self.h, _ptr(src), nch, self.H, self.W, _ptr(self.cpatches if cond else self.patches), x96.shape[0], self.p,
+                                            _ptr(x96), x96.shape[-1], c_off, dtype_code, stream))
+
+    def update(self, step, eps, xt, x0_prev, noise, x0, xn, stream, rows=None):
+        """Scatter-mean of eps + the step's update -> x0, xn: second order where step.m is given, else DDIM with or without `noise`.  rows = (lo, hi): the
+        slice of the identity list a chunk works on -- those rows of every tensor, as a batch of their own."""
+        L, m, pc = self.L, step.m, xt.shape[1]
+        assert rows is None or self.patches is None, "only the identity list splits by rows"
+        eps, xt, x0_prev, noise, x0, xn = _rows(rows, eps, xt, x0_prev, noise, x0, xn)
+        n, nimg = (self.n, self.nimg) if rows is None else (rows[1] - rows[0],) * 2
+        head = (self.h, _ptr(eps), _ptr(self.patches), n, self.p, pc, _ptr(xt))
+        if m is not None:
+            if noise is not None:
+                raise ValueError("the multistep update has no stochastic term: noise is given with a second-order step")
+            rc = L.wdm_multistep_update_c(*head, _ptr(x0_prev), nimg, self.H, self.W, step.s1m, step.sa, m["cx"], m["c0"], m["cp"], _ptr(x0), _ptr(xn), stream)
+        elif noise is not None:
+            rc = L.wdm_ddim_update_eta_c(*head, nimg, self.H, self.W, step.s1m, step.sa, step.san, step.c1, step.c2, _ptr(noise), _ptr(x0), _ptr(xn), stream)
+        else:
+            rc = L.wdm_ddim_update_c(*head, nimg, self.H, self.W, step.s1m, step.sa, step.san, step.c2, _ptr(x0), _ptr(xn), stream)
+        _lib.check(rc)
+
+    def accumulate(self, eps, pc, acc_cnt, stream):
+        """Patch-sharded: this rank's partial overlap sums | counts -> acc_cnt, 2 * nimg * pc * H * W floats."""
+        _lib.check(self.L.wdm_patch_accumulate_c(self.h, _ptr(eps), _ptr(self.patches), self.n, self.p, pc, self.nimg, self.H, self.W, _ptr(acc_cnt), stream))
+
+    def from_sums(self, step, acc_cnt, xt, x0_prev, x0, xn, stream):
+        """Patch-sharded: the step's update from the all-reduced acc_cnt (eta = 0)."""
+        L, m, geo = self.L, step.m, (xt.shape[1], self.nimg, self.H, self.W)
+        if m is not None:
+            rc = L.wdm_multistep_from_sums_c(self.h, _ptr(acc_cnt), _ptr(xt), _ptr(x0_prev), *geo, step.s1m, step.sa, m["cx"], m["c0"], m["cp"], _ptr(x0), _ptr(xn), stream)
+        else:
+            rc = L.wdm_ddim_from_sums_c(self.h, _ptr(acc_cnt), _ptr(xt), *geo, step.s1m, step.sa, step.san, step.c2, _ptr(x0), _ptr(xn), stream)
+        _lib.check(rc)
+
+
+class _Ragged:
+    """The geometry of a call on a RaggedLayout: flat tensors, the image's size looked up per patch.  Every ragged pack / update launch is issued here."""
+
+    def __init__(self, L, h, layout, dev):
+        self.L, self.h, self.p, self.n, self.nimg, self.npix, self.nblk = L, h, layout.p, layout.n, layout.nimg, layout.pix_off[-1], layout.blk_off[-1]
+        self.tables = layout.tables(dev)                  # patches, img_tab, blk_tab, pix_off: alive as long as the launches that read them
+        self.pptr, self.iptr, self.bptr, self.optr = map(_ptr, self.tables)
+
+    def pack(self, src, nch, c_off, x96, dtype_code, stream, cond=False, rows=None):
+        _lib.check(self.L.wdm_pack_channels_ragged(self.h, _ptr(src), nch, self.iptr, self.optr, self.nimg, self.pptr, self.n, self.p, _ptr(x96), x96.shape[-1],
+                                                   c_off, dtype_code, stream))
+
+    def update(self, step, eps, xt, x0_prev, noise, x0, xn, stream, rows=None):
+        assert rows is None and noise is None, "a ragged call keeps to one stream and eta = 0"
+        L, m = self.L, step.m
+        head = (self.h, _ptr(eps), self.pptr, self.n, self.p, xt.numel() // self.npix, _ptr(xt))
+        tabs = (self.iptr, self.bptr, self.optr, self.nimg, self.nblk)
+        if m is not None:
+            rc = L.wdm_multistep_update_ragged(*head, _ptr(x0_prev), *tabs, step.s1m, step.sa, m["cx"], m["c0"], m["cp"], _ptr(x0), _ptr(xn), stream)
+        else:
+            rc = L.wdm_ddim_update_ragged(*head, *tabs, step.s1m, step.sa, step.san, step.c2, _ptr(x0), _ptr(xn), stream)
+        _lib.check(rc)
+
+
+def _sample_loop(geo, unet, x, x_cond, x_other, nch, seq, abar, coef, t_dev, n_steps, keep_set, max_batch, call_b, eta=0.0, all_reduce=None, ns=1):
+    """THE sampling loop, for every call form: every launch goes to the CURRENT stream (or the chunks' streams) -- also the body a hipGraph is captured from.
+    `geo` (_Stitched / _Ragged) issues the gathers and the updates; nch = (ncond, pc, nother) is the channel split of the UNet input.  What a mode changes is
+    how one step advances: pack, UNet calls, update on one stream; with `all_reduce` (patch-sharded) pack, UNet calls, accumulate, all_reduce(acc_cnt),
+    from_sums; with ns > 1 each of ns chunks of independent crops does its pack, UNet calls and update on a stream of its own."""
+    (ncond, pc, nother), dev, n, p, st = nch, x.device, geo.n, geo.p, _lib.stream_ptr()
+    x96 = torch.empty(max(n, 1), p, p, unet.in_channels, device=dev, dtype=unet._torch_dtype)
+    geo.pack(x_cond, ncond, 0, x96, unet._dtype_code, st, cond=True)
+    if nother:
+        geo.pack(x_other, nother, ncond + pc, x96, unet._dtype_code, st, cond=True)
+    eps = torch.empty(max(n, 1), pc, p, p, device=dev, dtype=torch.float32)
+    acc_cnt = torch.empty(2 * x.numel(), device=dev, dtype=torch.float32) if all_reduce is not None else None
+    # the timestep-dependent part of the UNet (embedding MLP, every temb_proj) for the WHOLE sequence at once: four launches per run instead of per step
+    temb = unet.temb_table(t_dev, B=min(max(n, 1), call_b)) if os.environ.get("WAVEDM_TEMB_TABLE", "1") != "0" else None
+
+    def advance(k, step, xt, x0_prev, noise, x0, xn, stream=st, rows=None, size=call_b, slot=0):
+        lo, hi = (0, n) if rows is None else rows
+        geo.pack(xt, pc, ncond, x96, unet._dtype_code, stream, rows=rows)
+        for i in range(lo, hi, size):
+            j = min(i + size, hi)
+            unet.forward_nhwc(x96[i:j], t_dev[k:k + 1], eps[i:j], temb_row=None if temb is None else temb[k], ws_slot=slot)
+        if all_reduce is None:
+            geo.update(step, eps, xt, x0_prev, noise, x0, xn, stream, rows=rows)
+        else:
+            geo.accumulate(eps, pc, acc_cnt, stream)
+            all_reduce(acc_cnt)
+            geo.from_sums(step, acc_cnt, xt, x0_prev, x0, xn, stream)
+
+    chunks = None
+    if ns > 1:                                                    # chunks of independent crops, one HIP stream each (ddim_sample's `streams`)
+        per, main = -(-n // ns), torch.cuda.current_stream()
+        chunks = [(lo, min(lo + per, n), sc) for lo, sc in zip(range(0, n, per), _chunk_streams(dev, ns))]
+        for (_, _, sc) in chunks:
+            sc.wait_stream(main)                                  # inputs, x96's constant channels and the temb table are ready
+        for ci, (lo, hi, _) in enumerate(chunks):                # the chunks' workspaces, allocated HERE, on the caller's stream, each for the largest
+            unet.workspace(min(max_batch, hi - lo), dev, ci)     # call its slot will run (smaller calls reuse it: DiffusionUNet.workspace)
+        _lib.set_concurrent_streams(len(chunks))                  # tile rules that count one launch's workgroups count the chunks' together (whole loop)
+    S, xs, x0_preds, xt = len(seq), [x], [], x
+    x0_prev, held = None, []          # dpmpp2m: the previous step's x0, alive here whatever `keep` drops (with side streams reading it: until the join)
+    kept = lambda q: keep_set is None or (q - (S + 1)) in keep_set          # xs[q] was asked for
+    try:
+        for k, (i_t, j_t) in enumerate(zip(reversed(seq), reversed([-1] + seq[:-1]))):
+            if _TRACE is not None:
+                _TRACE(f"sampler: step {k}")
+            if k >= n_steps:
+                x0_preds.append(None)
+                xs.append(None)
+                continue
+            step = _Step(*_step_scalars(abar, i_t, j_t, eta), coef[k])
+            noise = torch.randn_like(x) if eta != 0.0 else None               # one draw of x's shape per step, like the reference
+            x0, xn = torch.empty_like(x), torch.empty_like(x)
+            if chunks is None:
+                advance(k, step, xt, x0_prev, noise, x0, xn)
+            else:
+                for ci, (lo, hi, sc) in enumerate(chunks):                    # same kernels, same per-image bits
+                    with torch.cuda.stream(sc):
+                        advance(k, step, xt, x0_prev, noise, x0, xn, stream=sc.cuda_stream, rows=(lo, hi), size=max_batch, slot=ci)
+                if any(m is not None for m in coef):
+                    held.append(x0)
+            # lists as the reference returns them; with `keep` given, what nobody asked for is dropped at once (inside a captured graph its memory is reused)
+            x0_prev = x0
+            x0_preds.append(x0 if keep_set is None or (k - S) in keep_set else None)
+            xs.append(xn)
+            if chunks is None and len(xs) >= 3 and not kept(len(xs) - 2):
+                xs[-2] = None
+            xt = xn
+    finally:
+        if chunks is not None:
+            # also on an exception: x96, eps, xn and the temb table are released on the caller's stream, which must not happen while a side
+            # stream's kernels may still touch them
+            _lib.set_concurrent_streams(1)
+            for (_, _, sc) in chunks:
+                torch.cuda.current_stream().wait_stream(sc)        # the caller's stream sees every chunk's results
+    if chunks is not None:                                         # with side streams reading them the tensors stayed until this join
+        xs[1:-1] = [t if kept(q) else None for q, t in enumerate(xs[1:-1], 1)]
+    return xs, x0_preds
+
+
+def _enter(unet, x, x_cond, x_other):
+    """What both samplers do to their tensors first: fp32 on the GPU and contiguous, the library, the device's handle, the model's weights packed."""
+    x, x_cond = _lib.require_cuda_f32(x, "x"), _lib.require_cuda_f32(x_cond, "x_cond")
+    x_other = None if x_other is None else _lib.require_cuda_f32(x_other, "x_other")
+    L, h = _lib.lib(), _lib.handle(x.device.index or 0)
+    if hasattr(unet, "pack_weights"):
+        unet.pack_weights()                   # before the compute dtype is read: the automatic f16 mode may fall back while it packs (DiffusionUNet.pack_weights)
+    return x, x_cond, x_other, x.device, L, h
+
+
+def _run_plan(seq, betas, solver, stop_at, keep, n, max_batch, dev):
+    """What both samplers derive from their arguments alike: (seq, abar, coef, t_dev, n_run, keep_set, call_b)."""
+    seq = list(seq)
+    abar = alpha_bar_table(betas)
+    coef = solver_coefficients(seq, betas, solver)
+    t_dev = _device_const(dev, "timesteps", tuple(float(v) for v in reversed(seq)), torch.float32)
+    n_run = len(seq) if stop_at is None else len(seq) + int(stop_at) + 1
+    assert 1 <= n_run <= len(seq), f"stop_at={stop_at} out of range for {len(seq)} steps"
+    keep_set = None if keep == "all" else frozenset(int(v) for v in keep)
+    # UNet calls per step: ceil(n / max_batch) calls of (nearly) EQUAL size -- 360 patches under a cap of 128 run as 3 x 120, not 128 + 128 + 104
+    n_calls = max(1, -(-n // max_batch))
+    call_b = -(-n // n_calls) if os.environ.get("WAVEDM_EVEN_CALLS", "1") != "0" else max_batch
+    return seq, abar, coef, t_dev, n_run, keep_set, call_b
+
+
 def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=64, keep="all", stop_at=None, solver="ddim"):
-    """ddim_sample's plain loop (one stream, unsharded, eta = 0) for images of DIFFERENT sizes in one call.
+    """The sampling loop (_sample_loop: one stream, unsharded, eta = 0) for images of DIFFERENT sizes in one call.
 
     x (pc channels), x_cond (48) and x_other (or None) are ragged tensors of `layout` (RaggedLayout): flat fp32 buffers on the GPU.  The patches of all
     images form one list, gathered into one UNet input and run in the same equal-sized UNet calls (`call_b`) as ddim_sample's -- a call may hold the end of one
@@ -327,79 +527,19 @@ def ddim_sample_ragged(unet, x, x_cond, x_other, layout, seq, betas, max_batch=6
     flat tensors (layout.view gives an image's block).  With WAVEDM_GRAPH=1 a ragged call still launches directly: it is not captured.
     `solver`: as in ddim_sample (`wdm_multistep_update_ragged` on the second-order steps)."""
     check_solver(solver, "ddim_sample_ragged")
-    x = _lib.require_cuda_f32(x, "x")
-    x_cond = _lib.require_cuda_f32(x_cond, "x_cond")
-    if x_other is not None:
-        x_other = _lib.require_cuda_f32(x_other, "x_other")
-    dev = x.device
-    L, h = _lib.lib(), _lib.handle(dev.index or 0)
-    if hasattr(unet, "pack_weights"):
-        unet.pack_weights()
-    npix, p, n = layout.pix_off[-1], layout.p, layout.n
+    x, x_cond, x_other, dev, L, h = _enter(unet, x, x_cond, x_other)
+    npix = layout.pix_off[-1]
     if x.dim() != 1 or x_cond.dim() != 1 or (x_other is not None and x_other.dim() != 1):
         raise ValueError("ddim_sample_ragged: x, x_cond and x_other are flat ragged tensors")
     if x.numel() < npix or x.numel() % npix or x_cond.numel() % npix or (x_other is not None and x_other.numel() % npix):
         raise ValueError(f"ddim_sample_ragged: tensors of {x.numel()} / {x_cond.numel()} elements do not hold whole channels of the layout's {npix} pixels")
     pc, ncond, nother = x.numel() // npix, x_cond.numel() // npix, (x_other.numel() // npix if x_other is not None else 0)
-    cin = unet.in_channels
-    assert ncond + pc + nother == cin, f"channel split {ncond}+{pc}+{nother} != UNet in_channels {cin}"
-    assert p == unet.resolution, "patch size must equal config.data.image_size (unet.py:351)"
+    assert ncond + pc + nother == unet.in_channels, f"channel split {ncond}+{pc}+{nother} != UNet in_channels {unet.in_channels}"
+    assert layout.p == unet.resolution, "patch size must equal config.data.image_size (unet.py:351)"
     with torch.cuda.device(dev):
-        patches, img_tab, blk_tab, pix_off = layout.tables(dev)
-        pptr, iptr, bptr, optr = _lib.ptr(patches), _lib.ptr(img_tab), _lib.ptr(blk_tab), _lib.ptr(pix_off)
-        nimg, nblk = layout.nimg, layout.blk_off[-1]
-        seq = list(seq)
-        seq_next = [-1] + seq[:-1]
-        abar = alpha_bar_table(betas)
-        coef = solver_coefficients(seq, betas, solver)
-        t_dev = _device_const(dev, "timesteps", tuple(float(v) for v in reversed(seq)), torch.float32)
-        n_run = len(seq) if stop_at is None else len(seq) + int(stop_at) + 1
-        assert 1 <= n_run <= len(seq), f"stop_at={stop_at} out of range for {len(seq)} steps"
-        keep_set = None if keep == "all" else frozenset(int(v) for v in keep)
-        n_calls = max(1, -(-n // max_batch))                                    # ddim_sample's equal-sized calls
-        call_b = -(-n // n_calls) if os.environ.get("WAVEDM_EVEN_CALLS", "1") != "0" else max_batch
-        st = _lib.stream_ptr()
-        x96 = torch.empty(n, p, p, cin, device=dev, dtype=unet._torch_dtype)
-        _lib.check(L.wdm_pack_channels_ragged(h, _lib.ptr(x_cond), ncond, iptr, optr, nimg, pptr, n, p, _lib.ptr(x96), cin, 0, unet._dtype_code, st))
-        if nother:
-            _lib.check(L.wdm_pack_channels_ragged(h, _lib.ptr(x_other), nother, iptr, optr, nimg, pptr, n, p, _lib.ptr(x96), cin, ncond + pc, unet._dtype_code, st))
-        eps = torch.empty(n, pc, p, p, device=dev, dtype=torch.float32)
-        temb = unet.temb_table(t_dev, B=min(n, call_b)) if os.environ.get("WAVEDM_TEMB_TABLE", "1") != "0" else None
-        S = len(seq)
-        xs, x0_preds = [x], []
-        xt = x
-        x0_prev = None                                                          # the previous step's x0 (dpmpp2m), alive here whatever `keep` drops
-        for k, (i_t, j_t) in enumerate(zip(reversed(seq), reversed(seq_next))):
-            if _TRACE is not None:
-                _TRACE(f"sampler: step {k}")
-            if k >= n_run:
-                x0_preds.append(None)
-                xs.append(None)
-                continue
-            at, at_next = abar[i_t + 1], abar[j_t + 1]
-            s1m, sa = float((1 - at).sqrt()), float(at.sqrt())
-            san, c2 = float(at_next.sqrt()), float((1 - at_next).sqrt())
-            x0 = torch.empty_like(x)
-            xn = torch.empty_like(x)
-            _lib.check(L.wdm_pack_channels_ragged(h, _lib.ptr(xt), pc, iptr, optr, nimg, pptr, n, p, _lib.ptr(x96), cin, ncond, unet._dtype_code, st))
-            for i in range(0, n, call_b):
-                unet.forward_nhwc(x96[i:i + call_b], t_dev[k:k + 1], eps[i:i + call_b], temb_row=None if temb is None else temb[k])
-            if coef[k] is not None:
-                m = coef[k]
-                _lib.check(L.wdm_multistep_update_ragged(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), _lib.ptr(x0_prev), iptr, bptr, optr, nimg, nblk, s1m, sa,
-                                                         m["cx"], m["c0"], m["cp"], _lib.ptr(x0), _lib.ptr(xn), st))
-            else:
-                _lib.check(L.wdm_ddim_update_ragged(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), iptr, bptr, optr, nimg, nblk, s1m, sa, san, c2,
-                                                    _lib.ptr(x0), _lib.ptr(xn), st))
-            x0_prev = x0
-            x0_preds.append(x0 if keep_set is None or (k - S) in keep_set else None)
-            xs.append(xn)
-            if keep_set is not None and len(xs) >= 3:
-                xs[-2] = xs[-2] if (len(xs) - 2 - (S + 1)) in keep_set else None
-            xt = xn
-        if keep != "all":
-            x0_preds = [t if (i - S) in keep else None for i, t in enumerate(x0_preds)]
-        return xs, x0_preds
+        geo = _Ragged(L, h, layout, dev)
+        seq, abar, coef, t_dev, n_run, keep_set, call_b = _run_plan(seq, betas, solver, stop_at, keep, layout.n, max_batch, dev)
+        return _sample_loop(geo, unet, x, x_cond, x_other, (ncond, pc, nother), seq, abar, coef, t_dev, n_run, keep_set, max_batch, call_b)
 
 
 def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None, max_batch=64, keep="all", stop_at=None,
@@ -450,194 +590,60 @@ def ddim_sample(unet, x, x_cond, x_other, seq, betas, corners=None, p_size=None,
     if x.shape[0] != samples * x_cond.shape[0] or (samples > 1 and x_other is not None and x_other.shape[0] != x_cond.shape[0]):
         raise ValueError(f"ddim_sample: x has {x.shape[0]} rows, x_cond {x_cond.shape[0]}" + (f", x_other {x_other.shape[0]}" if x_other is not None else "") +
                          f": x.shape[0] must be samples * x_cond.shape[0] (samples = {samples})")
-    x = _lib.require_cuda_f32(x, "x")
-    x_cond = _lib.require_cuda_f32(x_cond, "x_cond")
-    if x_other is not None:
-        x_other = _lib.require_cuda_f32(x_other, "x_other")
-    dev = x.device
-    L, h = _lib.lib(), _lib.handle(dev.index or 0)
-    if hasattr(unet, "pack_weights"):
-        unet.pack_weights()                   # before the compute dtype is read: the automatic f16 mode may fall back while it packs (DiffusionUNet.pack_weights)
+    x, x_cond, x_other, dev, L, h = _enter(unet, x, x_cond, x_other)
     nimg, pc, H, W = x.shape
     ncond, nother = x_cond.shape[1], (x_other.shape[1] if x_other is not None else 0)      # x_other None: model.use_other_channels False
-    cin = unet.in_channels
-    assert ncond + pc + nother == cin, f"channel split {ncond}+{pc}+{nother} != UNet in_channels {cin}"
+    assert ncond + pc + nother == unet.in_channels, f"channel split {ncond}+{pc}+{nother} != UNet in_channels {unet.in_channels}"
     if pc < 1:
         raise ValueError("ddim_sample: x has no prediction channels")
     with torch.cuda.device(dev):
+        sharded, all_reduce = corners is not None and patch_group is not None, None
         if corners is None:
-            p = H
             assert H == W == unet.resolution
-            n, patches, pptr = nimg, None, None
-            tri = None
+            p, n, patches, tri = H, nimg, None, None
         else:
             p = int(p_size)
-            if all(len(c) == 2 for c in corners):
-                tri = [(im, int(c[0]), int(c[1])) for im in range(nimg) for c in corners]
-            else:
-                tri = [tuple(int(v) for v in c) for c in corners]
+            tri = ([(im, int(c[0]), int(c[1])) for im in range(nimg) for c in corners] if all(len(c) == 2 for c in corners) else
+                   [tuple(int(v) for v in c) for c in corners])
             for (im, hi, wi) in tri:
                 if not (0 <= im < nimg and 0 <= hi and hi + p <= H and 0 <= wi and wi + p <= W):
                     raise ValueError(f"patch {(im, hi, wi)} of size {p} outside the {nimg}x{H}x{W} image")
-            sharded = patch_group is not None
             if sharded:
                 import torch.distributed as dist
                 from .parallel import shard_range
                 grp = None if patch_group is True else patch_group
                 lo, hi = shard_range(len(tri), dist.get_rank(grp), dist.get_world_size(grp))
                 tri = tri[lo:hi]
+                all_reduce = lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=grp)
             n = len(tri)
             patches = _device_const(dev, "patches", tuple(tri) if tri else ((0, 0, 0),), torch.int32)
-            pptr = _lib.ptr(patches)
         # the conditioning's patch list: the same windows, of image row // samples (samples = 1: the list above itself)
-        cpatches, cptr = patches, pptr
+        cpatches = patches
         if samples > 1:
             ctri = tuple((im // samples, hi, wi) for (im, hi, wi) in tri) if tri is not None else tuple((im // samples, 0, 0) for im in range(nimg))
             cpatches = _device_const(dev, "patches", ctri, torch.int32)
-            cptr = _lib.ptr(cpatches)
         assert p == unet.resolution, "patch size must equal config.data.image_size (unet.py:351)"
-        sharded = corners is not None and patch_group is not None
         if patch_group is not None and corners is None:
             raise ValueError("patch_group needs a corner list: independent crops shard by image (parallel.restore_sharded)")
-        seq = list(seq)
-        seq_next = [-1] + seq[:-1]
-        abar = alpha_bar_table(betas)
-        coef = solver_coefficients(seq, betas, solver)
-        t_dev = _device_const(dev, "timesteps", tuple(float(v) for v in reversed(seq)), torch.float32)
-        n_run = len(seq) if stop_at is None else len(seq) + int(stop_at) + 1
-        assert 1 <= n_run <= len(seq), f"stop_at={stop_at} out of range for {len(seq)} steps"
-        keep_set = None if keep == "all" else frozenset(int(v) for v in keep)
+        geo = _Stitched(L, h, nimg, H, W, p, n, patches, cpatches)
+        seq, abar, coef, t_dev, n_run, keep_set, call_b = _run_plan(seq, betas, solver, stop_at, keep, n, max_batch, dev)
         eta = float(eta)
         if eta != 0.0 and sharded:
             raise NotImplementedError("ddim_sample: eta != 0 with patch_group (every rank would have to draw the same noise)")
         ns = int(os.environ.get("WAVEDM_STREAMS", "1")) if streams is None else int(streams)
         multi = corners is None and not sharded and ns > 1 and n >= 2 * ns and not _lib.prof_on() and eta == 0.0
-        # UNet calls per step: ceil(n / max_batch) calls of (nearly) EQUAL size -- 360 patches under a cap of 128 run as 3 x 120, not 128 + 128 + 104
-        # (per-image results do not depend on the batch an image sits in, tests/test_gpu_unet.py)
-        n_calls = max(1, -(-n // max_batch))
-        call_b = -(-n // n_calls) if os.environ.get("WAVEDM_EVEN_CALLS", "1") != "0" else max_batch
 
         def run_loop(x, x_cond, x_other, n_steps, use_chunks):
-            """The sampling loop proper: every launch goes to the CURRENT stream (or the chunks' streams) -- also the body a hipGraph is captured from."""
-            st = _lib.stream_ptr()
-            x96 = torch.empty(max(n, 1), p, p, cin, device=dev, dtype=unet._torch_dtype)
-            if n:
-                _lib.check(L.wdm_pack_channels(h, _lib.ptr(x_cond), ncond, H, W, cptr, n, p, _lib.ptr(x96), cin, 0, unet._dtype_code, st))
-                if nother:
-                    _lib.check(L.wdm_pack_channels(h, _lib.ptr(x_other), nother, H, W, cptr, n, p, _lib.ptr(x96), cin, ncond + pc, unet._dtype_code, st))
-            eps = torch.empty(max(n, 1), pc, p, p, device=dev, dtype=torch.float32)
-            acc_cnt = torch.empty(2 * x.numel(), device=dev, dtype=torch.float32) if sharded else None
-            # the timestep-dependent part of the UNet (embedding MLP, every temb_proj) for the WHOLE sequence at once: four launches per run instead of per step
-            temb = unet.temb_table(t_dev, B=min(max(n, 1), call_b)) if os.environ.get("WAVEDM_TEMB_TABLE", "1") != "0" else None
-            S = len(seq)
-            xs, x0_preds = [x], []
-            xt = x
-            x0_prev, held = None, []          # dpmpp2m: the previous step's x0, alive here whatever `keep` drops (with side streams reading it: until the join)
-            # chunks of independent crops, one HIP stream each (see `streams`)
-            chunks = None
-            if use_chunks:
-                per = -(-n // ns)
-                main = torch.cuda.current_stream()
-                chunks = []
-                pool = _chunk_streams(dev, ns)
-                for ci, lo in enumerate(range(0, n, per)):
-                    sc = pool[ci]
-                    sc.wait_stream(main)                                  # inputs, x96's constant channels and the temb table are ready
-                    chunks.append((lo, min(lo + per, n), sc))
-                for ci, (lo, hi, _) in enumerate(chunks):                # the chunks' workspaces, allocated HERE, on the caller's stream, each for the largest
-                    unet.workspace(min(max_batch, hi - lo), dev, ci)     # call its slot will run (smaller calls reuse it: DiffusionUNet.workspace)
-            if chunks is not None:
-                _lib.set_concurrent_streams(len(chunks))                  # tile rules that count one launch's workgroups count the chunks' together (whole loop)
-            try:
-                for k, (i_t, j_t) in enumerate(zip(reversed(seq), reversed(seq_next))):
-                    if _TRACE is not None:
-                        _TRACE(f"sampler: step {k}")
-                    if k >= n_steps:
-                        x0_preds.append(None)
-                        xs.append(None)
-                        continue
-                    at, at_next = abar[i_t + 1], abar[j_t + 1]                       # fp32 scalars, as compute_alpha returns
-                    s1m, sa = float((1 - at).sqrt()), float(at.sqrt())
-                    san, c2 = float(at_next.sqrt()), float((1 - at_next).sqrt())      # c1 = 0 (eta = 0)
-                    noise, c1 = None, 0.0
-                    if eta != 0.0:                                                    # ddm_wavelet.py:500-501, in fp32 tensors like the reference
-                        c1t = eta * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
-                        c1, c2 = float(c1t), float(((1 - at_next) - c1t ** 2).sqrt())
-                        noise = torch.randn_like(x)
-                    x0 = torch.empty_like(x)
-                    xn = torch.empty_like(x)
-                    m = coef[k]                                                       # None: a first-order step, the DDIM launches below as ever
-                    if chunks is not None:
-                        # independent crops: every chunk's step on its own stream (same kernels, same per-image bits)
-                        for ci, (lo, hi, sc) in enumerate(chunks):
-                            with torch.cuda.stream(sc):
-                                stc = sc.cuda_stream
-                                _lib.check(L.wdm_pack_channels(h, _lib.ptr(xt[lo:hi]), pc, H, W, None, hi - lo, p, _lib.ptr(x96[lo:hi]), cin, ncond, unet._dtype_code, stc))
-                                for i in range(lo, hi, max_batch):
-                                    j = min(i + max_batch, hi)
-                                    unet.forward_nhwc(x96[i:j], t_dev[k:k + 1], eps[i:j], temb_row=None if temb is None else temb[k], ws_slot=ci)
-                                if m is not None:
-                                    _lib.check(L.wdm_multistep_update_c(h, _lib.ptr(eps[lo:hi]), None, hi - lo, p, pc, _lib.ptr(xt[lo:hi]), _lib.ptr(x0_prev[lo:hi]),
-                                                                        hi - lo, H, W, s1m, sa, m["cx"], m["c0"], m["cp"], _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc))
-                                else:
-                                    _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps[lo:hi]), None, hi - lo, p, pc, _lib.ptr(xt[lo:hi]), hi - lo, H, W, s1m, sa, san, c2,
-                                                                   _lib.ptr(x0[lo:hi]), _lib.ptr(xn[lo:hi]), stc))
-                        if solver != "ddim":
-                            held.append(x0)
-                    else:
-                        if n:
-                            _lib.check(L.wdm_pack_channels(h, _lib.ptr(xt), pc, H, W, pptr, n, p, _lib.ptr(x96), cin, ncond, unet._dtype_code, st))
-                        for i in range(0, n, call_b):
-                            unet.forward_nhwc(x96[i:i + call_b], t_dev[k:k + 1], eps[i:i + call_b], temb_row=None if temb is None else temb[k])
-                        if sharded:
-                            _lib.check(L.wdm_patch_accumulate_c(h, _lib.ptr(eps), pptr, n, p, pc, nimg, H, W, _lib.ptr(acc_cnt), st))      # sums | counts: 2 * NIMG * pc * H * W floats
-                            dist.all_reduce(acc_cnt, op=dist.ReduceOp.SUM, group=grp)
-                            if m is not None:
-                                _lib.check(L.wdm_multistep_from_sums_c(h, _lib.ptr(acc_cnt), _lib.ptr(xt), _lib.ptr(x0_prev), pc, nimg, H, W, s1m, sa,
-                                                                       m["cx"], m["c0"], m["cp"], _lib.ptr(x0), _lib.ptr(xn), st))
-                            else:
-                                _lib.check(L.wdm_ddim_from_sums_c(h, _lib.ptr(acc_cnt), _lib.ptr(xt), pc, nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st))
-                        elif m is not None:
-                            _lib.check(L.wdm_multistep_update_c(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), _lib.ptr(x0_prev), nimg, H, W, s1m, sa,
-                                                                m["cx"], m["c0"], m["cp"], _lib.ptr(x0), _lib.ptr(xn), st))
-                        elif noise is not None:
-                            _lib.check(L.wdm_ddim_update_eta_c(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c1, c2, _lib.ptr(noise),
-                                                               _lib.ptr(x0), _lib.ptr(xn), st))
-                        else:
-                            _lib.check(L.wdm_ddim_update_c(h, _lib.ptr(eps), pptr, n, p, pc, _lib.ptr(xt), nimg, H, W, s1m, sa, san, c2, _lib.ptr(x0), _lib.ptr(xn), st))
-                    # lists as the reference returns them; with `keep` given, what nobody asked for is dropped at once (inside a captured graph its memory is reused)
-                    x0_prev = x0
-                    x0_preds.append(x0 if keep_set is None or (k - S) in keep_set else None)
-                    xs.append(xn)
-                    if keep_set is not None and len(xs) >= 3 and chunks is None:     # (with side streams still reading them the tensors stay until the loop's join)
-                        xs[-2] = xs[-2] if (len(xs) - 2 - (S + 1)) in keep_set else None
-                    xt = xn
-            finally:
-                if chunks is not None:
-                    # also on an exception: x96, eps, xn and the temb table are released on the caller's stream, which must not happen while a side
-                    # stream's kernels may still touch them
-                    _lib.set_concurrent_streams(1)
-                    for (_, _, sc) in chunks:
-                        torch.cuda.current_stream().wait_stream(sc)        # the caller's stream sees every chunk's results
-                    if keep_set is not None:                               # ... and only now lets go of what nobody asked for
-                        for q in range(1, len(xs) - 1):
-                            if (q - (S + 1)) not in keep_set:
-                                xs[q] = None
-                    del held[:]
-            return xs, x0_preds
+            return _sample_loop(geo, unet, x, x_cond, x_other, (ncond, pc, nother), seq, abar, coef, t_dev, n_steps, keep_set, max_batch, call_b,
+                                eta=eta, all_reduce=all_reduce, ns=ns if use_chunks else 1)
 
         graphed = (os.environ.get("WAVEDM_GRAPH", "0") == "1" and not sharded and not multi and n > 0 and not _lib.prof_on() and eta == 0.0 and
                    not torch.cuda.is_current_stream_capturing())
-        if graphed:
-            # everything the captured launch sequence depends on is in the key (ADVICE r5): shapes and the model's buffers (in _replay_graph), the timestep
-            # sequence, the patch list, the call size, what is kept, the schedule's bytes (cached per betas tensor: no read-back per call), the temb-table switch
-            xs, x0_preds = _replay_graph(unet, run_loop, x, x_cond, x_other, n_run,
-                                         (tuple(seq), None if corners is None else tuple(map(tuple, tri)), p, max_batch, call_b, keep_set, n_run, _betas_entry(betas)[1],
-                                          os.environ.get("WAVEDM_TEMB_TABLE", "1"), str(x_cond.dtype), None if x_other is None else str(x_other.dtype), solver, samples),
-                                         keepalive=(patches, cpatches, t_dev))
-        else:
-            xs, x0_preds = run_loop(x, x_cond, x_other, n_run, multi)
-        if keep != "all":
-            S = len(x0_preds)
-            x0_preds = [t if (i - S) in keep else None for i, t in enumerate(x0_preds)]
-        return xs, x0_preds
+        if not graphed:
+            return run_loop(x, x_cond, x_other, n_run, multi)
+        # everything the captured launch sequence depends on is in the key: shapes and the model's buffers (in _replay_graph), the timestep
+        # sequence, the patch list, the call size, what is kept, the schedule's bytes (cached per betas tensor: no read-back per call), the temb-table switch
+        return _replay_graph(unet, run_loop, x, x_cond, x_other, n_run,
+                             (tuple(seq), None if corners is None else tuple(map(tuple, tri)), p, max_batch, call_b, keep_set, n_run, _betas_entry(betas)[1],
+                              os.environ.get("WAVEDM_TEMB_TABLE", "1"), str(x_cond.dtype), None if x_other is None else str(x_other.dtype), solver, samples),
+                             keepalive=(patches, cpatches, t_dev))
