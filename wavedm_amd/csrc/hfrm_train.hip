@@ -24,31 +24,34 @@
 #include <string>
 
 #include "common.h"
+#include "hfrm_kernels.h"
 
 namespace hft {
 using namespace wdm;
 
 #define GS_LOOP(id, n) for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < (n); id += (long long)gridDim.x * blockDim.x)
 
-// T is the storage type of an activation or activation gradient: float (the exact mode: plain loads and stores, the code the fp32 trainer has always run) or
-// __bf16 (the mixed mode: converted to fp32 on load, rounded to nearest even on store; all arithmetic and every reduction in fp32 in the same fixed order).
-// The streaming kernels move 16 bytes per lane in the bf16 instantiation (8 channels: every channel count of the network is a multiple of 32).
-template <typename T> __device__ __forceinline__ float ldv(const T* p, long long i) { return TI<T>::ld(p, i); }
-template <typename T> __device__ __forceinline__ void stv(T* p, long long i, float v) { TI<T>::st(p, i, v); }
-template <typename T> __device__ __forceinline__ void ld8(const T* p, long long i, float* f) { TI<T>::unpack(*(const uint4*)(p + i), f); }
-template <typename T> __device__ __forceinline__ void st8(T* p, long long i, const float* f) { *(uint4*)(p + i) = TI<T>::pack(f); }
-template <typename T> constexpr bool H16 = sizeof(T) == 2;
+// T is the storage type of an activation or activation gradient: float (the exact mode) or __bf16 (the mixed mode: converted to fp32 on load, rounded to nearest
+// even on store).  All arithmetic and every reduction are fp32 in the same fixed order in both: every streaming kernel has ONE body, written over the V consecutive
+// channels a lane owns -- eight of 16-bit storage (16 bytes), one float.  (Not TI<float>::VEC = 4: one channel per lane is the layout, and so the summation order
+// and the bits, of the fp32 trainer.)  Every channel count of the network is a multiple of 32.
+template <typename T> struct Lane {
+    static constexpr int V = 8;
+    __device__ static __forceinline__ void ld(const T* p, long long i, float* f) { TI<T>::unpack(*(const uint4*)(p + i), f); }
+    __device__ static __forceinline__ void st(T* p, long long i, const float* f) { *(uint4*)(p + i) = TI<T>::pack(f); }
+};
+template <> struct Lane<float> {
+    static constexpr int V = 1;
+    __device__ static __forceinline__ void ld(const float* p, long long i, float* f) { f[0] = p[i]; }
+    __device__ static __forceinline__ void st(float* p, long long i, const float* f) { p[i] = f[0]; }
+};
 
-__device__ __forceinline__ float team_sum(float v) {      // sum over the 32 lanes of a half wave
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// ---- LayerNorm2d (arch.py:7-43), a team of 32 lanes per pixel, channel c = lane + 32 j --------------------------------
-constexpr int LN_TEAMS = 8;
-// bf16: a lane owns 8 consecutive channels (16 bytes), a team of C / 8 lanes (at most 32; two vectors per lane at C = 512) a pixel
-template <int C> struct Ln16 { static constexpr int TEAM = C / 8 < 32 ? C / 8 : 32, NV = C / (8 * TEAM), PPB = 256 / TEAM; };
+// ---- LayerNorm2d (arch.py:7-43): a team of C / V lanes (at most 32: NV vectors per lane beyond) per pixel, lane tl owns the channels (tl + TEAM v) V + e.
+// fp32: 32 lanes, channel tl + 32 v, 8 pixels per workgroup; bf16: 4 .. 32 lanes (two vectors per lane at C = 512), 64 .. 8 pixels per workgroup
+template <typename T> constexpr int ln_team(int C) { return C / Lane<T>::V < 32 ? C / Lane<T>::V : 32; }      // (the kernels' layout and the host's grid both come from this)
+template <typename T, int C> struct Ln {
+    static constexpr int V = Lane<T>::V, TEAM = ln_team<T>(C), NV = C / (V * TEAM), PPB = 256 / TEAM;
+};
 template <int TEAM> __device__ __forceinline__ float team_sum_n(float v) {
 #pragma unroll
     for (int o = TEAM / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
@@ -57,47 +60,28 @@ template <int TEAM> __device__ __forceinline__ float team_sum_n(float v) {
 template <typename T, int NJ>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, long long M, const float* __restrict__ w,
                                                      const float* __restrict__ b) {
-    constexpr int C = 32 * NJ;
-    if constexpr (H16<T>) {
-        constexpr int TEAM = Ln16<C>::TEAM, NV = Ln16<C>::NV, PPB = Ln16<C>::PPB;
-        const int tl = threadIdx.x % TEAM;
-        for (long long p = (long long)blockIdx.x * PPB + threadIdx.x / TEAM; p < M; p += (long long)gridDim.x * PPB) {
-            float f[NV][8], s = 0.f;
+    constexpr int C = 32 * NJ, V = Lane<T>::V, TEAM = Ln<T, C>::TEAM, NV = Ln<T, C>::NV, PPB = Ln<T, C>::PPB;
+    const int tl = threadIdx.x % TEAM;
+    for (long long p = (long long)blockIdx.x * PPB + threadIdx.x / TEAM; p < M; p += (long long)gridDim.x * PPB) {
+        float f[NV * V], s = 0.f;
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                ld8(x, p * C + (tl + TEAM * v) * 8, f[v]);
+        for (int v = 0; v < NV; ++v) {
+            Lane<T>::ld(x, p * C + (tl + TEAM * v) * V, f + v * V);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) s += f[v][e];
-            }
-            const float mu = team_sum_n<TEAM>(s) / (float)C;
-            float q = 0.f;
-#pragma unroll
-            for (int v = 0; v < NV; ++v)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float dd = f[v][e] - mu; q += dd * dd; }
-            const float rstd = 1.0f / sqrtf(team_sum_n<TEAM>(q) / (float)C + 1e-6f);
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int c = (tl + TEAM * v) * 8;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) f[v][e] = (f[v][e] - mu) * rstd * w[c + e] + b[c + e];
-                st8(y, p * C + c, f[v]);
-            }
+            for (int e = 0; e < V; ++e) s += f[v * V + e];
         }
-        return;
-    }
-    const int lane = threadIdx.x & 31;
-    for (long long p = (long long)blockIdx.x * LN_TEAMS + (threadIdx.x >> 5); p < M; p += (long long)gridDim.x * LN_TEAMS) {
-        float f[NJ], s = 0.f;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) { f[j] = ldv(x, p * C + lane + 32 * j); s += f[j]; }
-        const float mu = team_sum(s) / (float)C;
+        const float mu = team_sum_n<TEAM>(s) / (float)C;
         float q = 0.f;
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) { const float dd = f[j] - mu; q += dd * dd; }
-        const float rstd = 1.0f / sqrtf(team_sum(q) / (float)C + 1e-6f);
+        for (int i = 0; i < NV * V; ++i) { const float dd = f[i] - mu; q += dd * dd; }      // (one loop: as two nested ones hipcc fuses the other of the first two products)
+        const float rstd = 1.0f / sqrtf(team_sum_n<TEAM>(q) / (float)C + 1e-6f);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) { const int c = lane + 32 * j; stv(y, p * C + c, (f[j] - mu) * rstd * w[c] + b[c]); }
+        for (int v = 0; v < NV; ++v) {
+            const int c = (tl + TEAM * v) * V;
+#pragma unroll
+            for (int e = 0; e < V; ++e) f[v * V + e] = (f[v * V + e] - mu) * rstd * w[c + e] + b[c + e];
+            Lane<T>::st(y, p * C + c, f + v * V);
+        }
     }
 }
 
@@ -106,107 +90,62 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, T*
 template <typename T, int NJ>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dn, const float* __restrict__ w, const T* dres,
                                                      T* dx, long long M, float* __restrict__ part) {
-    constexpr int C = 32 * NJ;
-    if constexpr (H16<T>) {
-        constexpr int TEAM = Ln16<C>::TEAM, NV = Ln16<C>::NV, PPB = Ln16<C>::PPB;
-        __shared__ float red16[PPB][2][C];
-        const int tl = threadIdx.x % TEAM, tm = threadIdx.x / TEAM;
-        float aw[NV][8], ab[NV][8];
+    constexpr int C = 32 * NJ, V = Lane<T>::V, TEAM = Ln<T, C>::TEAM, NV = Ln<T, C>::NV, PPB = Ln<T, C>::PPB;
+    __shared__ float red[PPB][2][C];
+    const int tl = threadIdx.x % TEAM, tm = threadIdx.x / TEAM;
+    float aw[NV][V], ab[NV][V];
 #pragma unroll
-        for (int v = 0; v < NV; ++v)
+    for (int v = 0; v < NV; ++v)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { aw[v][e] = 0.f; ab[v][e] = 0.f; }
-        for (long long p = (long long)blockIdx.x * PPB + tm; p < M; p += (long long)gridDim.x * PPB) {
-            float f[NV][8], g[NV][8], s = 0.f;
+        for (int e = 0; e < V; ++e) { aw[v][e] = 0.f; ab[v][e] = 0.f; }
+    for (long long p = (long long)blockIdx.x * PPB + tm; p < M; p += (long long)gridDim.x * PPB) {
+        float f[NV * V], g[NV * V], s = 0.f;
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                ld8(x, p * C + (tl + TEAM * v) * 8, f[v]);
+        for (int v = 0; v < NV; ++v) {
+            Lane<T>::ld(x, p * C + (tl + TEAM * v) * V, f + v * V);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) s += f[v][e];
-            }
-            const float mu = team_sum_n<TEAM>(s) / (float)C;
-            float q = 0.f;
-#pragma unroll
-            for (int v = 0; v < NV; ++v)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float dd = f[v][e] - mu; q += dd * dd; }
-            const float rstd = 1.0f / sqrtf(team_sum_n<TEAM>(q) / (float)C + 1e-6f);
-            float sg = 0.f, sgy = 0.f;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int c = (tl + TEAM * v) * 8;
-                float d[8];
-                ld8(dn, p * C + c, d);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    f[v][e] = (f[v][e] - mu) * rstd;                      // xh
-                    g[v][e] = d[e] * w[c + e];
-                    sg += g[v][e]; sgy += g[v][e] * f[v][e];
-                    aw[v][e] += d[e] * f[v][e]; ab[v][e] += d[e];
-                }
-            }
-            const float mg = team_sum_n<TEAM>(sg) / (float)C, mgy = team_sum_n<TEAM>(sgy) / (float)C;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const long long i = p * C + (tl + TEAM * v) * 8;
-                float r[8];
-                ld8(dres, i, r);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) r[e] += rstd * (g[v][e] - f[v][e] * mgy - mg);
-                st8(dx, i, r);
-            }
+            for (int e = 0; e < V; ++e) s += f[v * V + e];
         }
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { red16[tm][0][(tl + TEAM * v) * 8 + e] = aw[v][e]; red16[tm][1][(tl + TEAM * v) * 8 + e] = ab[v][e]; }
-        __syncthreads();
-        for (int i = threadIdx.x; i < 2 * C; i += 256) {
-            const int k = i / C, c = i % C;
-            float s = 0.f;
-            for (int t = 0; t < PPB; ++t) s += red16[t][k][c];
-            part[(long long)blockIdx.x * 2 * C + i] = s;
-        }
-        return;
-    }
-    __shared__ float red[LN_TEAMS][2][C];
-    const int lane = threadIdx.x & 31, team = threadIdx.x >> 5;
-    float aw[NJ], ab[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { aw[j] = 0.f; ab[j] = 0.f; }
-    for (long long p = (long long)blockIdx.x * LN_TEAMS + team; p < M; p += (long long)gridDim.x * LN_TEAMS) {
-        float f[NJ], g[NJ], s = 0.f;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) { f[j] = ldv(x, p * C + lane + 32 * j); s += f[j]; }
-        const float mu = team_sum(s) / (float)C;
+        const float mu = team_sum_n<TEAM>(s) / (float)C;
         float q = 0.f;
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) { const float dd = f[j] - mu; q += dd * dd; }
-        const float rstd = 1.0f / sqrtf(team_sum(q) / (float)C + 1e-6f);
+        for (int i = 0; i < NV * V; ++i) { const float dd = f[i] - mu; q += dd * dd; }      // (one loop, as in ln_fwd_kernel)
+        const float rstd = 1.0f / sqrtf(team_sum_n<TEAM>(q) / (float)C + 1e-6f);
         float sg = 0.f, sgy = 0.f;
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int c = lane + 32 * j;
-            const float d = ldv(dn, p * C + c);
-            f[j] = (f[j] - mu) * rstd;                      // xh
-            g[j] = d * w[c];
-            sg += g[j]; sgy += g[j] * f[j];
-            aw[j] += d * f[j]; ab[j] += d;
-        }
-        const float mg = team_sum(sg) / (float)C, mgy = team_sum(sgy) / (float)C;
+        for (int v = 0; v < NV; ++v) {
+            const int c = (tl + TEAM * v) * V;
+            float d[V];
+            Lane<T>::ld(dn, p * C + c, d);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const long long i = p * C + lane + 32 * j;
-            stv(dx, i, ldv(dres, i) + rstd * (g[j] - f[j] * mgy - mg));
+            for (int e = 0; e < V; ++e) {
+                const int i = v * V + e;
+                f[i] = (f[i] - mu) * rstd;                      // xh
+                g[i] = d[e] * w[c + e];
+                sg += g[i]; sgy += g[i] * f[i];
+                aw[v][e] += d[e] * f[i]; ab[v][e] += d[e];
+            }
+        }
+        const float mg = team_sum_n<TEAM>(sg) / (float)C, mgy = team_sum_n<TEAM>(sgy) / (float)C;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const long long i = p * C + (tl + TEAM * v) * V;
+            float r[V];
+            Lane<T>::ld(dres, i, r);
+#pragma unroll
+            for (int e = 0; e < V; ++e) r[e] += rstd * (g[v * V + e] - f[v * V + e] * mgy - mg);
+            Lane<T>::st(dx, i, r);
         }
     }
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) { red[team][0][lane + 32 * j] = aw[j]; red[team][1][lane + 32 * j] = ab[j]; }
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int e = 0; e < V; ++e) { red[tm][0][(tl + TEAM * v) * V + e] = aw[v][e]; red[tm][1][(tl + TEAM * v) * V + e] = ab[v][e]; }
     __syncthreads();
     for (int i = threadIdx.x; i < 2 * C; i += 256) {
         const int k = i / C, c = i % C;
         float s = 0.f;
-        for (int t = 0; t < LN_TEAMS; ++t) s += red[t][k][c];
+        for (int t = 0; t < PPB; ++t) s += red[t][k][c];
         part[(long long)blockIdx.x * 2 * C + i] = s;
     }
 }
@@ -216,57 +155,37 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ x, co
 template <typename T>
 __global__ __launch_bounds__(256) void chan_part_kernel(const T* __restrict__ a, const T* __restrict__ m, int C, int HW, int chunk, int nk,
                                                         float* __restrict__ part) {
-    if constexpr (H16<T>) {      // a thread sums 8 channels of every (256 / (cols / 8))-th pixel row; the rows are then joined in ascending order
-        __shared__ float red16[256 * 8];
-        const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
-        const int cols = min(C - cb * 256, 256), colsv = cols / 8, rows = 256 / colsv;
-        const int col = threadIdx.x % colsv, r = threadIdx.x / colsv, c = cb * 256 + col * 8;
-        float s[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s[e] = 0.f;
-        if (r < rows) {
-            const int p1 = min((k + 1) * chunk, HW);
-            for (int p = k * chunk + r; p < p1; p += rows) {
-                const long long i = ((long long)b * HW + p) * C + c;
-                float f[8], g[8];
-                ld8(a, i, f);
-                if (m) {
-                    ld8(m, i, g);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s[e] += f[e] * g[e];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s[e] += f[e];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) red16[r * cols + col * 8 + e] = s[e];
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < cols) {
-            float t = 0.f;
-            for (int rr = 0; rr < rows; ++rr) t += red16[rr * cols + threadIdx.x];
-            part[((long long)b * nk + k) * C + cb * 256 + threadIdx.x] = t;
-        }
-        return;
-    }
-    __shared__ float red[256];
+    constexpr int V = Lane<T>::V;      // a thread sums V channels of every (256 / (cols / V))-th pixel row; the rows are then joined in ascending order
+    __shared__ float red[256 * V];
     const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
-    const int cols = min(C - cb * 256, 256), rows = 256 / cols;
-    const int col = threadIdx.x % cols, r = threadIdx.x / cols, c = cb * 256 + col;
-    float s = 0.f;
+    const int cols = min(C - cb * 256, 256), colsv = cols / V, rows = 256 / colsv;
+    const int col = threadIdx.x % colsv, r = threadIdx.x / colsv, c = cb * 256 + col * V;
+    float s[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) s[e] = 0.f;
     if (r < rows) {
         const int p1 = min((k + 1) * chunk, HW);
         for (int p = k * chunk + r; p < p1; p += rows) {
             const long long i = ((long long)b * HW + p) * C + c;
-            s += m ? ldv(a, i) * ldv(m, i) : ldv(a, i);
+            float f[V], g[V];
+            Lane<T>::ld(a, i, f);
+            if (m) {
+                Lane<T>::ld(m, i, g);
+#pragma unroll
+                for (int e = 0; e < V; ++e) s[e] += f[e] * g[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < V; ++e) s[e] += f[e];
+            }
         }
+#pragma unroll
+        for (int e = 0; e < V; ++e) red[r * cols + col * V + e] = s[e];
     }
-    red[threadIdx.x] = s;
     __syncthreads();
-    if (r == 0) {
-        for (int rr = 1; rr < rows; ++rr) s += red[rr * cols + col];
-        part[((long long)b * nk + k) * C + c] = s;
+    if ((int)threadIdx.x < cols) {
+        float t = red[threadIdx.x];
+        for (int rr = 1; rr < rows; ++rr) t += red[rr * cols + threadIdx.x];
+        part[((long long)b * nk + k) * C + cb * 256 + threadIdx.x] = t;
     }
 }
 // out = scale * sum of the partial rows, images and chunks ascending.  per_image: one output row per image (o0[b][c]); else the
@@ -290,62 +209,47 @@ __global__ __launch_bounds__(256) void chan_final_kernel(const float* __restrict
 // SimpleGate (arch.py:132-141): g[p][c] = a[p][c] * a[p][d + c]  (* sc[b][c] when sc is given)
 template <typename T>
 __global__ __launch_bounds__(256) void gate_kernel(const T* __restrict__ a, T* __restrict__ g, long long n, int d, const float* __restrict__ sc, int HW) {
-    if constexpr (H16<T>) {
-        GS_LOOP(iv, n / 8) {
-            const long long id = iv * 8, p = id / d;
-            const int c = (int)(id % d);
-            float u[8], v[8];
-            ld8(a, p * 2 * d + c, u); ld8(a, p * 2 * d + d + c, v);
+    constexpr int V = Lane<T>::V;
+    GS_LOOP(iv, n / V) {
+        const long long id = iv * V, p = id / d;
+        const int c = (int)(id % d);
+        float u[V], v[V];
+        Lane<T>::ld(a, p * 2 * d + c, u); Lane<T>::ld(a, p * 2 * d + d + c, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { v[e] *= u[e]; if (sc) v[e] *= sc[(p / HW) * d + c + e]; }
-            st8(g, id, v);
-        }
-    } else {
-        GS_LOOP(id, n) {
-            const long long p = id / d;
-            const int c = (int)(id % d);
-            float v = a[p * 2 * d + c] * a[p * 2 * d + d + c];
-            if (sc) v *= sc[(p / HW) * d + c];
-            g[id] = v;
-        }
+        for (int e = 0; e < V; ++e) { v[e] *= u[e]; if (sc) v[e] *= sc[(p / HW) * d + c + e]; }
+        Lane<T>::st(g, id, v);
     }
 }
 template <typename T>
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const T* __restrict__ dg, const T* __restrict__ a, T* __restrict__ da, long long n, int d) {
-    if constexpr (H16<T>) {
-        GS_LOOP(iv, n / 8) {
-            const long long id = iv * 8, p = id / d;
-            const int c = (int)(id % d);
-            float g[8], u[8], v[8];
-            ld8(dg, id, g); ld8(a, p * 2 * d + c, u); ld8(a, p * 2 * d + d + c, v);
+    constexpr int V = Lane<T>::V;
+    GS_LOOP(iv, n / V) {
+        const long long id = iv * V, p = id / d;
+        const int c = (int)(id % d);
+        float g[V], u[V], v[V];
+        Lane<T>::ld(dg, id, g); Lane<T>::ld(a, p * 2 * d + c, u); Lane<T>::ld(a, p * 2 * d + d + c, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { const float t = g[e] * v[e]; v[e] = g[e] * u[e]; u[e] = t; }
-            st8(da, p * 2 * d + c, u); st8(da, p * 2 * d + d + c, v);
-        }
-    } else {
-        GS_LOOP(id, n) {
-            const long long p = id / d;
-            const int c = (int)(id % d);
-            const float g = dg[id];
-            da[p * 2 * d + c] = g * a[p * 2 * d + d + c];
-            da[p * 2 * d + d + c] = g * a[p * 2 * d + c];
-        }
+        for (int e = 0; e < V; ++e) { const float t = g[e] * v[e]; v[e] = g[e] * u[e]; u[e] = t; }
+        Lane<T>::st(da, p * 2 * d + c, u); Lane<T>::st(da, p * 2 * d + d + c, v);
     }
 }
 // out[p][c] = x[p][c] + s[c] * v[p][c]   (x == nullptr: s[c] * v[p][c])
 template <typename T>
 __global__ __launch_bounds__(256) void axpy_chan_kernel(const T* __restrict__ x, const float* __restrict__ s, const T* __restrict__ v, T* __restrict__ out,
                                                         long long n, int C) {
-    if constexpr (H16<T>) {
-        GS_LOOP(iv, n / 8) {
-            const long long id = iv * 8;
+    // The one kernel that keeps a body per width, for the bits: hipcc's contraction made x + s v ONE fma in the vector body and the rounded product plus an add
+    // in the scalar one (its add sits behind the branch on x, in another basic block).  One body gives both widths the fma.
+    constexpr int V = Lane<T>::V;
+    if constexpr (V > 1) {
+        GS_LOOP(iv, n / V) {
+            const long long id = iv * V;
             const int c = (int)(id % C);
-            float f[8], xf[8];
-            ld8(v, id, f);
-            if (x) ld8(x, id, xf);
+            float f[V], xf[V];
+            Lane<T>::ld(v, id, f);
+            if (x) Lane<T>::ld(x, id, xf);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { const float t = s[c + e] * f[e]; f[e] = x ? xf[e] + t : t; }
-            st8(out, id, f);
+            for (int e = 0; e < V; ++e) { const float t = s[c + e] * f[e]; f[e] = x ? xf[e] + t : t; }
+            Lane<T>::st(out, id, f);
         }
     } else {
         GS_LOOP(id, n) {
@@ -358,23 +262,16 @@ __global__ __launch_bounds__(256) void axpy_chan_kernel(const T* __restrict__ x,
 template <typename T>
 __global__ __launch_bounds__(256) void ca_dg_kernel(T* __restrict__ dg, const float* __restrict__ sc, const float* __restrict__ dpool, long long n, int d, int HW,
                                                     float inv_hw) {
-    if constexpr (H16<T>) {
-        GS_LOOP(iv, n / 8) {
-            const long long id = iv * 8;
-            const int c = (int)(id % d);
-            const long long b = id / d / HW;
-            float f[8];
-            ld8(dg, id, f);
+    constexpr int V = Lane<T>::V;
+    GS_LOOP(iv, n / V) {
+        const long long id = iv * V;
+        const int c = (int)(id % d);
+        const long long b = id / d / HW;
+        float f[V];
+        Lane<T>::ld(dg, id, f);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = f[e] * sc[b * d + c + e] + dpool[b * d + c + e] * inv_hw;
-            st8(dg, id, f);
-        }
-    } else {
-        GS_LOOP(id, n) {
-            const int c = (int)(id % d);
-            const long long b = id / d / HW;
-            dg[id] = dg[id] * sc[b * d + c] + dpool[b * d + c] * inv_hw;
-        }
+        for (int e = 0; e < V; ++e) f[e] = f[e] * sc[b * d + c + e] + dpool[b * d + c + e] * inv_hw;
+        Lane<T>::st(dg, id, f);
     }
 }
 // channel attention backward, vector side (sc = W pooled + bias, B x d): dW[o][i] = sum_b dsc[b][o] pooled[b][i], db[o] = sum_b dsc[b][o],
@@ -406,116 +303,102 @@ __global__ __launch_bounds__(256) void ca_bwd_kernel(const float* __restrict__ d
 template <typename T>
 __global__ __launch_bounds__(256) void dw_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int H, int W, int C, long long n, const float* __restrict__ w,
                                                      const float* __restrict__ bias) {
-    if constexpr (H16<T>) {
-        GS_LOOP(iv, n / 8) {
-            const long long id = iv * 8;
-            const int c = (int)(id % C);
-            const long long p = id / C;
-            const int px = (int)(p % W), py = (int)((p / W) % H);
-            const long long img = p - (long long)py * W - px;
-            float s[8], f[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s[e] = bias[c + e];
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-                    ld8(x, (img + (long long)yy * W + xx) * C + c, f);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s[e] += f[e] * w[(c + e) * 9 + t];
-                }
-            }
-            st8(y, id, s);
-        }
-    } else
-    GS_LOOP(id, n) {
+    constexpr int V = Lane<T>::V;
+    GS_LOOP(iv, n / V) {
+        const long long id = iv * V;
         const int c = (int)(id % C);
         const long long p = id / C;
         const int px = (int)(p % W), py = (int)((p / W) % H);
         const long long img = p - (long long)py * W - px;
-        float s = bias[c];
+        float s[V], f[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = bias[c + e];
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) s += x[(img + (long long)yy * W + xx) * C + c] * w[c * 9 + t];
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                Lane<T>::ld(x, (img + (long long)yy * W + xx) * C + c, f);
+#pragma unroll
+                for (int e = 0; e < V; ++e) s[e] += f[e] * w[(c + e) * 9 + t];
+            }
         }
-        y[id] = s;
+        Lane<T>::st(y, id, s);
     }
 }
 // dx[q][c] = sum_t w[c][t] dy[q - (t / 3 - 1, t % 3 - 1)][c]
 template <typename T>
 __global__ __launch_bounds__(256) void dw_dgrad_kernel(const T* __restrict__ dy, T* __restrict__ dx, int H, int W, int C, long long n, const float* __restrict__ w) {
-    if constexpr (H16<T>) {
-        GS_LOOP(iv, n / 8) {
-            const long long id = iv * 8;
-            const int c = (int)(id % C);
-            const long long p = id / C;
-            const int px = (int)(p % W), py = (int)((p / W) % H);
-            const long long img = p - (long long)py * W - px;
-            float s[8], f[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s[e] = 0.f;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = py - (t / 3 - 1), xx = px - (t % 3 - 1);
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-                    ld8(dy, (img + (long long)yy * W + xx) * C + c, f);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s[e] += f[e] * w[(c + e) * 9 + t];
-                }
-            }
-            st8(dx, id, s);
-        }
-    } else
-    GS_LOOP(id, n) {
+    constexpr int V = Lane<T>::V;
+    GS_LOOP(iv, n / V) {
+        const long long id = iv * V;
         const int c = (int)(id % C);
         const long long p = id / C;
         const int px = (int)(p % W), py = (int)((p / W) % H);
         const long long img = p - (long long)py * W - px;
-        float s = 0.f;
+        float s[V], f[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = 0.f;
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int yy = py - (t / 3 - 1), xx = px - (t % 3 - 1);
-            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) s += dy[(img + (long long)yy * W + xx) * C + c] * w[c * 9 + t];
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                Lane<T>::ld(dy, (img + (long long)yy * W + xx) * C + c, f);
+#pragma unroll
+                for (int e = 0; e < V; ++e) s[e] += f[e] * w[(c + e) * 9 + t];
+            }
         }
-        dx[id] = s;
+        Lane<T>::st(dx, id, s);
     }
 }
 // part[(b * nk + k)][c][10]: sum over chunk k of image b of dy[p][c] x[p + tap][c] (taps 0..8) and of dy[p][c] (slot 9)
 template <typename T>
 __global__ __launch_bounds__(256) void dw_wgrad_part_kernel(const T* __restrict__ dy, const T* __restrict__ x, int H, int W, int C, int chunk, int nk,
                                                             float* __restrict__ part) {
-    if constexpr (H16<T>) {      // a thread holds the ten sums of 8 channels; the pixel rows are joined through LDS five slots at a time, in ascending order
-        __shared__ float red16[256 * 8 * 5];
-        const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
-        const int HW = H * W;
-        const int cols = min(C - cb * 256, 256), colsv = cols / 8, rows = 256 / colsv;
-        const int col = threadIdx.x % colsv, r = threadIdx.x / colsv, c = cb * 256 + col * 8;
-        float acc[10][8];
+    constexpr int V = Lane<T>::V;      // a thread holds the ten sums of V channels; the pixel rows are joined through LDS in ascending order
+    __shared__ float red[256 * (V == 1 ? 10 : V * 5)];
+    const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
+    const int HW = H * W;
+    const int cols = min(C - cb * 256, 256), colsv = cols / V, rows = 256 / colsv;
+    const int col = threadIdx.x % colsv, r = threadIdx.x / colsv, c = cb * 256 + col * V;
+    float acc[10][V];
 #pragma unroll
-        for (int t = 0; t < 10; ++t)
+    for (int t = 0; t < 10; ++t)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) acc[t][e] = 0.f;
-        if (r < rows) {
-            const long long img = (long long)b * HW;
-            const int p1 = min((k + 1) * chunk, HW);
-            for (int p = k * chunk + r; p < p1; p += rows) {
-                const int py = p / W, px = p - py * W;
-                float g[8], f[8];
-                ld8(dy, (img + p) * C + c, g);
+        for (int e = 0; e < V; ++e) acc[t][e] = 0.f;
+    if (r < rows) {
+        const long long img = (long long)b * HW;
+        const int p1 = min((k + 1) * chunk, HW);
+        for (int p = k * chunk + r; p < p1; p += rows) {
+            const int py = p / W, px = p - py * W;
+            float g[V], f[V];
+            Lane<T>::ld(dy, (img + p) * C + c, g);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) acc[9][e] += g[e];
+            for (int e = 0; e < V; ++e) acc[9][e] += g[e];
 #pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                    if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-                        ld8(x, (img + (long long)yy * W + xx) * C + c, f);
+            for (int t = 0; t < 9; ++t) {
+                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                    Lane<T>::ld(x, (img + (long long)yy * W + xx) * C + c, f);
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) acc[t][e] += g[e] * f[e];
-                    }
+                    for (int e = 0; e < V; ++e) acc[t][e] += g[e] * f[e];
                 }
             }
         }
+    }
+    // The join, rows ascending from row 0's value, keeps a form per width: with the five-slot form below the fp32 kernel measured 1 % slower than with this one
+    // (profiles/hfrm_train_one_body.md), and all ten slots of eight channels per lane would take 80 KB.
+    if constexpr (V == 1) {      // all ten slots at once (10 KB): row 0's thread adds the other rows to its own sums and stores its ten
+#pragma unroll
+        for (int t = 0; t < 10; ++t) red[threadIdx.x * 10 + t] = acc[t][0];
+        __syncthreads();
+        if (r == 0) {
+            for (int rr = 1; rr < rows; ++rr)
+#pragma unroll
+                for (int t = 0; t < 10; ++t) acc[t][0] += red[(rr * cols + col) * 10 + t];
+#pragma unroll
+            for (int t = 0; t < 10; ++t) part[(((long long)b * nk + k) * C + c) * 10 + t] = acc[t][0];
+        }
+    } else {                     // five slots at a time
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             if (half) __syncthreads();
@@ -523,49 +406,16 @@ __global__ __launch_bounds__(256) void dw_wgrad_part_kernel(const T* __restrict_
 #pragma unroll
                 for (int t = 0; t < 5; ++t)
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) red16[(r * 5 + t) * cols + col * 8 + e] = acc[half * 5 + t][e];
+                    for (int e = 0; e < V; ++e) red[(r * 5 + t) * cols + col * V + e] = acc[half * 5 + t][e];
             }
             __syncthreads();
             for (int o = threadIdx.x; o < 5 * cols; o += 256) {
                 const int t = o / cols, ch = o % cols;
-                float sum = 0.f;
-                for (int rr = 0; rr < rows; ++rr) sum += red16[(rr * 5 + t) * cols + ch];
+                float sum = red[t * cols + ch];
+                for (int rr = 1; rr < rows; ++rr) sum += red[(rr * 5 + t) * cols + ch];
                 part[(((long long)b * nk + k) * C + cb * 256 + ch) * 10 + half * 5 + t] = sum;
             }
         }
-        return;
-    }
-    __shared__ float red[256 * 10];
-    const int k = blockIdx.x, b = blockIdx.y, cb = blockIdx.z;
-    const int HW = H * W;
-    const int cols = min(C - cb * 256, 256), rows = 256 / cols;
-    const int col = threadIdx.x % cols, r = threadIdx.x / cols, c = cb * 256 + col;
-    float acc[10];
-#pragma unroll
-    for (int t = 0; t < 10; ++t) acc[t] = 0.f;
-    if (r < rows) {
-        const long long img = (long long)b * HW;
-        const int p1 = min((k + 1) * chunk, HW);
-        for (int p = k * chunk + r; p < p1; p += rows) {
-            const int py = p / W, px = p - py * W;
-            const float g = ldv(dy, (img + p) * C + c);
-            acc[9] += g;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) acc[t] += g * ldv(x, (img + (long long)yy * W + xx) * C + c);
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 10; ++t) red[threadIdx.x * 10 + t] = acc[t];
-    __syncthreads();
-    if (r == 0) {
-        for (int rr = 1; rr < rows; ++rr)
-#pragma unroll
-            for (int t = 0; t < 10; ++t) acc[t] += red[(rr * cols + col) * 10 + t];
-#pragma unroll
-        for (int t = 0; t < 10; ++t) part[(((long long)b * nk + k) * C + c) * 10 + t] = acc[t];
     }
 }
 __global__ __launch_bounds__(256) void dw_wgrad_final_kernel(const float* __restrict__ part, int nparts, int C, float* __restrict__ dw, float* __restrict__ db) {
@@ -584,50 +434,28 @@ template <typename T>
 __global__ __launch_bounds__(256) void unshuffle2_kernel(T* __restrict__ x, T* __restrict__ u, int B, int H, int W, int d, int add) {
     const int h2 = H / 2, w2 = W / 2;
     const long long n = (long long)B * h2 * w2 * 4 * d;
-    if constexpr (H16<T>) {
-        GS_LOOP(iv, n / 8) {
-            const long long id = iv * 8;
-            const int c = (int)(id % d);
-            const int ij = (int)((id / d) % 4);
-            const long long op = id / (4 * d);
-            const int ox = (int)(op % w2), oy = (int)((op / w2) % h2);
-            const long long b = op / ((long long)w2 * h2);
-            const long long xi = ((b * H + 2 * oy + (ij >> 1)) * W + 2 * ox + (ij & 1)) * d + c;
-            float f[8], g[8];
-            if (add) {
-                ld8(x, xi, f); ld8(u, id, g);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] += g[e];
-                st8(x, xi, f);
-            } else {
-                *(uint4*)(u + id) = *(const uint4*)(x + xi);
-            }
-        }
-    } else
-    GS_LOOP(id, n) {
+    constexpr int V = Lane<T>::V;
+    GS_LOOP(iv, n / V) {
+        const long long id = iv * V;
         const int c = (int)(id % d);
         const int ij = (int)((id / d) % 4);
         const long long op = id / (4 * d);
         const int ox = (int)(op % w2), oy = (int)((op / w2) % h2);
         const long long b = op / ((long long)w2 * h2);
         const long long xi = ((b * H + 2 * oy + (ij >> 1)) * W + 2 * ox + (ij & 1)) * d + c;
-        if (add) x[xi] += u[id];
-        else u[id] = x[xi];
+        float f[V], g[V];
+        if (add) {
+            Lane<T>::ld(u, id, g); Lane<T>::ld(x, xi, f);      // (u first: with x first the compiler hoists x's load above the branch, and the fp32 gather measured 8 % slower)
+#pragma unroll
+            for (int e = 0; e < V; ++e) f[e] += g[e];
+            Lane<T>::st(x, xi, f);
+        } else {
+            Lane<T>::ld(x, xi, f);
+            Lane<T>::st(u, id, f);
+        }
     }
 }
-// forward: out[b][2y+i][2x+j][c] = p[b][y][x][c*4 + i*2 + j] + skip[...];  adjoint: dp[b][y][x][c*4 + i*2 + j] = dout[b][2y+i][2x+j][c]
-template <typename T>
-__global__ __launch_bounds__(256) void pixel_shuffle_kernel(const T* __restrict__ p, const T* __restrict__ skip, T* __restrict__ out, int B, int h, int w,
-                                                            int dout) {
-    const long long n = (long long)B * 4 * h * w * dout;
-    GS_LOOP(id, n) {
-        const int c = (int)(id % dout);
-        const long long op = id / dout;
-        const int X = (int)(op % (2 * w)), Y = (int)((op / (2 * w)) % (2 * h));
-        const long long b = op / ((long long)4 * w * h);
-        stv(out, id, ldv(p, ((b * h + (Y >> 1)) * w + (X >> 1)) * (4LL * dout) + c * 4 + (Y & 1) * 2 + (X & 1)) + ldv(skip, id));
-    }
-}
+// the adjoint of PixelShuffle(2) (the forward is hfrm_kernels.h's pixel_shuffle_add_kernel): dp[b][y][x][c*4 + i*2 + j] = dout[b][2y+i][2x+j][c]
 template <typename T>
 __global__ __launch_bounds__(256) void pixel_unshuffle_kernel(const T* __restrict__ dout, T* __restrict__ dp, int B, int h, int w, int dch) {
     const long long n = (long long)B * h * w * 4 * dch;
@@ -637,7 +465,7 @@ __global__ __launch_bounds__(256) void pixel_unshuffle_kernel(const T* __restric
         const int x = (int)(q % w), y = (int)((q / w) % h);
         const long long b = q / ((long long)w * h);
         const int c = k >> 2, i = (k >> 1) & 1, j = k & 1;
-        stv(dp, id, ldv(dout, ((b * 2 * h + 2 * y + i) * (2 * w) + 2 * x + j) * dch + c));
+        TI<T>::st(dp, id, TI<T>::ld(dout, ((b * 2 * h + 2 * y + i) * (2 * w) + 2 * x + j) * dch + c));
     }
 }
 // GEMM-order weight gradient [cout][(i*2+j)*cin + c] -> OIHW [cout][cin][2][2]
@@ -662,47 +490,7 @@ __global__ __launch_bounds__(256) void pack_gemm_kernel(const float* __restrict_
         else { o = (int)(id / K); kc = (int)(id % K); }
         float v = 0.f;
         if (o < cout && kc < K) v = w[((long long)o * cin + kc % cin) * kk + kc / cin];
-        stv(dst, id, v);
-    }
-}
-
-// ---- conv_in (3 -> 32, 3x3) forward on the NCHW image, as in the inference forward (hfrm.hip) -----------------------------------
-template <typename T, int DIM>
-__global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ x, T* __restrict__ y, int B, int H, int W, int cin, const float* __restrict__ w,
-                                                      const float* __restrict__ bias) {
-    __shared__ float ws[16 * 9 * DIM + DIM];
-    for (int i = threadIdx.x; i < cin * 9 * DIM; i += 256) {
-        const int co = i % DIM, k = i / DIM;
-        ws[i] = w[(long long)co * cin * 9 + k];
-    }
-    for (int i = threadIdx.x; i < DIM; i += 256) ws[cin * 9 * DIM + i] = bias[i];
-    __syncthreads();
-    const long long M = (long long)B * H * W;
-    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (pix >= M) return;
-    const int px = (int)(pix % W), py = (int)((pix / W) % H);
-    const long long b = pix / ((long long)W * H);
-    float acc[DIM];
-#pragma unroll
-    for (int o = 0; o < DIM; ++o) acc[o] = ws[cin * 9 * DIM + o];
-    for (int ci = 0; ci < cin; ++ci) {
-        const float* xp = x + (b * cin + ci) * H * W;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-            const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-            const float v = in ? xp[(long long)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)] : 0.f;
-            const float* wr = ws + (ci * 9 + t) * DIM;
-#pragma unroll
-            for (int o = 0; o < DIM; ++o) acc[o] += v * wr[o];
-        }
-    }
-    if constexpr (H16<T>) {
-#pragma unroll
-        for (int o = 0; o < DIM; o += 8) st8(y, pix * DIM + o, acc + o);
-    } else {
-#pragma unroll
-        for (int o = 0; o < DIM; ++o) y[pix * DIM + o] = acc[o];
+        TI<T>::st(dst, id, v);
     }
 }
 
@@ -731,13 +519,8 @@ __global__ __launch_bounds__(256) void conv_out_dgrad_kernel(const float* __rest
             for (int ci = 0; ci < DIM; ++ci) acc[ci] += v * ws[(co * DIM + ci) * 9 + t];
         }
     }
-    if constexpr (H16<T>) {
 #pragma unroll
-        for (int ci = 0; ci < DIM; ci += 8) st8(dt, pix * DIM + ci, acc + ci);
-    } else {
-#pragma unroll
-        for (int ci = 0; ci < DIM; ++ci) dt[pix * DIM + ci] = acc[ci];
-    }
+    for (int ci = 0; ci < DIM; ci += Lane<T>::V) Lane<T>::st(dt, pix * DIM + ci, acc + ci);
 }
 
 // Weight gradient of a 3x3 pad-1 conv between a DIM-channel NHWC map A ("wide") and an NC-channel NCHW map N ("narrow"):
@@ -759,7 +542,7 @@ __global__ __launch_bounds__(256) void wgrad3_small_part_kernel(const T* __restr
     for (long long p = p0 + r; p < p1; p += ROWS) {
         const int px = (int)(p % W), py = (int)((p / W) % H);
         const long long b = p / HW;
-        const float a = ldv(A, p * DIM + c);
+        const float a = TI<T>::ld(A, p * DIM + c);
         acc[NC * 9] += a;
 #pragma unroll
         for (int n = 0; n < NC; ++n) {
@@ -915,8 +698,8 @@ struct wdm_hfrm_trainer {
     }
 };
 
-// elements of a streaming kernel's grid-stride loop: one per lane in fp32, eight (16 bytes) in bf16
-template <typename T> static int egrid(long long n) { return grid_capped_min1(sizeof(T) == 2 ? n / 8 : n, 256); }
+// grid of a streaming kernel's grid-stride loop over n elements, V per lane
+template <typename T> static int egrid(long long n) { return grid_capped_min1(n / Lane<T>::V, 256); }
 
 int wdm_hfrm_trainer::gemm_run(Ctx& c, const void* w, int rows, int K, int N, const float* bias, const void* x, long long M, void* y) {
     if (c.dry) return WDM_OK;
@@ -954,9 +737,9 @@ int wdm_hfrm_trainer::chan_sums(Ctx& c, const T* a, const T* m, int C, int H, in
     return WDM_OK;
 }
 
-// pixels a workgroup normalises at a time: 8 teams of 32 lanes in fp32, 256 / (d / 8) teams (at least 8) in bf16
+// four rounds of Ln<T, d>::PPB pixels per workgroup, at most 1024 workgroups
 template <typename T> static int ln_grid(long long M, int d) {
-    const int ppb = sizeof(T) == 2 ? 256 / std::min(d / 8, 32) : LN_TEAMS;
+    const int ppb = 256 / ln_team<T>(d);
     return (int)std::min<long long>(1024, (M + ppb * 4 - 1) / (ppb * 4));
 }
 
@@ -1136,7 +919,7 @@ int wdm_hfrm_trainer::step_t(Ctx& c, const float* x, const float* target, const 
     std::vector<T*> enc_out(nlev), up_in(cfg.n_dec);
     T* cur = A(M0 * dim);
     if (!cur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer)");
-    if (!c.dry) hipLaunchKernelGGL((conv_in_kernel<T, 32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, cur, B, H, W, nc, prm(L.conv_in.w), prm(L.conv_in.b));
+    if (!c.dry) hipLaunchKernelGGL((conv3x3_cin3_kernel<T, 32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, cur, B, H, W, nc, prm(L.conv_in.w), prm(L.conv_in.b));
     int d = dim, h = H, w = W;
     auto run_blocks = [&](const std::vector<TBlock>& bl) -> int {
         for (auto& b : bl) { BSave<T> s; WDM_TRY(fwd_block<T>(c, b, cur, B, h, w, s)); ins.push_back(cur); saves.push_back(s); cur = s.out; }
@@ -1161,7 +944,7 @@ int wdm_hfrm_trainer::step_t(Ctx& c, const float* x, const float* target, const 
         T* nt = A(M * 2 * d);           // (2h x 2w x d/2)
         if (!p || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up)");
         WDM_TRY(fwd_gemm(c, ups[i], cur, M, p));
-        if (!c.dry) hipLaunchKernelGGL(pixel_shuffle_kernel<T>, dim3(grid_capped_min1(M * 2 * d, 256)), dim3(256), 0, c.s, p, enc_out[nlev - 1 - i], nt, B, h, w, d / 2);
+        if (!c.dry) hipLaunchKernelGGL(pixel_shuffle_add_kernel<T>, dim3(grid_capped_min1(M * 2 * d, 256)), dim3(256), 0, c.s, p, enc_out[nlev - 1 - i], nt, B, h, w, d / 2);
         c.ar->free(p);
         up_in[i] = cur;
         cur = nt; d /= 2; h *= 2; w *= 2;
