@@ -515,6 +515,24 @@ int wdm_hfrm_trainer_set_precision(wdm_hfrm_trainer* t, int act_dtype);
 size_t wdm_hfrm_trainer_workspace_bytes(const wdm_hfrm_trainer* t, int B, int H, int W);
 int wdm_hfrm_trainer_step(wdm_hfrm_trainer* t, const float* x, const float* target, const float* dy, int B, int H, int W, float* loss, float* out,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* One stage of the training step on its own (unit tests), the trainer's counterpart of wdm_hfrm_stage_forward: the forward and then the backward of one stage, through
+ * the very members wdm_hfrm_trainer_step chains (fwd_block / bwd_block, down_fwd / down_bwd, up_fwd / up_bwd, conv_in_fwd / conv_in_wgrad, conv_out_fwd / conv_out_bwd),
+ * on the caller's tensors, with the weights packed from the parameter buffer as a step packs them.  Activations and their gradients are NHWC in the trainer's current
+ * storage type (wdm_hfrm_trainer_set_precision: f32 or bf16); kinds and indices as wdm_hfrm_stage_forward.
+ *   WDM_HFRM_STAGE_BLOCK:    x, y, dy, dx (B, H, W, d); every gradient entry of the block is written
+ *   WDM_HFRM_STAGE_DOWN:     x (B, H, W, d) -> y (B, H/2, W/2, 2d); dy like y; dx (B, H, W, d) holds on entry the gradient that arrived over the skip connection and on
+ *                            return that gradient plus the adjoint of the gather (unshuffle2_kernel's add form); downs[index] weight and bias; H and W even
+ *   WDM_HFRM_STAGE_UP:       x (B, H, W, d), skip (B, 2H, 2W, d/2) -> y like skip; dy like y -> dx (B, H, W, d); ups[index] weight.  The gradient of skip is dy itself:
+ *                            no kernel runs for it and none is returned
+ *   WDM_HFRM_STAGE_CONV_IN:  x (B, 3, H, W) NCHW f32 -> y (B, H, W, 32); dy like y; there is no dx (may be NULL); conv_in weight and bias
+ *   WDM_HFRM_STAGE_CONV_OUT: x (B, H, W, 32), skip = the image (B, 3, H, W) NCHW f32 -> y (B, 3, H, W) NCHW f32; dy NCHW f32 -> dx (B, H, W, 32); conv_out weight and
+ *                            bias; H and W multiples of 8 -- the smallest tile of the conv kernel its forward runs on is 8 x 8 pixels
+ * Any other H, W >= 1.  Only the stage's own entries of the gradient buffer are written, everything else stays untouched.  All tensors 16-byte aligned; the workspace
+ * 256-byte aligned and at least wdm_hfrm_trainer_stage_workspace_bytes (0 on a bad kind, index or shape), checked before the first launch (WDM_ENOMEM).  Waits for the
+ * stream -- a test entry, not a building block.  Additions to the ABI: WDM_ABI_VERSION stays 1. */
+size_t wdm_hfrm_trainer_stage_workspace_bytes(const wdm_hfrm_trainer* t, int kind, int index, int B, int H, int W);
+int wdm_hfrm_trainer_stage(wdm_hfrm_trainer* t, int kind, int index, const void* x, const void* skip, const void* dy, int B, int H, int W, void* y, void* dx,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* the betas are doubles: torch forms 1 - beta and the bias corrections from the Python floats (an fp32 0.999 puts 1 - beta2 1.3e-5 off) */
 int wdm_hfrm_trainer_adam(wdm_hfrm_trainer* t, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay, void* stream);
 

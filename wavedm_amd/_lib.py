@@ -150,6 +150,8 @@ def lib():
         "wdm_hfrm_trainer_set_precision": (i, [vp, i]),
         "wdm_hfrm_trainer_workspace_bytes": (sz, [vp, i, i, i]),
         "wdm_hfrm_trainer_step": (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]),
+        "wdm_hfrm_trainer_stage_workspace_bytes": (sz, [vp, i, i, i, i, i]),
+        "wdm_hfrm_trainer_stage": (i, [vp, i, i, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]),
         "wdm_hfrm_trainer_adam": (i, [vp, i64, f, C.c_double, C.c_double, f, f, vp]),
         "wdm_dwt_fwd_affine": (i, [vp, vp, f, f, vp, i, i, i, vp]),
         "wdm_dwt_inv_compose": (i, [vp, vp, i, i, vp, vp, i, i, i, i, vp]),
@@ -183,7 +185,7 @@ EXPORTED = ["wdm_abi_version", "wdm_last_error", "wdm_create", "wdm_destroy", "w
             "wdm_hfrm_set_packed", "wdm_hfrm_load_param", "wdm_hfrm_finalize", "wdm_hfrm_workspace_bytes",
             "wdm_hfrm_forward", "wdm_hfrm_set_local", "wdm_hfrm_local_kernel", "wdm_hfrm_local_pool", "wdm_hfrm_set_max_launch_bytes", "wdm_hfrm_chunk_rows", "wdm_hfrm_conv_out", "wdm_hfrm_stage_workspace_bytes", "wdm_hfrm_stage_forward", "wdm_image_sqdiff", "wdm_to_u8_hwc", "wdm_image_ingest", "wdm_to_u8_hwc_crop", "wdm_image_ssim_scratch_bytes", "wdm_image_ssim", "wdm_conv_backward", "wdm_gn_act_backward", "wdm_dropout_mask", "wdm_gn_act_dropout", "wdm_trainer_create", "wdm_trainer_destroy", "wdm_trainer_num_params",
             "wdm_trainer_num_floats", "wdm_trainer_param_info", "wdm_trainer_set_buffers", "wdm_trainer_set_objective", "wdm_trainer_set_dropout", "wdm_trainer_step", "wdm_trainer_adam_ema", "wdm_trainer_set_optimizer", "wdm_trainer_optim_step", "wdm_optim_step", "wdm_trainer_set_grad_events", "wdm_trainer_grad_buckets", "wdm_hfrm_trainer_create", "wdm_hfrm_trainer_destroy", "wdm_hfrm_trainer_num_params", "wdm_hfrm_trainer_num_floats",
-            "wdm_hfrm_trainer_param_info", "wdm_hfrm_trainer_set_buffers", "wdm_hfrm_trainer_set_precision", "wdm_hfrm_trainer_workspace_bytes", "wdm_hfrm_trainer_step", "wdm_hfrm_trainer_adam", "wdm_dwt_fwd_affine", "wdm_dwt_inv_compose", "wdm_ensemble_compose", "wdm_conv2d_direct", "wdm_groupnorm", "wdm_cross_attention", "wdm_upsample_add",
+            "wdm_hfrm_trainer_param_info", "wdm_hfrm_trainer_set_buffers", "wdm_hfrm_trainer_set_precision", "wdm_hfrm_trainer_workspace_bytes", "wdm_hfrm_trainer_step", "wdm_hfrm_trainer_stage_workspace_bytes", "wdm_hfrm_trainer_stage", "wdm_hfrm_trainer_adam", "wdm_dwt_fwd_affine", "wdm_dwt_inv_compose", "wdm_ensemble_compose", "wdm_conv2d_direct", "wdm_groupnorm", "wdm_cross_attention", "wdm_upsample_add",
             "wdm_prof_enable", "wdm_prof_report", "wdm_env_refresh", "wdm_set_concurrent_streams"]
 
 

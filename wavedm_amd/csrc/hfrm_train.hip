@@ -690,6 +690,22 @@ struct wdm_hfrm_trainer {
     template <typename T> int ln_bwd(Ctx& c, const T* x, const T* dn, const float* w, T* dio, long long M, int d, float* dw, float* db);
     template <typename T> int fwd_block(Ctx& c, const TBlock& b, const T* X, int B, int H, int W, BSave<T>& s);
     template <typename T> int bwd_block(Ctx& c, const TBlock& b, const T* X, int B, int H, int W, const BSave<T>& s, T* dO);
+    // the stages outside the blocks: step_t is a chain of these members (and fwd_block / bwd_block), wdm_hfrm_trainer_stage runs one of them on the caller's tensors
+    template <typename T> int conv_in_fwd(Ctx& c, const float* x, int B, int H, int W, T* y);
+    template <typename T> int conv_in_wgrad(Ctx& c, const float* x, const T* dy, int B, int H, int W);
+    template <typename T> int down_fwd(Ctx& c, int i, const T* x, int B, int H, int W, T* y);
+    template <typename T> int down_bwd(Ctx& c, int i, const T* x, const T* dy, int B, int H, int W, T* dx);
+    template <typename T> int up_fwd(Ctx& c, int i, const T* x, const T* skip, int B, int H, int W, T* y);
+    template <typename T> int up_bwd(Ctx& c, int i, const T* x, const T* dy, int B, int H, int W, T* dx);
+    template <typename T> int conv_out_fwd(Ctx& c, const T* t, const float* img, T* xin, int B, int H, int W, float* y);
+    template <typename T> int conv_out_bwd(Ctx& c, const T* t, const float* dy, int B, int H, int W, T* dt);
+    int l1_loss(Ctx& c, const float* out, const float* target, long long n, float* dy, float* part, float* loss);
+    template <typename T> int pack_all(Ctx& c);
+    template <typename T> int stage_t(Ctx& c, int kind, int index, const void* x, const void* skip, const void* dy, int B, int H, int W, void* y, void* dx);
+    int stage(Ctx& c, int kind, int index, const void* x, const void* skip, const void* dy, int B, int H, int W, void* y, void* dx) {
+        c.dtype = act;
+        return act == WDM_BF16 ? stage_t<__bf16>(c, kind, index, x, skip, dy, B, H, W, y, dx) : stage_t<float>(c, kind, index, x, skip, dy, B, H, W, y, dx);
+    }
     template <typename T> int pack(hipStream_t s);
     template <typename T> int step_t(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out);
     int step(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out) {
@@ -904,14 +920,148 @@ int wdm_hfrm_trainer::pack(hipStream_t s) {
 }
 
 template <typename T>
+int wdm_hfrm_trainer::pack_all(Ctx& c) {
+    pk = (char*)c.ar->alloc(poff(pack_bytes));
+    if (!pk) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer weights)");
+    if (!c.dry) WDM_TRY(pack<T>(c.s));
+    return WDM_OK;
+}
+
+// ---- the stages outside the blocks.  Each allocates its own scratch and frees it; inputs, outputs and gradients are the caller's -----------------------------
+// conv_in (3 -> 32, 3x3 pad 1): x NCHW f32 -> y NHWC
+template <typename T>
+int wdm_hfrm_trainer::conv_in_fwd(Ctx& c, const float* x, int B, int H, int W, T* y) {
+    const long long M0 = (long long)B * H * W;
+    if (cfg.in_channel != 3) WDM_FAIL(WDM_EINVAL, "HFRM trainer: in_channel must be 3");
+    if (!c.dry) {
+        hipLaunchKernelGGL((conv3x3_cin3_kernel<T, 32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, y, B, H, W, cfg.in_channel, prm(L.conv_in.w), prm(L.conv_in.b));
+        WDM_HIP(hipGetLastError());
+    }
+    return WDM_OK;
+}
+// conv_in: weight and bias gradients only (the image needs no gradient)
+template <typename T>
+int wdm_hfrm_trainer::conv_in_wgrad(Ctx& c, const float* x, const T* dy, int B, int H, int W) {
+    const long long M0 = (long long)B * H * W;
+    const int chunk = 2048, nbk = ceil_div(M0, chunk);
+    constexpr int NOUT = 32 * 3 * 9 + 32 + 3;
+    float* part = (float*)c.ar->alloc((size_t)nbk * NOUT * 4);
+    if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_in wgrad)");
+    if (!c.dry) {
+        hipLaunchKernelGGL((wgrad3_small_part_kernel<T, 32, 3>), dim3(nbk), dim3(256), 0, c.s, dy, x, B, H, W, 1, chunk, part);
+        hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 1, grd(L.conv_in.w), grd(L.conv_in.b));
+        WDM_HIP(hipGetLastError());
+    }
+    c.ar->free(part);
+    return WDM_OK;
+}
+// downs[i] (d -> 2d, 2x2 stride 2): x (B, H, W, d) -> y (B, H/2, W/2, 2d) = W . unshuffle(x) + b
+template <typename T>
+int wdm_hfrm_trainer::down_fwd(Ctx& c, int i, const T* x, int B, int H, int W, T* y) {
+    const int d = downs[i].cin;
+    const long long Mn = (long long)B * (H / 2) * (W / 2);
+    T* u = (T*)c.ar->alloc((size_t)Mn * 4 * d * sizeof(T));
+    if (!u) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down)");
+    if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * d)), dim3(256), 0, c.s, const_cast<T*>(x), u, B, H, W, d, 0);
+    WDM_TRY(fwd_gemm(c, downs[i], u, Mn, y));
+    c.ar->free(u);
+    return WDM_OK;
+}
+// its backward: dy (B, H/2, W/2, 2d) -> the weight and bias gradients, and dx (B, H, W, d) += the adjoint of the gather (dx holds the skip connection's gradient on entry)
+template <typename T>
+int wdm_hfrm_trainer::down_bwd(Ctx& c, int i, const T* x, const T* dy, int B, int H, int W, T* dx) {
+    const int d = downs[i].cin, h2 = H / 2, w2 = W / 2;
+    const long long Mn = (long long)B * h2 * w2;
+    T* u = (T*)c.ar->alloc((size_t)Mn * 4 * d * sizeof(T));
+    float* gw = (float*)c.ar->alloc((size_t)2 * d * 4 * d * 4);
+    if (!u || !gw) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down backward)");
+    if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * d)), dim3(256), 0, c.s, const_cast<T*>(x), u, B, H, W, d, 0);
+    WDM_TRY(wgrad(c, u, 4 * d, dy, 2 * d, h2, w2, gw, grd(downs[i].pb)));
+    if (!c.dry) hipLaunchKernelGGL(permute_down_grad_kernel, dim3(grid_capped_min1((long long)2 * d * 4 * d, 256)), dim3(256), 0, c.s, gw, grd(downs[i].pw), 2 * d, d, 4);
+    WDM_TRY(dgrad_gemm(c, downs[i], dy, Mn, u));           // d u, over u
+    if (!c.dry) {
+        hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * d)), dim3(256), 0, c.s, dx, u, B, H, W, d, 1);
+        WDM_HIP(hipGetLastError());
+    }
+    c.ar->free(gw); c.ar->free(u);
+    return WDM_OK;
+}
+// ups[i] (d -> 2d, 1x1, no bias) + PixelShuffle(2) + skip: x (B, H, W, d), skip and y (B, 2H, 2W, d/2)
+template <typename T>
+int wdm_hfrm_trainer::up_fwd(Ctx& c, int i, const T* x, const T* skip, int B, int H, int W, T* y) {
+    const int d = ups[i].cin;
+    const long long M = (long long)B * H * W;
+    T* p = (T*)c.ar->alloc((size_t)M * 2 * d * sizeof(T));
+    if (!p) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up)");
+    WDM_TRY(fwd_gemm(c, ups[i], x, M, p));
+    if (!c.dry) {
+        hipLaunchKernelGGL(pixel_shuffle_add_kernel<T>, dim3(grid_capped_min1(M * 2 * d, 256)), dim3(256), 0, c.s, p, skip, y, B, H, W, d / 2);
+        WDM_HIP(hipGetLastError());
+    }
+    c.ar->free(p);
+    return WDM_OK;
+}
+// its backward: dy (B, 2H, 2W, d/2) -> the weight gradient and dx (B, H, W, d).  The skip's gradient is dy itself: no kernel runs for it
+template <typename T>
+int wdm_hfrm_trainer::up_bwd(Ctx& c, int i, const T* x, const T* dy, int B, int H, int W, T* dx) {
+    const int d = ups[i].cin;
+    const long long M = (long long)B * H * W;
+    T* dp = (T*)c.ar->alloc((size_t)M * 2 * d * sizeof(T));
+    if (!dp) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up backward)");
+    if (!c.dry) hipLaunchKernelGGL(pixel_unshuffle_kernel<T>, dim3(grid_capped_min1(M * 2 * d, 256)), dim3(256), 0, c.s, dy, dp, B, H, W, d / 2);
+    WDM_TRY(wgrad(c, x, d, dp, 2 * d, H, W, grd(ups[i].pw), nullptr));
+    WDM_TRY(dgrad_gemm(c, ups[i], dp, M, dx));
+    c.ar->free(dp);
+    return WDM_OK;
+}
+// conv_out 3x3 + the input image (run_conv, as the inference forward): t NHWC, img NCHW f32 -> y NCHW f32; xin: the caller's scratch for the image in NHWC (B H W 3)
+template <typename T>
+int wdm_hfrm_trainer::conv_out_fwd(Ctx& c, const T* t_, const float* img, T* xin, int B, int H, int W, float* y) {
+    const int dim = cfg.dim, nc = cfg.in_channel;
+    if (!c.dry) WDM_TRY(k_nchw_to_nhwc(img, xin, B, nc, H, W, c.dtype, c.s));
+    ConvW cwo; cwo.w = pk + poff(cout_off); cwo.b = prm(L.conv_out.b); cwo.cin = dim; cwo.cout = nc; cwo.k = 3; cwo.rows_pad = conv_rows_pad(nc);
+    Tens t; t.p = const_cast<T*>(t_); t.C = dim; t.H = H; t.W = W; t.xs = dim;
+    Tens xi; xi.p = xin; xi.C = nc; xi.H = H; xi.W = W; xi.xs = nc;
+    Tens dummy;
+    Ctx cc = c; cc.B = B;
+    return run_conv(cc, cwo, MODE_S1, {.x0 = &t, .res = &xi, .y_mode = Y_NCHW_F32, .y_ext = y}, &dummy);
+}
+// its backward on the raw fp32 weights: dy NCHW f32 -> dt NHWC, and the weight and bias gradients
+template <typename T>
+int wdm_hfrm_trainer::conv_out_bwd(Ctx& c, const T* t, const float* dy, int B, int H, int W, T* dt) {
+    const long long M0 = (long long)B * H * W;
+    const int chunk = 2048, nbk = ceil_div(M0, chunk);
+    constexpr int NOUT = 32 * 3 * 9 + 32 + 3;
+    float* part = (float*)c.ar->alloc((size_t)nbk * NOUT * 4);
+    if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_out wgrad)");
+    if (cfg.in_channel != 3) WDM_FAIL(WDM_EINVAL, "HFRM trainer: in_channel must be 3");
+    if (!c.dry) {
+        hipLaunchKernelGGL((conv_out_dgrad_kernel<T, 32, 3>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, dy, prm(L.conv_out.w), dt, B, H, W);
+        hipLaunchKernelGGL((wgrad3_small_part_kernel<T, 32, 3>), dim3(nbk), dim3(256), 0, c.s, t, dy, B, H, W, -1, chunk, part);
+        hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 0, grd(L.conv_out.w), grd(L.conv_out.b));
+        WDM_HIP(hipGetLastError());
+    }
+    c.ar->free(part);
+    return WDM_OK;
+}
+// 510 * mean|out - target| (loss may be null) and its gradient dy; lpart: the caller's LOSS_BLOCKS floats
+int wdm_hfrm_trainer::l1_loss(Ctx& c, const float* out, const float* target, long long n, float* dy, float* lpart, float* loss) {
+    if (!c.dry) {
+        const float sc = 510.0f / (float)n;
+        hipLaunchKernelGGL(l1_loss_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, c.s, out, target, dy, n, sc, lpart);
+        if (loss) hipLaunchKernelGGL(l1_loss_final_kernel, dim3(1), dim3(256), 0, c.s, lpart, LOSS_BLOCKS, sc, loss);
+        WDM_HIP(hipGetLastError());
+    }
+    return WDM_OK;
+}
+
+template <typename T>
 int wdm_hfrm_trainer::step_t(Ctx& c, const float* x, const float* target, const float* dyext, int B, int H, int W, float* loss, float* out) {
     const int nlev = cfg.n_enc, dim = cfg.dim, nc = cfg.in_channel;
     if (H % (1 << nlev) || W % (1 << nlev) || H % 16 || W % 16) WDM_FAIL(WDM_EINVAL, "HFRM trainer: H=%d W=%d must be multiples of 16 and of %d", H, W, 1 << nlev);
     auto A = [&](long long elems) { return (T*)c.ar->alloc((size_t)elems * sizeof(T)); };
     auto AF = [&](long long floats) { return (float*)c.ar->alloc((size_t)floats * 4); };
-    pk = (char*)c.ar->alloc(poff(pack_bytes));
-    if (!pk) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer weights)");
-    if (!c.dry) WDM_TRY(pack<T>(c.s));
+    WDM_TRY(pack_all<T>(c));
     const long long M0 = (long long)B * H * W;
     // ---- forward, keeping what the backward reads
     std::vector<const T*> ins;          // block inputs in execution order
@@ -919,7 +1069,7 @@ int wdm_hfrm_trainer::step_t(Ctx& c, const float* x, const float* target, const 
     std::vector<T*> enc_out(nlev), up_in(cfg.n_dec);
     T* cur = A(M0 * dim);
     if (!cur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer)");
-    if (!c.dry) hipLaunchKernelGGL((conv3x3_cin3_kernel<T, 32>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, x, cur, B, H, W, nc, prm(L.conv_in.w), prm(L.conv_in.b));
+    WDM_TRY(conv_in_fwd<T>(c, x, B, H, W, cur));
     int d = dim, h = H, w = W;
     auto run_blocks = [&](const std::vector<TBlock>& bl) -> int {
         for (auto& b : bl) { BSave<T> s; WDM_TRY(fwd_block<T>(c, b, cur, B, h, w, s)); ins.push_back(cur); saves.push_back(s); cur = s.out; }
@@ -928,72 +1078,34 @@ int wdm_hfrm_trainer::step_t(Ctx& c, const float* x, const float* target, const 
     for (int i = 0; i < nlev; ++i) {
         WDM_TRY(run_blocks(L.enc[i]));
         enc_out[i] = cur;
-        const long long Mn = (long long)B * (h / 2) * (w / 2);
-        T* u = A(Mn * 4 * d);
-        T* nt = A(Mn * 2 * d);
-        if (!u || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down)");
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * d)), dim3(256), 0, c.s, cur, u, B, h, w, d, 0);
-        WDM_TRY(fwd_gemm(c, downs[i], u, Mn, nt));
-        c.ar->free(u);
+        T* nt = A((long long)B * (h / 2) * (w / 2) * 2 * d);
+        if (!nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down)");
+        WDM_TRY(down_fwd<T>(c, i, cur, B, h, w, nt));
         cur = nt; d *= 2; h /= 2; w /= 2;
     }
     WDM_TRY(run_blocks(L.mid));
     for (int i = 0; i < cfg.n_dec; ++i) {
-        const long long M = (long long)B * h * w;
-        T* p = A(M * 2 * d);
-        T* nt = A(M * 2 * d);           // (2h x 2w x d/2)
-        if (!p || !nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up)");
-        WDM_TRY(fwd_gemm(c, ups[i], cur, M, p));
-        if (!c.dry) hipLaunchKernelGGL(pixel_shuffle_add_kernel<T>, dim3(grid_capped_min1(M * 2 * d, 256)), dim3(256), 0, c.s, p, enc_out[nlev - 1 - i], nt, B, h, w, d / 2);
-        c.ar->free(p);
+        T* nt = A((long long)B * h * w * 2 * d);           // (2h x 2w x d/2)
+        if (!nt) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up)");
+        WDM_TRY(up_fwd<T>(c, i, cur, enc_out[nlev - 1 - i], B, h, w, nt));
         up_in[i] = cur;
         cur = nt; d /= 2; h *= 2; w *= 2;
         WDM_TRY(run_blocks(L.dec[i]));
     }
-    // conv_out 3x3 + input (run_conv, as the inference forward), NCHW f32
-    T* xin = A(M0 * nc);
-    float* yo = out ? out : AF(M0 * nc);
-    float* dY = AF(M0 * nc);
+    const long long ny = M0 * nc;
+    T* xin = A(ny);
+    float* yo = out ? out : AF(ny);
+    float* dY = AF(ny);
     float* lpart = AF(LOSS_BLOCKS);
     if (!xin || !yo || !dY || !lpart) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer output)");
-    {
-        if (!c.dry) WDM_TRY(k_nchw_to_nhwc(x, xin, B, nc, H, W, c.dtype, c.s));
-        ConvW cwo; cwo.w = pk + poff(cout_off); cwo.b = prm(L.conv_out.b); cwo.cin = dim; cwo.cout = nc; cwo.k = 3; cwo.rows_pad = conv_rows_pad(nc);
-        Tens t; t.p = cur; t.C = dim; t.H = H; t.W = W; t.xs = dim;
-        Tens xi; xi.p = xin; xi.C = nc; xi.H = H; xi.W = W; xi.xs = nc;
-        Tens dummy;
-        Ctx cc = c; cc.B = B;
-        WDM_TRY(run_conv(cc, cwo, MODE_S1, {.x0 = &t, .res = &xi, .y_mode = Y_NCHW_F32, .y_ext = yo}, &dummy));
-    }
+    WDM_TRY(conv_out_fwd<T>(c, cur, x, xin, B, H, W, yo));
     // ---- loss
-    const long long ny = M0 * nc;
-    if (!c.dry) {
-        if (target) {
-            const float sc = 510.0f / (float)ny;
-            hipLaunchKernelGGL(l1_loss_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, c.s, yo, target, dY, ny, sc, lpart);
-            if (loss) hipLaunchKernelGGL(l1_loss_final_kernel, dim3(1), dim3(256), 0, c.s, lpart, LOSS_BLOCKS, sc, loss);
-        } else {
-            WDM_HIP(hipMemcpyAsync(dY, dyext, (size_t)ny * 4, hipMemcpyDeviceToDevice, c.s));
-        }
-        WDM_HIP(hipGetLastError());
-    }
+    if (target) WDM_TRY(l1_loss(c, yo, target, ny, dY, lpart, loss));
+    else if (!c.dry) WDM_HIP(hipMemcpyAsync(dY, dyext, (size_t)ny * 4, hipMemcpyDeviceToDevice, c.s));
     // ---- backward
     T* dT = A(M0 * dim);
     if (!dT) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer backward)");
-    {
-        const int chunk = 2048, nbk = ceil_div(M0, chunk);
-        constexpr int NOUT = 32 * 3 * 9 + 32 + 3;
-        float* part = AF((long long)nbk * NOUT);
-        if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_out wgrad)");
-        if (nc != 3) WDM_FAIL(WDM_EINVAL, "HFRM trainer: in_channel must be 3");
-        if (!c.dry) {
-            hipLaunchKernelGGL((conv_out_dgrad_kernel<T, 32, 3>), dim3(ceil_div(M0, 256)), dim3(256), 0, c.s, dY, prm(L.conv_out.w), dT, B, H, W);
-            hipLaunchKernelGGL((wgrad3_small_part_kernel<T, 32, 3>), dim3(nbk), dim3(256), 0, c.s, cur, dY, B, H, W, -1, chunk, part);
-            hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 0, grd(L.conv_out.w), grd(L.conv_out.b));
-            WDM_HIP(hipGetLastError());
-        }
-        c.ar->free(part);
-    }
+    WDM_TRY(conv_out_bwd<T>(c, cur, dY, B, H, W, dT));
     int k = (int)saves.size();
     auto back_blocks = [&](const std::vector<TBlock>& bl) -> int {
         for (int j = (int)bl.size() - 1; j >= 0; --j) {
@@ -1007,50 +1119,81 @@ int wdm_hfrm_trainer::step_t(Ctx& c, const float* x, const float* target, const 
     std::vector<T*> dskip(nlev);
     for (int i = cfg.n_dec - 1; i >= 0; --i) {
         WDM_TRY(back_blocks(L.dec[i]));
-        // ups[i]: nt = PixelShuffle(W up_in) + skip
-        const int dl = 2 * d;                                   // channels of up_in
-        const int hl = h / 2, wl = w / 2;
-        const long long M = (long long)B * hl * wl;
-        T* dp = A(M * 2 * dl);
-        T* dcur = A(M * dl);
-        if (!dp || !dcur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up backward)");
-        if (!c.dry) hipLaunchKernelGGL(pixel_unshuffle_kernel<T>, dim3(grid_capped_min1(M * 2 * dl, 256)), dim3(256), 0, c.s, dT, dp, B, hl, wl, d);
+        // ups[i]: nt = PixelShuffle(W up_in) + skip; the skip's gradient is dT itself
+        const int dl = 2 * d, hl = h / 2, wl = w / 2;         // channels and map of up_in
+        T* dcur = A((long long)B * hl * wl * dl);
+        if (!dcur) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer up backward)");
         dskip[nlev - 1 - i] = dT;
-        WDM_TRY(wgrad(c, up_in[i], dl, dp, 2 * dl, hl, wl, grd(ups[i].pw), nullptr));
-        WDM_TRY(dgrad_gemm(c, ups[i], dp, M, dcur));
-        c.ar->free(dp);
+        WDM_TRY(up_bwd<T>(c, i, up_in[i], dT, B, hl, wl, dcur));
         dT = dcur; d = dl; h = hl; w = wl;
     }
     WDM_TRY(back_blocks(L.mid));
     for (int i = nlev - 1; i >= 0; --i) {
         // downs[i]: level i+1 input = W . unshuffle(enc_out[i]) + b
-        const int dl = d / 2, hl = 2 * h, wl = 2 * w;
-        const long long Mn = (long long)B * h * w;
-        T* u = A(Mn * 4 * dl);
-        float* gw = AF((long long)2 * dl * 4 * dl);
-        if (!u || !gw) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer down backward)");
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * dl)), dim3(256), 0, c.s, enc_out[i], u, B, hl, wl, dl, 0);
-        WDM_TRY(wgrad(c, u, 4 * dl, dT, 2 * dl, h, w, gw, grd(downs[i].pb)));
-        if (!c.dry) hipLaunchKernelGGL(permute_down_grad_kernel, dim3(grid_capped_min1((long long)2 * dl * 4 * dl, 256)), dim3(256), 0, c.s, gw, grd(downs[i].pw), 2 * dl, dl, 4);
-        WDM_TRY(dgrad_gemm(c, downs[i], dT, Mn, u));           // d u, over u
-        if (!c.dry) hipLaunchKernelGGL(unshuffle2_kernel<T>, dim3(egrid<T>(Mn * 4 * dl)), dim3(256), 0, c.s, dskip[i], u, B, hl, wl, dl, 1);
-        c.ar->free(gw); c.ar->free(u); c.ar->free(dT);
-        dT = dskip[i]; d = dl; h = hl; w = wl;
+        WDM_TRY(down_bwd<T>(c, i, enc_out[i], dT, B, 2 * h, 2 * w, dskip[i]));
+        c.ar->free(dT);
+        dT = dskip[i]; d /= 2; h *= 2; w *= 2;
         WDM_TRY(back_blocks(L.enc[i]));
     }
-    {   // conv_in: weight and bias only (the image needs no gradient)
-        const int chunk = 2048, nbk = ceil_div(M0, chunk);
-        constexpr int NOUT = 32 * 3 * 9 + 32 + 3;
-        float* part = AF((long long)nbk * NOUT);
-        if (!part) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM conv_in wgrad)");
+    return conv_in_wgrad<T>(c, x, dT, B, H, W);
+}
+
+// One stage on its own (wdm_hfrm_trainer_stage): forward, then backward, through the members step_t runs, on the caller's tensors.
+template <typename T>
+int wdm_hfrm_trainer::stage_t(Ctx& c, int kind, int index, const void* x, const void* skip, const void* dy, int B, int H, int W, void* y, void* dx) {
+    const int nlev = cfg.n_enc;
+    if ((long long)B * H * W > (1LL << 27)) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: %d x %d x %d pixels exceed the bound of 2^27", B, H, W);
+    if (kind < WDM_HFRM_STAGE_BLOCK || kind > WDM_HFRM_STAGE_CONV_OUT) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: unknown kind %d", kind);
+    if (!c.dry && kind != WDM_HFRM_STAGE_CONV_IN && !dx) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: dx is null");
+    WDM_TRY(pack_all<T>(c));
+    int rc = WDM_OK;
+    switch (kind) {
+    case WDM_HFRM_STAGE_BLOCK: {
+        const TBlock* blk = nullptr;
+        L.for_each_block([&](const TBlock& b) { if (b.idx == index) blk = &b; });
+        if (!blk) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: no block %d (the model has %d)", index, L.n_blocks);
+        const size_t bytes = (size_t)B * H * W * blk->d * sizeof(T);
+        BSave<T> s;
+        WDM_TRY(fwd_block<T>(c, *blk, (const T*)x, B, H, W, s));
         if (!c.dry) {
-            hipLaunchKernelGGL((wgrad3_small_part_kernel<T, 32, 3>), dim3(nbk), dim3(256), 0, c.s, (const T*)dT, x, B, H, W, 1, chunk, part);
-            hipLaunchKernelGGL((wgrad3_small_final_kernel<32, 3>), dim3(ceil_div(NOUT, 256)), dim3(256), 0, c.s, part, nbk, 1, grd(L.conv_in.w), grd(L.conv_in.b));
-            WDM_HIP(hipGetLastError());
+            WDM_HIP(hipMemcpyAsync(y, s.out, bytes, hipMemcpyDeviceToDevice, c.s));
+            WDM_HIP(hipMemcpyAsync(dx, dy, bytes, hipMemcpyDeviceToDevice, c.s));      // bwd_block works in place
         }
-        c.ar->free(part);
+        rc = bwd_block<T>(c, *blk, (const T*)x, B, H, W, s, (T*)dx);
+        c.ar->free(s.sc); c.ar->free(s.pooled); c.ar->free(s.out); c.ar->free(s.c5); c.ar->free(s.a4); c.ar->free(s.y); c.ar->free(s.c3); c.ar->free(s.a2); c.ar->free(s.a1);
+        break;
     }
-    return WDM_OK;
+    case WDM_HFRM_STAGE_DOWN:
+        if (index < 0 || index >= nlev) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: no downs[%d]", index);
+        if (H % 2 || W % 2) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: downs takes an even map, not %d x %d", H, W);
+        WDM_TRY(down_fwd<T>(c, index, (const T*)x, B, H, W, (T*)y));
+        rc = down_bwd<T>(c, index, (const T*)x, (const T*)dy, B, H, W, (T*)dx);
+        break;
+    case WDM_HFRM_STAGE_UP:
+        if (index < 0 || index >= cfg.n_dec) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: no ups[%d]", index);
+        if (!c.dry && !skip) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: ups needs its skip tensor");
+        WDM_TRY(up_fwd<T>(c, index, (const T*)x, (const T*)skip, B, H, W, (T*)y));
+        rc = up_bwd<T>(c, index, (const T*)x, (const T*)dy, B, H, W, (T*)dx);
+        break;
+    case WDM_HFRM_STAGE_CONV_IN:
+        WDM_TRY(conv_in_fwd<T>(c, (const float*)x, B, H, W, (T*)y));
+        rc = conv_in_wgrad<T>(c, (const float*)x, (const T*)dy, B, H, W);
+        break;
+    case WDM_HFRM_STAGE_CONV_OUT:
+        if (!c.dry && !skip) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: conv_out needs the image (skip)");
+        // the conv kernel's smallest tile is 8 x 8 pixels and its dispatcher refuses a map that is no multiple of it
+        if (H % 8 || W % 8) WDM_FAIL(WDM_EINVAL, "HFRM trainer stage: conv_out runs on the conv kernel, whose tiles are 8 x 8 pixels: %d x %d is no multiple", H, W);
+        {
+            T* xin = (T*)c.ar->alloc((size_t)B * H * W * cfg.in_channel * sizeof(T));
+            if (!xin) WDM_FAIL(WDM_ENOMEM, "workspace too small (HFRM trainer stage conv_out)");
+            WDM_TRY(conv_out_fwd<T>(c, (const T*)x, (const float*)skip, xin, B, H, W, (float*)y));
+            rc = conv_out_bwd<T>(c, (const T*)x, (const float*)dy, B, H, W, (T*)dx);
+            c.ar->free(xin);
+        }
+        break;
+    }
+    c.ar->free(pk);
+    return rc;
 }
 
 // =================================================================================================
@@ -1118,6 +1261,33 @@ int wdm_hfrm_trainer_step(wdm_hfrm_trainer* t, const float* x, const float* targ
     Arena ar(workspace, workspace_bytes);
     Ctx c{(hipStream_t)stream, t->act, B, &ar, false};
     return t->step(c, x, target, dy, B, H, W, loss, out);
+}
+/* one stage of the trainer on its own (unit tests): forward, then backward, through the members wdm_hfrm_trainer_step runs, on the caller's tensors; waits for the stream */
+size_t wdm_hfrm_trainer_stage_workspace_bytes(const wdm_hfrm_trainer* t, int kind, int index, int B, int H, int W) {
+    if (!t || B <= 0 || H <= 0 || W <= 0) return 0;
+    Arena ar = Arena::dry();
+    Ctx c{nullptr, t->act, B, &ar, true};
+    if (const_cast<wdm_hfrm_trainer*>(t)->stage(c, kind, index, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr) != WDM_OK) return 0;
+    return ar.peak() + 4096;
+}
+int wdm_hfrm_trainer_stage(wdm_hfrm_trainer* t, int kind, int index, const void* x, const void* skip, const void* dy, int B, int H, int W, void* y, void* dx,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (!t || !x || !dy || !y || !workspace) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_stage: null argument");
+    if (!t->P || !t->G) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_trainer_stage: call wdm_hfrm_trainer_set_buffers first");
+    if (B <= 0 || H <= 0 || W <= 0) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_stage: bad shape");
+    if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)skip) | ((uintptr_t)dy) | ((uintptr_t)dx)) & 15) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_stage: tensors must be 16-byte aligned");
+    if (((uintptr_t)workspace) & 255) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_stage: workspace must be 256-byte aligned");
+    // sized before the first launch, as in wdm_hfrm_trainer_step
+    const size_t need = wdm_hfrm_trainer_stage_workspace_bytes(t, kind, index, B, H, W);
+    if (!need) return WDM_EINVAL;                                                   // (the dry run has set the message)
+    if (workspace_bytes < need)
+        WDM_FAIL(WDM_ENOMEM, "wdm_hfrm_trainer_stage: workspace too small (%zu bytes given, wdm_hfrm_trainer_stage_workspace_bytes asks for %zu)", workspace_bytes, need);
+    Arena ar(workspace, workspace_bytes);
+    Ctx c{(hipStream_t)stream, t->act, B, &ar, false};
+    const int rc = t->stage(c, kind, index, x, skip, dy, B, H, W, y, dx);
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (rc == WDM_OK && e != hipSuccess) WDM_FAIL(WDM_EHIP, "wdm_hfrm_trainer_stage: %s", hipGetErrorString(e));
+    return rc;
 }
 int wdm_hfrm_trainer_adam(wdm_hfrm_trainer* t, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay, void* stream) {
     if (!t || !t->P || !t->G || !t->Mo || !t->V) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_trainer_adam: buffers not set");

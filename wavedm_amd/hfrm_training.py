@@ -237,6 +237,48 @@ class HFRMTrainer:
         self._step(inp, None, dy, out)
         return out
 
+    STAGES = {"block": 0, "down": 1, "up": 2, "conv_in": 3, "conv_out": 4}
+
+    def stage(self, kind, index, x, dy, skip=None, dres=None):
+        """One stage's forward and backward on their own (wdm_hfrm_trainer_stage, for unit tests): the members a step runs, on the caller's tensors, in the
+        current precision.  kind / index as HFRM.stage_forward.  x, dy, skip, dres: fp32 NCHW on the GPU, stored here in the activation type as NHWC (conv_in's
+        image, conv_out's image `skip` and its dy stay fp32 NCHW); dres (kind "down" only): the gradient that arrived over the skip connection, zero when absent.
+        -> (y, dx) fp32 NCHW, exactly the values the stage stored (dx is None for conv_in); the stage's entries of self.grads are written, no others."""
+        code = self.STAGES[kind]
+        x = _lib.require_cuda_f32(x, "HFRM stage input")
+        dy = _lib.require_cuda_f32(dy, "HFRM stage dy")
+        dt = torch.bfloat16 if self._act_code == _lib.WDM_BF16 else torch.float32
+        nhwc = lambda t: t.permute(0, 2, 3, 1).to(dt).contiguous()
+        B, Cc, H, W = x.shape
+        dim, nc = self.hfrm_args["dim"], self.hfrm_args["in_channel"]
+        xd = x if kind == "conv_in" else nhwc(x)
+        dyd = dy if kind == "conv_out" else nhwc(dy)
+        sk = None
+        if skip is not None:
+            skip = _lib.require_cuda_f32(skip, "HFRM stage skip")
+            sk = skip if kind == "conv_out" else nhwc(skip)
+        shape = {"block": (B, H, W, Cc), "down": (B, H // 2, W // 2, 2 * Cc), "up": (B, 2 * H, 2 * W, Cc // 2), "conv_in": (B, H, W, dim)}.get(kind)
+        y = torch.empty(shape, dtype=dt, device=x.device) if shape else torch.empty(B, nc, H, W, dtype=torch.float32, device=x.device)
+        if tuple(dyd.shape) != tuple(y.shape):
+            raise ValueError(f"HFRMTrainer.stage: dy has shape {tuple(dy.shape)}, the stage's output {tuple(y.shape)} (NHWC)")
+        if dres is not None and kind != "down":
+            raise ValueError("HFRMTrainer.stage: dres is the skip gradient of kind 'down' only")
+        dx = None
+        if kind != "conv_in":
+            dx = nhwc(_lib.require_cuda_f32(dres, "HFRM stage dres")) if dres is not None else torch.zeros(xd.shape, dtype=dt, device=x.device)
+            if tuple(dx.shape) != tuple(xd.shape):
+                raise ValueError("HFRMTrainer.stage: dres must have the input's shape")
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            n = int(L.wdm_hfrm_trainer_stage_workspace_bytes(self._t, code, int(index), B, H, W))
+            if n == 0:
+                raise RuntimeError("wdm_hfrm_trainer_stage_workspace_bytes failed: " + L.wdm_last_error().decode(errors="replace"))
+            ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            _lib.check(L.wdm_hfrm_trainer_stage(self._t, code, int(index), _lib.ptr(xd), _lib.ptr(sk) if sk is not None else None, _lib.ptr(dyd), B, H, W, _lib.ptr(y),
+                                                _lib.ptr(dx) if dx is not None else None, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        back = lambda t: t.permute(0, 3, 1, 2).float().contiguous()
+        return (y if kind == "conv_out" else back(y)), (None if dx is None else back(dx))
+
     def optimizer_step(self, lr=None):
         """torch.optim.Adam step number self.step + 1 (no weight decay, no EMA); lr defaults to the reference's schedule on self.lr."""
         self.step += 1
