@@ -455,6 +455,35 @@ int wdm_trainer_set_objective(wdm_trainer* t, int use_mse);
 int wdm_trainer_set_dropout(wdm_trainer* t, float p, int64_t seed, int64_t step);
 int wdm_trainer_step(wdm_trainer* t, const float* x0, const float* tt, const float* sqrt_a, const float* sqrt_1ma, const float* e,
                      int B, int c_t0, float* loss, float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
+/* One stage of the training step on its own (a test entry: it waits for the stream): the forward and then the backward of the stage through the very
+ * members and graph ops wdm_trainer_step chains, on the caller's tensors, with every conv's weights packed from the parameter buffer as a step packs them.
+ * Activations and their gradients are NHWC in the trainer's dtype; the map H x W is the caller's (not cfg.resolution).  A stage writes only its own entries
+ * of the gradient buffer and only its own rows of d_temb_all.  `dx0_set` / `dx1_set`: the gradient buffer already holds a later consumer's gradient, and the
+ * stage adds to it as the step does from the second consumer on.
+ *   RESBLOCK index = the block's position among the ResnetBlocks in wdm_trainer_param_info order (also its dropout layer): x0 (B, H, W, cin - c1), x1
+ *            (B, H, W, c1) the skip half of a concat (c1 = 0: none), temb_all (B, temb_rows) f32, dy -> y (B, H, W, cout), dx0, dx1, the block's rows of
+ *            d_temb_all (B, temb_rows), its gradient entries.  Dropout as set by wdm_trainer_set_dropout.
+ *   ATTN     index = the AttnBlock's position: x0, dy -> y, dx0 (B, H, W, c); H x W a token count the trainer's attention takes.
+ *   CONV     index = the conv's position among the 4-d weights: conv_in (no dx0), a Downsample (y on H/2 x W/2) or an Upsample (y on 2H x 2W).
+ *   TEMB     t (B), d_temb_all (B, temb_rows) -> temb_all, the gradients of temb.dense.0 / .1 and of every temb_proj weight and bias.
+ *   INPUT    x0 (B, in_channels, H, W) NCHW f32, e (B, out_ch, H, W), sa, s1m (B), c_t0 -> x96 (B, H, W, in_channels) the built input, y conv_in's output;
+ *            with dy also conv_in's gradients.  No dx.
+ *   HEAD     x0 = h (B, H, W, ch), e, and sa / s1m under use_mse -> out_nchw (optional), loss, dx0, the gradients of norm_out and conv_out.
+ * Tensors 16-byte aligned; the workspace 256-byte aligned and at least wdm_trainer_stage_workspace_bytes (0 on a bad kind, index or shape), all checked
+ * before the first launch. */
+enum { WDM_TRAINER_STAGE_RESBLOCK = 0, WDM_TRAINER_STAGE_ATTN = 1, WDM_TRAINER_STAGE_CONV = 2, WDM_TRAINER_STAGE_TEMB = 3, WDM_TRAINER_STAGE_INPUT = 4,
+       WDM_TRAINER_STAGE_HEAD = 5 };
+typedef struct wdm_trainer_stage_io {
+    const void *x0, *x1, *dy;
+    float *temb_all, *d_temb_all;
+    const float *t, *e, *sa, *s1m;
+    void *y, *x96, *dx0, *dx1;
+    float *out_nchw, *loss;
+    int c1, c_t0, dx0_set, dx1_set;
+} wdm_trainer_stage_io;
+size_t wdm_trainer_stage_workspace_bytes(const wdm_trainer* t, int kind, int index, int B, int H, int W);
+int wdm_trainer_stage(wdm_trainer* t, int kind, int index, const wdm_trainer_stage_io* io, int B, int H, int W, void* workspace, size_t workspace_bytes,
+                      void* stream);
 int wdm_trainer_adam_ema(wdm_trainer* t, int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay,
                          float ema_mu, void* stream);
 /* The other optimizers utils/optimize.py:5-14 can build, as torch 2.10's single-tensor rules, each with the EMA update in the same pass over the flat

@@ -355,6 +355,15 @@ struct wdm_trainer {
     int op_gn_act(const NormP& p, TT* x0, TT* x1, int silu, TT** out, const Dropout* drop = nullptr);
     int op_resblock(const ResP& r, TT* x0, TT* x1, TT** out);
     int op_attn(const AttnP& a, TT* x, TT** out);
+    // the stages of a step outside the blocks: step() is a chain of these members and the ops above, wdm_trainer_stage runs one of them on the caller's tensors
+    struct TembSave { float *emb = nullptr, *pre0 = nullptr, *t0 = nullptr, *t1 = nullptr, *s1 = nullptr; };
+    int pack_weights(Ctx& cc);
+    int temb_fwd(Ctx& cc, const float* t, TembSave& ts);
+    int temb_bwd(Ctx& cc, const TembSave& ts);
+    int input(Ctx& cc, const float* x0, const float* e, const float* sa, const float* s1m, int c_t0, int H, int W, TT** xin);
+    int head(Ctx& cc, TT* h, const float* e, const float* sa, const float* s1m, float* loss, float* out_nchw);
+    int run_tape(Ctx& cc, bool with_events);
+    int stage(Ctx& cc, int kind, int index, const wdm_trainer_stage_io& io, int H, int W);
     int step(Ctx& cc, const float* x0, const float* t, const float* sa, const float* s1m, const float* e, int c_t0, float* loss, float* out_nchw);
 };
 
@@ -521,16 +530,162 @@ int wdm_trainer::op_attn(const AttnP& a, TT* x, TT** out) {
     return op_conv(a.proj, MODE_P1, o, nullptr, -1, x, out);
 }
 
+// ---- forward and dgrad weight layouts of all convs (the parameters changed in the last optimiser step): a dozen launches for ~90 layers
+int wdm_trainer::pack_weights(Ctx& cc) {
+    size_t bytes = 0;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    for (const ConvP& q : L.convs) bytes += up(conv_packed_bytes(q.cin, q.cout, q.k, cc.dtype)) + up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
+    char* pack_region = (char*)cc.ar->alloc(bytes);
+    if (!pack_region) WDM_FAIL(WDM_ENOMEM, "training workspace too small (packed weights)");
+    packed.assign(L.convs.size(), {nullptr, nullptr});
+    std::vector<PackDesc> d3, d1;
+    size_t at = 0;
+    for (const ConvP& q : L.convs) {
+        PackDesc d{};
+        d.w = P + off[q.w]; d.cout = q.cout; d.cin = q.cin; d.rows_total = conv_rows_pad(q.cout);
+        d.dstf = pack_region + at; at += up(conv_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
+        d.dstd = pack_region + at; at += up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
+        packed[q.idx] = {d.dstf, d.dstd};
+        (q.k == 3 ? d3 : d1).push_back(d);
+    }
+    if (!cc.dry) {
+        WDM_TRY(k_pack_conv_both_batch(d3.data(), (int)d3.size(), 3, cc.dtype, cc.s));
+        WDM_TRY(k_pack_conv_both_batch(d1.data(), (int)d1.size(), 1, cc.dtype, cc.s));
+    }
+    return WDM_OK;
+}
+
+// ---- temb MLP (fp32) into temb_all, values kept for the backward pass
+int wdm_trainer::temb_fwd(Ctx& cc, const float* t, TembSave& ts) {
+    const int B = cc.B, temb_ch = L.temb_ch, temb_rows = L.temb_rows;
+    const size_t d0w = off[L.d0w], d0b = off[L.d0b], d1w = off[L.d1w], d1b = off[L.d1b];
+    auto af = [&](size_t n) -> float* { return (float*)cc.ar->alloc(n * 4); };
+    ts.emb = af((size_t)B * cfg.ch); ts.pre0 = af((size_t)B * temb_ch); ts.t0 = af((size_t)B * temb_ch); ts.t1 = af((size_t)B * temb_ch); ts.s1 = af((size_t)B * temb_ch);
+    if (!ts.emb || !ts.pre0 || !ts.t0 || !ts.t1 || !ts.s1 || !temb_all) WDM_FAIL(WDM_ENOMEM, "training workspace too small (temb)");
+    WDM_TRY(k_timestep_embedding(t, B, cfg.ch, ts.emb, cc.s));
+    WDM_TRY(k_linear(ts.emb, B, cfg.ch, P + d0w, P + d0b, temb_ch, ts.pre0, 0, cc.s));
+    hipLaunchKernelGGL(silu_f32_kernel, dim3(ceil_div((long long)B * temb_ch, 256)), dim3(256), 0, cc.s, ts.pre0, ts.t0, (long long)B * temb_ch);
+    WDM_TRY(k_linear(ts.t0, B, temb_ch, P + d1w, P + d1b, temb_ch, ts.t1, 0, cc.s));
+    hipLaunchKernelGGL(silu_f32_kernel, dim3(ceil_div((long long)B * temb_ch, 256)), dim3(256), 0, cc.s, ts.t1, ts.s1, (long long)B * temb_ch);
+    WDM_TRY(k_linear(ts.s1, B, temb_ch, P + tw, P + tb, temb_rows, temb_all, 0, cc.s));
+    return WDM_OK;
+}
+
+// ---- temb MLP backward from d_temb_all: the gradients of temb_proj (matrix and bias), temb.dense.1 and temb.dense.0
+int wdm_trainer::temb_bwd(Ctx& cc, const TembSave& ts) {
+    const int B = cc.B, temb_ch = L.temb_ch, temb_rows = L.temb_rows;
+    const size_t d0w = off[L.d0w], d0b = off[L.d0b], d1w = off[L.d1w], d1b = off[L.d1b];
+    auto af = [&](size_t n) -> float* { return (float*)cc.ar->alloc(n * 4); };
+    const long long n4 = (long long)B * temb_ch;
+    // csc: l_colsum's partials, colsum_chunks(B) = ceil(B / 256) (at most 256) rows of its widest operand
+    const size_t chunks = std::min<size_t>(256, std::max<size_t>(1, ((size_t)B + 255) / 256));
+    float *d_s1 = af(n4), *d_t1 = af(n4), *d_t0 = af(n4), *d_pre0 = af(n4), *csc = af(std::max<size_t>(4, chunks) * std::max(temb_rows, temb_ch)), *xpart = af((size_t)64 * n4);
+    if (!d_s1 || !d_t1 || !d_t0 || !d_pre0 || !csc || !xpart) WDM_FAIL(WDM_ENOMEM, "training workspace too small (temb backward)");
+    hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_rows * temb_ch, 256)), dim3(256), 0, cc.s, d_temb_all, ts.s1, B, temb_rows, temb_ch, G + tw);
+    l_colsum_f32(cc.s, d_temb_all, temb_rows, B, G + tb, csc);
+    hipLaunchKernelGGL(lin_bwd_x_part_kernel, dim3(ceil_div(n4, 256), 64), dim3(256), 0, cc.s, d_temb_all, P + tw, B, temb_rows, temb_ch, xpart);
+    hipLaunchKernelGGL(lin_bwd_x_final_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, xpart, n4, d_s1);
+    hipLaunchKernelGGL(silu_bwd_f32_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, ts.t1, d_s1, d_t1, n4);
+    hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_ch * temb_ch, 256)), dim3(256), 0, cc.s, d_t1, ts.t0, B, temb_ch, temb_ch, G + d1w);
+    l_colsum_f32(cc.s, d_t1, temb_ch, B, G + d1b, csc);
+    hipLaunchKernelGGL(lin_bwd_x_part_kernel, dim3(ceil_div(n4, 256), 64), dim3(256), 0, cc.s, d_t1, P + d1w, B, temb_ch, temb_ch, xpart);
+    hipLaunchKernelGGL(lin_bwd_x_final_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, xpart, n4, d_t0);
+    hipLaunchKernelGGL(silu_bwd_f32_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, ts.pre0, d_t0, d_pre0, n4);
+    hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_ch * cfg.ch, 256)), dim3(256), 0, cc.s, d_pre0, ts.emb, B, temb_ch, cfg.ch, G + d0w);
+    l_colsum_f32(cc.s, d_pre0, temb_ch, B, G + d0b, csc);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
+// ---- network input: [x_cond | x_t | x_other] with x_t = sqrt(a) x_tar + sqrt(1-a) e
+int wdm_trainer::input(Ctx& cc, const float* x0, const float* e, const float* sa, const float* s1m, int c_t0, int H, int W, TT** out) {
+    TT* xin = new_act();
+    xin->needs_grad = false;
+    WDM_TRY(alloc_tens(cc, cfg.in_channels, H, W, &xin->t));
+    BYT(cc.dtype, l_build_input, cc.s, x0, e, sa, s1m, cfg.in_channels, H * W, c_t0, cfg.out_ch, xin->t.p, (long long)cc.B * H * W * cfg.in_channels);
+    *out = xin;
+    return WDM_OK;
+}
+
+// ---- the network's end on the map of h: norm_out (on the tape), conv_out in fp32 NHWC, the loss and its gradient, conv_out's backward by hand
+int wdm_trainer::head(Ctx& cc, TT* h, const float* e, const float* sa, const float* s1m, float* loss, float* out_nchw) {
+    const int B = cc.B, H = h->t.H, W = h->t.W, pc = cfg.out_ch;
+    const ConvP& conv_out = L.conv_out;
+    const size_t cout_w = off[conv_out.w], cout_b = off[conv_out.b];
+    const size_t es = dsize(cc.dtype);
+    TT* an;
+    WDM_TRY(op_gn_act(L.norm_out, h, nullptr, 1, &an));
+    // conv_out in fp32 NHWC for the loss
+    float* outf = (float*)cc.ar->alloc((size_t)B * H * W * pc * 4);
+    if (!outf) WDM_FAIL(WDM_ENOMEM, "training workspace too small (output)");
+    {
+        ConvW w; w.cin = conv_out.cin; w.cout = pc; w.k = 3; w.rows_pad = conv_rows_pad(pc); w.b = P + cout_b;
+        w.w = packed[conv_out.idx].first;
+        Tens dummy;
+        WDM_TRY(run_conv(cc, w, MODE_S1, {.x0 = &an->t, .y_mode = Y_NHWC_F32, .y_ext = outf}, &dummy));
+    }
+    // ---- loss and its gradient
+    void* dout = cc.ar->alloc((size_t)B * H * W * pc * es);
+    if (!dout) WDM_FAIL(WDM_ENOMEM, "training workspace too small (loss gradient)");
+    {
+        double* lpart = (double*)cc.ar->alloc(LOSS_WGS * sizeof(double));
+        if (!lpart) WDM_FAIL(WDM_ENOMEM, "training workspace too small (loss partials)");
+        if (!cc.dry) BYT(cc.dtype, l_loss, cc.s, outf, e, B, pc, H * W, dout, loss, out_nchw, use_mse ? sa : nullptr, use_mse ? s1m : nullptr, lpart);
+        cc.ar->free(lpart);
+    }
+    // ---- backward: conv_out by hand (the tape holds the rest)
+    {
+        Tens dy; dy.p = dout; dy.C = pc; dy.H = H; dy.W = W; dy.xs = pc;
+        WDM_TRY(colsum(cc, dy, G + cout_b, false, false));
+        WDM_TRY(conv_wgrad(cc, MODE_S1, an->t, nullptr, dy, pc, G + cout_w, false));
+        bool f; WDM_TRY(grad_buf(an, &f));
+        WDM_TRY(conv_dgrad(cc, MODE_S1, P + cout_w, conv_out.cin, pc, dy, H, W, an->g, false, packed[conv_out.idx].second));
+    }
+    return WDM_OK;
+}
+
+// The tape runs in reverse; the parameters sit in the flat buffers in forward order, so the gradient buffer fills from its END.  With events set
+// (wdm_trainer_set_grad_events) the range finished so far is cut into buckets and an event is recorded behind each: the caller's all-reduce of a bucket
+// can start while the rest of the backward still runs (the reference's DistributedDataParallel does the same with 25 MB buckets, ddm_wavelet.py:168).
+// A cut at entry i is valid when no earlier entry writes at or above the running minimum.
+int wdm_trainer::run_tape(Ctx& cc, bool with_events) {
+    const ConvP& conv_out = L.conv_out;
+    const size_t cout_w = off[conv_out.w], cout_b = off[conv_out.b];
+    const int pc = cfg.out_ch;
+    gbounds.clear();
+    std::vector<long long> prefix_hi(tape.size() + 1, 0);
+    for (size_t i = 0; i < tape.size(); ++i) prefix_hi[i + 1] = std::max(prefix_hi[i], tape_rng[i].second);
+    long long run_lo = (long long)std::min(cout_w, cout_b);
+    const long long body_hi = (long long)std::max(cout_w + (size_t)pc * conv_out.cin * 9, cout_b + (size_t)pc);
+    long long body_lo = run_lo;
+    for (size_t i = 0; i < tape.size(); ++i) if (tape_rng[i].first >= 0) body_lo = std::min(body_lo, tape_rng[i].first);
+    const size_t nev = with_events ? gev.size() : 0;
+    const long long target = nev ? (body_hi - body_lo + (long long)nev - 1) / (long long)nev : 0;
+    long long prev = body_hi;
+    if (nev) gbounds.push_back(body_hi);
+    for (size_t i = tape.size(); i-- > 0;) {
+        WDM_TRY(tape[i]());
+        if (tape_rng[i].first >= 0) run_lo = std::min(run_lo, tape_rng[i].first);
+        if (nev && gbounds.size() < nev && i > 0 && prefix_hi[i] <= run_lo && prev - run_lo >= target) {
+            WDM_HIP(hipEventRecord(gev[gbounds.size() - 1], cc.s));
+            gbounds.push_back(run_lo);
+            prev = run_lo;
+        }
+    }
+    if (nev && prev > run_lo) {
+        WDM_HIP(hipEventRecord(gev[gbounds.size() - 1], cc.s));
+        gbounds.push_back(run_lo);
+    }
+    return WDM_OK;
+}
+
 int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa, const float* s1m, const float* e, int c_t0, float* loss, float* out_nchw) {
     c = &cc;
     acts.clear(); tape.clear(); tape_rng.clear();
     const int nres = cfg.n_levels, nrb = cfg.num_res_blocks, R = cfg.resolution, B = cc.B;
-    const int temb_ch = L.temb_ch, temb_rows = L.temb_rows;
-    const size_t d0w = off[L.d0w], d0b = off[L.d0b], d1w = off[L.d1w], d1b = off[L.d1b];
+    const int temb_rows = L.temb_rows;
     const auto &down_res = L.down_res, &up_res = L.up_res;
     const auto &down_attn = L.down_attn, &up_attn = L.up_attn;
-    const ConvP& conv_out = L.conv_out;
-    const size_t cout_w = off[conv_out.w], cout_b = off[conv_out.b];
     const size_t es = dsize(cc.dtype);
     auto af = [&](size_t n) -> float* { return (float*)cc.ar->alloc(n * 4); };
     for (int l = 0; l < nres; ++l)      // every map that carries an AttnBlock, before the first launch
@@ -547,48 +702,15 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
         if (kept + transient > cc.ar->capacity())
             WDM_FAIL(WDM_ENOMEM, "training workspace too small (attention: %zu bytes of kept softmax matrices and backward transients, %zu given)", kept + transient, cc.ar->capacity());
     }
-    // ---- temb MLP (fp32), values kept for the backward pass
-    float *emb = af((size_t)B * cfg.ch), *pre0 = af((size_t)B * temb_ch), *t0 = af((size_t)B * temb_ch), *t1 = af((size_t)B * temb_ch), *s1 = af((size_t)B * temb_ch);
     temb_all = af((size_t)B * temb_rows);
     d_temb_all = af((size_t)B * temb_rows);
-    if (!emb || !pre0 || !t0 || !t1 || !s1 || !temb_all || !d_temb_all) WDM_FAIL(WDM_ENOMEM, "training workspace too small (temb)");
-    WDM_TRY(k_timestep_embedding(t, B, cfg.ch, emb, cc.s));
-    WDM_TRY(k_linear(emb, B, cfg.ch, P + d0w, P + d0b, temb_ch, pre0, 0, cc.s));
-    hipLaunchKernelGGL(silu_f32_kernel, dim3(ceil_div((long long)B * temb_ch, 256)), dim3(256), 0, cc.s, pre0, t0, (long long)B * temb_ch);
-    WDM_TRY(k_linear(t0, B, temb_ch, P + d1w, P + d1b, temb_ch, t1, 0, cc.s));
-    hipLaunchKernelGGL(silu_f32_kernel, dim3(ceil_div((long long)B * temb_ch, 256)), dim3(256), 0, cc.s, t1, s1, (long long)B * temb_ch);
-    WDM_TRY(k_linear(s1, B, temb_ch, P + tw, P + tb, temb_rows, temb_all, 0, cc.s));
+    if (!temb_all || !d_temb_all) WDM_FAIL(WDM_ENOMEM, "training workspace too small (temb)");
+    TembSave ts;
+    WDM_TRY(temb_fwd(cc, t, ts));
     WDM_HIP(hipMemsetAsync(d_temb_all, 0, (size_t)B * temb_rows * 4, cc.s));
-    // ---- forward and dgrad weight layouts of all convs (the parameters changed in the last optimiser step): a dozen launches for ~90 layers
-    char* pack_region = nullptr;
-    {
-        size_t bytes = 0;
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        for (const ConvP& q : L.convs) bytes += up(conv_packed_bytes(q.cin, q.cout, q.k, cc.dtype)) + up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
-        pack_region = (char*)cc.ar->alloc(bytes);
-        if (!pack_region) WDM_FAIL(WDM_ENOMEM, "training workspace too small (packed weights)");
-        packed.assign(L.convs.size(), {nullptr, nullptr});
-        std::vector<PackDesc> d3, d1;
-        size_t at = 0;
-        for (const ConvP& q : L.convs) {
-            PackDesc d{};
-            d.w = P + off[q.w]; d.cout = q.cout; d.cin = q.cin; d.rows_total = conv_rows_pad(q.cout);
-            d.dstf = pack_region + at; at += up(conv_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
-            d.dstd = pack_region + at; at += up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, cc.dtype));
-            packed[q.idx] = {d.dstf, d.dstd};
-            (q.k == 3 ? d3 : d1).push_back(d);
-        }
-        if (!cc.dry) {
-            WDM_TRY(k_pack_conv_both_batch(d3.data(), (int)d3.size(), 3, cc.dtype, cc.s));
-            WDM_TRY(k_pack_conv_both_batch(d1.data(), (int)d1.size(), 1, cc.dtype, cc.s));
-        }
-    }
-    // ---- network input: [x_cond | x_t | x_other] with x_t = sqrt(a) x_tar + sqrt(1-a) e
-    TT* xin = new_act();
-    xin->needs_grad = false;
-    WDM_TRY(alloc_tens(cc, cfg.in_channels, R, R, &xin->t));
-    const int pc = cfg.out_ch;
-    BYT(cc.dtype, l_build_input, cc.s, x0, e, sa, s1m, cfg.in_channels, R * R, c_t0, pc, xin->t.p, (long long)B * R * R * cfg.in_channels);
+    WDM_TRY(pack_weights(cc));
+    TT* xin;
+    WDM_TRY(input(cc, x0, e, sa, s1m, c_t0, R, R, &xin));
     // ---- forward
     std::vector<TT*> hs;
     TT* h;
@@ -617,85 +739,174 @@ int wdm_trainer::step(Ctx& cc, const float* x0, const float* t, const float* sa,
         }
         if (l != 0) { TT* o; WDM_TRY(op_conv(L.up_us[l], MODE_UPS, h, nullptr, -1, nullptr, &o)); h = o; }
     }
-    TT* an;
-    WDM_TRY(op_gn_act(L.norm_out, h, nullptr, 1, &an));
-    // conv_out in fp32 NHWC for the loss
-    float* outf = af((size_t)B * R * R * pc);
-    if (!outf) WDM_FAIL(WDM_ENOMEM, "training workspace too small (output)");
-    {
-        ConvW w; w.cin = conv_out.cin; w.cout = pc; w.k = 3; w.rows_pad = conv_rows_pad(pc); w.b = P + cout_b;
-        w.w = packed[conv_out.idx].first;
-        Tens dummy;
-        WDM_TRY(run_conv(cc, w, MODE_S1, {.x0 = &an->t, .y_mode = Y_NHWC_F32, .y_ext = outf}, &dummy));
-    }
-    // ---- loss and its gradient
-    void* dout = cc.ar->alloc((size_t)B * R * R * pc * es);
-    if (!dout) WDM_FAIL(WDM_ENOMEM, "training workspace too small (loss gradient)");
-    {
-        double* lpart = (double*)cc.ar->alloc(LOSS_WGS * sizeof(double));
-        if (!lpart) WDM_FAIL(WDM_ENOMEM, "training workspace too small (loss partials)");
-        if (!cc.dry) BYT(cc.dtype, l_loss, cc.s, outf, e, B, pc, R * R, dout, loss, out_nchw, use_mse ? sa : nullptr, use_mse ? s1m : nullptr, lpart);
-        cc.ar->free(lpart);
-    }
-    // ---- backward: conv_out by hand, then the tape in reverse
-    {
-        Tens dy; dy.p = dout; dy.C = pc; dy.H = R; dy.W = R; dy.xs = pc;
-        WDM_TRY(colsum(cc, dy, G + cout_b, false, false));
-        WDM_TRY(conv_wgrad(cc, MODE_S1, an->t, nullptr, dy, pc, G + cout_w, false));
-        bool f; WDM_TRY(grad_buf(an, &f));
-        WDM_TRY(conv_dgrad(cc, MODE_S1, P + cout_w, conv_out.cin, pc, dy, R, R, an->g, false, packed[conv_out.idx].second));
-    }
-    // The tape runs in reverse; the parameters sit in the flat buffers in forward order, so the gradient buffer fills from its END.  With events set
-    // (wdm_trainer_set_grad_events) the range finished so far is cut into buckets and an event is recorded behind each: the caller's all-reduce of a bucket
-    // can start while the rest of the backward still runs (the reference's DistributedDataParallel does the same with 25 MB buckets, ddm_wavelet.py:168).
-    // A cut at entry i is valid when no earlier entry writes at or above the running minimum.
-    gbounds.clear();
-    {
-        std::vector<long long> prefix_hi(tape.size() + 1, 0);
-        for (size_t i = 0; i < tape.size(); ++i) prefix_hi[i + 1] = std::max(prefix_hi[i], tape_rng[i].second);
-        long long run_lo = (long long)std::min(cout_w, cout_b);
-        const long long body_hi = (long long)std::max(cout_w + (size_t)pc * conv_out.cin * 9, cout_b + (size_t)pc);
-        long long body_lo = run_lo;
-        for (size_t i = 0; i < tape.size(); ++i) if (tape_rng[i].first >= 0) body_lo = std::min(body_lo, tape_rng[i].first);
-        const size_t nev = gev.size();
-        const long long target = nev ? (body_hi - body_lo + (long long)nev - 1) / (long long)nev : 0;
-        long long prev = body_hi;
-        if (nev) gbounds.push_back(body_hi);
-        for (size_t i = tape.size(); i-- > 0;) {
-            WDM_TRY(tape[i]());
-            if (tape_rng[i].first >= 0) run_lo = std::min(run_lo, tape_rng[i].first);
-            if (nev && gbounds.size() < nev && i > 0 && prefix_hi[i] <= run_lo && prev - run_lo >= target) {
-                WDM_HIP(hipEventRecord(gev[gbounds.size() - 1], cc.s));
-                gbounds.push_back(run_lo);
-                prev = run_lo;
-            }
-        }
-        if (nev && prev > run_lo) {
-            WDM_HIP(hipEventRecord(gev[gbounds.size() - 1], cc.s));
-            gbounds.push_back(run_lo);
-        }
-    }
-    // ---- temb MLP backward
-    {
-        const long long n4 = (long long)B * temb_ch;
-        float *d_s1 = af(n4), *d_t1 = af(n4), *d_t0 = af(n4), *d_pre0 = af(n4), *csc = af((size_t)4 * temb_rows), *xpart = af((size_t)64 * n4);
-        if (!d_s1 || !d_t1 || !d_t0 || !d_pre0 || !csc || !xpart) WDM_FAIL(WDM_ENOMEM, "training workspace too small (temb backward)");
-        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_rows * temb_ch, 256)), dim3(256), 0, cc.s, d_temb_all, s1, B, temb_rows, temb_ch, G + tw);
-        l_colsum_f32(cc.s, d_temb_all, temb_rows, B, G + tb, csc);
-        hipLaunchKernelGGL(lin_bwd_x_part_kernel, dim3(ceil_div(n4, 256), 64), dim3(256), 0, cc.s, d_temb_all, P + tw, B, temb_rows, temb_ch, xpart);
-        hipLaunchKernelGGL(lin_bwd_x_final_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, xpart, n4, d_s1);
-        hipLaunchKernelGGL(silu_bwd_f32_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, t1, d_s1, d_t1, n4);
-        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_ch * temb_ch, 256)), dim3(256), 0, cc.s, d_t1, t0, B, temb_ch, temb_ch, G + d1w);
-        l_colsum_f32(cc.s, d_t1, temb_ch, B, G + d1b, csc);
-        hipLaunchKernelGGL(lin_bwd_x_part_kernel, dim3(ceil_div(n4, 256), 64), dim3(256), 0, cc.s, d_t1, P + d1w, B, temb_ch, temb_ch, xpart);
-        hipLaunchKernelGGL(lin_bwd_x_final_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, xpart, n4, d_t0);
-        hipLaunchKernelGGL(silu_bwd_f32_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, cc.s, pre0, d_t0, d_pre0, n4);
-        hipLaunchKernelGGL(lin_bwd_w_kernel, dim3(ceil_div((long long)temb_ch * cfg.ch, 256)), dim3(256), 0, cc.s, d_pre0, emb, B, temb_ch, cfg.ch, G + d0w);
-        l_colsum_f32(cc.s, d_pre0, temb_ch, B, G + d0b, csc);
-        WDM_HIP(hipGetLastError());
-    }
+    WDM_TRY(head(cc, h, e, sa, s1m, loss, out_nchw));
+    WDM_TRY(run_tape(cc, true));
+    WDM_TRY(temb_bwd(cc, ts));
     acts.clear(); tape.clear(); tape_rng.clear();
     return WDM_OK;
+}
+
+// One stage on its own (wdm_trainer_stage): forward, then backward, through the members and ops step() chains, on the caller's tensors.  A caller's tensor is an
+// activation whose storage and gradient buffer are the caller's; `*_set` marks the gradient buffer as already holding a later consumer's gradient (grad_buf's "not first").
+namespace {
+struct StageShape { int cin0 = 0, cin1 = 0, cout = 0, Ho = 0, Wo = 0, mode = MODE_S1; const ResP* res = nullptr; const AttnP* attn = nullptr; const ConvP* conv = nullptr; };
+}
+static int stage_shape(const wdm_trainer& t, int kind, int index, int H, int W, StageShape* out) {
+    const UNetLayout& L = t.L;
+    StageShape s; s.Ho = H; s.Wo = W;
+    auto each_res = [&](auto&& f) { for (auto& lv : L.down_res) for (auto& r : lv) f(r); f(L.mid1); f(L.mid2); for (int l = (int)L.up_res.size() - 1; l >= 0; --l) for (auto& r : L.up_res[l]) f(r); };
+    switch (kind) {
+    case WDM_TRAINER_STAGE_RESBLOCK:
+        each_res([&](const ResP& r) { if (r.layer == index) s.res = &r; });
+        if (!s.res) WDM_FAIL(WDM_EINVAL, "trainer stage: no ResnetBlock %d (the model has %d)", index, L.n_res);
+        s.cin0 = s.res->cin; s.cout = s.res->cout;
+        break;
+    case WDM_TRAINER_STAGE_ATTN: {
+        int n = 0;
+        auto take = [&](const AttnP& a) { if (n++ == index) s.attn = &a; };
+        for (auto& lv : L.down_attn) for (auto& a : lv) take(a);
+        take(L.mid_attn);
+        for (int l = (int)L.up_attn.size() - 1; l >= 0; --l) for (auto& a : L.up_attn[l]) take(a);
+        if (!s.attn) WDM_FAIL(WDM_EINVAL, "trainer stage: no AttnBlock %d (the model has %d)", index, n);
+        WDM_TRY(attn_tokens_check(H, W));
+        s.cin0 = s.cout = s.attn->c;
+        break;
+    }
+    case WDM_TRAINER_STAGE_CONV: {
+        if (index < 0 || index >= (int)L.convs.size()) WDM_FAIL(WDM_EINVAL, "trainer stage: no conv %d (the model has %d)", index, (int)L.convs.size());
+        s.conv = &L.convs[index];
+        s.mode = -1;
+        if (index == L.conv_in.idx) s.mode = MODE_S1;
+        for (auto& d : L.down_ds) if (d.cout && d.idx == index) s.mode = MODE_S2;
+        for (auto& u : L.up_us) if (u.cout && u.idx == index) s.mode = MODE_UPS;
+        if (s.mode < 0) WDM_FAIL(WDM_EINVAL, "trainer stage: conv %d is not conv_in, a Downsample or an Upsample (the others run inside their blocks)", index);
+        if (s.mode == MODE_S2 && (H % 2 || W % 2)) WDM_FAIL(WDM_EINVAL, "trainer stage: a Downsample takes an even map, not %d x %d", H, W);
+        if (s.mode == MODE_S2) { s.Ho = H / 2; s.Wo = W / 2; }
+        if (s.mode == MODE_UPS) { s.Ho = 2 * H; s.Wo = 2 * W; }
+        s.cin0 = s.conv->cin; s.cout = s.conv->cout;
+        break;
+    }
+    case WDM_TRAINER_STAGE_TEMB: break;
+    case WDM_TRAINER_STAGE_INPUT: s.conv = &L.conv_in; s.cin0 = L.conv_in.cin; s.cout = L.conv_in.cout; break;
+    case WDM_TRAINER_STAGE_HEAD: s.conv = &L.conv_out; s.cin0 = L.conv_out.cin; s.cout = L.conv_out.cin; break;
+    default: WDM_FAIL(WDM_EINVAL, "trainer stage: unknown kind %d", kind);
+    }
+    *out = s;
+    return WDM_OK;
+}
+
+// An upper bound of what a stage asks of the arena, in closed form (the trainer's ops have no sizing pass): the packed weights of every conv, every activation,
+// gradient and operand copy of the stage (96 maps of the widest tensor is several times what the longest stage, a ResnetBlock over a concat, keeps), the weight
+// gradient's partial sums, the attention matrices, the temb MLP's rows.
+static size_t stage_need(const wdm_trainer& t, int kind, int index, int B, int H, int W) {
+    StageShape s;
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W > (1LL << 24)) { set_error("trainer stage: bad shape %d x %d x %d", B, H, W); return 0; }
+    if (stage_shape(t, kind, index, H, W, &s) != WDM_OK) return 0;
+    const int dt = t.cfg.dtype;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t need = (size_t)64 << 20;
+    for (const ConvP& q : t.L.convs) need += up(conv_packed_bytes(q.cin, q.cout, q.k, dt)) + up(conv_dgrad_packed_bytes(q.cin, q.cout, q.k, dt));
+    if (kind == WDM_TRAINER_STAGE_TEMB) return need + (size_t)4 * ((size_t)B * (t.cfg.ch + 80 * (size_t)t.L.temb_ch + 2 * (size_t)t.L.temb_rows) + 260 * (size_t)std::max(t.L.temb_rows, t.L.temb_ch));
+    const int cin = s.res && s.res->has_nin ? s.res->cin : s.cin0, cw = std::max(std::max(cin, s.cout), 64);
+    const size_t px = (size_t)B * std::max(H * W, s.Ho * s.Wo);
+    need += 96 * px * cw * 4;
+    const size_t rows_g = (size_t)align_up((size_t)cw, 64), ntile = ((cw + 127) / 128) * (size_t)((cw + 63) / 64);
+    need += 2 * 9 * 4 * rows_g * cw * std::max<size_t>((size_t)B, 257 / ntile + 1);
+    if (kind == WDM_TRAINER_STAGE_ATTN) need += (size_t)B * H * W * H * W * 32;
+    return need;
+}
+
+int wdm_trainer::stage(Ctx& cc, int kind, int index, const wdm_trainer_stage_io& io, int H, int W) {
+    c = &cc;
+    acts.clear(); tape.clear(); tape_rng.clear();
+    StageShape s;
+    WDM_TRY(stage_shape(*this, kind, index, H, W, &s));
+    const size_t es = dsize(cc.dtype);
+    const int B = cc.B;
+    // a caller's tensor as an activation of the graph
+    auto wrap = [&](const void* p, int C, int h, int w, void* g, int gset, bool needs) {
+        TT* t = new_act();
+        t->t.p = const_cast<void*>(p); t->t.C = C; t->t.H = h; t->t.W = w; t->t.xs = C;
+        t->g = g; t->gset = gset != 0; t->needs_grad = needs;
+        return t;
+    };
+    // the stage's output: its values to the caller, the caller's dy as its gradient
+    auto finish = [&](TT* o, void* y, const void* dy) -> int {
+        if (o->t.xs != o->t.C) WDM_FAIL(WDM_ESTATE, "trainer stage: the output is not dense");
+        if (y) WDM_HIP(hipMemcpyAsync(y, o->t.p, (size_t)B * o->t.H * o->t.W * o->t.C * es, hipMemcpyDeviceToDevice, cc.s));
+        o->g = const_cast<void*>(dy); o->gset = true;
+        return WDM_OK;
+    };
+    auto need = [&](bool ok, const char* what) -> int { if (!ok) WDM_FAIL(WDM_EINVAL, "trainer stage: %s", what); return WDM_OK; };
+    int rc = WDM_OK;
+    switch (kind) {
+    case WDM_TRAINER_STAGE_RESBLOCK: {
+        const ResP& r = *s.res;
+        WDM_TRY(need(io.x0 && io.dy && io.y && io.dx0 && io.temb_all && io.d_temb_all, "a ResnetBlock needs x0, dy, y, dx0, temb_all and d_temb_all"));
+        WDM_TRY(need(io.c1 >= 0 && io.c1 < r.cin && (io.c1 == 0 || r.has_nin), "c1 must lie in [0, cin), and be 0 on an identity shortcut"));
+        WDM_TRY(need(io.c1 == 0 ? !io.x1 : (io.x1 && io.dx1), "x1 and dx1 go with c1 > 0"));
+        WDM_TRY(pack_weights(cc));
+        temb_all = io.temb_all; d_temb_all = io.d_temb_all;
+        TT* x0 = wrap(io.x0, r.cin - io.c1, H, W, io.dx0, io.dx0_set, true);
+        TT* x1 = io.c1 ? wrap(io.x1, io.c1, H, W, io.dx1, io.dx1_set, true) : nullptr;
+        TT* o;
+        WDM_TRY(op_resblock(r, x0, x1, &o));
+        WDM_TRY(finish(o, io.y, io.dy));
+        rc = run_tape(cc, false);
+        break;
+    }
+    case WDM_TRAINER_STAGE_ATTN: {
+        WDM_TRY(need(io.x0 && io.dy && io.y && io.dx0, "an AttnBlock needs x0, dy, y and dx0"));
+        WDM_TRY(pack_weights(cc));
+        TT* x = wrap(io.x0, s.attn->c, H, W, io.dx0, io.dx0_set, true);
+        TT* o;
+        WDM_TRY(op_attn(*s.attn, x, &o));
+        WDM_TRY(finish(o, io.y, io.dy));
+        rc = run_tape(cc, false);
+        break;
+    }
+    case WDM_TRAINER_STAGE_CONV: {
+        const bool first_layer = s.conv->idx == L.conv_in.idx;
+        WDM_TRY(need(io.x0 && io.dy && io.y && (first_layer || io.dx0), "a conv needs x0, dy, y and (but for conv_in) dx0"));
+        WDM_TRY(pack_weights(cc));
+        TT* x = wrap(io.x0, s.conv->cin, H, W, first_layer ? nullptr : io.dx0, io.dx0_set, !first_layer);
+        TT* o;
+        WDM_TRY(op_conv(*s.conv, s.mode, x, nullptr, -1, nullptr, &o));
+        WDM_TRY(finish(o, io.y, io.dy));
+        rc = run_tape(cc, false);
+        break;
+    }
+    case WDM_TRAINER_STAGE_TEMB: {
+        WDM_TRY(need(io.t && io.temb_all && io.d_temb_all, "the temb MLP needs t, temb_all and d_temb_all"));
+        temb_all = io.temb_all; d_temb_all = io.d_temb_all;
+        TembSave ts;
+        WDM_TRY(temb_fwd(cc, io.t, ts));
+        rc = temb_bwd(cc, ts);
+        break;
+    }
+    case WDM_TRAINER_STAGE_INPUT: {
+        WDM_TRY(need(io.x0 && io.e && io.sa && io.s1m && io.y && io.x96, "the input stage needs x0, e, sa, s1m, x96 and y"));
+        WDM_TRY(need(io.c_t0 >= 0 && io.c_t0 + cfg.out_ch <= cfg.in_channels, "c_t0 + out_ch exceeds in_channels"));
+        WDM_TRY(pack_weights(cc));
+        TT *xin, *o;
+        WDM_TRY(input(cc, (const float*)io.x0, io.e, io.sa, io.s1m, io.c_t0, H, W, &xin));
+        WDM_HIP(hipMemcpyAsync(io.x96, xin->t.p, (size_t)B * H * W * cfg.in_channels * es, hipMemcpyDeviceToDevice, cc.s));
+        WDM_TRY(op_conv(L.conv_in, MODE_S1, xin, nullptr, -1, nullptr, &o));
+        WDM_TRY(finish(o, io.y, io.dy));
+        if (io.dy) rc = run_tape(cc, false);
+        break;
+    }
+    case WDM_TRAINER_STAGE_HEAD: {
+        WDM_TRY(need(io.x0 && io.e && io.loss && io.dx0 && (!use_mse || (io.sa && io.s1m)), "the head needs x0, e, loss, dx0 and, under use_mse, sa and s1m"));
+        WDM_TRY(pack_weights(cc));
+        TT* h = wrap(io.x0, L.norm_out.c, H, W, io.dx0, io.dx0_set, true);
+        WDM_TRY(head(cc, h, io.e, io.sa, io.s1m, io.loss, io.out_nchw));
+        rc = run_tape(cc, false);
+        break;
+    }
+    }
+    acts.clear(); tape.clear(); tape_rng.clear();
+    return rc;
 }
 
 // =====================================================================================================================
@@ -767,6 +978,29 @@ int wdm_trainer_step(wdm_trainer* t, const float* x0, const float* tt, const flo
     Arena ar(workspace, workspace_bytes);
     Ctx c{(hipStream_t)stream, t->cfg.dtype, B, &ar, false};
     return t->step(c, x0, tt, sqrt_a, sqrt_1ma, e, c_t0, loss, out_nchw);
+}
+/* one stage of the trainer on its own (unit tests): forward, then backward, through the members and ops wdm_trainer_step chains, on the caller's tensors; waits for the stream */
+size_t wdm_trainer_stage_workspace_bytes(const wdm_trainer* t, int kind, int index, int B, int H, int W) {
+    if (!t) return 0;
+    return stage_need(*t, kind, index, B, H, W);
+}
+int wdm_trainer_stage(wdm_trainer* t, int kind, int index, const wdm_trainer_stage_io* io, int B, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!t || !io || !workspace) WDM_FAIL(WDM_EINVAL, "wdm_trainer_stage: null argument");
+    if (!t->P || !t->G) WDM_FAIL(WDM_ESTATE, "wdm_trainer_stage: call wdm_trainer_set_buffers first");
+    if (((uintptr_t)workspace) & 255) WDM_FAIL(WDM_EINVAL, "wdm_trainer_stage: workspace must be 256-byte aligned");
+    if ((((uintptr_t)io->x0) | ((uintptr_t)io->x1) | ((uintptr_t)io->dy) | ((uintptr_t)io->y) | ((uintptr_t)io->x96) | ((uintptr_t)io->dx0) | ((uintptr_t)io->dx1)) & 15)
+        WDM_FAIL(WDM_EINVAL, "wdm_trainer_stage: tensors must be 16-byte aligned");
+    // sized, and kind, index and shape checked, before the first launch
+    const size_t need = wdm_trainer_stage_workspace_bytes(t, kind, index, B, H, W);
+    if (!need) return WDM_EINVAL;                                                   // (the message is set)
+    if (workspace_bytes < need)
+        WDM_FAIL(WDM_ENOMEM, "wdm_trainer_stage: workspace too small (%zu bytes given, wdm_trainer_stage_workspace_bytes asks for %zu)", workspace_bytes, need);
+    Arena ar(workspace, workspace_bytes);
+    Ctx c{(hipStream_t)stream, t->cfg.dtype, B, &ar, false};
+    const int rc = t->stage(c, kind, index, *io, H, W);
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (rc == WDM_OK && e != hipSuccess) WDM_FAIL(WDM_EHIP, "wdm_trainer_stage: %s", hipGetErrorString(e));
+    return rc;
 }
 int wdm_trainer_adam_ema(wdm_trainer* t, int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float ema_mu, void* stream) {
     if (!t || !t->P || !t->G || !t->M || !t->V) WDM_FAIL(WDM_ESTATE, "wdm_trainer_adam_ema: buffers not set");

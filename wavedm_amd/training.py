@@ -277,6 +277,101 @@ class Trainer:
                 break
         return (self._loss[0], out) if return_output else self._loss[0]
 
+    # ---- one stage of the step on its own ------------------------------------------------------------------------------
+    def stage_names(self, kind):
+        """The stages of `kind` ("resblock", "attn", "conv") by state_dict prefix, in the library's index order."""
+        if kind == "resblock":
+            return [k[:-len(".norm2.weight")] for k in self.layout if k.endswith(".norm2.weight")]
+        if kind == "attn":
+            return [k[:-len(".q.weight")] for k in self.layout if k.endswith(".q.weight")]
+        return [k[:-len(".weight")] for k, (_, shape) in self.layout.items() if k.endswith(".weight") and len(shape) == 4]
+
+    def stage(self, kind, index=0, x0=None, x1=None, dy=None, temb_all=None, d_temb_all=None, t=None, e=None, sa=None, s1m=None, c_t0=None, dx0=None, dx1=None):
+        """One stage's forward and backward on their own (wdm_trainer_stage, for unit tests): the members and graph ops a step chains, on the caller's tensors, with
+        the weights packed from self.params as a step packs them.  kind: "resblock", "attn", "conv", "temb", "input", "head"; index: a position in stage_names(kind)
+        or one of its names.  Activations (x0, x1, dy) and activation gradients (dx0, dx1) are fp32 NCHW on the GPU here and are stored as NHWC in the trainer's
+        dtype for the call; dx0 / dx1 given = the gradient a later consumer already left, to which the stage adds.  temb_all / d_temb_all: (B, temb_rows) fp32 --
+        a resblock reads temb_all and writes ITS rows of d_temb_all in place; "temb" reads d_temb_all.  "input": x0 the fp32 NCHW image, e, sa, s1m, c_t0; "head": x0 = h, e
+        (sa, s1m under use_mse).  Dropout as a step of self.step + 1 draws it.
+        -> dict of fp32 tensors: y, dx0, dx1 (NCHW, the stored values), x96 (input), temb_all (temb), out (head, NCHW), loss; the stage's entries of self.grads are written."""
+        L = _lib.lib()
+        code = _lib.WDM_TRAINER_STAGES[kind]
+        if isinstance(index, str):
+            index = self.stage_names(kind).index(index)
+        dt = torch.bfloat16 if self._dtype_code == _lib.WDM_BF16 else torch.float32
+        dev = self.device
+        nhwc = lambda v, n: _lib.require_cuda_f32(v, n).permute(0, 2, 3, 1).to(dt).contiguous()
+        back = lambda v: v.permute(0, 3, 1, 2).float().contiguous()
+        f32 = lambda v, n: None if v is None else _lib.require_cuda_f32(v, n)
+        io, keep, out = _lib.TrainerStageIO(), [], {}
+
+        def put(field, v):
+            if v is not None:
+                keep.append(v)
+                setattr(io, field, v.data_ptr())
+            return v
+        m = self.config.model
+        if kind == "temb":
+            t = put("t", f32(t.float(), "t"))
+            B, H, W = int(t.shape[0]), 1, 1
+            put("d_temb_all", f32(d_temb_all, "d_temb_all"))
+            out["temb_all"] = put("temb_all", torch.empty_like(d_temb_all))
+        else:
+            B, _, H, W = x0.shape
+            if kind == "input":
+                put("x0", f32(x0, "x0"))
+                x96 = put("x96", torch.empty(B, H, W, int(x0.shape[1]), dtype=dt, device=dev))
+                io.c_t0 = int(self._c_t0 if c_t0 is None else c_t0)
+            else:
+                xd = put("x0", nhwc(x0, "x0"))
+            for n_, v in (("e", e), ("sa", sa), ("s1m", s1m)):
+                put(n_, f32(v, n_))
+            if kind == "resblock":
+                put("temb_all", f32(temb_all, "temb_all"))
+                out["d_temb_all"] = put("d_temb_all", f32(d_temb_all, "d_temb_all"))
+                if x1 is not None:
+                    x1d = put("x1", nhwc(x1, "x1"))
+                    io.c1 = int(x1.shape[1])
+            if kind != "input":
+                dx0d = put("dx0", nhwc(dx0, "dx0") if dx0 is not None else torch.zeros_like(xd)) if not (kind == "conv" and index == 0) else None
+                io.dx0_set = int(dx0 is not None)
+                if x1 is not None:
+                    dx1d = put("dx1", nhwc(dx1, "dx1") if dx1 is not None else torch.zeros_like(x1d))
+                    io.dx1_set = int(dx1 is not None)
+            if kind == "head":
+                out["out"] = put("out_nchw", torch.empty(B, int(m.out_ch), H, W, device=dev))
+                out["loss"] = put("loss", torch.zeros(1, device=dev))
+            else:
+                names = self.stage_names("conv" if kind == "input" else kind)
+                name = names[0 if kind == "input" else index]
+                cout = self.layout[name + (".conv2.weight" if kind == "resblock" else ".proj_out.weight" if kind == "attn" else ".weight")][1][0]
+                sc = (0.5 if ".downsample." in name else 2 if ".upsample." in name else 1) if kind == "conv" else 1
+                y = put("y", torch.empty(B, int(H * sc), int(W * sc), cout, dtype=dt, device=dev))
+                if dy is not None:
+                    dyd = put("dy", nhwc(dy, "dy"))
+                    if tuple(dyd.shape) != tuple(y.shape):
+                        raise ValueError(f"Trainer.stage: dy has shape {tuple(dyd.shape)} (NHWC), the stage's output {tuple(y.shape)}")
+                elif kind != "input":
+                    raise ValueError("Trainer.stage: dy is required")
+        with torch.cuda.device(dev):
+            if kind == "resblock" and (self.dropout > 0.0 or self._dropout_armed):
+                _lib.check(L.wdm_trainer_set_dropout(self._t, self.dropout, self.rank_dropout_seed(), self.step + 1))
+                self._dropout_armed = self.dropout > 0.0
+            n = int(L.wdm_trainer_stage_workspace_bytes(self._t, code, int(index), B, H, W))
+            if n == 0:
+                raise RuntimeError("wdm_trainer_stage_workspace_bytes failed: " + L.wdm_last_error().decode(errors="replace"))
+            ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+            _lib.check(L.wdm_trainer_stage(self._t, code, int(index), C.byref(io), B, H, W, _lib.ptr(ws), n, _lib.stream_ptr()))
+        if kind == "input":
+            out["x96"] = back(x96)
+        if kind not in ("temb", "head"):
+            out["y"] = back(y)
+        if kind not in ("temb", "input") and dx0d is not None:
+            out["dx0"] = back(dx0d)
+        if kind == "resblock" and x1 is not None:
+            out["dx1"] = back(dx1d)
+        return out
+
     # ---- dropout ------------------------------------------------------------------------------------------------------
     def _ensure_dropout_seed(self):
         if self.dropout_seed is None:
