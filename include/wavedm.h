@@ -246,6 +246,21 @@ int wdm_unet_temb_rows(const wdm_unet* u);
 int wdm_unet_temb_table(wdm_unet* u, const float* t, int n, float* temb_out, void* workspace, size_t workspace_bytes, void* stream);
 int wdm_unet_forward_temb(wdm_unet* u, const void* x96, const float* temb_row, int B, float* eps_out,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* Taps on the forward (unit tests): wdm_unet_forward_taps IS wdm_unet_forward -- the same launches on the same arena -- and copies every layer's output to a caller
+ * buffer right behind the launch that produced it (device to device, on `stream`, before the arena reuses the memory).  The layers are listed by
+ * wdm_unet_num_taps / wdm_unet_tap_info in executor order under their state_dict prefixes: conv_in, down.L.block.B, down.L.attn.B, down.L.downsample, mid.block_1,
+ * mid.attn_1, mid.block_2, up.L.block.B, up.L.attn.B, up.L.upsample.  C, H, W: the output's shape; kind: WDM_UNET_TAP_*; in0: the tap the layer reads (-1: the
+ * network's input); in1: for a ResnetBlock of the up path the tap of its skip connection, the second half of the concat [in0 | in1], else -1.
+ *   taps[i]     : device pointer to (B, H, W, C) NHWC in the model dtype, or NULL to skip the layer; the array itself is a host array and may be NULL
+ *   nrm_taps[i] : likewise; receives act(GroupNorm_consumer(output)), the normalised copy the producing conv wrote for its consumer, where it wrote one, and is
+ *                 left untouched where it wrote none
+ * With both arrays NULL nothing is added to wdm_unet_forward: the same launches, the same bits.  Arguments, workspace and refusals as wdm_unet_forward.
+ * Additions to the ABI: WDM_ABI_VERSION stays 1. */
+enum { WDM_UNET_TAP_RESBLOCK = 0, WDM_UNET_TAP_ATTN = 1, WDM_UNET_TAP_CONV_IN = 2, WDM_UNET_TAP_DOWN = 3, WDM_UNET_TAP_UP = 4 };
+int wdm_unet_num_taps(const wdm_unet* u);
+int wdm_unet_tap_info(const wdm_unet* u, int i, const char** name, int* C, int* H, int* W, int* kind, int* in0, int* in1);
+int wdm_unet_forward_taps(wdm_unet* u, const void* x96, const float* t, int n_t, int B, float* eps_out, void* const* taps, void* const* nrm_taps,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- per-block entry points (unit parity tests; same code the UNet executor runs) -----------
  * Weights are given in the reference layout as fp32 device pointers and packed on the fly into

@@ -97,7 +97,7 @@ def _gn_f32(xs, gamma, beta, variant):
     return (xs.double() * scale.double() + shift.double()).float()
 
 
-def _run(sd, name, x, kind, form, dt, on, x3, vbias_behind, defect, gn="device"):
+def _run(sd, name, x, kind, form, dt, on, x3, vbias_behind, defect, gn="device", hn=None):
     g = lambda k: torch.as_tensor(sd[name + "." + k])
     ch = _Chain(kind, dt, on, x3, defect)
     x = torch.as_tensor(x)
@@ -107,7 +107,9 @@ def _run(sd, name, x, kind, form, dt, on, x3, vbias_behind, defect, gn="device")
     if form in ("folded", "stream", "fused"):
         assert kind in H16, "the fused and streaming cores are 16-bit"
     xs = ch.st(x.to(dt))                                                             # the stored input
-    if dt == torch.float64:
+    if hn is not None:                                                               # the stored GroupNorm(x) the device took from the producer of x
+        hn = torch.as_tensor(hn).to(dt)
+    elif dt == torch.float64:
         hn = group_norm(xs, g("norm.weight"), g("norm.bias"))
     else:
         hn = _gn_f32(xs, g("norm.weight").float(), g("norm.bias").float(), gn)
@@ -193,19 +195,20 @@ def _run(sd, name, x, kind, form, dt, on, x3, vbias_behind, defect, gn="device")
     return back(y), back(Mg)
 
 
-def attn_block_ref(sd, name, x, kind, form, x3=4, vbias_behind=None, rounding=True):
+def attn_block_ref(sd, name, x, kind, form, x3=4, vbias_behind=None, rounding=True, hn=None):
     """(ref, M) of an AttnBlock in float64 at the device's rounding points (module docstring).  form: "gemm", "fused", "folded" (also the block-diagonal
     8 x 8 form: pass 8 x 8 maps) or "stream".  x3: the f32x3 product form, 4 or 3 terms, one for all or a dict over the launches qk / v / s / pv / proj.
     vbias_behind: V stored without its bias, which is added to P.V (default: where the device does so).  rounding = False: the plain block.
+    hn: the stored GroupNorm(x) where the device took it from the producer of x (its normalised copy) instead of normalising x itself.
     ref is the unrounded output; M the per-element magnitude of its sum."""
-    y, M = _run(sd, name, x, kind, form, torch.float64, rounding, x3, vbias_behind, None)
+    y, M = _run(sd, name, x, kind, form, torch.float64, rounding, x3, vbias_behind, None, hn=hn)
     return y, M
 
 
-def attn_block_emu(sd, name, x, kind, form, x3=4, vbias_behind=None, defect=None, gn="device"):
+def attn_block_emu(sd, name, x, kind, form, x3=4, vbias_behind=None, defect=None, gn="device", hn=None):
     """The same chain in fp32 on the host (torch.float32 matmuls, exp, reciprocal; the same rounding points), as the device would store it: the yardstick the
     bounds come from.  gn: the fp32 GroupNorm (GN_VARIANTS).  defect: one of drop_key, swap_v, trunc_p, no_vbias, scale, denom_last, leak -- a "device" that is wrong in that one way."""
-    y, _ = _run(sd, name, x, kind, form, torch.float32, True, x3, vbias_behind, defect, gn)
+    y, _ = _run(sd, name, x, kind, form, torch.float32, True, x3, vbias_behind, defect, gn, hn=hn)
     return rnd(y, kind)
 
 

@@ -126,19 +126,24 @@ def group_norm(x, gamma, beta):
     return O.group_norm({"n.weight": torch.as_tensor(gamma).double(), "n.bias": torch.as_tensor(beta).double()}, "n", x)
 
 
-def resblock_ref(sd, name, x0, x1, temb, kind, x3=4, shortcut="fused", gn=group_norm):
+def resblock_ref(sd, name, x0, x1, temb, kind, x3=4, shortcut="fused", gn=group_norm, temb_proj=None, a1=None):
     """(ref, M, A) of a ResnetBlock at the device's rounding points (module docstring).  temb: (n_t, 512) with n_t = 1 (shared) or B.
     x3: the f32x3 form of (conv1, conv2, 1x1 shortcut), or one for all.  shortcut: "fused" (the 1x1 over the stored x in conv2's accumulator, one
     rounding), "gemm" (its own launch: rounded, then added), ignored without one.  gn: the GroupNorm (a perturbation can replace it).
+    temb_proj: the block's rows of the temb table instead of temb, (n_t, cout) fp32 as the device holds them (wdm_unet_temb_table: conv1's epilogue adds the row in fp32).
+    a1: conv1's stored operand act(norm1(x)) where the device took it from somewhere else than its own GroupNorm of x (the normalised copy the producer of x wrote).
     A: a per-element allowance for an intermediate rounding whose input the device sums in another order -- one ulp of the separately rounded shortcut
     (fp32 accumulation may put it on the other side of a midpoint, and |shortcut| may far exceed |y|); zero elsewhere."""
     g = lambda k: torch.as_tensor(sd[name + "." + k])
     f1, f2, fn = (x3, x3, x3) if isinstance(x3, int) else x3
     xin = x0 if x1 is None else torch.cat([x0, x1], 1)
     xs = rnd(xin, kind) if kind in H16 else torch.as_tensor(xin).double()       # the stored input (fp32 modes: exact)
-    a1 = O.silu(gn(xs, g("norm1.weight"), g("norm1.bias")))
+    a1 = O.silu(gn(xs, g("norm1.weight"), g("norm1.bias"))) if a1 is None else torch.as_tensor(a1).double()
     h, _ = _conv_pair(lambda ww, aa: F.conv2d(aa, ww, padding=1), Operand(g("conv1.weight"), kind), Operand(a1, kind), f1)
-    tp = F.linear(O.silu(torch.as_tensor(temb).double()), g("temb_proj.weight").double(), g("temb_proj.bias").double())       # fp32 on the device (k_linear)
+    if temb_proj is not None:
+        tp = torch.as_tensor(temb_proj).double()
+    else:
+        tp = F.linear(O.silu(torch.as_tensor(temb).double()), g("temb_proj.weight").double(), g("temb_proj.bias").double())       # fp32 on the device (k_linear)
     h = h + g("conv1.bias").double().view(1, -1, 1, 1) + tp[:, :, None, None]
     h1 = rnd(h, kind) if kind in H16 else h
     a2 = O.silu(gn(h1, g("norm2.weight"), g("norm2.bias")))

@@ -43,6 +43,7 @@ class TrainerStageIO(C.Structure):
                [(n, C.c_int) for n in ("c1", "c_t0", "dx0_set", "dx1_set")]
 
 
+WDM_UNET_TAP_KINDS = ("resblock", "attn", "conv_in", "down", "up")      # WDM_UNET_TAP_* (include/wavedm.h)
 WDM_TRAINER_STAGES = {"resblock": 0, "attn": 1, "conv": 2, "temb": 3, "input": 4, "head": 5}
 
 
@@ -103,6 +104,9 @@ def lib():
         "wdm_unet_temb_rows": (i, [vp]),
         "wdm_unet_temb_table": (i, [vp, vp, i, vp, vp, sz, vp]),
         "wdm_unet_forward_temb": (i, [vp, vp, vp, i, vp, vp, sz, vp]),
+        "wdm_unet_num_taps": (i, [vp]),
+        "wdm_unet_tap_info": (i, [vp, i, C.POINTER(C.c_char_p)] + [C.POINTER(i)] * 6),
+        "wdm_unet_forward_taps": (i, [vp, vp, vp, i, i, vp, C.POINTER(vp), C.POINTER(vp), vp, sz, vp]),
         "wdm_resblock_forward": (i, [vp, C.POINTER(ResblockParams), vp, i, vp, i, vp, i, i, i, i, i, vp, i, vp, sz, vp]),
         "wdm_attn_forward": (i, [vp, C.POINTER(AttnParams), vp, i, i, i, vp, i, vp, sz, vp]),
         "wdm_conv_forward": (i, [vp, vp, vp, i, i, i, vp, i, i, i, vp, i, vp, sz, vp]),
@@ -191,7 +195,7 @@ EXPORTED = ["wdm_abi_version", "wdm_last_error", "wdm_create", "wdm_destroy", "w
             "wdm_multistep_update_c", "wdm_multistep_from_sums_c", "wdm_multistep_update_ragged", "wdm_nchw_to_nhwc", "wdm_nhwc_to_nchw", "wdm_unet_create",
             "wdm_unet_destroy", "wdm_unet_num_params", "wdm_unet_param_info", "wdm_unet_packed_bytes",
             "wdm_unet_set_packed", "wdm_unet_load_param", "wdm_unet_mark_loaded", "wdm_unet_workspace_bytes",
-            "wdm_unet_forward", "wdm_unet_temb_rows", "wdm_unet_temb_table", "wdm_unet_forward_temb", "wdm_resblock_forward", "wdm_attn_forward", "wdm_conv_forward", "wdm_temb_forward",
+            "wdm_unet_forward", "wdm_unet_temb_rows", "wdm_unet_temb_table", "wdm_unet_forward_temb", "wdm_unet_num_taps", "wdm_unet_tap_info", "wdm_unet_forward_taps", "wdm_resblock_forward", "wdm_attn_forward", "wdm_conv_forward", "wdm_temb_forward",
             "wdm_hfrm_create", "wdm_hfrm_destroy", "wdm_hfrm_num_params", "wdm_hfrm_param_info", "wdm_hfrm_packed_bytes",
             "wdm_hfrm_set_packed", "wdm_hfrm_load_param", "wdm_hfrm_finalize", "wdm_hfrm_workspace_bytes",
             "wdm_hfrm_forward", "wdm_hfrm_set_local", "wdm_hfrm_local_kernel", "wdm_hfrm_local_pool", "wdm_hfrm_set_max_launch_bytes", "wdm_hfrm_chunk_rows", "wdm_hfrm_conv_out", "wdm_hfrm_stage_workspace_bytes", "wdm_hfrm_stage_forward", "wdm_image_sqdiff", "wdm_to_u8_hwc", "wdm_image_ingest", "wdm_to_u8_hwc_crop", "wdm_image_ssim_scratch_bytes", "wdm_image_ssim", "wdm_conv_backward", "wdm_gn_act_backward", "wdm_dropout_mask", "wdm_gn_act_dropout", "wdm_trainer_create", "wdm_trainer_destroy", "wdm_trainer_num_params",

@@ -92,6 +92,9 @@ struct Ctx {
     int B;
     Arena* ar;
     bool dry;     // no launches, only arena accounting
+    // wdm_unet_forward_taps: host arrays of device pointers, one entry per layer output of the UNet executor (unet.hip: wdm_unet::taps), or null
+    void* const* taps = nullptr;
+    void* const* nrm_taps = nullptr;
 };
 
 // ---- packed parameter views (device pointers) -------------------------------------------------

@@ -39,6 +39,9 @@ struct ConvD { size_t w_off, b_off; int cin, cout, k, rows_pad; size_t up4_off, 
 // reloaded; the biases' fp32 copies are the ones the unfolded convs use
 enum { FR_QW = 0, FR_KW, FR_VW, FR_PW, FR_QB, FR_VB, FR_PB, FR_N };
 struct FoldD { int c; size_t stage_off; ConvD qk, v, proj, qf, pf; int slot[FR_N]; };
+// a layer output of the forward that a caller can have copied out (wdm_unet_forward_taps), in executor order.  in0: the tap the layer reads (-1: the network's input);
+// in1: an up block's skip, the second half of its concat (else -1)
+struct TapD { std::string name; int C, H, W, kind, in0, in1; };
 
 }  // namespace
 
@@ -60,6 +63,7 @@ struct wdm_unet {
     char* packed = nullptr;
     bool all_loaded = false;
     size_t temb_w_off = 0, temb_b_off = 0;
+    std::vector<TapD> taps;         // wdm_unet_tap_info: one per launch sequence of forward() that leaves a layer's output
 
     // ---- the packed buffer, laid out in one pass over the layout (the order of the take() calls IS the buffer's format: it is broadcast between ranks)
     size_t take(size_t bytes) { size_t o = packed_bytes; packed_bytes = align_up(packed_bytes + bytes, 256); return o; }
@@ -186,6 +190,38 @@ int wdm_unet::build() {
         row += e.cout;
     }
     for (size_t i = 0; i < L.params.size(); ++i) index[L.params[i].name] = (int)i;
+
+    // the tap list: forward()'s order, the skip stack replayed on tap indices
+    {
+        const int nrb = cfg.num_res_blocks, R = cfg.resolution;
+        const auto S = [](int v) { return std::to_string(v); };
+        std::vector<int> hs;
+        auto add = [&](const std::string& n, int C, int hw, int kind, int in0, int in1) { taps.push_back({n, C, hw, hw, kind, in0, in1}); return (int)taps.size() - 1; };
+        int h = add("conv_in", cfg.ch, R, WDM_UNET_TAP_CONV_IN, -1, -1);
+        hs.push_back(h);
+        for (int l = 0; l < nres; ++l) {
+            const std::string lv = "down." + S(l);
+            for (int b = 0; b < nrb; ++b) {
+                h = add(lv + ".block." + S(b), L.down_res[l][b].cout, R >> l, WDM_UNET_TAP_RESBLOCK, hs.back(), -1);
+                if (!L.down_attn[l].empty()) h = add(lv + ".attn." + S(b), L.down_attn[l][b].c, R >> l, WDM_UNET_TAP_ATTN, h, -1);
+                hs.push_back(h);
+            }
+            if (l != nres - 1) hs.push_back(add(lv + ".downsample", L.down_ds[l].cout, R >> (l + 1), WDM_UNET_TAP_DOWN, hs.back(), -1));
+        }
+        h = add("mid.block_1", L.mid1.cout, R >> (nres - 1), WDM_UNET_TAP_RESBLOCK, hs.back(), -1);
+        h = add("mid.attn_1", L.mid_attn.c, R >> (nres - 1), WDM_UNET_TAP_ATTN, h, -1);
+        h = add("mid.block_2", L.mid2.cout, R >> (nres - 1), WDM_UNET_TAP_RESBLOCK, h, -1);
+        for (int l = nres - 1; l >= 0; --l) {
+            const std::string lv = "up." + S(l);
+            for (int b = 0; b <= nrb; ++b) {
+                const int skip = hs.back();
+                hs.pop_back();
+                h = add(lv + ".block." + S(b), L.up_res[l][b].cout, R >> l, WDM_UNET_TAP_RESBLOCK, h, skip);
+                if (!L.up_attn[l].empty()) h = add(lv + ".attn." + S(b), L.up_attn[l][b].c, R >> l, WDM_UNET_TAP_ATTN, h, -1);
+            }
+            if (l != 0) h = add(lv + ".upsample", L.up_us[l].cout, R >> (l - 1), WDM_UNET_TAP_UP, h, -1);
+        }
+    }
     return WDM_OK;
 }
 
@@ -278,7 +314,20 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
     }
     std::vector<Tens> hs;
     Tens h;
+    // wdm_unet_forward_taps: a layer's output (and the normalised copy its producer wrote for the consumer, where it wrote one) copied to the caller right behind the
+    // launch that produced it, on the same stream -- before the arena can hand the memory to anything else.  Without tap arrays: a counter, nothing launched
+    size_t ti = 0;
+    auto tap = [&](const Tens& o) -> int {
+        const size_t i = ti++;
+        if (c.dry || (!c.taps && !c.nrm_taps)) return WDM_OK;
+        if (i >= taps.size() || o.C != taps[i].C || o.H != taps[i].H || o.W != taps[i].W || o.xs != o.C) WDM_FAIL(WDM_ESTATE, "internal: tap %zu does not match the tap list", i);
+        const size_t bytes = (size_t)c.B * o.H * o.W * o.C * dsize(c.dtype);
+        if (c.taps && c.taps[i]) WDM_HIP(hipMemcpyAsync(c.taps[i], o.p, bytes, hipMemcpyDeviceToDevice, c.s));
+        if (c.nrm_taps && c.nrm_taps[i] && o.nrm) WDM_HIP(hipMemcpyAsync(c.nrm_taps[i], o.nrm, bytes, hipMemcpyDeviceToDevice, c.s));
+        return WDM_OK;
+    };
     WDM_TRY(run_conv(c, cw(L.conv_in), MODE_S1, {.x0 = &x, .stats = true}, &h));
+    WDM_TRY(tap(h));
     if (xpad) c.ar->free(xpad);
     hs.push_back(h);
     for (int l = 0; l < nres; ++l) {
@@ -294,9 +343,11 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
                 else if (l == nres - 1) { nn = rw(mid1, temb_all, n_t).n1; nn_silu = 1; have_nn = true; }
             }
             WDM_TRY(run_resblock(c, rw(down_res[l][b], temb_all, n_t), hs.back(), nullptr, &o, have_nn ? &nn : nullptr, nn_silu));
+            WDM_TRY(tap(o));
             if (!down_attn[l].empty()) {
                 Tens o2;
                 WDM_TRY(run_attn(c, aw(down_attn[l][b]), o, &o2));
+                WDM_TRY(tap(o2));
                 free_tens(c, o);
                 o = o2;
             }
@@ -305,6 +356,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
         if (l != nres - 1) {
             Tens o;
             WDM_TRY(run_conv(c, cw(L.down_ds[l]), MODE_S2, {.x0 = &hs.back(), .stats = true}, &o));
+            WDM_TRY(tap(o));
             hs.push_back(o);
         }
     }
@@ -312,9 +364,12 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
     Tens m1, m2;
     const NormW mid_n = aw(mid_attn).n;
     WDM_TRY(run_resblock(c, rw(mid1, temb_all, n_t), hs.back(), nullptr, &m1, &mid_n, 0));
+    WDM_TRY(tap(m1));
     WDM_TRY(run_attn(c, aw(mid_attn), m1, &m2));
+    WDM_TRY(tap(m2));
     free_tens(c, m1);
     WDM_TRY(run_resblock(c, rw(mid2, temb_all, n_t), m2, nullptr, &h));
+    WDM_TRY(tap(h));
     free_tens(c, m2);
     // ---- up path: ResnetBlock on cat([h, skip]) without materialising the concat
     for (int l = nres - 1; l >= 0; --l) {
@@ -325,12 +380,14 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
             NormW nn;
             if (!up_attn[l].empty()) nn = aw(up_attn[l][b]).n;
             WDM_TRY(run_resblock(c, rw(up_res[l][b], temb_all, n_t), h, &skip, &o, up_attn[l].empty() ? nullptr : &nn, 0));
+            WDM_TRY(tap(o));
             free_tens(c, h);
             free_tens(c, skip);
             h = o;
             if (!up_attn[l].empty()) {
                 Tens o2;
                 WDM_TRY(run_attn(c, aw(up_attn[l][b]), h, &o2));
+                WDM_TRY(tap(o2));
                 free_tens(c, h);
                 h = o2;
             }
@@ -338,6 +395,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
         if (l != 0) {
             Tens o;
             WDM_TRY(run_conv(c, cw(L.up_us[l]), MODE_UPS, {.x0 = &h, .stats = true}, &o));
+            WDM_TRY(tap(o));
             free_tens(c, h);
             h = o;
         }
@@ -353,6 +411,7 @@ int wdm_unet::forward(Ctx& c, const void* x96, const float* t, int n_t, float* e
     free_tens(c, h);
     if (!temb_pre) c.ar->free(temb_all);
     if (!hs.empty()) WDM_FAIL(WDM_ESTATE, "internal: skip stack not empty (%zu)", hs.size());
+    if (ti != taps.size()) WDM_FAIL(WDM_ESTATE, "internal: %zu layer outputs, the tap list has %zu", ti, taps.size());
     return WDM_OK;
 }
 
@@ -486,6 +545,29 @@ int wdm_unet_forward(wdm_unet* u, const void* x96, const float* t, int n_t, int 
     if (((uintptr_t)workspace) & 255) WDM_FAIL(WDM_EINVAL, "wdm_unet_forward: workspace must be 256-byte aligned");
     Arena ar(workspace, workspace_bytes);
     Ctx c{(hipStream_t)stream, u->cfg.dtype, B, &ar, false};
+    return u->forward(c, x96, t, n_t, eps_out);
+}
+int wdm_unet_num_taps(const wdm_unet* u) { return u ? (int)u->taps.size() : 0; }
+int wdm_unet_tap_info(const wdm_unet* u, int i, const char** name, int* C, int* H, int* W, int* kind, int* in0, int* in1) {
+    if (!u || i < 0 || i >= (int)u->taps.size()) WDM_FAIL(WDM_EINVAL, "wdm_unet_tap_info: index %d out of range", i);
+    const TapD& t = u->taps[i];
+    if (name) *name = t.name.c_str();
+    if (C) *C = t.C;
+    if (H) *H = t.H;
+    if (W) *W = t.W;
+    if (kind) *kind = t.kind;
+    if (in0) *in0 = t.in0;
+    if (in1) *in1 = t.in1;
+    return WDM_OK;
+}
+int wdm_unet_forward_taps(wdm_unet* u, const void* x96, const float* t, int n_t, int B, float* eps_out, void* const* taps, void* const* nrm_taps, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    if (!u || !x96 || !t || !eps_out || !workspace) WDM_FAIL(WDM_EINVAL, "wdm_unet_forward_taps: null argument");
+    if (!u->all_loaded) WDM_FAIL(WDM_ESTATE, "wdm_unet_forward_taps: parameters not loaded");
+    if (B <= 0 || (n_t != 1 && n_t != B)) WDM_FAIL(WDM_EINVAL, "wdm_unet_forward_taps: n_t=%d must be 1 or B=%d", n_t, B);
+    if (((uintptr_t)workspace) & 255) WDM_FAIL(WDM_EINVAL, "wdm_unet_forward_taps: workspace must be 256-byte aligned");
+    Arena ar(workspace, workspace_bytes);
+    Ctx c{(hipStream_t)stream, u->cfg.dtype, B, &ar, false, taps, nrm_taps};
     return u->forward(c, x96, t, n_t, eps_out);
 }
 

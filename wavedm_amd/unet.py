@@ -284,6 +284,41 @@ class DiffusionUNet(nn.Module):
                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
         return eps_out
 
+    def tap_table(self):
+        """The layer outputs wdm_unet_forward_taps can copy out, in executor order (include/wavedm.h: wdm_unet_tap_info):
+        [{name, C, H, W, kind, in0, in1}], kind one of _lib.WDM_UNET_TAP_KINDS, in0 / in1 the NAMES of the taps the layer reads (None: the network's
+        input / no second input; in1 is an up block's skip, the second half of its concat)."""
+        L = _lib.lib()
+        name = C.c_char_p()
+        v = [C.c_int() for _ in range(6)]
+        rows = []
+        for i in range(L.wdm_unet_num_taps(self._u)):
+            _lib.check(L.wdm_unet_tap_info(self._u, i, C.byref(name), *[C.byref(x) for x in v]))
+            rows.append([name.value.decode()] + [int(x.value) for x in v])
+        at = lambda i: None if i < 0 else rows[i][0]
+        return [dict(name=r[0], C=r[1], H=r[2], W=r[3], kind=_lib.WDM_UNET_TAP_KINDS[r[4]], in0=at(r[5]), in1=at(r[6])) for r in rows]
+
+    def forward_nhwc_taps(self, x96, t, eps_out, ws_slot=0):
+        """forward_nhwc(x96, t, eps_out) -- the same launches, the same bits -- that also returns every layer's output as the device stored it:
+        ({name: (B, H, W, C) NHWC tensor in the compute dtype}, {name: the normalised copy the layer's last conv wrote for its consumer} for the
+        layers that wrote one).  A test entry (wdm_unet_forward_taps): every tap is one more device-to-device copy on the stream."""
+        B = x96.shape[0]
+        assert x96.is_contiguous() and x96.dtype == self._torch_dtype and tuple(x96.shape[1:]) == (self.resolution, self.resolution, self.in_channels)
+        assert eps_out.is_contiguous() and eps_out.dtype == torch.float32 and tuple(eps_out.shape) == (B, self.out_ch, self.resolution, self.resolution)
+        assert t.dtype == torch.float32 and t.is_cuda and t.numel() in (1, B)
+        self.pack_weights()
+        table = self.tap_table()
+        with torch.cuda.device(x96.device):
+            ws = self.workspace(B, x96.device, ws_slot)
+            taps = [torch.empty(B, r["H"], r["W"], r["C"], dtype=self._torch_dtype, device=x96.device) for r in table]
+            # a normalised copy is recognised by what it overwrites: NaN in every element (no GroupNorm output is NaN on finite input)
+            nrms = [torch.full_like(v, float("nan")) for v in taps]
+            arr = lambda ts: (C.c_void_p * len(ts))(*[v.data_ptr() for v in ts])
+            _lib.check(_lib.lib().wdm_unet_forward_taps(self._u, _lib.ptr(x96), _lib.ptr(t), int(t.numel()), B, _lib.ptr(eps_out), arr(taps), arr(nrms),
+                                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+            written = [not bool(torch.isnan(v.flatten()[0])) for v in nrms]
+        return ({r["name"]: v for r, v in zip(table, taps)}, {r["name"]: v for r, v, w in zip(table, nrms, written) if w})
+
     # ---- unet.py:309-344 ---------------------------------------------------------------------------
     @staticmethod
     def to_win(x, p):
