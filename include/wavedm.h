@@ -521,6 +521,36 @@ int wdm_trainer_optim_step(wdm_trainer* t, int64_t step, double lr, double beta1
 int wdm_optim_step(wdm_handle* h, int rule, float* params, const float* grads, float* state0, float* state1, float* state2, float* ema,
                    int64_t n, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay, double ema_mu,
                    void* stream);
+/* ---- guard of the training step: global gradient-norm clipping and non-finite skip (no counterpart in the reference's loop) ----
+ * wdm_grad_guard takes the 2-norm of a flat fp32 buffer of n >= 0 floats (any alignment) on the device and writes a record of four words:
+ *   norm           sqrt(sum g^2) -- every square and the whole sum in fp64 (a square of an fp32 is exact there), rounded to fp32 once.  One gradient of 1e30 gives
+ *                  1e30, where an fp32 sum of squares gives infinity.  Two launches whose shape follows n alone, fixed summation order, no atomics: the same
+ *                  buffer gives the same bits.
+ *   coef           torch.nn.utils.clip_grad_norm_'s factor in fp32, min(1, max_norm / (norm + 1e-6f)); exactly 1.0f when max_norm <= 0 (clipping off).  A
+ *                  non-finite norm gives what that arithmetic gives (NaN from NaN, 0 from infinity), as clip_grad_norm_(error_if_nonfinite=False) does.
+ *   skip           skip_nonfinite && some gradient is NaN or infinite (the fp64 sum cannot overflow, so it is non-finite exactly then)
+ *   skipped_total  += skip: the caller zeroes the record once, before its first step
+ * scratch: wdm_grad_guard_scratch_bytes bytes, 8-byte aligned, only live between the two launches.  The gradient buffer is read only.  WDM_EINVAL: a null
+ * pointer, n < 0, NaN max_norm, scratch too small.
+ * The _guarded steps are wdm_optim_step (all four rules, plain Adam too), wdm_trainer_optim_step and wdm_hfrm_trainer_adam behind such a record, which they read
+ * on the device -- nothing returns to the host and no launch argument depends on it.  skip != 0: the kernel returns before its first store; parameters, every
+ * state buffer and the EMA shadow keep their bits.  Otherwise g = grad * coef is formed first, as a product of its own (torch scales .grad in place before the
+ * optimizer sees it, so weight decay is added to the scaled gradient), and the rule's arithmetic follows unchanged: coef == 1 gives the bits of the unguarded
+ * entry.  `step` is the caller's count of CALLS and advances over a skipped step too (bias corrections, dropout counters, checkpoints and lr schedules count
+ * calls).  WDM_OPT_SGD: a step 1 that may be skipped needs a zeroed momentum buffer -- the skipped kernel leaves it untouched and step 2 forms beta1 * 0 + g, the
+ * buffer step 1 would have created. */
+typedef struct wdm_grad_record {
+    float norm, coef;
+    int32_t skip, skipped_total;
+} wdm_grad_record;
+size_t wdm_grad_guard_scratch_bytes(void);
+int wdm_grad_guard(wdm_handle* h, const float* grads, int64_t n, float max_norm, int skip_nonfinite, wdm_grad_record* record, void* scratch,
+                   size_t scratch_bytes, void* stream);
+int wdm_optim_step_guarded(wdm_handle* h, int rule, float* params, const float* grads, float* state0, float* state1, float* state2, float* ema,
+                           int64_t n, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay, double ema_mu,
+                           const wdm_grad_record* record, void* stream);
+int wdm_trainer_optim_step_guarded(wdm_trainer* t, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                   double ema_mu, const wdm_grad_record* record, void* stream);
 /* Gradient buckets for a data-parallel all-reduce that overlaps the backward (the reference wraps the model in DistributedDataParallel, ddm_wavelet.py:168,
  * which all-reduces 25 MB buckets while the backward runs).  The parameters sit in the flat buffers in forward order and the backward runs in reverse, so the
  * gradient buffer fills from its end: with n events set (hipEvent_t handles owned by the caller; n = 0 switches the feature off) every following
@@ -579,6 +609,9 @@ int wdm_hfrm_trainer_stage(wdm_hfrm_trainer* t, int kind, int index, const void*
                            void* workspace, size_t workspace_bytes, void* stream);
 /* the betas are doubles: torch forms 1 - beta and the bias corrections from the Python floats (an fp32 0.999 puts 1 - beta2 1.3e-5 off) */
 int wdm_hfrm_trainer_adam(wdm_hfrm_trainer* t, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay, void* stream);
+/* ... behind the record of wdm_grad_guard over the trainer's gradient buffer (see there) */
+int wdm_hfrm_trainer_adam_guarded(wdm_hfrm_trainer* t, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay,
+                                  const wdm_grad_record* record, void* stream);
 
 /* ---- live kernel timing (bench.py roofline leg) ----------------------------------------------
  * While enabled, every convolution launch is bracketed by two HIP events on its own stream and

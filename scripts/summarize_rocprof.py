@@ -90,6 +90,9 @@ def _short(name: str) -> str:
     m = re.match(r"_ZN3wdm\d+(gn_apply_kernel|gn_bwd_sums_kernel|gn_bwd_apply_kernel)I(?:DF16b|DF16_|f)Lb1E", name)
     if m:                                            # training with model.dropout: the instantiations that draw the mask (csrc/dropout.h)
         return m.group(1) + "<dropout>"
+    m = re.match(r"_ZN3wdm\d+optim_ema_guarded_kernelILi(\d)E", name)
+    if m:                                            # ... behind the record of the gradient guard (grad_sumsq_kernel + grad_guard_final_kernel), all four rules
+        return "optim_ema_guarded_kernel<" + {"0": "adam", "1": "amsgrad", "2": "rmsprop", "3": "sgd"}.get(m.group(1), m.group(1)) + ">"
     m = re.match(r"_ZN3wdm\d+optim_ema_kernelILi(\d)E", name)
     if m:                                            # the optimizer pass, <RULE> = WDM_OPT_* of include/wavedm.h (plain Adam is adam_ema_kernel)
         return "optim_ema_kernel<" + {"1": "amsgrad", "2": "rmsprop", "3": "sgd"}.get(m.group(1), m.group(1)) + ">"

@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.0, help="model.dropout of the step (masks drawn in the GroupNorm kernels, csrc/dropout.h); 0: the plain step")
     ap.add_argument("--optimizer", default="Adam", choices=["Adam", "AMSGrad", "RMSProp", "SGD"],
                     help="optim.optimizer of the step (AMSGrad: Adam with optim.amsgrad: True); utils/optimize.py:5-14")
+    ap.add_argument("--grad_clip", type=float, default=0.0, help="optim.grad_clip of the step: > 0 adds the gradient-norm reduction and the guarded optimizer kernel; 0: the plain step")
+    ap.add_argument("--skip_nonfinite", action="store_true", help="optim.skip_nonfinite of the step (the same two launches as --grad_clip)")
     ap.add_argument("--prof", action="store_true", help="one more step under the library's per-launch event profiler: per (kernel | shape) rows on stderr")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -31,7 +33,7 @@ def main():
     cfg.device = dev
     cfg.optim.optimizer, cfg.optim.amsgrad = ("Adam", True) if a.optimizer == "AMSGrad" else (a.optimizer, False)
     sd = P.procedural_state_dict(cfg, seed=61)
-    tr = Trainer(cfg, dtype=a.dtype, dropout=a.dropout, dropout_seed=3)
+    tr = Trainer(cfg, dtype=a.dtype, dropout=a.dropout, dropout_seed=3, grad_clip=a.grad_clip, skip_nonfinite=a.skip_nonfinite)
     tr.load_state_dict(sd)
     g = torch.Generator().manual_seed(1)
     x0 = torch.randn(a.batch, 96, 64, 64, generator=g).to(dev)
@@ -46,10 +48,12 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.iters
     out = {"what": f"training step (loss + backward + {a.optimizer} + EMA), raindrop_wavelet UNet 156.5 M params", "batch": a.batch, "dtype": a.dtype, "dropout": a.dropout,
-           "optimizer": a.optimizer,
+           "optimizer": a.optimizer, "grad_clip": a.grad_clip, "skip_nonfinite": a.skip_nonfinite,
            "ms_per_step": dt * 1e3, "samples_per_s": a.batch / dt, "loss_first": losses[0], "loss_last": float(loss),
            # forward 80 GFLOP per sample, backward ~2x
            "approx_tflops": a.batch * 79.94e9 * 3 / dt / 1e12}
+    if tr.grad_norm is not None:
+        out.update(grad_norm=float(tr.grad_norm), clip_coef=float(tr.clip_coef), skipped_steps=tr.skipped_steps)
     if a.prof:
         from wavedm_amd import _lib
         _lib.prof_enable(True)

@@ -47,6 +47,8 @@ def parse_args(argv=None):
     p.add_argument("--dtype", type=str, default="f32", choices=("f32", "bf16-mixed"),
                    help="f32: exact fp32; bf16-mixed: bf16 activations and GEMMs over fp32 parameters, gradients and Adam state")
     p.add_argument("--sample_interval", type=int, default=0, help="write a sample sheet every this many batches of an epoch (0: none; the reference uses 1000)")
+    p.add_argument("--grad_clip", type=float, default=0.0, help="clip the global gradient norm to this value before Adam (0: off; not in the reference)")
+    p.add_argument("--skip_nonfinite", action="store_true", help="drop a step whose gradient holds a NaN or an infinity: parameters and moments keep their bits")
     p.add_argument("--sample_dir", type=str, default="train_result", help="directory of the sample sheets")
     return p.parse_args(argv)
 
@@ -56,7 +58,7 @@ def main(argv=None):
     print(opt)
     out_dir = os.path.join(opt.save_dir, opt.dataset_name)
     os.makedirs(out_dir, exist_ok=True)
-    trainer = HFRMTrainer(**HFRM_DEFAULTS, lr=opt.lr, betas=(opt.b1, opt.b2), dtype=opt.dtype)
+    trainer = HFRMTrainer(**HFRM_DEFAULTS, lr=opt.lr, betas=(opt.b1, opt.b2), dtype=opt.dtype, grad_clip=opt.grad_clip, skip_nonfinite=opt.skip_nonfinite)
     writer = AsyncImageWriter(workers=1) if opt.sample_interval > 0 else None
     print("HFRM parameters:", sum(int(np.prod(s)) for _, s in trainer.layout.values()))
     if opt.epoch != 0:
@@ -85,6 +87,8 @@ def main(argv=None):
             if i % 100 == 0:
                 lv = loss.item()
                 print("G loss: %f", lv)
+                if trainer.grad_norm is not None:
+                    print("grad norm: %f, clip coef: %f, skipped steps: %d" % (float(trainer.grad_norm), float(trainer.clip_coef), trainer.skipped_steps))
                 sys.stdout.write("\r[Epoch %d/%d] [Batch %d/%d] [G loss: %f, pixel: %f] ETA: %s" %
                                  (epoch, opt.n_epochs, i, len(loader), lv, lv / 510.0, time_left))
             if opt.max_steps and trainer.step >= opt.max_steps:

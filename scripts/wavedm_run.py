@@ -13,6 +13,7 @@ OWN SIZE, without ground truth and without the evaluation protocol's 720x480 res
 --config is a file name under ./configs or a path.  Under torchrun every rank restores its share of the validation images (the
 loaders use a DistributedSampler) and rank 0 prints the PSNR over all of them; training all-reduces gradients over RCCL.
 Extras: --solver {ddim,dpmpp2m} and --x0_index K (eval, restore: the sampler's integrator and which x0 prediction becomes the image), --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train),
+--grad_clip X and --skip_nonfinite (train: clip the global gradient norm to X / drop a step whose gradient is not finite; they override optim.grad_clip and optim.skip_nonfinite of the config),
 --hfrm-local [--hfrm-base-size H W] [--hfrm-train-size H W] (eval, restore: the HFRM's channel attention pools over a window instead of the whole image)."""
 import argparse
 import os
@@ -68,6 +69,10 @@ def parse(argv=None):
     ap.add_argument("--hfrm-train-size", dest="hfrm_train_size", type=int, nargs=2, metavar=("H", "W"), default=None,
                     help="with --hfrm-local: the size of the HFRM's training images (default 480 720)")
     ap.add_argument("--max_steps", type=int, default=None)
+    ap.add_argument("--grad_clip", type=float, default=None, metavar="X",
+                    help="train: clip the global 2-norm of the gradient to X before the optimizer step (overrides optim.grad_clip; 0: off)")
+    ap.add_argument("--skip_nonfinite", action="store_true",
+                    help="train: drop a step whose gradient holds a NaN or an infinity -- parameters, optimizer state and EMA keep their bits (overrides optim.skip_nonfinite)")
     ap.add_argument("--no_save", action="store_true", help="eval: metrics only, no PNGs")
     ap.add_argument("--ssim", action="store_true", help="eval: also SSIM (Y channel) of every output against its gt, on the device; prints an `ssim all` line")
     ap.add_argument("--samples", type=int, default=1,
@@ -110,8 +115,21 @@ def parse(argv=None):
         a.hfrm_local = (base, (1, 3) + tuple(train))
     if a.mode == "restore" and not (a.input and (a.output or a.no_save)):
         ap.error("restore needs --input DIR and --output DIR (or --no_save)")
+    if a.mode != "train" and (a.grad_clip is not None or a.skip_nonfinite):
+        ap.error("--grad_clip and --skip_nonfinite are training options")
     path = a.config if os.path.isfile(a.config) else os.path.join("configs", a.config)
-    return a, load_config(path)
+    config = load_config(path)
+    if a.grad_clip is not None or a.skip_nonfinite:        # the flags override the config; the Trainer reads optim.grad_clip / optim.skip_nonfinite
+        from types import SimpleNamespace
+        from wavedm_amd.training import grad_guard_settings
+        try:
+            clip, skip = grad_guard_settings(config, a.grad_clip, True if a.skip_nonfinite else None)
+        except ValueError as e:
+            ap.error(str(e))
+        if getattr(config, "optim", None) is None:
+            config.optim = SimpleNamespace()
+        config.optim.grad_clip, config.optim.skip_nonfinite = clip, skip
+    return a, config
 
 
 def main(argv=None):
@@ -151,6 +169,10 @@ def main(argv=None):
         diffusion.train(DATASET, max_steps=args.max_steps)
         if args.rank == 0 and getattr(diffusion, "last_loss", None) is not None:
             print(f"=> trained to step {diffusion.step}: last loss {float(diffusion.last_loss)}, every loss finite: {bool(diffusion.losses_finite)}")
+            tr = diffusion.trainer
+            if tr.grad_norm is not None:
+                print(f"=> last step: grad norm: {float(tr.grad_norm)}, clip coef: {float(tr.clip_coef)}, skipped steps: {tr.skipped_steps} (grad_clip {tr.grad_clip}, "
+                      f"skip_nonfinite {tr.skip_nonfinite})")
         if args.world_size > 1:
             dist.destroy_process_group()
         return 0

@@ -154,6 +154,10 @@ def lib():
         "wdm_trainer_set_optimizer": (i, [vp, i, vp, vp, vp]),
         "wdm_trainer_optim_step": (i, [vp, i64] + [C.c_double] * 6 + [vp]),
         "wdm_optim_step": (i, [vp, i, vp, vp, vp, vp, vp, vp, i64, i64] + [C.c_double] * 6 + [vp]),
+        "wdm_grad_guard_scratch_bytes": (sz, []),
+        "wdm_grad_guard": (i, [vp, vp, i64, f, i, vp, vp, sz, vp]),
+        "wdm_optim_step_guarded": (i, [vp, i, vp, vp, vp, vp, vp, vp, i64, i64] + [C.c_double] * 6 + [vp, vp]),
+        "wdm_trainer_optim_step_guarded": (i, [vp, i64] + [C.c_double] * 6 + [vp, vp]),
         "wdm_trainer_set_grad_events": (i, [vp, C.POINTER(vp), i]),
         "wdm_trainer_grad_buckets": (i, [vp, C.POINTER(i64), i, C.POINTER(i)]),
         "wdm_hfrm_trainer_create": (i, [vp, C.POINTER(HFRMConfig), C.POINTER(vp)]),
@@ -168,6 +172,7 @@ def lib():
         "wdm_hfrm_trainer_stage_workspace_bytes": (sz, [vp, i, i, i, i, i]),
         "wdm_hfrm_trainer_stage": (i, [vp, i, i, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]),
         "wdm_hfrm_trainer_adam": (i, [vp, i64, f, C.c_double, C.c_double, f, f, vp]),
+        "wdm_hfrm_trainer_adam_guarded": (i, [vp, i64, f, C.c_double, C.c_double, f, f, vp, vp]),
         "wdm_dwt_fwd_affine": (i, [vp, vp, f, f, vp, i, i, i, vp]),
         "wdm_dwt_inv_compose": (i, [vp, vp, i, i, vp, vp, i, i, i, i, vp]),
         "wdm_ensemble_compose": (i, [vp, vp, i, i, i, vp, vp, vp, vp, i, i, i, i, vp]),
@@ -199,8 +204,9 @@ EXPORTED = ["wdm_abi_version", "wdm_last_error", "wdm_create", "wdm_destroy", "w
             "wdm_hfrm_create", "wdm_hfrm_destroy", "wdm_hfrm_num_params", "wdm_hfrm_param_info", "wdm_hfrm_packed_bytes",
             "wdm_hfrm_set_packed", "wdm_hfrm_load_param", "wdm_hfrm_finalize", "wdm_hfrm_workspace_bytes",
             "wdm_hfrm_forward", "wdm_hfrm_set_local", "wdm_hfrm_local_kernel", "wdm_hfrm_local_pool", "wdm_hfrm_set_max_launch_bytes", "wdm_hfrm_chunk_rows", "wdm_hfrm_conv_out", "wdm_hfrm_stage_workspace_bytes", "wdm_hfrm_stage_forward", "wdm_image_sqdiff", "wdm_to_u8_hwc", "wdm_image_ingest", "wdm_to_u8_hwc_crop", "wdm_image_ssim_scratch_bytes", "wdm_image_ssim", "wdm_conv_backward", "wdm_gn_act_backward", "wdm_dropout_mask", "wdm_gn_act_dropout", "wdm_trainer_create", "wdm_trainer_destroy", "wdm_trainer_num_params",
-            "wdm_trainer_num_floats", "wdm_trainer_param_info", "wdm_trainer_set_buffers", "wdm_trainer_set_objective", "wdm_trainer_set_dropout", "wdm_trainer_step", "wdm_trainer_stage_workspace_bytes", "wdm_trainer_stage", "wdm_trainer_adam_ema", "wdm_trainer_set_optimizer", "wdm_trainer_optim_step", "wdm_optim_step", "wdm_trainer_set_grad_events", "wdm_trainer_grad_buckets", "wdm_hfrm_trainer_create", "wdm_hfrm_trainer_destroy", "wdm_hfrm_trainer_num_params", "wdm_hfrm_trainer_num_floats",
-            "wdm_hfrm_trainer_param_info", "wdm_hfrm_trainer_set_buffers", "wdm_hfrm_trainer_set_precision", "wdm_hfrm_trainer_workspace_bytes", "wdm_hfrm_trainer_step", "wdm_hfrm_trainer_stage_workspace_bytes", "wdm_hfrm_trainer_stage", "wdm_hfrm_trainer_adam", "wdm_dwt_fwd_affine", "wdm_dwt_inv_compose", "wdm_ensemble_compose", "wdm_conv2d_direct", "wdm_groupnorm", "wdm_cross_attention", "wdm_upsample_add",
+            "wdm_trainer_num_floats", "wdm_trainer_param_info", "wdm_trainer_set_buffers", "wdm_trainer_set_objective", "wdm_trainer_set_dropout", "wdm_trainer_step", "wdm_trainer_stage_workspace_bytes", "wdm_trainer_stage", "wdm_trainer_adam_ema", "wdm_trainer_set_optimizer", "wdm_trainer_optim_step", "wdm_optim_step", "wdm_grad_guard_scratch_bytes", "wdm_grad_guard", "wdm_optim_step_guarded", "wdm_trainer_optim_step_guarded",
+            "wdm_trainer_set_grad_events", "wdm_trainer_grad_buckets", "wdm_hfrm_trainer_create", "wdm_hfrm_trainer_destroy", "wdm_hfrm_trainer_num_params", "wdm_hfrm_trainer_num_floats",
+            "wdm_hfrm_trainer_param_info", "wdm_hfrm_trainer_set_buffers", "wdm_hfrm_trainer_set_precision", "wdm_hfrm_trainer_workspace_bytes", "wdm_hfrm_trainer_step", "wdm_hfrm_trainer_stage_workspace_bytes", "wdm_hfrm_trainer_stage", "wdm_hfrm_trainer_adam", "wdm_hfrm_trainer_adam_guarded", "wdm_dwt_fwd_affine", "wdm_dwt_inv_compose", "wdm_ensemble_compose", "wdm_conv2d_direct", "wdm_groupnorm", "wdm_cross_attention", "wdm_upsample_add",
             "wdm_prof_enable", "wdm_prof_report", "wdm_env_refresh", "wdm_set_concurrent_streams"]
 
 

@@ -331,6 +331,13 @@ int k_adam_ema(float* P, const float* G, float* M, float* V, float* E, long long
 // beta1: Adam's beta1 / SGD's momentum; beta2: Adam's beta2 / RMSProp's alpha.  WDM_OPT_ADAM launches k_adam_ema.
 int k_optim_ema(int rule, float* P, const float* G, float* S0, float* S1, float* S2, float* E, long long n, int64_t step, double lr, double beta1, double beta2,
                 double eps, double weight_decay, double ema_mu, hipStream_t s);
+// The guard of a step (train_unet.hip; include/wavedm.h: wdm_grad_guard): the fp64 global norm of G in two launches of a shape that follows n alone, and the record
+// {norm, coef, skip, skipped_total}; partial: room for guard_partial_count() doubles.  k_optim_ema_guarded: k_optim_ema (all four rules) behind that record --
+// returns before its first store when rec->skip is set, scales the gradient by rec->coef first otherwise; coef == 1 gives k_optim_ema's bits.
+int guard_partial_count();
+int k_grad_guard(const float* G, long long n, float max_norm, int skip_nonfinite, wdm_grad_record* rec, double* partial, hipStream_t s);
+int k_optim_ema_guarded(int rule, float* P, const float* G, float* S0, float* S1, float* S2, float* E, long long n, int64_t step, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, double ema_mu, const wdm_grad_record* rec, hipStream_t s);
 
 }  // namespace wdm
 

@@ -1294,5 +1294,14 @@ int wdm_hfrm_trainer_adam(wdm_hfrm_trainer* t, int64_t step, float lr, double be
     if (step < 1) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_adam: step counts from 1");
     return k_adam_ema(t->P, t->G, t->Mo, t->V, nullptr, (long long)t->nfloats, step, lr, beta1, beta2, eps, weight_decay, 0.f, (hipStream_t)stream);
 }
+// ... behind the record of wdm_grad_guard over the gradient buffer (train_unet.hip: k_optim_ema_guarded; the float arguments widen exactly)
+int wdm_hfrm_trainer_adam_guarded(wdm_hfrm_trainer* t, int64_t step, float lr, double beta1, double beta2, float eps, float weight_decay, const wdm_grad_record* record,
+                                  void* stream) {
+    if (!t || !t->P || !t->G || !t->Mo || !t->V) WDM_FAIL(WDM_ESTATE, "wdm_hfrm_trainer_adam_guarded: buffers not set");
+    if (!record) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_adam_guarded: null record");
+    if (step < 1) WDM_FAIL(WDM_EINVAL, "wdm_hfrm_trainer_adam_guarded: step counts from 1");
+    return k_optim_ema_guarded(WDM_OPT_ADAM, t->P, t->G, t->Mo, t->V, nullptr, nullptr, (long long)t->nfloats, step, lr, beta1, beta2, eps, weight_decay, 0.0, record,
+                               (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -298,6 +298,192 @@ int k_optim_ema(int rule, float* P, const float* G, float* S0, float* S1, float*
     return WDM_OK;
 }
 
+// ---- the guard of a training step: global gradient norm, clipping coefficient, non-finite skip (include/wavedm.h: wdm_grad_guard) ---------------------------------
+// Pass 1: GUARD_WGS workgroups x 256 lanes over the flat buffer, 16-byte loads behind a scalar head (four of them in flight per lane: a read-only stream has no stores
+// to keep the memory system busy), scalar ends.  Every lane sums (double)g * (double)g -- exact, an fp32 square has 48 significant bits -- in the order of its own
+// indices; the wave's 64 sums meet in a butterfly (every lane ends with the same bits), the workgroup's four in wave order through LDS.  One fp64 partial per
+// workgroup, no atomics: the launch shape follows n alone, so the result is a function of the buffer (its values, its length, its alignment).
+// 512 workgroups: the fastest of 128 ... 2 048 over 156 M floats (profiles/grad_guard.md), as for k_optim_ema.
+#ifndef WDM_GUARD_WGS
+#define WDM_GUARD_WGS 512
+#endif
+constexpr int GUARD_WGS = WDM_GUARD_WGS;
+int guard_partial_count() { return GUARD_WGS; }
+inline int guard_wgs(long long n) { const long long g = (n + 1023) / 1024; return (int)(g > GUARD_WGS ? GUARD_WGS : g < 1 ? 1 : g); }
+
+__device__ __forceinline__ void sq_acc(double& acc, const float4& g) {
+    acc += (double)g.x * (double)g.x; acc += (double)g.y * (double)g.y; acc += (double)g.z * (double)g.z; acc += (double)g.w * (double)g.w;
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ G, long long n, long long head, long long nvec, double* __restrict__ partial) {
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+    const float4* __restrict__ G4 = reinterpret_cast<const float4*>(G + head);        // 16-byte aligned (the launcher chose head so)
+    double acc = 0.0;
+    long long v = tid;
+    for (; v + 3 * nth < nvec; v += 4 * nth) {
+        const float4 a = G4[v], b = G4[v + nth], c = G4[v + 2 * nth], d = G4[v + 3 * nth];
+        sq_acc(acc, a); sq_acc(acc, b); sq_acc(acc, c); sq_acc(acc, d);
+    }
+    for (; v < nvec; v += nth) sq_acc(acc, G4[v]);
+    const long long tail0 = head + 4 * nvec, nsc = head + (n - tail0);
+    for (long long k = tid; k < nsc; k += nth) { const float g = G[k < head ? k : tail0 + (k - head)]; acc += (double)g * (double)g; }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+    __shared__ double wsum[4];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+// Pass 2: one workgroup adds the partials in index order, rounds sqrt(sum) to fp32 once and writes the record from one lane.  coef is torch's clip_grad_norm_
+// coefficient in fp32 (a NaN norm gives NaN, an infinite one 0: the comparison keeps what torch.clamp(max = 1) keeps); the fp64 sum of squares of fp32 values cannot
+// overflow (2^28 terms below 2^256), so it is non-finite exactly when some gradient is.
+__global__ __launch_bounds__(256) void grad_guard_final_kernel(const double* __restrict__ partial, int nparts, float max_norm, int skip_nonfinite,
+                                                               wdm_grad_record* __restrict__ rec) {
+    __shared__ double part[GUARD_WGS];
+    for (int k = threadIdx.x; k < nparts; k += 256) part[k] = partial[k];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sum = 0.0;
+    for (int k = 0; k < nparts; ++k) sum += part[k];
+    const float norm = (float)sqrt(sum);
+    float coef = 1.0f;
+    if (max_norm > 0.f) { const float c = max_norm / (norm + 1e-6f); coef = c > 1.0f ? 1.0f : c; }
+    const int skip = (skip_nonfinite && !isfinite(sum)) ? 1 : 0;
+    rec->norm = norm; rec->coef = coef; rec->skip = skip; rec->skipped_total += skip;
+}
+int k_grad_guard(const float* G, long long n, float max_norm, int skip_nonfinite, wdm_grad_record* rec, double* partial, hipStream_t s) {
+    const uintptr_t mis = (uintptr_t)G & 15;
+    long long head = (mis & 3) == 0 ? (long long)(((16 - mis) & 15) / 4) : n;       // not even 4-byte aligned to a 16-byte boundary: scalar throughout
+    if (head > n) head = n;
+    const long long nvec = (n - head) / 4;
+    const int wgs = guard_wgs(n);
+    const bool prof = prof_enabled();                                               // (wdm_prof_report: the launches of a guarded step show under their names)
+    if (prof) prof_begin(s, "grad_sumsq_kernel", 2.0 * n, 4.0 * n);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(wgs), dim3(256), 0, s, G, n, head, nvec, partial);
+    if (prof) { prof_end(s); prof_begin(s, "grad_guard_final_kernel", (double)wgs, 8.0 * wgs + 16.0); }
+    hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(256), 0, s, partial, wgs, max_norm, skip_nonfinite, rec);
+    if (prof) prof_end(s);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
+// ---- the guarded optimizer step: every rule, plain Adam included, behind the record of k_grad_guard ---------------------------------------------------------------
+// The record is read through its device pointer (one uniform load per lane, no launch argument depends on it: the step stays capturable).  skip != 0: return before
+// the first store.  Otherwise g = G[id] * coef is a product of its own (mul_own: never contracted into the weight-decay sum, as torch scales .grad in place before
+// the optimizer sees it), then the arithmetic of opt_update<RULE> / adam_ema_kernel, line for line.
+// One rounding each, never contracted with a neighbour: hip's __fmul_rn / __fadd_rn are plain operators, which the compiler is free to fuse into an fma.
+__device__ __forceinline__ float mul_own(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_own(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+struct GuardArgs { OptArgs a; const wdm_grad_record* rec; float bc1; };             // (a.bc2_sqrt, bc1: Adam's, formed as k_adam_ema forms them)
+template <int RULE> struct GuardSlots { static constexpr int n = RULE == WDM_OPT_AMSGRAD ? 3 : RULE == WDM_OPT_ADAM ? 2 : 1; };
+template <int RULE>
+__device__ __forceinline__ float guarded_update(const GuardArgs& q, float coef, float p, float g, float& s0, float& s1, float& s2) {
+    g = mul_own(g, coef);
+    if (RULE != WDM_OPT_ADAM) return opt_update<RULE>(q.a, p, g, s0, s1, s2);
+    // adam_ema_kernel's arithmetic with the roundings it compiles to spelled out (the vector loop here must not come to contract differently from that scalar kernel)
+    const OptArgs& a = q.a;
+    if (a.wd != 0.f) g = __fmaf_rn(a.wd, p, g);
+    const float m = __fmaf_rn(a.b1, s0, mul_own(a.omb1, g));
+    const float v = __fmaf_rn(a.b2, s1, mul_own(g, mul_own(a.omb2, g)));
+    s0 = m; s1 = v;
+    const float denom = add_own(sqrtf(v) / a.bc2_sqrt, a.eps);
+    return __fmaf_rn(-(a.lr / q.bc1), m / denom, p);
+}
+// The EMA update as the unguarded kernels round it: optim_ema_kernel's vector loop fuses the sum, its scalar ends and adam_ema_kernel do not.
+template <int RULE, bool VEC> __device__ __forceinline__ float guarded_ema(const OptArgs& a, float pn, float e) {
+    if (VEC && RULE != WDM_OPT_ADAM) return __fmaf_rn(1.0f - a.mu, pn, mul_own(a.mu, e));
+    return add_own(mul_own(1.0f - a.mu, pn), mul_own(a.mu, e));
+}
+template <int RULE> __device__ __forceinline__ void guarded_scalar(const GuardArgs& q, float coef, long long id) {
+    const OptArgs& a = q.a;
+    float s0 = (RULE == WDM_OPT_SGD && a.first) ? 0.f : a.S0[id], s1 = 0.f, s2 = 0.f;
+    if (GuardSlots<RULE>::n >= 2) s1 = a.S1[id];
+    if (GuardSlots<RULE>::n == 3) s2 = a.S2[id];
+    const float pn = guarded_update<RULE>(q, coef, a.P[id], a.G[id], s0, s1, s2);
+    a.S0[id] = s0;
+    if (GuardSlots<RULE>::n >= 2) a.S1[id] = s1;
+    if (GuardSlots<RULE>::n == 3) a.S2[id] = s2;
+    a.P[id] = pn;
+    if (a.E) a.E[id] = guarded_ema<RULE, false>(a, pn, a.E[id]);
+}
+template <int RULE> __global__ __launch_bounds__(256) void optim_ema_guarded_kernel(const GuardArgs q) {
+    if (q.rec->skip != 0) return;                                                    // parameters, every state buffer and the EMA keep their bits
+    const float coef = q.rec->coef;
+    const OptArgs& a = q.a;
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+    for (long long v = tid; v < a.nvec; v += nth) {
+        const long long id = a.head + 4 * v;
+        OptF4 p, g, s0, s1, s2, e;
+        p.v = *reinterpret_cast<const float4*>(a.P + id);
+        g.v = *reinterpret_cast<const float4*>(a.G + id);
+        if (RULE == WDM_OPT_SGD && a.first) s0.v = make_float4(0.f, 0.f, 0.f, 0.f);
+        else s0.v = *reinterpret_cast<const float4*>(a.S0 + id);
+        s1.v = GuardSlots<RULE>::n >= 2 ? *reinterpret_cast<const float4*>(a.S1 + id) : make_float4(0.f, 0.f, 0.f, 0.f);
+        s2.v = GuardSlots<RULE>::n == 3 ? *reinterpret_cast<const float4*>(a.S2 + id) : make_float4(0.f, 0.f, 0.f, 0.f);
+        e.v = a.E ? *reinterpret_cast<const float4*>(a.E + id) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            p.f[k] = guarded_update<RULE>(q, coef, p.f[k], g.f[k], s0.f[k], s1.f[k], s2.f[k]);
+            if (a.E) e.f[k] = guarded_ema<RULE, true>(a, p.f[k], e.f[k]);
+        }
+        *reinterpret_cast<float4*>(a.S0 + id) = s0.v;
+        if (GuardSlots<RULE>::n >= 2) *reinterpret_cast<float4*>(a.S1 + id) = s1.v;
+        if (GuardSlots<RULE>::n == 3) *reinterpret_cast<float4*>(a.S2 + id) = s2.v;
+        *reinterpret_cast<float4*>(a.P + id) = p.v;
+        if (a.E) *reinterpret_cast<float4*>(a.E + id) = e.v;
+    }
+    const long long tail0 = a.head + 4 * a.nvec, nsc = a.head + (a.n - tail0);
+    for (long long k = tid; k < nsc; k += nth) guarded_scalar<RULE>(q, coef, k < a.head ? k : tail0 + (k - a.head));
+}
+
+// k_optim_ema behind a record (common.h).  The scalars of each rule are formed exactly as its unguarded launcher forms them -- Adam's as k_adam_ema does, in fp32
+// from the fp32 lr and bias corrections -- so that coef == 1 gives the unguarded kernel's bits.
+int k_optim_ema_guarded(int rule, float* P, const float* G, float* S0, float* S1, float* S2, float* E, long long n, int64_t step, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, double ema_mu, const wdm_grad_record* rec, hipStream_t s) {
+    if (rule < WDM_OPT_ADAM || rule > WDM_OPT_SGD) WDM_FAIL(WDM_EINVAL, "k_optim_ema_guarded: unknown rule %d", rule);
+    if (n <= 0) return WDM_OK;
+    GuardArgs q{};
+    OptArgs& a = q.a;
+    q.rec = rec;
+    a.P = P; a.G = G; a.S0 = S0; a.S1 = S1; a.S2 = S2; a.E = E; a.n = n;
+    a.lr = (float)lr; a.b1 = (float)beta1; a.b2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
+    a.eps = (float)eps; a.wd = (float)weight_decay; a.mu = (float)ema_mu; a.first = step == 1;
+    if (rule == WDM_OPT_ADAM) {
+        q.bc1 = 1.0f - (float)std::pow(beta1, (double)step);
+        a.bc2_sqrt = std::sqrt(1.0f - (float)std::pow(beta2, (double)step));
+    } else {
+        a.step_size = (float)(lr / (1.0 - std::pow(beta1, (double)step)));
+        a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)step));
+    }
+    const int slots = rule == WDM_OPT_AMSGRAD ? 3 : rule == WDM_OPT_ADAM ? 2 : 1;
+    const float* bufs[6] = {P, G, S0, slots >= 2 ? S1 : nullptr, slots == 3 ? S2 : nullptr, E};
+    const uintptr_t mis = (uintptr_t)P & 15;
+    bool same = (mis & 3) == 0;
+    for (const float* b : bufs) same = same && (!b || ((uintptr_t)b & 15) == mis);
+    a.head = same ? (long long)(((16 - mis) & 15) / 4) : n;
+    if (a.head > n) a.head = n;
+    a.nvec = (n - a.head) / 4;
+    const long long nsc = n - 4 * a.nvec, work = a.nvec > nsc ? a.nvec : nsc;
+    const long long want = (work + 255) / 256;
+    const dim3 grid((unsigned)(want > 512 ? 512 : want)), blk(256);                 // k_optim_ema's shape: 512 workgroups, grid-stride beyond
+    const bool prof = prof_enabled();
+    static const char* const names[4] = {"optim_ema_guarded_kernel<adam>", "optim_ema_guarded_kernel<amsgrad>", "optim_ema_guarded_kernel<rmsprop>",
+                                         "optim_ema_guarded_kernel<sgd>"};
+    if (prof) prof_begin(s, names[rule], 0.0, 4.0 * n * (3.0 + 2.0 * slots + (E ? 2.0 : 0.0)));      // P, slots, E read and written, G read
+    if (rule == WDM_OPT_ADAM) hipLaunchKernelGGL(optim_ema_guarded_kernel<WDM_OPT_ADAM>, grid, blk, 0, s, q);
+    else if (rule == WDM_OPT_AMSGRAD) hipLaunchKernelGGL(optim_ema_guarded_kernel<WDM_OPT_AMSGRAD>, grid, blk, 0, s, q);
+    else if (rule == WDM_OPT_RMSPROP) hipLaunchKernelGGL(optim_ema_guarded_kernel<WDM_OPT_RMSPROP>, grid, blk, 0, s, q);
+    else hipLaunchKernelGGL(optim_ema_guarded_kernel<WDM_OPT_SGD>, grid, blk, 0, s, q);
+    if (prof) prof_end(s);
+    WDM_HIP(hipGetLastError());
+    return WDM_OK;
+}
+
 }  // namespace wdm
 
 // =====================================================================================================================
@@ -1037,6 +1223,38 @@ int wdm_optim_step(wdm_handle* h, int rule, float* params, const float* grads, f
     const int need = rule == WDM_OPT_AMSGRAD ? 3 : rule == WDM_OPT_ADAM ? 2 : 1;
     if (!state0 || (need >= 2 && !state1) || (need == 3 && !state2)) WDM_FAIL(WDM_EINVAL, "wdm_optim_step: rule %d needs %d state buffers", rule, need);
     return k_optim_ema(rule, params, grads, state0, state1, state2, ema, (long long)n, step, lr, beta1, beta2, eps, weight_decay, ema_mu, (hipStream_t)stream);
+}
+// The guard of a training step and the guarded forms of the three entries above (include/wavedm.h)
+size_t wdm_grad_guard_scratch_bytes(void) { return (size_t)guard_partial_count() * sizeof(double); }
+int wdm_grad_guard(wdm_handle* h, const float* grads, int64_t n, float max_norm, int skip_nonfinite, wdm_grad_record* record, void* scratch, size_t scratch_bytes,
+                   void* stream) {
+    if (!h || !grads || !record || !scratch) WDM_FAIL(WDM_EINVAL, "wdm_grad_guard: null argument");
+    if (n < 0) WDM_FAIL(WDM_EINVAL, "wdm_grad_guard: n = %lld", (long long)n);
+    if (max_norm != max_norm) WDM_FAIL(WDM_EINVAL, "wdm_grad_guard: max_norm is NaN");
+    if (scratch_bytes < wdm_grad_guard_scratch_bytes() || ((uintptr_t)scratch & 7))
+        WDM_FAIL(WDM_EINVAL, "wdm_grad_guard: scratch of %zu bytes, needs %zu (wdm_grad_guard_scratch_bytes), 8-byte aligned", scratch_bytes, wdm_grad_guard_scratch_bytes());
+    return k_grad_guard(grads, (long long)n, max_norm, skip_nonfinite != 0, record, (double*)scratch, (hipStream_t)stream);
+}
+int wdm_trainer_optim_step_guarded(wdm_trainer* t, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay, double ema_mu,
+                                   const wdm_grad_record* record, void* stream) {
+    if (!t || !t->P || !t->G) WDM_FAIL(WDM_ESTATE, "wdm_trainer_optim_step_guarded: buffers not set");
+    if (!record) WDM_FAIL(WDM_EINVAL, "wdm_trainer_optim_step_guarded: null record");
+    if (step < 1) WDM_FAIL(WDM_EINVAL, "wdm_trainer_optim_step_guarded: step counts from 1");
+    const bool adam = t->opt_rule == WDM_OPT_ADAM;
+    if (adam ? (!t->M || !t->V) : !t->S[0]) WDM_FAIL(WDM_ESTATE, "wdm_trainer_optim_step_guarded: state buffers not set");
+    return k_optim_ema_guarded(t->opt_rule, t->P, t->G, adam ? t->M : t->S[0], adam ? t->V : t->S[1], t->S[2], t->E, (long long)t->nfloats, step, lr, beta1, beta2, eps,
+                               weight_decay, ema_mu, record, (hipStream_t)stream);
+}
+int wdm_optim_step_guarded(wdm_handle* h, int rule, float* params, const float* grads, float* state0, float* state1, float* state2, float* ema, int64_t n, int64_t step,
+                           double lr, double beta1, double beta2, double eps, double weight_decay, double ema_mu, const wdm_grad_record* record, void* stream) {
+    if (!h || !params || !grads) WDM_FAIL(WDM_EINVAL, "wdm_optim_step_guarded: null argument");
+    if (!record) WDM_FAIL(WDM_EINVAL, "wdm_optim_step_guarded: null record");
+    if (rule < WDM_OPT_ADAM || rule > WDM_OPT_SGD) WDM_FAIL(WDM_EINVAL, "wdm_optim_step_guarded: unknown rule %d", rule);
+    if (n < 0 || step < 1) WDM_FAIL(WDM_EINVAL, "wdm_optim_step_guarded: n = %lld, step = %lld (step counts from 1)", (long long)n, (long long)step);
+    const int need = rule == WDM_OPT_AMSGRAD ? 3 : rule == WDM_OPT_ADAM ? 2 : 1;
+    if (!state0 || (need >= 2 && !state1) || (need == 3 && !state2)) WDM_FAIL(WDM_EINVAL, "wdm_optim_step_guarded: rule %d needs %d state buffers", rule, need);
+    return k_optim_ema_guarded(rule, params, grads, state0, state1, state2, ema, (long long)n, step, lr, beta1, beta2, eps, weight_decay, ema_mu, record,
+                               (hipStream_t)stream);
 }
 
 }  // extern "C"

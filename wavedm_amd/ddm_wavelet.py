@@ -252,7 +252,8 @@ class DenoisingDiffusion_Wavelet(object):
                 fin = torch.isfinite(loss)
                 self.last_loss, self.losses_finite = loss, fin if getattr(self, "losses_finite", None) is None else self.losses_finite & fin
                 if self.step % 10 == 0 and rank0:
-                    print(f"step: {self.step}, loss: {float(loss)}, loss mean: {float(loss) / npix}")
+                    guard = "" if tr.grad_norm is None else f", grad norm: {float(tr.grad_norm)}, clip coef: {float(tr.clip_coef)}, skipped steps: {tr.skipped_steps}"
+                    print(f"step: {self.step}, loss: {float(loss)}, loss mean: {float(loss) / npix}{guard}")
                 world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
                 vfreq = int(getattr(self.config.training, "validation_freq", 0) or 0) if world > 1 else 10
                 if rank0 and vfreq > 0 and self.step % vfreq == 0:                                    # :273-278

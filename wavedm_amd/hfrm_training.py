@@ -100,7 +100,9 @@ def reference_init_state_dict(shapes, seed: int = 0):
 
 class HFRMTrainer:
     def __init__(self, in_channel=3, dim=32, mid_blk_num=6, enc_blk_nums=(2, 2, 2, 4), dec_blk_nums=(2, 2, 2, 2), device=None, dtype=None,
-                 lr=2e-4, betas=(0.5, 0.999), eps=1e-8):
+                 lr=2e-4, betas=(0.5, 0.999), eps=1e-8, grad_clip=None, skip_nonfinite=None):
+        from .training import grad_guard_settings
+        self.grad_clip, self.skip_nonfinite = grad_guard_settings(None, grad_clip, skip_nonfinite)      # off unless asked for (Trainer's pair; no config here)
         self._act_code = _resolve_train_dtype(dtype)
         self._dtype_code = _lib.WDM_F32                 # parameters and optimizer state: fp32 in both precisions
         if len(enc_blk_nums) != len(dec_blk_nums):
@@ -137,6 +139,8 @@ class HFRMTrainer:
             self.exp_avg = torch.zeros(n, device=self.device)
             self.exp_avg_sq = torch.zeros(n, device=self.device)
             self._loss = torch.zeros(1, device=self.device)
+            from .training import GradGuard
+            self._guard = GradGuard(self.grads, self.grad_clip, self.skip_nonfinite) if (self.grad_clip > 0.0 or self.skip_nonfinite) else None
         _lib.check(L.wdm_hfrm_trainer_set_buffers(t, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq)))
         self.step = 0
         self._ws = None
@@ -284,7 +288,16 @@ class HFRMTrainer:
         self.step += 1
         lr = hfrm_lr(self.step, self.lr) if lr is None else float(lr)
         with torch.cuda.device(self.device):
+            if self._guard is not None:      # norm of self.grads, then Adam behind the record; self.step counts calls, a skipped step included (Trainer.optimizer_step)
+                self._guard.run()
+                _lib.check(_lib.lib().wdm_hfrm_trainer_adam_guarded(self._t, self.step, lr, self.betas[0], self.betas[1], self.eps, 0.0, self._guard.ptr,
+                                                                    _lib.stream_ptr()))
+                return
             _lib.check(_lib.lib().wdm_hfrm_trainer_adam(self._t, self.step, lr, self.betas[0], self.betas[1], self.eps, 0.0, _lib.stream_ptr()))
+
+    grad_norm = property(lambda self: self._guard.norm if self._guard is not None else None, doc="Trainer.grad_norm")
+    clip_coef = property(lambda self: self._guard.coef if self._guard is not None else None, doc="Trainer.clip_coef")
+    skipped_steps = property(lambda self: self._guard.skipped_steps if self._guard is not None else 0, doc="Trainer.skipped_steps")
 
     def train_step(self, inp, gt, return_output=False):
         """One iteration of train_hfrm.py's loop: loss, backward, Adam.  Returns (loss, per-image PSNR of this step's output), both on the device

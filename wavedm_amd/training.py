@@ -64,6 +64,43 @@ def optimizer_spec(config):
     return spec
 
 
+def grad_guard_settings(config=None, grad_clip=None, skip_nonfinite=None):
+    """(grad_clip, skip_nonfinite) of a run: the arguments where given, else `optim.grad_clip` (the maximal global 2-norm of the gradient, what the DDIM code base
+    hands to clip_grad_norm_; 0 = off) and `optim.skip_nonfinite` (drop a step whose gradient holds a NaN or an infinity) of the config, else off.  Both keys are
+    this package's: the reference's configs have neither and the shipped ones stay as they are.  A negative or NaN grad_clip is a ValueError.  Needs no GPU."""
+    opt = getattr(config, "optim", None)
+    clip = getattr(opt, "grad_clip", 0) if grad_clip is None else grad_clip
+    skip = getattr(opt, "skip_nonfinite", False) if skip_nonfinite is None else skip_nonfinite
+    clip = 0.0 if clip is None else float(clip)
+    if clip != clip or clip < 0.0:
+        raise ValueError(f"optim.grad_clip = {clip!r}: a maximal gradient norm is positive (0 switches clipping off)")
+    return clip, bool(skip)
+
+
+class GradGuard:
+    """The guard of one flat gradient buffer on the device (include/wavedm.h: wdm_grad_guard): its record {norm, coef, skip, skipped_total} and the scratch of the
+    reduction.  `run()` enqueues the two launches; nothing comes back to the host until somebody reads `skipped_steps`."""
+
+    def __init__(self, grads, grad_clip, skip_nonfinite):
+        self.grads, self.grad_clip, self.skip_nonfinite = grads, float(grad_clip), bool(skip_nonfinite)
+        self.record = torch.zeros(4, dtype=torch.int32, device=grads.device)
+        self._floats = self.record.view(torch.float32)
+        self._scratch = torch.empty(int(_lib.lib().wdm_grad_guard_scratch_bytes()) // 8, dtype=torch.float64, device=grads.device)
+
+    def run(self):
+        dev = self.grads.device
+        _lib.check(_lib.lib().wdm_grad_guard(_lib.handle(dev.index or 0), _lib.ptr(self.grads), self.grads.numel(), self.grad_clip, int(self.skip_nonfinite),
+                                             _lib.ptr(self.record), _lib.ptr(self._scratch), self._scratch.numel() * 8, _lib.stream_ptr()))
+
+    @property
+    def ptr(self):
+        return _lib.ptr(self.record)
+
+    norm = property(lambda self: self._floats[0])
+    coef = property(lambda self: self._floats[1])
+    skipped_steps = property(lambda self: int(self.record[3].item()))
+
+
 def torch_optimizer(spec, parameters, **kw):
     """The torch.optim object of an optimizer_spec over `parameters` (what the reference instantiates; the tests' yardstick)."""
     if spec["rule"] in ("adam", "amsgrad"):
@@ -134,8 +171,10 @@ def attn_long_workspace_bytes(model, B: int, R: int, dsize: int) -> int:
 
 
 class Trainer:
-    def __init__(self, config, device=None, dtype=None, lr=None, betas=(0.9, 0.999), eps=None, weight_decay=None, ema_mu=0.9999, use_mse=None, dropout=None, dropout_seed=None):
+    def __init__(self, config, device=None, dtype=None, lr=None, betas=(0.9, 0.999), eps=None, weight_decay=None, ema_mu=0.9999, use_mse=None, dropout=None, dropout_seed=None,
+                 grad_clip=None, skip_nonfinite=None):
         self.config = config
+        self.grad_clip, self.skip_nonfinite = grad_guard_settings(config, grad_clip, skip_nonfinite)
         self.device = torch.device(device if device is not None else getattr(config, "device", "cuda:0"))
         if self.device.type != "cuda":
             raise RuntimeError("wavedm_amd.Trainer runs on MI355X only (no CPU path)")
@@ -180,6 +219,9 @@ class Trainer:
             # only the state the rule needs, under torch's names: exp_avg / exp_avg_sq (/ max_exp_avg_sq), square_avg, momentum_buffer -- also attributes of the trainer
             self.opt_state = OrderedDict((k, torch.zeros(n, device=self.device)) for k in STATE_NAMES[self.rule])
             self.ema = torch.zeros(n, device=self.device)
+            # the guard of the step (optim.grad_clip / optim.skip_nonfinite): only a trainer that asks for it owns a record, and only such a trainer launches
+            # the reduction and the guarded update -- without it optimizer_step is the call it always was
+            self._guard = GradGuard(self.grads, self.grad_clip, self.skip_nonfinite) if (self.grad_clip > 0.0 or self.skip_nonfinite) else None
         for k, buf in self.opt_state.items():
             setattr(self, k, buf)
         self._momentum_fresh = True                     # SGD: no step has filled the momentum buffer yet (torch creates it from the first gradient)
@@ -468,9 +510,44 @@ class Trainer:
         main.wait_stream(side)
         self.grads.div_(dist.get_world_size(group))
 
+    # ---- the guard of the step -------------------------------------------------------------------------
+    @property
+    def grad_norm(self):
+        """Global 2-norm of the last guarded step's gradient (after the all-reduce), a 0-dim device tensor: reading it here causes no wait.  None without a guard."""
+        return self._guard.norm if self._guard is not None else None
+
+    @property
+    def clip_coef(self):
+        """The factor the last guarded step scaled its gradient by: min(1, grad_clip / (norm + 1e-6)), 1 with clipping off.  Device tensor; None without a guard."""
+        return self._guard.coef if self._guard is not None else None
+
+    @property
+    def skipped_steps(self):
+        """How many steps skip_nonfinite has dropped so far (reads the device counter: this one waits)."""
+        return self._guard.skipped_steps if self._guard is not None else 0
+
+    def _guarded_optimizer_step(self):
+        """optimizer_step behind the guard: the norm of self.grads, then the rule's guarded kernel, which reads the record on the device.  self.step counts calls -- a
+        skipped step advances it too (bias corrections, dropout counters, checkpoints and schedules count calls; the device alone knows that the step was dropped).
+        SGD: a skipped first step leaves the zero-initialised momentum buffer alone, and the next step's momentum * 0 + g is the buffer it would have created."""
+        self._guard.run()
+        if self.rule == "adam":         # the unguarded Adam entry takes its hyper-parameters as floats: the same values here
+            f32 = lambda v: C.c_float(v).value
+            args = (self.step, f32(self.lr), f32(self.betas[0]), f32(self.betas[1]), f32(self.eps), f32(self.weight_decay), f32(self.ema_mu))
+        else:
+            b1, b2 = {"amsgrad": self.betas, "rmsprop": (0.0, self.alpha), "sgd": (self.momentum, 0.0)}[self.rule]
+            step = self.step
+            if self.rule == "sgd":
+                step = 1 if self._momentum_fresh else max(2, self.step)
+                self._momentum_fresh = False
+            args = (step, self.lr, b1, b2, self.eps, self.weight_decay, self.ema_mu)
+        _lib.check(_lib.lib().wdm_trainer_optim_step_guarded(self._t, *args, self._guard.ptr, _lib.stream_ptr()))
+
     def optimizer_step(self):
         self.step += 1
         with torch.cuda.device(self.device):
+            if self._guard is not None:
+                return self._guarded_optimizer_step()
             if self.rule == "adam":
                 _lib.check(_lib.lib().wdm_trainer_adam_ema(self._t, self.step, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_mu,
                                                            _lib.stream_ptr()))
@@ -485,7 +562,8 @@ class Trainer:
 
     def train_step(self, x0, group=None, generator=None):
         """The body of the reference's loop for one batch of wavelet-domain samples x0 (B,Cin,R,R): noise (model.out_ch channels), antithetic timesteps
-        (ddm_wavelet.py:249-256), loss, backward, all-reduce, Adam, EMA.  Returns the loss (device tensor)."""
+        (ddm_wavelet.py:249-256), loss, backward, all-reduce, [the guard, taken behind the all-reduce and its division: every rank reduces the same buffer to the same
+        coefficient and the same skip decision, and a NaN on one rank reaches all through the sum -- no collective is added,] optimizer, EMA.  Returns the loss (device tensor)."""
         n = x0.shape[0]
         e = torch.randn((n, int(self.config.model.out_ch)) + tuple(x0.shape[2:]), device=self.device, generator=generator)
         t = torch.randint(low=0, high=self.num_timesteps, size=(n // 2 + 1,), device=self.device, generator=generator)
