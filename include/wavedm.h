@@ -404,6 +404,32 @@ int wdm_to_u8_hwc(wdm_handle* h, const float* x, int B, int C, int H, int W, uin
 int wdm_image_ingest(wdm_handle* h, const uint8_t* src, int B, int H, int W, float* dst, int Hp, int Wp, void* stream);
 int wdm_to_u8_hwc_crop(wdm_handle* h, const float* x, int B, int C, int Hp, int Wp, int H, int W, uint8_t* y, void* stream);
 
+/* ---- training data resident in HBM (wavedm_amd/device_data.py: DeviceImageStore; csrc/device_data.hip) ----------------
+ * The store: N (input, ground truth) pairs as uint8 HWC in one flat device buffer `pixels` without padding; `offsets` (N,2) int64 = byte offset of pair i's
+ * input and ground truth, `sizes` (N,2) int32 = H, W of pair i (both images of a pair).  Read-only for every call here.
+ * wdm_data_draw: the (img, row, col) int32 triples of the n_items * patch_n samples of a step whose first item has global number g0.  Item G = g0 + j lies in
+ *   epoch E = G / N at position G % N and takes image perms[(E - perm_epoch0) * N + G % N] (`perms`: n_perm permutations of N int32, epochs perm_epoch0 ...; the
+ *   items' epochs must lie inside, else WDM_EINVAL).  Crop q of item G: u = G * patch_n + q as a 64-bit number, Philox4x32-10 (csrc/dropout.h) with key
+ *   (data_seed low word, high word) at counter (u low, u high, 0x43524F50, 0) gives words w0, w1: row = (w0 * (H - p + 1)) >> 32, col = (w1 * (W - p + 1)) >> 32
+ *   in 64-bit arithmetic.  p == 0: whole images, row = col = 0.  Images smaller than p are the caller's to refuse (the store does).
+ * wdm_train_sample_gather: triples (n) -> x0 (n, 48 + pred_channels + 48 - other_channels_begin, p/4, p/4) f32 NCHW =
+ *   [DWT(2 in - 1) | DWT(2 gt - 1)[:pred_channels] | DWT(2 gt - 1)[other_channels_begin:]] of each p x p crop, in = u8 / 255 correctly rounded (wdm_image_ingest's
+ *   rule), the transform wdm_dwt_fwd's arithmetic: the bits of assemble_training_sample (model.use_gt_in_train) on the same crops cut on the host.  crops01
+ *   (optional, 16-byte aligned): (n, 6, p, p) f32 = [in | gt] in [0,1].  p a multiple of 4; 1 <= pred_channels <= 48; 0 <= other_channels_begin <= 48; n >= 1 and
+ *   within the launch grid; else WDM_EINVAL and nothing is launched.  64-bit element offsets (a store may exceed 4 GB); no load wider than a byte from an
+ *   address that is not a multiple of its width.
+ *   CONTRACT: the kernel cannot check a triple against its image.  0 <= img < N, 0 <= row <= H - p, 0 <= col <= W - p are the caller's to guarantee
+ *   (wdm_data_draw's triples do); so is the truth of the tables.
+ * wdm_store_gather_images: images idx[k * idx_stride] (k < n) of a store whose images all measure H x W -> inp, gt (n,3,H,W) f32 NCHW in [0,1] (u8 / 255,
+ *   to_tensor's bits): the HFRM trainer's batch.  idx may be the first column of a triple buffer (idx_stride 3).
+ * All three are queued on `stream`; no launch argument depends on a device result; no host synchronisation. */
+int wdm_data_draw(wdm_handle* h, const int32_t* sizes, int64_t n_images, const int32_t* perms, int64_t perm_epoch0, int n_perm, int64_t g0, int n_items,
+                  int patch_n, int p, int64_t data_seed, int32_t* triples, void* stream);
+int wdm_train_sample_gather(wdm_handle* h, const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, const int32_t* triples, int n, int p,
+                            int pred_channels, int other_channels_begin, float* x0, float* crops01, void* stream);
+int wdm_store_gather_images(wdm_handle* h, const uint8_t* pixels, const int64_t* offsets, const int32_t* idx, int idx_stride, int n, int H, int W, float* inp,
+                            float* gt, void* stream);
+
 /* wdm_image_ssim: a, b (B images each, layout by `kind`) on the device -> out[B] (device, fp64): SSIM of each pair as calculate_ssim defines it
  * (utils/metrics.py:82-149; Y conversion :152-255) -- 11x11 Gaussian window (sigma 1.5) over the valid (H-10) x (W-10) region, C1 = (0.01*255)^2,
  * C2 = (0.03*255)^2, moments and map in fp64, the map's mean.

@@ -50,7 +50,28 @@ def parse_args(argv=None):
     p.add_argument("--grad_clip", type=float, default=0.0, help="clip the global gradient norm to this value before Adam (0: off; not in the reference)")
     p.add_argument("--skip_nonfinite", action="store_true", help="drop a step whose gradient holds a NaN or an infinity: parameters and moments keep their bits")
     p.add_argument("--sample_dir", type=str, default="train_result", help="directory of the sample sheets")
+    p.add_argument("--device_data", action="store_true",
+                   help="decode the training images once into device memory and gather every batch there (no loader workers; the order of the images is a function of "
+                        "--data_seed and the step)")
+    p.add_argument("--data_seed", type=int, default=None, help="with --device_data: the seed of the image order (default: --seed)")
     return p.parse_args(argv)
+
+
+class StoreBatches:
+    """--device_data: what the loop iterates over instead of a DataLoader -- len(store) // batch_size batches per epoch, each gathered on the device from the
+    store's item stream at the trainer's next step."""
+
+    def __init__(self, store, trainer, batch_size, data_seed):
+        if store.uniform_size is None:
+            raise SystemExit("train_hfrm --device_data: the training images differ in size (whole-image batches need one size)")
+        self.store, self.trainer, self.batch_size, self.data_seed = store, trainer, batch_size, data_seed
+
+    def __len__(self):
+        return max(1, len(self.store) // self.batch_size)
+
+    def __iter__(self):
+        for _ in range(len(self)):
+            yield self.store.step_images(self.data_seed, self.trainer.step + 1, self.batch_size)
 
 
 def main(argv=None):
@@ -65,7 +86,14 @@ def main(argv=None):
         trainer.load_state_dict(torch.load(os.path.join(out_dir, "best.pth"), map_location="cpu"), strict=True)
     else:
         trainer.init_reference(opt.seed)
-    loader = datasets.hfrm_train_loader(os.path.join(opt.data_dir, opt.dataset_name, "train"), batch_size=opt.batch_size, num_workers=opt.n_cpu)
+    train_root = os.path.join(opt.data_dir, opt.dataset_name, "train")
+    if opt.device_data:
+        from wavedm_amd.device_data import DeviceImageStore
+        store = DeviceImageStore.from_hfrm_folder(train_root, device=trainer.device)
+        loader = StoreBatches(store, trainer, opt.batch_size, opt.seed if opt.data_seed is None else opt.data_seed)
+        print(f"device-resident data: {len(store)} pairs, {store.nbytes} bytes, data_seed {loader.data_seed}")
+    else:
+        loader = datasets.hfrm_train_loader(train_root, batch_size=opt.batch_size, num_workers=opt.n_cpu)
     print("data loader finish!")
     best_psnr = opt.best_psnr
     prev_time = time.time()

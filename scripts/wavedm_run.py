@@ -13,6 +13,7 @@ OWN SIZE, without ground truth and without the evaluation protocol's 720x480 res
 --config is a file name under ./configs or a path.  Under torchrun every rank restores its share of the validation images (the
 loaders use a DistributedSampler) and rank 0 prints the PSNR over all of them; training all-reduces gradients over RCCL.
 Extras: --solver {ddim,dpmpp2m} and --x0_index K (eval, restore: the sampler's integrator and which x0 prediction becomes the image), --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train),
+--device_data [--data_seed S] (train: the training images live in device memory, crops are drawn and cut there),
 --grad_clip X and --skip_nonfinite (train: clip the global gradient norm to X / drop a step whose gradient is not finite; they override optim.grad_clip and optim.skip_nonfinite of the config),
 --hfrm-local [--hfrm-base-size H W] [--hfrm-train-size H W] (eval, restore: the HFRM's channel attention pools over a window instead of the whole image)."""
 import argparse
@@ -73,6 +74,11 @@ def parse(argv=None):
                     help="train: clip the global 2-norm of the gradient to X before the optimizer step (overrides optim.grad_clip; 0: off)")
     ap.add_argument("--skip_nonfinite", action="store_true",
                     help="train: drop a step whose gradient holds a NaN or an infinity -- parameters, optimizer state and EMA keep their bits (overrides optim.skip_nonfinite)")
+    ap.add_argument("--device_data", action="store_true",
+                    help="train: decode the training images once into device memory and draw and cut every step's crops there (no DataLoader workers, no pinned batches; "
+                         "the draws depend on (data_seed, step, rank, world) alone, so a resumed run continues with the crops the first would have cut; DESIGN.md 3.6.4)")
+    ap.add_argument("--data_seed", type=int, default=None, metavar="S",
+                    help="train, with --device_data: the seed of the image order and the crop positions (default: drawn from the run's --seed; a resumed checkpoint's wins)")
     ap.add_argument("--no_save", action="store_true", help="eval: metrics only, no PNGs")
     ap.add_argument("--ssim", action="store_true", help="eval: also SSIM (Y channel) of every output against its gt, on the device; prints an `ssim all` line")
     ap.add_argument("--samples", type=int, default=1,
@@ -117,6 +123,10 @@ def parse(argv=None):
         ap.error("restore needs --input DIR and --output DIR (or --no_save)")
     if a.mode != "train" and (a.grad_clip is not None or a.skip_nonfinite):
         ap.error("--grad_clip and --skip_nonfinite are training options")
+    if a.mode != "train" and a.device_data:
+        ap.error("--device_data is a training option")
+    if a.data_seed is not None and not a.device_data:
+        ap.error("--data_seed needs --device_data")
     path = a.config if os.path.isfile(a.config) else os.path.join("configs", a.config)
     config = load_config(path)
     if a.grad_clip is not None or a.skip_nonfinite:        # the flags override the config; the Trainer reads optim.grad_clip / optim.skip_nonfinite

@@ -16,8 +16,9 @@ from .imageio import AsyncImageWriter
 from .metrics import ssim, calculate_ssim
 from .training import Trainer, optimizer_spec
 from .hfrm_training import HFRMTrainer
+from .device_data import DeviceImageStore
 
 __all__ = ["WaveletTransform", "DiffusionUNet", "DiffusionUNet_Global", "DenoisingDiffusion_Wavelet", "DiffusiveRestoration",
            "data_transform", "inverse_data_transform", "torchPSNR", "get_beta_schedule", "compute_alpha",
-           "overlapping_grid_indices", "ddim_sample", "HFRM", "RainDrop", "RainDropDataset", "HFRMImageFolder", "ImageFolder", "image_loader", "AsyncImageWriter", "Trainer", "HFRMTrainer",
+           "overlapping_grid_indices", "ddim_sample", "HFRM", "RainDrop", "RainDropDataset", "HFRMImageFolder", "ImageFolder", "image_loader", "AsyncImageWriter", "Trainer", "HFRMTrainer", "DeviceImageStore",
            "ssim", "calculate_ssim", "optimizer_spec"]

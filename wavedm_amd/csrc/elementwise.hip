@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dwt_block.h"
 #include "gn_group.h"
 
 namespace wdm {
@@ -17,22 +18,6 @@ static inline int nblocks(long long n, int bs) { return (int)((n + bs - 1) / bs)
 // add/sub lifting stages and one scale.  Output channel = j*3 + c (sub-band major), integer-exact bookkeeping.
 // One thread per 4x4 block: 4 coalesced 16-byte reads, 16 coalesced 4-byte writes (one per sub-band plane).
 // =================================================================================================
-__device__ __forceinline__ void wht16(float* v) {
-#pragma unroll
-    for (int s = 1; s < 16; s <<= 1) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            if ((i & s) == 0) {
-                const float a = v[i], b = v[i | s];
-                v[i] = a + b;
-                v[i | s] = a - b;
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] *= 0.25f;
-}
-
 // pre-affine: the transform of (scale * x + shift) -- data_transform (2x - 1, restoration.py:8-9) folded into the load
 __global__ __launch_bounds__(256) void dwt_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, float scale, float shift) {
     const int h = H >> 2, w = W >> 2;

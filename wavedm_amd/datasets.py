@@ -150,6 +150,23 @@ class RainDrop:
                                                  num_workers=cfg.data.num_workers, pin_memory=True, **wk)
         return train_loader, val_loader
 
+    def device_store(self, split="train", max_bytes=None):
+        """The split's pairs decoded once into HBM (device_data.DeviceImageStore.from_raindrop): what train() draws its crops from under data.device_data."""
+        from .device_data import DeviceImageStore
+        return DeviceImageStore.from_raindrop(self.config, split=split, max_bytes=max_bytes)
+
+    def get_val_loader(self, parse_patches=False, validation="raindrop"):
+        """get_loaders' validation loader alone -- for a run whose training data never passes through a DataLoader."""
+        cfg = self.config
+        val_dataset = RainDropDataset(dir=os.path.join(cfg.data.data_dir, "raindrop", "raindrop_test"), n=cfg.training.patch_n, patch_size=cfg.data.patch_size,
+                                      transforms=self.transforms, filelist=None, parse_patches=parse_patches)
+        if not parse_patches:
+            cfg.sampling.batch_size = 1
+        ws, rank = getattr(self.args, "world_size", 1), getattr(self.args, "rank", 0)
+        return torch.utils.data.DataLoader(val_dataset, batch_size=cfg.sampling.batch_size, shuffle=False,
+                                           sampler=DistributedSampler(val_dataset, num_replicas=ws, rank=rank),
+                                           num_workers=cfg.data.num_workers, pin_memory=True, **worker_kwargs(cfg, cfg.data.num_workers))
+
 
 class HFRMImageFolder(torch.utils.data.Dataset):
     """The HFRM training set: the reference's `myImageFloder` (datasets/dataset.py:77-132) as train_hfrm.py builds it (crop=False,

@@ -152,6 +152,7 @@ class DenoisingDiffusion_Wavelet(object):
         self.ema_shadow = ckpt.get("ema_helper")
         self.optimizer_state = ckpt.get("optimizer")                            # restored into the trainer (ddm_wavelet.py:186)
         self.dropout_seed = ckpt.get("dropout_seed")                            # Trainer.save_checkpoint's extra key (None: a checkpoint without it)
+        self.data_seed = ckpt.get("data_seed")                                  # ... and the device-resident data path's (None: a checkpoint without it)
         self._resumed = True
         if ema and self.ema_shadow is not None:                                # EMAHelper.ema, ddm_wavelet.py:55-60
             with torch.no_grad():
@@ -181,6 +182,8 @@ class DenoisingDiffusion_Wavelet(object):
             tr.step = self.step = max(tr.step, self.step)
         if getattr(self, "_resumed", False) and "dropout_seed" not in kw:
             tr.restore_dropout_seed(getattr(self, "dropout_seed", None))        # the masks of step n depend on (seed, n) alone: the resumed run draws what the first would have
+        if getattr(self, "_resumed", False) and "data_seed" not in kw:
+            tr.restore_data_seed(getattr(self, "data_seed", None))              # the crops of step n depend on (seed, n, rank, world) alone
         tr.broadcast_state(src=0)                                               # DDP's construction-time broadcast (ddm_wavelet.py:168)
         tr.announce_dropout_seed()
         import torch.distributed as dist
@@ -229,6 +232,66 @@ class DenoisingDiffusion_Wavelet(object):
         self.step = tr.step
         return loss
 
+    def _hfrm_other_bands(self, inp01):
+        """assemble_training_sample's `other` without model.use_gt_in_train: DWT(2 * HFRM(input crops) - 1)."""
+        if self.generator is _identity_generator and not getattr(self, "_warned_identity_train", False):
+            import warnings
+            self._warned_identity_train = True
+            warnings.warn("model.use_gt_in_train: False with the identity stand-in for .generator: the UNet trains on the degraded image's own bands", stacklevel=2)
+        return self.wavelet_dec.forward_affine(self.generator(inp01).contiguous())
+
+    def train_step_from_store(self, store, group=None):
+        """train_step with the batch drawn and cut on the device from a DeviceImageStore (Trainer.train_step_from_store): no loader, no host-to-device copy."""
+        tr = getattr(self, "trainer", None) or self.make_trainer()
+        loss = tr.train_step_from_store(store, group=group, other_bands=self._hfrm_other_bands)
+        self.step = tr.step
+        return loss
+
+    def device_data_enabled(self):
+        return bool(getattr(self.config.data, "device_data", False) or getattr(self.args, "device_data", False))
+
+    def _train_from_store(self, DATASET, max_steps=None):
+        """train() without a training DataLoader (data.device_data / args.device_data): the training split is decoded once into a DeviceImageStore and every
+        step draws and cuts its crops there.  Checkpoints are named by the epoch of rank 0's first item of the step; logging, validation, snapshots and max_steps
+        are train()'s."""
+        import torch.distributed as dist
+        from .device_data import first_item
+        if getattr(self.config.data, "global_attn", False):
+            raise NotImplementedError("data.device_data with data.global_attn: the global-attention model needs `total`, the whole resized image of every item, "
+                                      "which the device-resident store does not keep")
+        store = DATASET.device_store("train")
+        tr = getattr(self, "trainer", None) or self.make_trainer()
+        if getattr(self.args, "data_seed", None) is not None and not (getattr(self, "_resumed", False) and getattr(self, "data_seed", None) is not None):
+            tr.data_seed = int(self.args.data_seed) & ((1 << 63) - 1)           # (a resumed checkpoint's seed wins: the run continues with the crops it would have cut)
+        tr.broadcast_data_seed(src=0)
+        npix = self.config.model.pred_channels * self.config.data.image_size ** 2
+        ddp = dist.is_available() and dist.is_initialized()
+        rank0, world = not ddp or dist.get_rank() == 0, dist.get_world_size() if ddp else 1
+        b, n_epochs = int(self.config.training.batch_size), int(self.config.training.n_epochs)
+        if rank0:
+            print(f"=> device-resident data: {len(store)} pairs, {store.nbytes} bytes on {store.device}, data_seed {tr.data_seed}")
+        while True:
+            epoch = first_item(self.step + 1, world, 0, b) // len(store)        # the epoch of rank 0's first item of the step about to be computed
+            if epoch >= n_epochs:
+                return
+            loss = self.train_step_from_store(store)
+            fin = torch.isfinite(loss)
+            self.last_loss, self.losses_finite = loss, fin if getattr(self, "losses_finite", None) is None else self.losses_finite & fin
+            if self.step % 10 == 0 and rank0:
+                guard = "" if tr.grad_norm is None else f", grad norm: {float(tr.grad_norm)}, clip coef: {float(tr.clip_coef)}, skipped steps: {tr.skipped_steps}"
+                print(f"step: {self.step}, loss: {float(loss)}, loss mean: {float(loss) / npix}{guard}")
+            vfreq = int(getattr(self.config.training, "validation_freq", 0) or 0) if world > 1 else 10
+            if rank0 and vfreq > 0 and self.step % vfreq == 0:
+                self.sync_from_trainer()
+                val_loader = DATASET.get_val_loader(parse_patches=False, validation=self.args.test_set)
+                self.restore(val_loader, validation=self.args.test_set, r=self.args.grid_r, epoch=epoch)
+            if rank0 and (self.step % self.config.training.snapshot_freq == 0 or self.step == 1):
+                path = os.path.join(self.config.data.data_dir, "ckpts", f"{self.config.data.dataset}_epoch{epoch + 1}_ddpm.pth.tar")
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                tr.save_checkpoint(path, epoch=epoch + 1)
+            if max_steps is not None and self.step >= max_steps:
+                return
+
     def sync_from_trainer(self, ema=False):
         """Copy the trained (or EMA) weights back into the inference model."""
         sd = self.trainer.ema_state_dict() if ema else self.trainer.state_dict()
@@ -241,6 +304,8 @@ class DenoisingDiffusion_Wavelet(object):
         `training.validation_freq` steps (every 10 when single-process, as the reference) and a checkpoint in the reference's format
         every `training.snapshot_freq` steps.  `max_steps` bounds the run (tests, benchmarks)."""
         import torch.distributed as dist
+        if self.device_data_enabled():                   # opt-in: crops drawn and cut on the device (DESIGN.md 3.6.4); nothing below runs
+            return self._train_from_store(DATASET, max_steps=max_steps)
         train_loader, _ = DATASET.get_loaders()
         tr = getattr(self, "trainer", None) or self.make_trainer()
         npix = self.config.model.pred_channels * self.config.data.image_size ** 2

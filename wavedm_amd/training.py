@@ -172,8 +172,11 @@ def attn_long_workspace_bytes(model, B: int, R: int, dsize: int) -> int:
 
 class Trainer:
     def __init__(self, config, device=None, dtype=None, lr=None, betas=(0.9, 0.999), eps=None, weight_decay=None, ema_mu=0.9999, use_mse=None, dropout=None, dropout_seed=None,
-                 grad_clip=None, skip_nonfinite=None):
+                 grad_clip=None, skip_nonfinite=None, data_seed=None):
         self.config = config
+        # the seed of the device-resident data path (train_step_from_store; device_data.py): given, restored from a checkpoint, or drawn at the first step from
+        # the store -- never by a trainer that is fed tensors, which consumes the random numbers it always did
+        self.data_seed = (int(data_seed) & _MASK63) if data_seed is not None else None
         self.grad_clip, self.skip_nonfinite = grad_guard_settings(config, grad_clip, skip_nonfinite)
         self.device = torch.device(device if device is not None else getattr(config, "device", "cuda:0"))
         if self.device.type != "cuda":
@@ -576,6 +579,63 @@ class Trainer:
         self.optimizer_step()
         return loss
 
+    # ---- the step fed from images resident in HBM (device_data.py) --------------------------------------------------------------------
+    def _ensure_data_seed(self):
+        if self.data_seed is None:
+            from .device_data import draw_data_seed
+            self.data_seed = draw_data_seed()
+        return self.data_seed
+
+    def restore_data_seed(self, seed):
+        """--resume: the checkpoint's 'data_seed' (None -- a checkpoint without the key -- changes nothing: a seed is drawn when the store is first used)."""
+        if seed is not None:
+            self.data_seed = int(seed) & _MASK63
+
+    def broadcast_data_seed(self, src=0, group=None):
+        """Every rank draws from rank `src`'s seed (the ranks' items differ by their global item numbers, not by their seeds)."""
+        import torch.distributed as dist
+        self._ensure_data_seed()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            st = torch.tensor([self.data_seed], device=self.device, dtype=torch.int64)
+            dist.broadcast(st, src=src, group=group)
+            self.data_seed = int(st.item())
+        return self.data_seed
+
+    def store_draw(self, store, group=None, step=None):
+        """The (img, row, col) triples of the samples optimizer step `step` (default: the next one) takes on this rank: training.batch_size items of
+        training.patch_n crops of data.patch_size pixels, a function of (data_seed, step, rank, world) alone (device_data.first_item)."""
+        import torch.distributed as dist
+        from .device_data import first_item
+        world, rank = (dist.get_world_size(group), dist.get_rank(group)) if (dist.is_available() and dist.is_initialized()) else (1, 0)
+        b, patch_n = int(self.config.training.batch_size), int(self.config.training.patch_n)
+        g0 = first_item(self.step + 1 if step is None else step, world, rank, b)
+        return store.draw(self._ensure_data_seed(), g0, b, patch_n, int(self.config.data.patch_size))
+
+    def sample_from_store(self, store, group=None, other_bands=None, step=None):
+        """x0 of the next step, drawn and cut on the device: assemble_training_sample's tensor without a float crop, a second DWT launch or a cat.  With
+        model.use_gt_in_train: False the kernel also writes the [0,1] crops and `other_bands(input crops (n,3,p,p)) -> (n,48,p/4,p/4)` supplies the bands from
+        other_channels_begin on (DenoisingDiffusion_Wavelet passes its HFRM -> DWT(2x - 1) path)."""
+        m = self.config.model
+        if getattr(self.config.data, "global_attn", False):
+            raise NotImplementedError("the device-resident data path does not feed the data.global_attn model: it needs `total`, the whole resized image, which the store does not keep")
+        if not m.use_other_channels:
+            raise NotImplementedError("training with model.use_other_channels: False is not built (DenoisingDiffusion_Wavelet.assemble_training_sample)")
+        triples = self.store_draw(store, group, step)
+        p, pc, ob = int(self.config.data.patch_size), int(m.pred_channels), int(m.other_channels_begin)
+        if getattr(m, "use_gt_in_train", True) or ob >= 48:
+            return store.gather_training_samples(triples, p, pc, ob)
+        if other_bands is None:
+            raise ValueError("Trainer.sample_from_store: model.use_gt_in_train: False needs other_bands (the HFRM path of assemble_training_sample)")
+        head, crops = store.gather_training_samples(triples, p, pc, 48, want_crops=True)
+        with torch.no_grad():
+            other = other_bands(crops[:, :3].contiguous())
+        return torch.cat([head, other[:, ob:]], dim=1).contiguous()
+
+    def train_step_from_store(self, store, group=None, generator=None, other_bands=None):
+        """train_step on samples drawn and cut from a DeviceImageStore: two launches (wdm_data_draw, wdm_train_sample_gather) in front of the unchanged step; noise and
+        timesteps come from torch's device generator exactly as in train_step."""
+        return self.train_step(self.sample_from_store(store, group, other_bands), group=group, generator=generator)
+
     # ---- optimizer state in torch.optim.Adam's state_dict layout (what the reference saves and restores, ddm_wavelet.py:186, :288) ---------
     def param_order(self):
         """Parameter names in the reference's `model.parameters()` order: torch.optim indexes its state by that position."""
@@ -645,10 +705,13 @@ class Trainer:
     def save_checkpoint(self, path, epoch=0):
         """The reference's checkpoint dict (ddm_wavelet.py:282-292): its own `load_ddm_ckpt` (:180-190) reads this file -- it looks up named keys only, so the
         one key added here, 'dropout_seed' (the BASE seed: a resumed run continues with the masks the uninterrupted run would have drawn), does not disturb it."""
-        torch.save({"epoch": epoch, "step": self.step, "state_dict": {k: v.cpu() for k, v in self.state_dict().items()},
-                    "optimizer": self.optimizer_state_dict(),
-                    "ema_helper": {k: v.cpu() for k, v in self.ema_state_dict().items()}, "params": None, "config": None,
-                    "dropout_seed": self.dropout_seed}, path)                 # (None from a trainer that never used dropout: resumes like a file without the key)
+        ck = {"epoch": epoch, "step": self.step, "state_dict": {k: v.cpu() for k, v in self.state_dict().items()},
+              "optimizer": self.optimizer_state_dict(),
+              "ema_helper": {k: v.cpu() for k, v in self.ema_state_dict().items()}, "params": None, "config": None,
+              "dropout_seed": self.dropout_seed}                                # (None from a trainer that never used dropout: resumes like a file without the key)
+        if self.data_seed is not None:                                          # only a trainer fed from a DeviceImageStore has one: every other checkpoint keeps its keys
+            ck["data_seed"] = self.data_seed
+        torch.save(ck, path)
 
     def restore_dropout_seed(self, seed):
         """--resume: take the checkpoint's base seed; a checkpoint without one (the reference's, or an older one of this package) keeps the fresh seed drawn at
