@@ -430,6 +430,27 @@ int wdm_train_sample_gather(wdm_handle* h, const uint8_t* pixels, const int64_t*
 int wdm_store_gather_images(wdm_handle* h, const uint8_t* pixels, const int64_t* offsets, const int32_t* idx, int idx_stride, int n, int H, int W, float* inp,
                             float* gt, void* stream);
 
+/* ---- orientations of those crops and images (data.augment) ----------------
+ * Orientation code o in 0 .. 7 on a square crop or a whole image t (.., H, W), in this order: o & 1: t = t.flip(-1) (mirror left-right); o & 2: t = t.flip(-2)
+ * (mirror top-bottom); o & 4: t = t.transpose(-1, -2) -- the eight symmetries of the square, each once.  The input and the ground truth of a sample take the same o.
+ * orient_mask in 0 .. 7 (else WDM_EINVAL): 0 none, 1 hflip, 3 flips, 7 d4.
+ * wdm_data_draw_oriented: wdm_data_draw's arguments, checks and triples (same values, same layout), and orient[j * patch_n + q] = (w2 >> 29) & orient_mask, w2 =
+ *   word 2 of the crop counter that gives row and col.  With p == 0 (whole images; the triples take no Philox word) the same counter is evaluated, u = G * patch_n + q.
+ *   Whether bit 2 suits the images (whole images must be square) is the caller's to decide through orient_mask.
+ * wdm_train_sample_gather_oriented: wdm_train_sample_gather's arguments, checks and outputs, each sample's crop oriented by orient[sample] first: x0 and crops01
+ *   are the bits of assemble_training_sample on the host-cut crops after the three torch operations above.  One launch serves samples of different codes.
+ *   CONTRACT: like the triples, the codes cannot be checked against anything on the device; values outside 0 .. 7 are the caller's responsibility.  The kernel
+ *   uses orient[sample] & 7, so no value can address outside the crop.
+ * wdm_store_gather_images_oriented: wdm_store_gather_images's outputs with image k oriented by orient[k] & orient_mask.  orient_mask & 4 needs H == W (a transposed
+ *   H x W image is W x H and would not fit the batch), else WDM_EINVAL; with it cleared, no device value can transpose.
+ * Every WDM_EINVAL launches nothing.  Queued on `stream`; no launch argument depends on a device result; no host synchronisation. */
+int wdm_data_draw_oriented(wdm_handle* h, const int32_t* sizes, int64_t n_images, const int32_t* perms, int64_t perm_epoch0, int n_perm, int64_t g0, int n_items,
+                           int patch_n, int p, int64_t data_seed, int orient_mask, int32_t* triples, int32_t* orient, void* stream);
+int wdm_train_sample_gather_oriented(wdm_handle* h, const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, const int32_t* triples,
+                                     const int32_t* orient, int n, int p, int pred_channels, int other_channels_begin, float* x0, float* crops01, void* stream);
+int wdm_store_gather_images_oriented(wdm_handle* h, const uint8_t* pixels, const int64_t* offsets, const int32_t* idx, int idx_stride, const int32_t* orient,
+                                     int orient_mask, int n, int H, int W, float* inp, float* gt, void* stream);
+
 /* wdm_image_ssim: a, b (B images each, layout by `kind`) on the device -> out[B] (device, fp64): SSIM of each pair as calculate_ssim defines it
  * (utils/metrics.py:82-149; Y conversion :152-255) -- 11x11 Gaussian window (sigma 1.5) over the valid (H-10) x (W-10) region, C1 = (0.01*255)^2,
  * C2 = (0.03*255)^2, moments and map in fp64, the map's mean.

@@ -4,7 +4,9 @@
     ceiling    Trainer.train_step on one batch that is already resident on the device (no data path at all)
     loader4    DenoisingDiffusion_Wavelet.train() fed by the DataLoader with 4 workers   (--parent-tree: run on another checkout's build)
     loader16   ... with 16 workers
-    store      train() fed by the device-resident store (data.device_data; wavedm_amd/device_data.py)
+    store      train() fed by the device-resident store (data.device_data; wavedm_amd/device_data.py); --augment MODE ...: once per mode (data.augment), the
+               modes alternating inside each round, rows "store" (none) and "store+MODE"
+    store_parent   the store variant on --parent-tree's build (without augmentation: what `store` must match, since it launches the same kernels)
 
 on a training set the script generates itself (64 pairs of 480x720 PNGs under a temporary <data_dir>/raindrop/train).  Every measurement is a process of its
 own (a build is chosen at import), the variants alternate within each round, and each process times --steps steps behind --warmup untimed ones, from a
@@ -25,7 +27,8 @@ import time
 from types import SimpleNamespace
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VARIANTS = ("ceiling", "loader4", "loader16", "store")
+VARIANTS = ("ceiling", "loader4", "loader16", "store", "store_parent")
+AUGMENTS = ("none", "hflip", "flips", "d4")
 
 
 def write_pairs(root, n=64, size=(720, 480), seed=5):
@@ -77,8 +80,10 @@ def child(a):
         out["steps_per_s"] = a.steps / (time.perf_counter() - t0)
         print(json.dumps(out))
         return 0
-    if a.variant == "store":
+    if a.variant in ("store", "store_parent"):
         cfg.data.device_data = True
+        if a.augment[0] != "none":
+            cfg.data.augment = a.augment[0]
     else:
         cfg.data.num_workers = int(a.variant[len("loader"):])
     args = SimpleNamespace(resume="", sampling_timesteps=25, local_rank=0, image_folder=os.path.join(a.data, "img"), test_set="raindrop", grid_r=16, rank=0, world_size=1)
@@ -90,7 +95,8 @@ def child(a):
     d.sync_from_trainer = lambda *x, **k: None
     tr.save_checkpoint = lambda *x, **k: None
     mark = {}
-    name = "train_step_from_store" if a.variant == "store" else "train_step"
+    from_store = a.variant in ("store", "store_parent")
+    name = "train_step_from_store" if from_store else "train_step"
     inner = getattr(d, name)
 
     def timed(*x, **k):
@@ -106,8 +112,8 @@ def child(a):
     torch.cuda.synchronize()
     out["steps_per_s"] = a.steps / (time.perf_counter() - mark["t0"])
     out["loss_finite"] = bool(d.losses_finite)
-    if a.variant == "store":
-        out["data_seed"] = tr.data_seed
+    if from_store:
+        out["data_seed"], out["augment"] = tr.data_seed, a.augment[0]
     print(json.dumps(out))
     return 0
 
@@ -118,7 +124,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20, help="untimed steps in front of them (worker start-up, first-use allocations)")
     ap.add_argument("--rounds", type=int, default=2, help="how often every (variant, size) is measured; the variants alternate inside a round")
     ap.add_argument("--sizes", type=int, nargs="+", default=[8, 64], help="samples per step (multiples of 8: items of 8 crops)")
-    ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=VARIANTS)
+    ap.add_argument("--variants", nargs="+", default=list(VARIANTS[:4]), choices=VARIANTS)
+    ap.add_argument("--augment", nargs="+", default=["none"], choices=AUGMENTS, help="store variant: data.augment; several modes are measured in turn inside each round")
     ap.add_argument("--pairs", type=int, default=64, help="image pairs in the generated training set")
     ap.add_argument("--parent-tree", default=None, help="a built checkout of another commit: the loader variants import wavedm_amd from there")
     ap.add_argument("--timeout", type=int, default=300, help="seconds one measurement may take")
@@ -131,14 +138,18 @@ def main():
         return child(a)
     if any(s < 8 or s % 8 for s in a.sizes):
         ap.error("--sizes: multiples of 8")
+    if "store_parent" in a.variants and not a.parent_tree:
+        ap.error("the store_parent variant needs --parent-tree")
     data = tempfile.mkdtemp(prefix="wdm_feed_")
     try:
         write_pairs(data, n=a.pairs)
         results, failed = {}, []
-        for rnd, size, v in [(r, s, v) for r in range(a.rounds) for s in a.sizes for v in a.variants]:
-            tree = a.parent_tree if (a.parent_tree and v.startswith("loader")) else HERE
+        runs = [(v, m) for v in a.variants for m in (a.augment if v == "store" else ["none"])]
+        for rnd, size, (v, mode) in [(r, s, vm) for r in range(a.rounds) for s in a.sizes for vm in runs]:
+            tree = a.parent_tree if (a.parent_tree and (v.startswith("loader") or v == "store_parent")) else HERE
             cmd = [sys.executable, os.path.abspath(__file__), "--child", v, "--samples", str(size), "--steps", str(a.steps), "--warmup", str(a.warmup),
-                   "--data", data, "--tree", tree]
+                   "--data", data, "--tree", tree, "--augment", mode]
+            v = v if mode == "none" else f"{v}+{mode}"
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
             except subprocess.TimeoutExpired:      # it may have hung: nothing more is started on the device, what was measured is reported

@@ -54,24 +54,30 @@ def parse_args(argv=None):
                    help="decode the training images once into device memory and gather every batch there (no loader workers; the order of the images is a function of "
                         "--data_seed and the step)")
     p.add_argument("--data_seed", type=int, default=None, help="with --device_data: the seed of the image order (default: --seed)")
-    return p.parse_args(argv)
+    p.add_argument("--augment", type=str, default="none", choices=("none", "hflip", "flips", "d4"),
+                   help="with --device_data: every pair in a drawn orientation -- hflip: mirrored left-right or not; flips: both mirrors; d4: the eight symmetries "
+                        "of the square (images that are not square take no transpose: d4 acts as flips).  A function of (--data_seed, step) like the image order")
+    opt = p.parse_args(argv)
+    if opt.augment != "none" and not opt.device_data:       # before any file is opened
+        raise ValueError(f"train_hfrm: --augment {opt.augment} (data.augment) needs --device_data (data.device_data): augmenting the loader-fed path is not built")
+    return opt
 
 
 class StoreBatches:
     """--device_data: what the loop iterates over instead of a DataLoader -- len(store) // batch_size batches per epoch, each gathered on the device from the
     store's item stream at the trainer's next step."""
 
-    def __init__(self, store, trainer, batch_size, data_seed):
+    def __init__(self, store, trainer, batch_size, data_seed, augment="none"):
         if store.uniform_size is None:
             raise SystemExit("train_hfrm --device_data: the training images differ in size (whole-image batches need one size)")
-        self.store, self.trainer, self.batch_size, self.data_seed = store, trainer, batch_size, data_seed
+        self.store, self.trainer, self.batch_size, self.data_seed, self.augment = store, trainer, batch_size, data_seed, augment
 
     def __len__(self):
         return max(1, len(self.store) // self.batch_size)
 
     def __iter__(self):
         for _ in range(len(self)):
-            yield self.store.step_images(self.data_seed, self.trainer.step + 1, self.batch_size)
+            yield self.store.step_images(self.data_seed, self.trainer.step + 1, self.batch_size, augment=self.augment)
 
 
 def main(argv=None):
@@ -90,8 +96,10 @@ def main(argv=None):
     if opt.device_data:
         from wavedm_amd.device_data import DeviceImageStore
         store = DeviceImageStore.from_hfrm_folder(train_root, device=trainer.device)
-        loader = StoreBatches(store, trainer, opt.batch_size, opt.seed if opt.data_seed is None else opt.data_seed)
-        print(f"device-resident data: {len(store)} pairs, {store.nbytes} bytes, data_seed {loader.data_seed}")
+        loader = StoreBatches(store, trainer, opt.batch_size, opt.seed if opt.data_seed is None else opt.data_seed, opt.augment)
+        print(f"device-resident data: {len(store)} pairs, {store.nbytes} bytes, data_seed {loader.data_seed}, augment {opt.augment}")
+        if opt.augment == "d4" and store.whole_image_mask("d4") != 7:
+            print("augment d4: the images are {}x{} (H x W), not square -- no transpose, d4 acts as flips".format(*store.uniform_size))
     else:
         loader = datasets.hfrm_train_loader(train_root, batch_size=opt.batch_size, num_workers=opt.n_cpu)
     print("data loader finish!")

@@ -13,7 +13,7 @@ OWN SIZE, without ground truth and without the evaluation protocol's 720x480 res
 --config is a file name under ./configs or a path.  Under torchrun every rank restores its share of the validation images (the
 loaders use a DistributedSampler) and rank 0 prints the PSNR over all of them; training all-reduces gradients over RCCL.
 Extras: --solver {ddim,dpmpp2m} and --x0_index K (eval, restore: the sampler's integrator and which x0 prediction becomes the image), --dtype {f16,bf16,f32x3,f32} (default: f16 when the checkpoint fits fp16, else bf16 with a warning), --images_per_call N (eval: images per sampler call, default automatic), --full_length (eval: no early stop), --ssim (eval: SSIM of the outputs as well), --hfrm_ckpt PATH, --max_steps N (train),
---device_data [--data_seed S] (train: the training images live in device memory, crops are drawn and cut there),
+--device_data [--data_seed S] [--augment {none,hflip,flips,d4}] (train: the training images live in device memory, crops are drawn, oriented and cut there),
 --grad_clip X and --skip_nonfinite (train: clip the global gradient norm to X / drop a step whose gradient is not finite; they override optim.grad_clip and optim.skip_nonfinite of the config),
 --hfrm-local [--hfrm-base-size H W] [--hfrm-train-size H W] (eval, restore: the HFRM's channel attention pools over a window instead of the whole image)."""
 import argparse
@@ -79,6 +79,10 @@ def parse(argv=None):
                          "the draws depend on (data_seed, step, rank, world) alone, so a resumed run continues with the crops the first would have cut; DESIGN.md 3.6.4)")
     ap.add_argument("--data_seed", type=int, default=None, metavar="S",
                     help="train, with --device_data: the seed of the image order and the crop positions (default: drawn from the run's --seed; a resumed checkpoint's wins)")
+    ap.add_argument("--augment", default=None, choices=["none", "hflip", "flips", "d4"],
+                    help="train, with --device_data: every crop in a drawn orientation, applied inside the gather kernel -- hflip: mirrored left-right or not; flips: "
+                         "both mirrors; d4: the eight symmetries of the square.  Overrides data.augment; drawn from (data_seed, step, rank, world) like the crops, so "
+                         "--resume continues with the orientations of the uninterrupted run.  Its effect on restoration quality has not been measured.")
     ap.add_argument("--no_save", action="store_true", help="eval: metrics only, no PNGs")
     ap.add_argument("--ssim", action="store_true", help="eval: also SSIM (Y channel) of every output against its gt, on the device; prints an `ssim all` line")
     ap.add_argument("--samples", type=int, default=1,
@@ -127,8 +131,15 @@ def parse(argv=None):
         ap.error("--device_data is a training option")
     if a.data_seed is not None and not a.device_data:
         ap.error("--data_seed needs --device_data")
+    if a.mode != "train" and a.augment is not None:
+        ap.error("--augment is a training option")
     path = a.config if os.path.isfile(a.config) else os.path.join("configs", a.config)
     config = load_config(path)
+    if a.mode == "train":                                  # the flag overrides the config; refused without the device-resident path before any data is read
+        from wavedm_amd.device_data import augment_mode, refuse_augment_without_store
+        config.data.augment = augment_mode(config, a.augment)
+        if not (a.device_data or getattr(config.data, "device_data", False)):
+            refuse_augment_without_store(config.data.augment, "wavedm_run train")
     if a.grad_clip is not None or a.skip_nonfinite:        # the flags override the config; the Trainer reads optim.grad_clip / optim.skip_nonfinite
         from types import SimpleNamespace
         from wavedm_amd.training import grad_guard_settings

@@ -225,6 +225,8 @@ class DenoisingDiffusion_Wavelet(object):
     def train_step(self, x, group=None):
         """One iteration of the reference's loop body (:208-272) on a batch of crops x (n, 6, p, p): DWT, q-sample with antithetic
         timesteps, loss, backward, gradient all-reduce, Adam, EMA.  Returns the loss as a device tensor."""
+        from .device_data import augment_mode, refuse_augment_without_store
+        refuse_augment_without_store(augment_mode(self.config), "train_step on host crops")
         tr = getattr(self, "trainer", None) or self.make_trainer()
         _lib.pinned_dontfork(x)                          # (a pin_memory=True loader's batch: not copy-on-write at the loader's next fork -- _lib.pinned_dontfork)
         x = x.flatten(start_dim=0, end_dim=1) if x.ndim == 5 else x
@@ -240,10 +242,11 @@ class DenoisingDiffusion_Wavelet(object):
             warnings.warn("model.use_gt_in_train: False with the identity stand-in for .generator: the UNet trains on the degraded image's own bands", stacklevel=2)
         return self.wavelet_dec.forward_affine(self.generator(inp01).contiguous())
 
-    def train_step_from_store(self, store, group=None):
-        """train_step with the batch drawn and cut on the device from a DeviceImageStore (Trainer.train_step_from_store): no loader, no host-to-device copy."""
+    def train_step_from_store(self, store, group=None, augment=None):
+        """train_step with the batch drawn and cut on the device from a DeviceImageStore (Trainer.train_step_from_store): no loader, no host-to-device copy.
+        `augment` (default: data.augment, else "none"): the orientations the crops take there."""
         tr = getattr(self, "trainer", None) or self.make_trainer()
-        loss = tr.train_step_from_store(store, group=group, other_bands=self._hfrm_other_bands)
+        loss = tr.train_step_from_store(store, group=group, other_bands=self._hfrm_other_bands, augment=augment)
         self.step = tr.step
         return loss
 
@@ -255,7 +258,8 @@ class DenoisingDiffusion_Wavelet(object):
         step draws and cuts its crops there.  Checkpoints are named by the epoch of rank 0's first item of the step; logging, validation, snapshots and max_steps
         are train()'s."""
         import torch.distributed as dist
-        from .device_data import first_item
+        from .device_data import augment_mode, first_item
+        mode = augment_mode(self.config, getattr(self.args, "augment", None))    # (a bad name is refused before any file is opened)
         if getattr(self.config.data, "global_attn", False):
             raise NotImplementedError("data.device_data with data.global_attn: the global-attention model needs `total`, the whole resized image of every item, "
                                       "which the device-resident store does not keep")
@@ -269,12 +273,12 @@ class DenoisingDiffusion_Wavelet(object):
         rank0, world = not ddp or dist.get_rank() == 0, dist.get_world_size() if ddp else 1
         b, n_epochs = int(self.config.training.batch_size), int(self.config.training.n_epochs)
         if rank0:
-            print(f"=> device-resident data: {len(store)} pairs, {store.nbytes} bytes on {store.device}, data_seed {tr.data_seed}")
+            print(f"=> device-resident data: {len(store)} pairs, {store.nbytes} bytes on {store.device}, data_seed {tr.data_seed}, augment {mode}")
         while True:
             epoch = first_item(self.step + 1, world, 0, b) // len(store)        # the epoch of rank 0's first item of the step about to be computed
             if epoch >= n_epochs:
                 return
-            loss = self.train_step_from_store(store)
+            loss = self.train_step_from_store(store, augment=mode)
             fin = torch.isfinite(loss)
             self.last_loss, self.losses_finite = loss, fin if getattr(self, "losses_finite", None) is None else self.losses_finite & fin
             if self.step % 10 == 0 and rank0:
@@ -306,6 +310,8 @@ class DenoisingDiffusion_Wavelet(object):
         import torch.distributed as dist
         if self.device_data_enabled():                   # opt-in: crops drawn and cut on the device; nothing below runs
             return self._train_from_store(DATASET, max_steps=max_steps)
+        from .device_data import augment_mode, refuse_augment_without_store
+        refuse_augment_without_store(augment_mode(self.config, getattr(self.args, "augment", None)), "train() fed by the DataLoader")
         train_loader, _ = DATASET.get_loaders()
         tr = getattr(self, "trainer", None) or self.make_trainer()
         npix = self.config.model.pred_channels * self.config.data.image_size ** 2

@@ -8,6 +8,8 @@ What a step draws is DEFINED by counters (Philox4x32-10 exactly as csrc/dropout.
     perm_E = indices ordered by (key, i), key_i = word 0 of Philox at counter (i, 0, 0x50455231, E)
     crop q of item G: u = G * patch_n + q (64 bit), words at counter (u low, u high, 0x43524F50, 0):
         row = (w0 * (H - p + 1)) >> 32,  col = (w1 * (W - p + 1)) >> 32                                           (crop_position; wdm_data_draw on the device)
+        under data.augment: orientation o = (w2 >> 29) & mask, masks none 0, hflip 1, flips 3, d4 7           (crop_orientation; wdm_data_draw_oriented)
+        o & 1: flip(-1), then o & 2: flip(-2), then o & 4: transpose(-1, -2), applied inside the gather kernels to input and ground truth alike
 
 Over any N consecutive G -- across all ranks -- every image is used exactly once; an epoch boundary may fall inside a step (a stated departure from
 DistributedSampler's padded per-epoch partition).  Draws depend on (data_seed, s, r, W) alone: a resumed or re-sharded run sees the crops the uninterrupted
@@ -69,6 +71,38 @@ def crop_position(seed, G, q, patch_n, H, W, p):
     u = (int(G) * int(patch_n) + int(q)) & 0xFFFFFFFFFFFFFFFF
     w = philox4x32_10(u & 0xFFFFFFFF, u >> 32, CROP_TAG, 0, *_key(seed))
     return (int(w[0]) * (H - p + 1)) >> 32, (int(w[1]) * (W - p + 1)) >> 32
+
+
+AUGMENT_MASKS = {"none": 0b000, "hflip": 0b001, "flips": 0b011, "d4": 0b111}
+
+
+def augment_mask(mode):
+    """data.augment -> the 3-bit mask of the orientation draw (None = "none")."""
+    mode = "none" if mode is None else mode
+    if not isinstance(mode, str) or mode not in AUGMENT_MASKS:
+        raise ValueError(f"data.augment: {mode!r} is not one of {', '.join(AUGMENT_MASKS)}")
+    return AUGMENT_MASKS[mode]
+
+
+def augment_mode(config=None, augment=None):
+    """The mode in force: the keyword where given, else config.data.augment, else "none"; validated."""
+    mode = augment if augment is not None else getattr(getattr(config, "data", None), "augment", None)
+    mode = "none" if mode is None else mode
+    augment_mask(mode)
+    return mode
+
+
+def refuse_augment_without_store(mode, where):
+    """data.augment orients crops in the device-resident gather alone: any other feed is refused, before it reads data."""
+    if augment_mask(mode):
+        raise ValueError(f"{where}: data.augment: {mode} needs the device-resident data path (data.device_data: True / --device_data); "
+                         "augmenting the loader-fed path is not built")
+
+
+def crop_orientation(seed, G, q, patch_n, mask):
+    """Orientation code of crop q of item G -- the host's statement of wdm_data_draw_oriented: (word 2 of the crop counter >> 29) & mask."""
+    u = (int(G) * int(patch_n) + int(q)) & 0xFFFFFFFFFFFFFFFF
+    return (int(philox4x32_10(u & 0xFFFFFFFF, u >> 32, CROP_TAG, 0, *_key(seed))[2]) >> 29) & int(mask)
 
 
 def draw_data_seed():
@@ -249,8 +283,17 @@ class DeviceImageStore:
             self.perm_uploads += 1
         return self._perms, self._perm_epoch0
 
-    def draw(self, seed, g0, n_items, patch_n=1, patch_size=0):
-        """(n_items * patch_n, 3) int32 on the device: (img, row, col) of the samples of items g0 .. g0 + n_items - 1 (wdm_data_draw).  patch_size 0: whole images."""
+    def whole_image_mask(self, augment):
+        """The orientation mask whole images of this store can take: the mode's, without the transpose unless every image is square (a transposed H x W image
+        would change the batch's shape: `d4` then acts as `flips`)."""
+        hw = self.uniform_size
+        return augment_mask(augment) & (7 if hw is not None and hw[0] == hw[1] else 3)
+
+    def draw(self, seed, g0, n_items, patch_n=1, patch_size=0, augment=None):
+        """(n_items * patch_n, 3) int32 on the device: (img, row, col) of the samples of items g0 .. g0 + n_items - 1 (wdm_data_draw).  patch_size 0: whole images.
+        augment other than None / "none": (triples, orient) -- the same triples and one int32 orientation code per sample (wdm_data_draw_oriented), under
+        whole_image_mask for whole images."""
+        mask = augment_mask(augment)
         g0, n_items, patch_n, p = int(g0), int(n_items), int(patch_n), int(patch_size)
         if n_items < 1 or patch_n < 1 or g0 < 0:
             raise ValueError(f"DeviceImageStore.draw: g0 {g0}, n_items {n_items}, patch_n {patch_n}")
@@ -260,40 +303,72 @@ class DeviceImageStore:
         perms, e0 = self._perms_for(seed, g0 // N, (g0 + n_items - 1) // N)
         triples = torch.empty(n_items * patch_n, 3, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().wdm_data_draw(_lib.handle(self.device.index or 0), _lib.ptr(self._sizes), N, _lib.ptr(perms), e0, int(perms.shape[0]), g0, n_items,
-                                                patch_n, p, _signed64(seed), _lib.ptr(triples), _lib.stream_ptr()))
-        return triples
+            if not mask:
+                _lib.check(_lib.lib().wdm_data_draw(_lib.handle(self.device.index or 0), _lib.ptr(self._sizes), N, _lib.ptr(perms), e0, int(perms.shape[0]), g0,
+                                                    n_items, patch_n, p, _signed64(seed), _lib.ptr(triples), _lib.stream_ptr()))
+                return triples
+            if not p:
+                mask = self.whole_image_mask(augment)
+            orient = torch.empty(n_items * patch_n, dtype=torch.int32, device=self.device)
+            _lib.check(_lib.lib().wdm_data_draw_oriented(_lib.handle(self.device.index or 0), _lib.ptr(self._sizes), N, _lib.ptr(perms), e0, int(perms.shape[0]), g0,
+                                                         n_items, patch_n, p, _signed64(seed), mask, _lib.ptr(triples), _lib.ptr(orient), _lib.stream_ptr()))
+        return triples, orient
 
-    def gather_training_samples(self, triples, patch_size, pred_channels, other_channels_begin, want_crops=False):
+    def _check_orient(self, orient, n, where):
+        if not (orient.is_cuda and orient.dtype == torch.int32 and orient.dim() == 1 and orient.shape[0] == n and orient.is_contiguous()):
+            raise ValueError(f"DeviceImageStore.{where}: orient must be a contiguous ({n},) int32 tensor on the GPU, one code per sample")
+
+    def gather_training_samples(self, triples, patch_size, pred_channels, other_channels_begin, want_crops=False, orient=None):
         """triples (n, 3) int32 -> x0 (n, 48 + pc + 48 - ob, p/4, p/4) f32 [, crops01 (n, 6, p, p) f32] (wdm_train_sample_gather).  The triples must lie
-        inside their images (draw's do): the kernel cannot check them."""
+        inside their images (draw's do): the kernel cannot check them.  orient (n,) int32 codes 0 .. 7 (draw's, or the caller's own): every crop is oriented
+        before the transform (wdm_train_sample_gather_oriented)."""
         if not (triples.is_cuda and triples.dtype == torch.int32 and triples.dim() == 2 and triples.shape[1] == 3 and triples.is_contiguous()):
             raise ValueError("DeviceImageStore.gather_training_samples: triples must be a contiguous (n, 3) int32 tensor on the GPU")
         n, p, pc, ob = int(triples.shape[0]), int(patch_size), int(pred_channels), int(other_channels_begin)
+        if orient is not None:
+            self._check_orient(orient, n, "gather_training_samples")
         ok = p >= 4 and p % 4 == 0 and 1 <= pc <= 48 and 0 <= ob <= 48
         x0 = torch.empty((n, 48 + pc + 48 - ob, p // 4, p // 4) if ok else (1,), dtype=torch.float32, device=self.device)
         crops = torch.empty((n, 6, p, p) if ok else (1,), dtype=torch.float32, device=self.device) if want_crops else None
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().wdm_train_sample_gather(_lib.handle(self.device.index or 0), _lib.ptr(self._pixels), _lib.ptr(self._offsets), _lib.ptr(self._sizes),
-                                                          _lib.ptr(triples), n, p, pc, ob, _lib.ptr(x0), None if crops is None else _lib.ptr(crops), _lib.stream_ptr()))
+            if orient is None:
+                _lib.check(_lib.lib().wdm_train_sample_gather(_lib.handle(self.device.index or 0), _lib.ptr(self._pixels), _lib.ptr(self._offsets),
+                                                              _lib.ptr(self._sizes), _lib.ptr(triples), n, p, pc, ob, _lib.ptr(x0),
+                                                              None if crops is None else _lib.ptr(crops), _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().wdm_train_sample_gather_oriented(_lib.handle(self.device.index or 0), _lib.ptr(self._pixels), _lib.ptr(self._offsets),
+                                                                       _lib.ptr(self._sizes), _lib.ptr(triples), _lib.ptr(orient), n, p, pc, ob, _lib.ptr(x0),
+                                                                       None if crops is None else _lib.ptr(crops), _lib.stream_ptr()))
         return (x0, crops) if want_crops else x0
 
-    def gather_images(self, idx, idx_stride=1):
+    def gather_images(self, idx, idx_stride=1, orient=None):
         """Whole images idx[k * idx_stride] -> (inp, gt), each (n, 3, H, W) f32 in [0, 1] (wdm_store_gather_images).  idx: int32 on the GPU -- a (n,) list or the
-        (n, 3) triples of draw(patch_size=0) with idx_stride=3.  All images of the store must have one size."""
+        (n, 3) triples of draw(patch_size=0) with idx_stride=3.  All images of the store must have one size.  orient (n,) int32: image k is oriented by its code
+        (wdm_store_gather_images_oriented); on images that are not square bit 2 of every code is ignored."""
         hw = self.uniform_size
         if hw is None:
             raise ValueError("DeviceImageStore.gather_images: the images of the store differ in size (whole-image batches need one size)")
         if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() % idx_stride == 0 and idx.numel() > 0):
             raise ValueError("DeviceImageStore.gather_images: idx must be a contiguous int32 tensor on the GPU")
         n = idx.numel() // idx_stride
+        if orient is not None:
+            self._check_orient(orient, n, "gather_images")
         inp = torch.empty(n, 3, hw[0], hw[1], dtype=torch.float32, device=self.device)
         gt = torch.empty_like(inp)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().wdm_store_gather_images(_lib.handle(self.device.index or 0), _lib.ptr(self._pixels), _lib.ptr(self._offsets), _lib.ptr(idx),
-                                                          int(idx_stride), n, hw[0], hw[1], _lib.ptr(inp), _lib.ptr(gt), _lib.stream_ptr()))
+            if orient is None:
+                _lib.check(_lib.lib().wdm_store_gather_images(_lib.handle(self.device.index or 0), _lib.ptr(self._pixels), _lib.ptr(self._offsets), _lib.ptr(idx),
+                                                              int(idx_stride), n, hw[0], hw[1], _lib.ptr(inp), _lib.ptr(gt), _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().wdm_store_gather_images_oriented(_lib.handle(self.device.index or 0), _lib.ptr(self._pixels), _lib.ptr(self._offsets),
+                                                                       _lib.ptr(idx), int(idx_stride), _lib.ptr(orient), 7 if hw[0] == hw[1] else 3, n, hw[0], hw[1],
+                                                                       _lib.ptr(inp), _lib.ptr(gt), _lib.stream_ptr()))
         return inp, gt
 
-    def step_images(self, seed, step, batch, world=1, rank=0):
-        """The HFRM trainer's batch of optimizer step `step`: the item stream with whole images and no crop."""
-        return self.gather_images(self.draw(seed, first_item(step, world, rank, batch), batch, 1, 0), idx_stride=3)
+    def step_images(self, seed, step, batch, world=1, rank=0, augment=None):
+        """The HFRM trainer's batch of optimizer step `step`: the item stream with whole images and no crop; under `augment`, each pair in its drawn orientation."""
+        g0 = first_item(step, world, rank, batch)
+        if not augment_mask(augment):
+            return self.gather_images(self.draw(seed, g0, batch, 1, 0), idx_stride=3)
+        triples, orient = self.draw(seed, g0, batch, 1, 0, augment=augment)
+        return self.gather_images(triples, idx_stride=3, orient=orient)

@@ -307,15 +307,16 @@ class HFRMTrainer:
         self.optimizer_step()
         return (loss, psnr, out) if return_output else (loss, psnr)
 
-    def train_step_from_store(self, store, batch_size=8, data_seed=None, return_output=False, return_batch=False):
+    def train_step_from_store(self, store, batch_size=8, data_seed=None, return_output=False, return_batch=False, augment=None):
         """train_step on whole images of a DeviceImageStore (device_data.py): item j of step s is global item (s - 1) * batch_size + j of the store's item stream
         (epoch permutations keyed by the data seed; no crop), gathered to float on the device by one kernel.  All images must have one size.  The seed is
-        `data_seed`, else this trainer's (drawn once from torch's global generator).  return_batch appends (inp, gt)."""
+        `data_seed`, else this trainer's (drawn once from torch's global generator).  return_batch appends (inp, gt).  augment ("none", "hflip", "flips", "d4";
+        default none): each pair in its drawn orientation; images that are not square take no transpose (DeviceImageStore.whole_image_mask)."""
         if data_seed is not None:
             self.data_seed = int(data_seed) & ((1 << 63) - 1)
         if getattr(self, "data_seed", None) is None:
             from .device_data import draw_data_seed
             self.data_seed = draw_data_seed()
-        inp, gt = store.step_images(self.data_seed, self.step + 1, int(batch_size))
+        inp, gt = store.step_images(self.data_seed, self.step + 1, int(batch_size), augment=augment)
         res = self.train_step(inp, gt, return_output=return_output)
         return res + (inp, gt) if return_batch else res

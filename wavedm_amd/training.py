@@ -601,40 +601,51 @@ class Trainer:
             self.data_seed = int(st.item())
         return self.data_seed
 
-    def store_draw(self, store, group=None, step=None):
+    def store_draw(self, store, group=None, step=None, augment=None):
         """The (img, row, col) triples of the samples optimizer step `step` (default: the next one) takes on this rank: training.batch_size items of
-        training.patch_n crops of data.patch_size pixels, a function of (data_seed, step, rank, world) alone (device_data.first_item)."""
+        training.patch_n crops of data.patch_size pixels, a function of (data_seed, step, rank, world) alone (device_data.first_item).  Under data.augment
+        (or the keyword, which wins) other than "none": (triples, orientation codes), a function of the mode as well."""
         import torch.distributed as dist
-        from .device_data import first_item
+        from .device_data import augment_mode, first_item
         world, rank = (dist.get_world_size(group), dist.get_rank(group)) if (dist.is_available() and dist.is_initialized()) else (1, 0)
         b, patch_n = int(self.config.training.batch_size), int(self.config.training.patch_n)
         g0 = first_item(self.step + 1 if step is None else step, world, rank, b)
-        return store.draw(self._ensure_data_seed(), g0, b, patch_n, int(self.config.data.patch_size))
+        mode = augment_mode(self.config, augment)
+        if mode == "none":
+            return store.draw(self._ensure_data_seed(), g0, b, patch_n, int(self.config.data.patch_size))
+        return store.draw(self._ensure_data_seed(), g0, b, patch_n, int(self.config.data.patch_size), augment=mode)
 
-    def sample_from_store(self, store, group=None, other_bands=None, step=None):
+    def sample_from_store(self, store, group=None, other_bands=None, step=None, augment=None):
         """x0 of the next step, drawn and cut on the device: assemble_training_sample's tensor without a float crop, a second DWT launch or a cat.  With
         model.use_gt_in_train: False the kernel also writes the [0,1] crops and `other_bands(input crops (n,3,p,p)) -> (n,48,p/4,p/4)` supplies the bands from
-        other_channels_begin on (DenoisingDiffusion_Wavelet passes its HFRM -> DWT(2x - 1) path)."""
+        other_channels_begin on (DenoisingDiffusion_Wavelet passes its HFRM -> DWT(2x - 1) path).  Under data.augment (or `augment`) every crop takes its drawn
+        orientation inside the gather; the HFRM then sees the oriented crops."""
+        from .device_data import augment_mode
         m = self.config.model
         if getattr(self.config.data, "global_attn", False):
             raise NotImplementedError("the device-resident data path does not feed the data.global_attn model: it needs `total`, the whole resized image, which the store does not keep")
         if not m.use_other_channels:
             raise NotImplementedError("training with model.use_other_channels: False is not built (DenoisingDiffusion_Wavelet.assemble_training_sample)")
-        triples = self.store_draw(store, group, step)
+        mode = augment_mode(self.config, augment)
+        kw = {}                                                                 # `none`: the calls, kernels and arguments of a run without the key
+        if mode == "none":
+            triples = self.store_draw(store, group, step, augment=mode)
+        else:
+            triples, kw["orient"] = self.store_draw(store, group, step, augment=mode)
         p, pc, ob = int(self.config.data.patch_size), int(m.pred_channels), int(m.other_channels_begin)
         if getattr(m, "use_gt_in_train", True) or ob >= 48:
-            return store.gather_training_samples(triples, p, pc, ob)
+            return store.gather_training_samples(triples, p, pc, ob, **kw)
         if other_bands is None:
             raise ValueError("Trainer.sample_from_store: model.use_gt_in_train: False needs other_bands (the HFRM path of assemble_training_sample)")
-        head, crops = store.gather_training_samples(triples, p, pc, 48, want_crops=True)
+        head, crops = store.gather_training_samples(triples, p, pc, 48, want_crops=True, **kw)
         with torch.no_grad():
             other = other_bands(crops[:, :3].contiguous())
         return torch.cat([head, other[:, ob:]], dim=1).contiguous()
 
-    def train_step_from_store(self, store, group=None, generator=None, other_bands=None):
-        """train_step on samples drawn and cut from a DeviceImageStore: two launches (wdm_data_draw, wdm_train_sample_gather) in front of the unchanged step; noise and
-        timesteps come from torch's device generator exactly as in train_step."""
-        return self.train_step(self.sample_from_store(store, group, other_bands), group=group, generator=generator)
+    def train_step_from_store(self, store, group=None, generator=None, other_bands=None, augment=None):
+        """train_step on samples drawn and cut from a DeviceImageStore: two launches (wdm_data_draw, wdm_train_sample_gather; their *_oriented forms under
+        data.augment / `augment`) in front of the unchanged step; noise and timesteps come from torch's device generator exactly as in train_step."""
+        return self.train_step(self.sample_from_store(store, group, other_bands, augment=augment), group=group, generator=generator)
 
     # ---- optimizer state in torch.optim.Adam's state_dict layout (what the reference saves and restores, ddm_wavelet.py:186, :288) ---------
     def param_order(self):
