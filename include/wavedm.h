@@ -404,6 +404,21 @@ int wdm_to_u8_hwc(wdm_handle* h, const float* x, int B, int C, int H, int W, uin
 int wdm_image_ingest(wdm_handle* h, const uint8_t* src, int B, int H, int W, float* dst, int Hp, int Wp, void* stream);
 int wdm_to_u8_hwc_crop(wdm_handle* h, const float* x, int B, int C, int Hp, int Wp, int H, int W, uint8_t* y, void* stream);
 
+/* ---- orientations of whole fp32 pictures: the HFRM's test-time self-ensemble (csrc/imageio.hip) ----------------
+ * Orientation code o in 0 .. 7, data.augment's (the comment above wdm_data_draw_oriented): O_o(t) = o & 1: t.flip(-1), then o & 2: t.flip(-2), then o & 4: t.transpose(-1, -2).
+ * Its inverse D_o undoes the steps in reverse order: transpose if o & 4, then flip(-2) if o & 2, then flip(-1) if o & 1 -- the same map for every code but the
+ * two quarter turns 5 and 6, which are each other's inverse.
+ * wdm_image_orient: x (B,C,H,W) f32 NCHW -> y = O_o(x), (B,C,H,W) without bit 2 and (B,C,W,H) with it; a copy: the bits of x.
+ * wdm_image_deorient_accumulate: H and W are ACC's; y is (B,C,H,W) without bit 2 of o and (B,C,W,H) with it (what wdm_image_orient wrote for these H, W, o).
+ *   first != 0: acc = D_o(y) * scale;  first == 0: acc = (acc + D_o(y)) * scale -- fp32, the sum rounded once, then the product; 0 < scale <= 1, and 1.0f
+ *   leaves the bits alone.  The mean of K members in ascending order is K calls, first on the first, scale = 1/K on the last, 1.0f before; no atomics, and
+ *   every element of acc is written by one thread.
+ * Both: any B, C, H, W >= 1 within a grid of 2^31 - 1 tiles of 64 x 64; 64-bit element offsets; pointers 4-byte aligned, and 16-byte accesses on a side whose
+ * rows are a multiple of 4 long when both pointers are 16-byte aligned.  x and y (y and acc) must not overlap.  o outside 0 .. 7, a size below 1, a misaligned
+ * or null pointer, a scale outside (0, 1]: WDM_EINVAL, nothing is launched.  Queued on `stream`; no host synchronisation. */
+int wdm_image_orient(wdm_handle* h, const float* x, int B, int C, int H, int W, int o, float* y, void* stream);
+int wdm_image_deorient_accumulate(wdm_handle* h, const float* y, int B, int C, int H, int W, int o, int first, float scale, float* acc, void* stream);
+
 /* ---- training data resident in HBM (wavedm_amd/device_data.py: DeviceImageStore; csrc/device_data.hip) ----------------
  * The store: N (input, ground truth) pairs as uint8 HWC in one flat device buffer `pixels` without padding; `offsets` (N,2) int64 = byte offset of pair i's
  * input and ground truth, `sizes` (N,2) int32 = H, W of pair i (both images of a pair).  Read-only for every call here.

@@ -69,6 +69,11 @@ def parse(argv=None):
                     help="with --hfrm-local: the pooling window at full resolution (default 720 1080, 1.5 x the training size)")
     ap.add_argument("--hfrm-train-size", dest="hfrm_train_size", type=int, nargs=2, metavar=("H", "W"), default=None,
                     help="with --hfrm-local: the size of the HFRM's training images (default 480 720)")
+    ap.add_argument("--hfrm-self-ensemble", dest="hfrm_self_ensemble", default="none", choices=["none", "hflip", "flips", "d4"],
+                    help="eval, restore: the HFRM image is the mean of the HFRM's outputs over the orientations of the picture -- hflip: as it is and mirrored left-right; "
+                         "flips: both mirrors (4 passes); d4: the eight symmetries of the square (8 passes, the \"x8\" self-ensemble of NAFNet-style toolkits) -- each "
+                         "output turned back first, summed in fp32 in a fixed order (HFRM.forward_self_ensemble).  The sampler runs once, as without the flag.  Meant "
+                         "for an HFRM trained with --augment; its effect on restoration quality has not been measured.")
     ap.add_argument("--max_steps", type=int, default=None)
     ap.add_argument("--grad_clip", type=float, default=None, metavar="X",
                     help="train: clip the global 2-norm of the gradient to X before the optimizer step (overrides optim.grad_clip; 0: off)")
@@ -123,6 +128,8 @@ def parse(argv=None):
         train = tuple(a.hfrm_train_size) if a.hfrm_train_size else HFRM_LOCAL_DEFAULT[1][-2:]
         base = tuple(a.hfrm_base_size) if a.hfrm_base_size else (train[0] * 3 // 2, train[1] * 3 // 2)
         a.hfrm_local = (base, (1, 3) + tuple(train))
+    if a.hfrm_self_ensemble != "none" and a.mode == "train":
+        ap.error("--hfrm-self-ensemble is a test-time mode (eval, restore)")
     if a.mode == "restore" and not (a.input and (a.output or a.no_save)):
         ap.error("restore needs --input DIR and --output DIR (or --no_save)")
     if a.mode != "train" and (a.grad_clip is not None or a.skip_nonfinite):

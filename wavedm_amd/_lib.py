@@ -133,6 +133,8 @@ def lib():
         "wdm_to_u8_hwc": (i, [vp, vp, i, i, i, i, vp, vp]),
         "wdm_image_ingest": (i, [vp, vp, i, i, i, vp, i, i, vp]),
         "wdm_to_u8_hwc_crop": (i, [vp, vp, i, i, i, i, i, i, vp, vp]),
+        "wdm_image_orient": (i, [vp, vp, i, i, i, i, i, vp, vp]),
+        "wdm_image_deorient_accumulate": (i, [vp, vp, i, i, i, i, i, i, f, vp, vp]),
         "wdm_data_draw": (i, [vp, vp, i64, vp, i64, i, i64, i, i, i, i64, vp, vp]),
         "wdm_train_sample_gather": (i, [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp]),
         "wdm_store_gather_images": (i, [vp, vp, vp, vp, i, i, i, i, vp, vp, vp]),
@@ -209,7 +211,7 @@ EXPORTED = ["wdm_abi_version", "wdm_last_error", "wdm_create", "wdm_destroy", "w
             "wdm_unet_forward", "wdm_unet_temb_rows", "wdm_unet_temb_table", "wdm_unet_forward_temb", "wdm_unet_num_taps", "wdm_unet_tap_info", "wdm_unet_forward_taps", "wdm_resblock_forward", "wdm_attn_forward", "wdm_conv_forward", "wdm_temb_forward",
             "wdm_hfrm_create", "wdm_hfrm_destroy", "wdm_hfrm_num_params", "wdm_hfrm_param_info", "wdm_hfrm_packed_bytes",
             "wdm_hfrm_set_packed", "wdm_hfrm_load_param", "wdm_hfrm_finalize", "wdm_hfrm_workspace_bytes",
-            "wdm_hfrm_forward", "wdm_hfrm_set_local", "wdm_hfrm_local_kernel", "wdm_hfrm_local_pool", "wdm_hfrm_set_max_launch_bytes", "wdm_hfrm_chunk_rows", "wdm_hfrm_conv_out", "wdm_hfrm_stage_workspace_bytes", "wdm_hfrm_stage_forward", "wdm_image_sqdiff", "wdm_to_u8_hwc", "wdm_image_ingest", "wdm_to_u8_hwc_crop", "wdm_data_draw", "wdm_train_sample_gather", "wdm_store_gather_images", "wdm_data_draw_oriented", "wdm_train_sample_gather_oriented", "wdm_store_gather_images_oriented", "wdm_image_ssim_scratch_bytes", "wdm_image_ssim", "wdm_conv_backward", "wdm_gn_act_backward", "wdm_dropout_mask", "wdm_gn_act_dropout", "wdm_trainer_create", "wdm_trainer_destroy", "wdm_trainer_num_params",
+            "wdm_hfrm_forward", "wdm_hfrm_set_local", "wdm_hfrm_local_kernel", "wdm_hfrm_local_pool", "wdm_hfrm_set_max_launch_bytes", "wdm_hfrm_chunk_rows", "wdm_hfrm_conv_out", "wdm_hfrm_stage_workspace_bytes", "wdm_hfrm_stage_forward", "wdm_image_sqdiff", "wdm_to_u8_hwc", "wdm_image_ingest", "wdm_to_u8_hwc_crop", "wdm_image_orient", "wdm_image_deorient_accumulate", "wdm_data_draw", "wdm_train_sample_gather", "wdm_store_gather_images", "wdm_data_draw_oriented", "wdm_train_sample_gather_oriented", "wdm_store_gather_images_oriented", "wdm_image_ssim_scratch_bytes", "wdm_image_ssim", "wdm_conv_backward", "wdm_gn_act_backward", "wdm_dropout_mask", "wdm_gn_act_dropout", "wdm_trainer_create", "wdm_trainer_destroy", "wdm_trainer_num_params",
             "wdm_trainer_num_floats", "wdm_trainer_param_info", "wdm_trainer_set_buffers", "wdm_trainer_set_objective", "wdm_trainer_set_dropout", "wdm_trainer_step", "wdm_trainer_stage_workspace_bytes", "wdm_trainer_stage", "wdm_trainer_adam_ema", "wdm_trainer_set_optimizer", "wdm_trainer_optim_step", "wdm_optim_step", "wdm_grad_guard_scratch_bytes", "wdm_grad_guard", "wdm_optim_step_guarded", "wdm_trainer_optim_step_guarded",
             "wdm_trainer_set_grad_events", "wdm_trainer_grad_buckets", "wdm_hfrm_trainer_create", "wdm_hfrm_trainer_destroy", "wdm_hfrm_trainer_num_params", "wdm_hfrm_trainer_num_floats",
             "wdm_hfrm_trainer_param_info", "wdm_hfrm_trainer_set_buffers", "wdm_hfrm_trainer_set_precision", "wdm_hfrm_trainer_workspace_bytes", "wdm_hfrm_trainer_step", "wdm_hfrm_trainer_stage_workspace_bytes", "wdm_hfrm_trainer_stage", "wdm_hfrm_trainer_adam", "wdm_hfrm_trainer_adam_guarded", "wdm_dwt_fwd_affine", "wdm_dwt_inv_compose", "wdm_ensemble_compose", "wdm_conv2d_direct", "wdm_groupnorm", "wdm_cross_attention", "wdm_upsample_add",

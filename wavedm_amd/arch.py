@@ -176,13 +176,18 @@ class HFRM(nn.Module):
         self._packed_sig = sig
         return self._packed
 
-    def _workspace(self, B, H, W, device):
+    def _workspace(self, B, H, W, device, keep_transposed=False):
+        """The cached workspace of a (B, H, W) call.  One entry; with keep_transposed (forward_self_ensemble's members alternate between H x W and W x H) the
+        entry of (B, W, H) stays beside it, so that no member allocates once both exist."""
         key = (B, H, W, str(device), self._local)
         if key not in self._ws:
             n = int(_lib.lib().wdm_hfrm_workspace_bytes(self._m, B, H, W))
             if n == 0:
                 raise RuntimeError("wdm_hfrm_workspace_bytes failed: " + _lib.lib().wdm_last_error().decode())
-            self._ws = {key: torch.empty(n + 256, dtype=torch.uint8, device=device)}
+            other = (B, W, H) + key[3:]
+            kept = {other: self._ws[other]} if keep_transposed and other in self._ws else {}
+            self._ws = kept                                            # everything else is released before the new one is asked for
+            self._ws[key] = torch.empty(n + 256, dtype=torch.uint8, device=device)
         return self._ws[key]
 
     STAGES = {"block": 0, "down": 1, "up": 2, "conv_in": 3, "conv_out": 4}
@@ -213,6 +218,49 @@ class HFRM(nn.Module):
         return y if kind == "conv_out" else y.permute(0, 3, 1, 2).float().contiguous()
 
     def forward(self, x):
+        return self._forward(x)
+
+    def forward_self_ensemble(self, x, mode, return_members=False):
+        """Geometric self-ensemble at test time: the mean of the network's outputs over the orientations of `mode` -- "none", "hflip", "flips" or "d4",
+        device_data.AUGMENT_MASKS -- each output turned back.  Orientation o in 0 .. 7 is O_o(t) = o & 1: t.flip(-1), then o & 2: t.flip(-2), then o & 4:
+        t.transpose(-1, -2); its inverse D_o takes the steps back in reverse order.  The members are the codes o with o & ~mask == 0, ascending (K = 1, 2, 4, 8):
+
+            y_k = forward(O_{o_k}(x))                                    -- the bits forward returns for the host-oriented, contiguous batch
+            r   = (((D y_0 + D y_1) + ...) + D y_{K-1}) * (1 / K)       -- fp32, every sum rounded once, in this order; the product is exact
+
+        x (B, 3, H, W) fp32 on the GPU, H and W multiples of 16 (a transposed picture is W x H: legal).  "none" is forward(x): the same launches.  One member's
+        output is alive at a time; with return_members=True -> (r, [y_k]) (tests, diagnosis).  Test-time only: the trainer never calls it."""
+        from .device_data import augment_mask
+        mask = augment_mask(mode)
+        if mask == 0:
+            y = self.forward(x)
+            return (y, [y]) if return_members else y
+        x = _lib.require_cuda_f32(x, "HFRM input")
+        B, Cc, H, W = x.shape
+        codes = [o for o in range(8) if o & ~mask == 0]
+        L, h = _lib.lib(), _lib.handle(x.device.index or 0)
+        members, acc = [], None
+        with torch.cuda.device(x.device):
+            xo = torch.empty(x.numel(), dtype=torch.float32, device=x.device)
+            for k, o in enumerate(codes):
+                if o == 0:                                                  # O_0 and D_0 are the identity: the member reads x itself
+                    y = self._forward(x, keep_transposed=True)
+                else:
+                    xk = xo.view(B, Cc, W, H) if o & 4 else xo.view(B, Cc, H, W)
+                    _lib.check(L.wdm_image_orient(h, _lib.ptr(x), B, Cc, H, W, o, _lib.ptr(xk), _lib.stream_ptr()))
+                    y = self._forward(xk, keep_transposed=True)
+                if return_members:
+                    members.append(y)
+                if o == 0 and not return_members:
+                    acc = y                                                 # ... and its output is the accumulator's first value as it stands
+                    continue
+                if acc is None:
+                    acc = torch.empty_like(x)
+                scale = 1.0 / len(codes) if k == len(codes) - 1 else 1.0
+                _lib.check(L.wdm_image_deorient_accumulate(h, _lib.ptr(y), B, Cc, H, W, o, int(k == 0), scale, _lib.ptr(acc), _lib.stream_ptr()))
+        return (acc, members) if return_members else acc
+
+    def _forward(self, x, keep_transposed=False):
         x = _lib.require_cuda_f32(x, "HFRM input")
         B, Cc, H, W = x.shape
         if Cc != self.in_channel:
@@ -226,7 +274,7 @@ class HFRM(nn.Module):
         with torch.cuda.device(x.device):
             for b0 in range(0, B, chunk):
                 nb = min(chunk, B - b0)
-                ws = self._workspace(nb, H, W, x.device)
+                ws = self._workspace(nb, H, W, x.device, keep_transposed)
                 _lib.check(L.wdm_hfrm_forward(self._m, _lib.ptr(x[b0:b0 + nb]), nb, H, W, _lib.ptr(y[b0:b0 + nb]),
                                               _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
         return y

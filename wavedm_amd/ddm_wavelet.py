@@ -91,6 +91,17 @@ class DenoisingDiffusion_Wavelet(object):
                 import warnings
                 warnings.warn("args.hfrm_local is set, but .generator is not an HFRM (the identity stand-in, or a callable): ignored", stacklevel=2)
                 self.hfrm_local = None
+        # args.hfrm_self_ensemble: "none" (or absent), "hflip", "flips", "d4" -- at test time the HFRM image is the mean over these orientations
+        # (HFRM.forward_self_ensemble, called from DiffusiveRestoration._condition); self.hfrm_self_ensemble is the mode IN FORCE: "none" wherever no HFRM runs
+        from .device_data import augment_mode
+        self.hfrm_self_ensemble = augment_mode(None, getattr(args, "hfrm_self_ensemble", None))
+        if self.hfrm_self_ensemble != "none":
+            no_call = config.model.pred_channels >= config.model.in_channels
+            if no_call or not hasattr(self.generator, "forward_self_ensemble"):
+                import warnings
+                warnings.warn("args.hfrm_self_ensemble is set, but " + ("model.pred_channels == model.in_channels makes no HFRM call" if no_call else
+                              ".generator is not an HFRM (the identity stand-in, or a callable)") + ": ignored", stacklevel=2)
+                self.hfrm_self_ensemble = "none"
 
         if getattr(config.data, "global_attn", False):                          # ddm_wavelet.py:149-152
             from .unet_global import DiffusionUNet_Global

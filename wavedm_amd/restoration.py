@@ -143,15 +143,18 @@ def _workspace_bytes(kind, cfg, *dims, local=None):
     return _WS_BYTES[key]
 
 
-def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None, samples=1):
+def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None, samples=1, hfrm_self_ensemble=None):
     """The terms of estimate_restore_bytes, by name.  `hfrm_local`: what DenoisingDiffusion_Wavelet.hfrm_local holds -- None, or (base_size, train_size)
-    of the HFRM's local pooling, whose workspace is larger.  `samples`: trajectories per image (args.samples) -- the sampler's state (start noise, the kept
-    x_t and x0, eps, the gathered UNet input's rows) is held per sample, the conditioning and the HFRM per image."""
+    of the HFRM's local pooling, whose workspace is larger.  `hfrm_self_ensemble`: None / "none", "hflip", "flips", "d4" (HFRM.forward_self_ensemble): the HFRM
+    term grows by the oriented input, one member's output and the accumulator, and with "d4" by the workspace of the transposed picture.  `samples`:
+    trajectories per image (args.samples) -- the sampler's state (start noise, the kept x_t and x0, eps, the gathered UNet input's rows) is held per sample,
+    the conditioning and the HFRM per image."""
     samples = int(samples)
     if samples < 1:
         raise ValueError(f"restore_terms: samples = {samples} (at least 1)")
     from .arch import HFRM
     from .ddm_wavelet import DenoisingDiffusion_Wavelet
+    from .device_data import augment_mask
     from .procedural import unet_in_channels
     from .unet import _make_config, resolve_dtype
     m, p = config.model, int(config.data.image_size)
@@ -182,17 +185,24 @@ def restore_terms(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps
             hc.dec_blk_nums[i] = v
         local = HFRM.local_sizes(*hfrm_local) if hfrm_local else None
         hfrm = int(_workspace_bytes("hfrm", hc, 1, hp, wp, local=local) * min(float(n_img), max(1.0, HFRM.MAX_PIXELS / px)))
+        mask = augment_mask(hfrm_self_ensemble)
+        if mask:
+            # both workspaces are counted for a square picture as well: the term must not fall where a picture grows into a square
+            if mask & 4:
+                hfrm += int(_workspace_bytes("hfrm", hc, 1, wp, hp, local=local) * min(float(n_img), max(1.0, HFRM.MAX_PIXELS / px)))
+            hfrm += 3 * n_img * 3 * px * 4
     # the UNet's workspace is kept at the largest call's size (DiffusionUNet.workspace); the sampler's calls never exceed min(n, max_batch) patches
     unet = _workspace_bytes("unet", _make_config(config, code), min(n, mb))
     return dict(x96=n * p * p * cin * elsize, eps=n * pc * p * p * 4, full=full, hfrm=hfrm, unet=unet)
 
 
-def estimate_restore_bytes(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None, samples=1):
+def estimate_restore_bytes(h, w, n_img, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None, samples=1, hfrm_self_ensemble=None):
     """Device bytes one sampler call of restore_folder needs for `n_img` images of h x w pixels -- host arithmetic, nothing is allocated: the gathered UNet
     input (n patches x p x p x cin in the compute type), eps (n x pc x p x p f32), the f32 tensors of the group's padded size, the HFRM's workspace and the
     UNet's for the largest call.  `r`: the patch grid's stride (default 16), `steps`: the DDIM steps, `hfrm_local`: the HFRM's local-pooling mode (restore_terms).
-    `samples`: trajectories per image (restore_terms).  Non-decreasing in h, w, n_img and samples."""
-    return sum(restore_terms(h, w, n_img, config, max_batch, dtype, r, steps, hfrm_local, samples).values())
+    `samples`: trajectories per image (restore_terms).  `hfrm_self_ensemble`: the HFRM's self-ensemble mode (restore_terms).  Non-decreasing in h, w, n_img,
+    samples and the mode (none, hflip = flips, d4)."""
+    return sum(restore_terms(h, w, n_img, config, max_batch, dtype, r, steps, hfrm_local, samples, hfrm_self_ensemble).values())
 
 
 def folder_patch_count(h, w, p, r=None):
@@ -202,7 +212,7 @@ def folder_patch_count(h, w, p, r=None):
     return len(hl) * len(wl)
 
 
-def estimate_restore_bytes_mixed(sizes, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None):
+def estimate_restore_bytes_mixed(sizes, config, max_batch=None, dtype=None, r=None, steps=25, hfrm_local=None, hfrm_self_ensemble=None):
     """estimate_restore_bytes for ONE sampler call over photographs of different sizes (args.mix_sizes), `sizes` a list of (h, w) in pixels: every image's
     own x96, eps and full terms (all three are linear in the images), the LARGEST HFRM term -- the HFRM runs over one run of equal-sized images at a time;
     each image's term is taken as if the whole group had its size, the most any run of it can need, which also keeps the estimate from falling when an image
@@ -218,7 +228,7 @@ def estimate_restore_bytes_mixed(sizes, config, max_batch=None, dtype=None, r=No
         t = restore_terms(h, w, 1, config, mb, dtype, r, steps, hfrm_local)
         total += t["x96"] + t["eps"] + t["full"]
         n += folder_patch_count(h, w, p, r)
-        hfrm = max(hfrm, restore_terms(h, w, len(sizes), config, mb, dtype, r, steps, hfrm_local)["hfrm"])
+        hfrm = max(hfrm, restore_terms(h, w, len(sizes), config, mb, dtype, r, steps, hfrm_local, hfrm_self_ensemble=hfrm_self_ensemble)["hfrm"])
     return total + hfrm + _workspace_bytes("unet", _make_config(config, resolve_dtype(config, dtype)), min(n, mb))
 
 
@@ -521,7 +531,8 @@ class DiffusiveRestoration:
         split, use_other = self._bands()
         hf = hf_wav = x_other = None
         if split:
-            hf = d.generator(x)                                                # :94 (HFRM)
+            mode = getattr(d, "hfrm_self_ensemble", "none")
+            hf = d.generator(x) if mode == "none" else d.generator.forward_self_ensemble(x, mode)     # :94 (HFRM; the mean over its orientations)
             self._mark("main: HFRM queued")
             hf_wav = d.wavelet_dec.forward_affine(hf.contiguous())             # :95-96
             if use_other:                                                      # :102
@@ -652,7 +663,8 @@ class DiffusiveRestoration:
         """(fits, estimate, limit) of estimate(*sizes, config, max_batch, dtype, r, steps, hfrm_local=, ...) against args.max_restore_bytes if set, else 0.8 of
         the device memory that is free now (what torch's allocator holds without using counts as free: it is handed out again)."""
         d, dev = self.diffusion, self.diffusion.device
-        est = estimate(*sizes, self.config, self._max_batch(), d.model.dtype_name, r, int(d.args.sampling_timesteps), hfrm_local=getattr(d, "hfrm_local", None), **kw)
+        est = estimate(*sizes, self.config, self._max_batch(), d.model.dtype_name, r, int(d.args.sampling_timesteps), hfrm_local=getattr(d, "hfrm_local", None),
+                       hfrm_self_ensemble=getattr(d, "hfrm_self_ensemble", None), **kw)
         limit = getattr(self.args, "max_restore_bytes", None)
         if not limit:
             limit = 0.8 * (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
