@@ -13,6 +13,10 @@ the gap the per-stage module closes (run with -s for the table; the figure is th
   head_no_log2e    conv_out's prologue scale not multiplied by -log2 e                                          1.30e+0  caught by both
 (ragged model, bf16, tolerance 2e-2.)  Every one of them fails exactly one per-stage check, the one of the stage it sits in.
 
+Two more defects are ones only some shapes can show (unet_fwd_ref.SHAPE_DEFECTS; test_shape_defect_fails_its_case_of_a_new_model): a group reduction that stops after the
+first 256 (channel, slab) items fails top64's up.0.block.1 and is invisible to the five old models; a concat reduction that takes the skip's slab count for both tensors
+fails deep's up.0.block.0 -- and ragged's, wide's and wide32's up blocks behind the 8 x 8 Upsample too, which is reported there, not hidden.
+
 `python tests/test_host_unet_fwd_ref.py [model ...]` prints the NEED table of test_gpu_unet_fwd_ref.py: what the emulation needs per group, worst over the stages of every
 model, the four fp32 GroupNorms (attn_ref.GN_VARIANTS) and both summation orders, on the emulated network's own taps."""
 import sys
@@ -38,6 +42,9 @@ def host_forms(st, kind):
     """the forms the emulated device runs: what the real one picks at these shapes (blocks.hip: run_attn, conv_up4_eligible), the four-term f32x3 products, and for a
     nin shortcut the caller's choice"""
     if st["kind"] == "attn":
+        if st["H"] ** 2 > 512:      # run_attn: beyond 512 tokens the streaming core (16-bit, C a multiple of 128), else Q.K^T, softmax and P.V per block of query rows
+            stream = kind in H16 and st["C"] % 128 == 0
+            return dict(attn="stream" if stream else "gemm", group="stream" if stream else "gemm")
         folded = kind in H16 and st["C"] % 128 == 0
         return dict(attn="folded" if folded else "gemm", group=("bdiag" if st["H"] == 8 else "folded") if folded else "gemm")
     if st["kind"] == "up":
@@ -55,11 +62,14 @@ def to_run(kind, x, taps, nrms, eps, table):
 _HOST = {}
 
 
-def host_run(model, kind, defect=None):
-    key = (model, kind, defect)
+def host_run(model, kind, defect=None, images=None):
+    """images: the first so many images of the model's batch only (an image's values do not depend on the batch)"""
+    key = (model, kind, defect, images)
     if key not in _HOST:
         cfg, sd = U.config(model), U.state(model)
         x, t = U.inputs(model)
+        if images is not None:
+            x, t = x[:images], t[:images]
         e = U.Emu(sd, cfg, kind, defect=defect, forms=lambda s: host_forms(s, kind))
         _HOST[key] = to_run(kind, x, *e.forward(x, t))
     return _HOST[key]
@@ -148,7 +158,7 @@ PLANT = {
 }
 
 
-@pytest.mark.parametrize("defect", U.DEFECTS)
+@pytest.mark.parametrize("defect", [d for d in U.DEFECTS if d not in U.SHAPE_DEFECTS])
 def test_defect_is_rejected_at_its_stage_and_only_there(defect):
     kind = "bf16"
     model, stage, where, subtle = PLANT[defect]
@@ -164,6 +174,53 @@ def test_defect_is_rejected_at_its_stage_and_only_there(defect):
     assert e_good <= TOL_NET[kind]
     if subtle:
         assert e_bad <= TOL_NET[kind], e_bad
+
+
+# the defects only some shapes can show -> (model, stage): the GPU module's case `<model>-bf16-<stage>` that must reject it
+SHAPE_PLANT = {"group_first_256": ("top64", "up.0.block.1"),        # [128 | 128] on 64 x 64: 8 channels x 64 slabs = 512 items per group
+               "concat_skip_nslab": ("deep", "up.0.block.0")}       # [768 | 512] on 16 x 16: the sub-pixel Upsample's 8 slabs beside the fused core's 4
+OLD_MODELS = ("narrow", "ragged", "wide", "wide32", "padded")
+
+
+@pytest.mark.parametrize("defect", U.SHAPE_DEFECTS)
+def test_shape_defect_fails_its_case_of_a_new_model(defect):
+    """the stage of the new model on the emulated network's own taps (image 0 of the GPU case: an image's values do not depend on the batch), once healthy and once with
+    the defect in its norm1: the GPU module's check of that stage passes the one and rejects the other.  Beside it what the five old models make of the same device:
+      group_first_256    no group of theirs has more than 256 (channel, slab) items -- 64 at most (wide32: 4 channels x 16 slabs) -- so such a device computes their
+                         very bits: the old module cannot see it.
+      concat_skip_nslab  REPORTED, not a gap: the old models do reach concats whose tensors differ in slab count (ragged, wide: the 8 x 8 -> 16 x 16 sub-pixel Upsample's 8
+                         slabs beside the 4 of a 16 x 16 producer) and their cases reject it (asserted below on ragged).  top64 cannot show it at all: every producer of
+                         its concats leaves H W / 64 slabs.  deep shows it at widths 768 | 512."""
+    import test_gpu_unet_fwd_ref as T
+    kind = "bf16"
+    forms_fn = lambda s: host_forms(s, kind)
+
+    def planted(model, stage, images):
+        cfg, sd = U.config(model), U.state(model)
+        r = host_run(model, kind, images=images)
+        st = next(s for s in U.stages(cfg) if s["name"] == stage)
+        forms = host_forms(st, kind)
+        fig = check_stage(model, kind, st, r, stage, forms=forms)[0]      # the healthy device passes
+        x0, x1, pre = T.stage_inputs(r, st)
+        rows = r["table"][:, st["temb"][0]:st["temb"][0] + st["temb"][1]]
+        y = U.stage_emu(sd, cfg, st, kind, x0, x1, rows, forms, pre, defect=(defect, stage), net_forms=forms_fn)
+        bad = dict(r, taps=dict(r["taps"], **{stage: y.permute(0, 2, 3, 1).contiguous().to(TORCH_DT[kind])}))
+        with pytest.raises(AssertionError) as err:
+            check_stage(model, kind, st, bad, stage, forms=forms)
+        return fig, str(err.value)[:160]
+    model, stage = SHAPE_PLANT[defect]
+    assert stage in U.shape_defect_touches(U.config(model), defect, forms_fn)
+    fig, msg = planted(model, stage, 1)
+    print(f"SHAPE DEFECT {defect} at {model} {stage} ({kind}): healthy {fig}; rejected: {msg}")
+    old = {m: U.shape_defect_touches(U.config(m), defect, forms_fn) for m in OLD_MODELS}
+    print(f"SHAPE DEFECT {defect}: stages of the old models it changes: {old}")
+    if defect == "group_first_256":
+        assert not any(old.values()), old
+        assert U.shape_defect_touches(U.config("top64"), defect, forms_fn) == ["up.0.block.0", "up.0.block.1", "up.0.block.2"]      # the 64 x 64 concats, nothing else
+    else:
+        assert old["ragged"] == ["up.0.block.0"] and old["wide"] == ["up.0.block.0"] and not old["narrow"], old
+        assert not U.shape_defect_touches(U.config("top64"), defect, forms_fn)
+        print(f"SHAPE DEFECT {defect}: the old module rejects it too (ragged up.0.block.0): {planted('ragged', 'up.0.block.0', None)[1]}")
 
 
 # ---- the NEED table ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -184,6 +241,8 @@ def measure(model, kind, need=None):
             variants.append(dict(shortcut="gemm"))
         if st["kind"] == "attn" and variants[0]["attn"] == "folded" and st["H"] == 16:
             variants.append(dict(attn="fused", group="fused"))      # WDM_ATTN_FOLD=0: the fused core on the unfolded operands
+        if st["kind"] == "attn" and variants[0]["attn"] == "stream":
+            variants.append(dict(attn="gemm", group="gemm"))        # WDM_ATTN_STREAM=0: Q.K^T, softmax and P.V per block of query rows
         x0, x1, pre = T.stage_inputs(r, st)
         rows = r["table"][:, st["temb"][0]:st["temb"][0] + st["temb"][1]] if st["temb"] else None
         for forms in variants:
@@ -222,14 +281,23 @@ def test_need_table_is_current():
 
 if __name__ == "__main__":
     runs = [(m, k) for m in ("narrow", "ragged", "wide", "padded") for k in U.KINDS] + [("wide32", "bf16"), ("wide32", "f32x3")]
+    # the shipped network's level shapes: their rows are printed per model (`<layer>@<model>`); test_gpu_unet_fwd_ref.NEED lists those that exceed the group's row
+    new = [("top64", "bf16"), ("top64", "f32x3"), ("deep", "bf16"), ("deep", "f16"), ("deep", "f32x3")]
     if len(sys.argv) > 1:
-        runs = [r for r in runs if r[0] in sys.argv[1:]]
+        runs, new = [r for r in runs if r[0] in sys.argv[1:]], [r for r in new if r[0] in sys.argv[1:]]
     table = {}
     for m, k in runs:
         measure(m, k, table)
         print(f"# measured {m} {k}", file=sys.stderr, flush=True)
+    for m, k in new:
+        for g, v in measure(m, k).items():
+            if g[0] != "temb":      # (the temb table is checked on the three small models)
+                table[(f"{g[0]}@{m}",) + tuple(g[1:])] = v
+        print(f"# measured {m} {k}", file=sys.stderr, flush=True)
     print("NEED = {")
     for g, v in sorted(table.items()):
         val = f"({v[0]:.2e}, {v[1]:.2e})" if isinstance(v, tuple) else f"{v:.3g}"
-        print(f"    {g!r}: {val},")
+        base = NEED.get((g[0].split("@")[0],) + tuple(g[1:])) if "@" in g[0] else None
+        more = base is not None and any(a > b for a, b in zip(v if isinstance(v, tuple) else (v,), base if isinstance(base, tuple) else (base,)))
+        print(f"    {g!r}: {val},{'      # more than the group row' if more else ''}")
     print("}")

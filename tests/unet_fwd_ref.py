@@ -39,6 +39,9 @@ MODELS = {
     "wide": dict(ch=128, image=16, ch_mult=(1, 2), attn=(16,)),
     "wide32": dict(ch=128, image=32, ch_mult=(1, 1, 2), attn=(8,)),
     "padded": dict(ch=32, image=16, ch_mult=(1, 2), attn=(16,), no_other=True),
+    # the shipped network's four level shapes (configs/raindrop_wavelet.yml: ch 128, ch_mult (1, 2, 4, 6) on 64 x 64) in the two smallest models that carry them:
+    "top64": dict(ch=128, image=64, ch_mult=(1, 2), attn=(32,)),      # 128 on 64 x 64, 256 on 32 x 32; every AttnBlock 1024 tokens at C = 256
+    "deep": dict(ch=128, image=16, ch_mult=(4, 6), attn=(16,)),       # 512 on 16 x 16, 768 on 8 x 8: the shipped model's lower half layer for layer
 }
 B = 3
 T_IMAGES = (990.0, 10.0, 500.0)      # per-image timesteps of the main run; the forward_temb run takes the row of T_SHARED
@@ -222,7 +225,78 @@ def temb_ref(sd, cfg, t, dt=torch.float64, kflip=False):
 
 
 # ---- the executor restated in fp32: the host tests' "device" ----------------------------------------------------------------------------------------------------
-DEFECTS = ("slab_missing", "seam_x0_only", "stats_unrounded", "nrm_wrong_silu", "nrm_stale", "skip_order", "head_no_log2e")
+DEFECTS = ("slab_missing", "seam_x0_only", "stats_unrounded", "nrm_wrong_silu", "nrm_stale", "skip_order", "head_no_log2e", "group_first_256", "concat_skip_nslab")
+# the two defects of a norm1's group reduction that only some SHAPES can show (gn_group.h: gn_group_load / gn_group_reduce walk a group's (channel, slab) items, tensor 0's
+# channels first, each with its tensor's slab count):
+#   group_first_256    the reduction stops after the first 256 items (the loads gn_group_load has in flight; the loop behind them never runs), the pixel count kept
+#   concat_skip_nslab  the items of tensor 0 of a concat are counted with the SKIP tensor's slab count, so that only that many of its slabs are summed
+SHAPE_DEFECTS = ("group_first_256", "concat_skip_nslab")
+
+
+def nslab_of(st, forms):
+    """statistics slabs per image of the tensor a stage stores, as its producer's tiling gives them (conv_dispatch.inc: check_stats' first argument): 64-row slabs on the
+    16-pixel-multiple maps whatever the kernel, two 32-row slabs on an 8 x 8 map, and the sub-pixel Upsample of an 8 x 8 map (8 x 8 x 4 tile) four phases x two"""
+    if st["kind"] == "up" and st["H"] == 16 and forms.get("up4"):
+        return 8
+    return 2 if st["H"] <= 8 else st["H"] * st["H"] // 64
+
+
+def shape_defect_keep(defect, c0, c1, H, ns0, ns1):
+    """the (channel, pixel row) items a norm1 with one of SHAPE_DEFECTS still sums: a bool mask (c0 + c1, H), or None where the defect changes nothing at this shape.
+    A slab is modelled as a run of consecutive image rows (H / nslab of them): which pixels a slab holds differs between the tilings, how many it holds does not."""
+    C = c0 + c1
+    gw = C // 32
+    keep = torch.ones(C, H, dtype=torch.bool)
+    if defect == "concat_skip_nslab":
+        if c1 == 0 or ns1 >= ns0:      # (more slabs than tensor 0 has would be read from the next image's rows: not modelled)
+            return None
+        keep[:c0, H * ns1 // ns0:] = False
+        return keep
+    assert defect == "group_first_256"
+    hit = False
+    for g in range(32):
+        seen = 0
+        for c in range(g * gw, (g + 1) * gw):
+            ns = ns0 if c < c0 else ns1
+            left = max(0, min(ns, 256 - seen))      # slabs of this channel inside the first 256 items
+            if left < ns:
+                keep[c, H * left // ns:] = False
+                hit = True
+            seen += ns
+    return keep if hit else None
+
+
+def with_partial_sums(xin, keep):
+    """xin rebuilt per (image, group) as a tensor whose moments are what the partial sums over `keep` give against the FULL count: mean' = S_kept / N,
+    var' = Q_kept / N - mean'^2"""
+    out = xin.double().clone()
+    Bn, C, H, W = out.shape
+    gw = C // 32
+    k = keep[:, :, None].expand(C, H, W)
+    for b in range(Bn):
+        for g in range(32):
+            grp, kg = out[b, g * gw:(g + 1) * gw], k[g * gw:(g + 1) * gw]
+            if bool(kg.all()):
+                continue
+            Nn = grp.numel()
+            m1, m2 = grp[kg].sum() / Nn, (grp[kg] ** 2).sum() / Nn
+            sdv = torch.sqrt((m2 - m1 ** 2).clamp_min(0))
+            out[b, g * gw:(g + 1) * gw] = (grp - grp.mean()) / grp.std(unbiased=False) * sdv + m1
+    return out
+
+
+def shape_defect_touches(cfg, defect, forms):
+    """the stages of a network at which one of SHAPE_DEFECTS changes a norm1's statistics (forms: stage -> its forms, for the Upsample's tile)"""
+    sts = {s["name"]: s for s in stages(cfg)}
+    out = []
+    for s in stages(cfg):
+        if s["kind"] != "resblock" or s["in0"] is None:
+            continue
+        p0, p1 = sts[s["in0"]], sts.get(s["in1"])
+        c0 = p0["C"]
+        if shape_defect_keep(defect, c0, s["cin"] - c0, s["H"], nslab_of(p0, forms(p0)), nslab_of(p1, forms(p1)) if p1 else 1) is not None:
+            out.append(s["name"])
+    return out
 
 
 def _gn32(x, gamma, beta, variant, stats_of=None):
@@ -313,6 +387,12 @@ class Emu:
                 m1, sdv = own.mean((1, 2, 3), keepdim=True), own.std((1, 2, 3), unbiased=False, keepdim=True)
                 grp = stats_of[:, g * gw:(g + 1) * gw]
                 stats_of[:, g * gw:(g + 1) * gw] = (grp - grp.mean((1, 2, 3), keepdim=True)) / grp.std((1, 2, 3), unbiased=False, keepdim=True) * sdv + m1
+            if self.defect[0] in SHAPE_DEFECTS and self.defect[1] == n:
+                by = {q["name"]: q for q in self.st_list}
+                p0, p1 = by[s["in0"]], by.get(s["in1"])
+                keep = shape_defect_keep(self.defect[0], x0.shape[1], xin.shape[1] - x0.shape[1], xin.shape[2], nslab_of(p0, self.forms(p0)),
+                                         nslab_of(p1, self.forms(p1)) if p1 else 1)
+                stats_of = None if keep is None else with_partial_sums(xin, keep)
             a1 = self.st(self.act_gn(xin, n + ".norm1", 1, stats_of))
         f3 = lambda ww, aa: F.conv2d(aa, ww, padding=1)
         h = self.conv32(f3, self.sd[n + ".conv1.weight"], a1, x3[0]) + self.sd[n + ".conv1.bias"].float().view(1, -1, 1, 1) + temb_rows.float()[:, :, None, None]
@@ -381,10 +461,11 @@ class Emu:
         return taps, nrms, eps, table
 
 
-def stage_emu(sd, cfg, st, kind, x0, x1, temb_rows, forms, pre=None, gn="device", kflip=False):
+def stage_emu(sd, cfg, st, kind, x0, x1, temb_rows, forms, pre=None, gn="device", kflip=False, defect=None, net_forms=None):
     """one stage of the executor in fp32 on the given stored inputs, as the device would store it (float64 values of the model dtype): the yardstick of a stage's bound.
-    Arguments as stage_ref; gn: the fp32 GroupNorm (attn_ref.GN_VARIANTS); kflip: the other summation order (convs; the attention chain has one)"""
-    e = Emu(sd, cfg, kind, gn, kflip)
+    Arguments as stage_ref; gn: the fp32 GroupNorm (attn_ref.GN_VARIANTS); kflip: the other summation order (convs; the attention chain has one); defect, net_forms: Emu's
+    defect and forms (one of SHAPE_DEFECTS at this stage needs the forms of the stages that produced its inputs)"""
+    e = Emu(sd, cfg, kind, gn, kflip, defect=defect, forms=net_forms)
     x3 = forms.get("x3", 4)
     if st["kind"] == "resblock":
         y = e.resblock(st, x0.float(), None if x1 is None else x1.float(), torch.as_tensor(temb_rows), None if pre is None else pre.float(), forms.get("shortcut", "fused"),
